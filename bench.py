@@ -14,6 +14,12 @@ weak scaling: per-GPU batch fixed).  Inputs are pre-generated on the device
 Run: python bench.py [--gpus N --steps K --warmup W]; N > 1 under
 torch.distributed.run (one process per GPU, RCCL).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline
+fields (value, ms_per_step, ...).  --dump-outputs DIR also writes what the last
+timed step left (see dump_outputs).  --full adds every other leg to the line:
+the instrumented passes and rooflines, the eval forward, the Zipf and fp32
+lines, the measured peaks, configs[1], configs[4] and the CPU baselines.
 """
 from __future__ import annotations
 
@@ -467,6 +473,36 @@ def measured_peaks(dev, iters=10):
             "bf16_gemm_tflops": gemm_tf, "gemm": "8192^3 bf16 torch.mm (hipBLASLt)"}
 
 
+DUMP_SEED = 20240
+DUMP_EMB_SAMPLE = 1 << 22   # sampled embedding-segment elements (16 MB of fp32)
+
+
+def dump_outputs(path, trainer, loss):
+    """--dump-outputs: what a caller of the timed path holds after its last
+    step, as float32 .npy files (about 26 MB at the bench model):
+      loss.npy              the value trainer.step() returned (one element)
+      params_dense.npy      the dense parameters after the step (the flat
+                            buffer past the embedding segment, padding included)
+      params_emb_sample.npy DUMP_EMB_SAMPLE elements of the embedding segment
+                            (user, item and categorical tables) at sorted
+                            positions drawn once from a CPU generator seeded
+                            with DUMP_SEED: the same positions in every run
+      buffers.npy           the BatchNorm running statistics, in state_dict order
+    The weights, the batches and the dropout seeds are all seeded, so two runs
+    with the same arguments write the outputs of identical inputs."""
+    os.makedirs(path, exist_ok=True)
+    flat, E = trainer.flat.detach(), trainer.E
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    pos = torch.randint(0, E, (min(DUMP_EMB_SAMPLE, E),), generator=g).sort().values
+    bufs = [b.detach().reshape(-1).float() for b in trainer.model.buffers()]
+    arrays = {"loss": loss.detach().reshape(1).float(),
+              "params_dense": flat[E:],
+              "params_emb_sample": flat[pos.to(flat.device)],
+              "buffers": torch.cat(bufs) if bufs else torch.zeros(0)}
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(np.float32, copy=False))
+
+
 def pmc_traffic(kernel_class):
     """HBM bytes per launch from the committed rocprofv3 PMC summary, if any."""
     p = os.path.join(ROOT, "profiles", "pmc_traffic.json")
@@ -488,6 +524,13 @@ def main():
     ap.add_argument("--pool", type=int, default=0,
                     help="distinct synthetic batches (default: warmup + steps, a fresh batch "
                          "every step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every other leg (instrumented passes "
+                         "and rooflines, eval forward, Zipf ids, fp32 mode, measured peaks, "
+                         "configs[1], configs[4], CPU baselines; the --no-* options trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left (loss, parameters, BN statistics) "
+                         "as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-fp32", action="store_true", help="skip the fp32 parity-mode line")
     ap.add_argument("--eval-steps", type=int, default=10)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -590,6 +633,62 @@ def main():
 
     # timed region: K plain steps (the reported value)
     el, _, loss = timed(False)
+    trainer.check_indices()
+    final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, trainer, loss)
+
+    def headline():
+        return {
+            "metric": "fwd+bwd samples/sec (DCN-R train step) + scored (user,hotel) pairs/sec",
+            "value": world * B * args.steps / el,
+            "unit": "samples/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": el / args.steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": args.precision,
+            "data": "synthetic (uniform ids, U[0,1) dense, Bernoulli labels; a distinct batch per "
+                    "step, generated on the device before the timed region; weights seed 42, "
+                    "torch default init)",
+            "config": {"workload": "DCN-R train step: fwd (train BN, dropout 0.6) + BCE + bwd + "
+                                   "AdamW (+grad all-reduce), BASELINE configs[2]/[3]",
+                       "batch_per_gpu": B, "global_batch": world * B,
+                       "tables": "1M x 32 users, 100k x 32 hotels, 12 x 1000 x 32 cat, 8 dense",
+                       "deep": "3 cross + 4 x 512 residual", "parallelism": f"dp{world}",
+                       "backend": dist.get_backend() if world > 1 else None,
+                       "rank_devices": None if world == 1 else
+                       [f'{r["device"]} bus {r["pci_bus_id"]}' for r in ranks_info],
+                       "exchange": "none" if world == 1 else (
+                           "dense params: all-reduce started in the backward (overlapped); "
+                           "user/item tables: touched rows all_to_all to the shard owners + "
+                           "sharded AdamW + all-gather; categorical tables: all-reduce"
+                           if args.exchange == "sparse"
+                           else "dense params: all-reduce started in the backward (overlapped); "
+                                "tables: reduce-scatter + sharded AdamW + all-gather, "
+                                f"pipelined in {trainer.chunks} chunks"),
+                       "exchange_chunks": trainer.chunks if world > 1 else None},
+            "distributed": None if world == 1 else {
+                "backend": dist.get_backend(), "world_size": world, "ranks": ranks_info,
+                "distinct_devices": len({(r["pci_bus_id"], r["uuid"], r["local_rank"]) for r in ranks_info})},
+            "final_loss": final_loss,
+        }
+
+    if not args.full:
+        # a plain run: the headline fields only
+        if rank == 0:
+            out = headline()
+            if rehearse:
+                out["rehearsal"] = "DCNR_BENCH_REHEARSE: all ranks on cuda:0 over gloo (not a scaling number)"
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
     # the same K steps again with every libdcnr launch bracketed by HIP events
     # on its stream (per-kernel-class durations for the roofline); the events
     # serialise launches, so this pass is not the throughput number
@@ -599,7 +698,6 @@ def main():
     # time, the contention the alone-priced table above does not show
     _, prof_dw, _ = timed(2) if args.precision == "bf16" else (None, None, None)
     trainer.check_indices()
-    final_loss = float(loss.item())
     # N > 1: the same K steps with the other table exchange on the same
     # trainer (both are ZeRO-1: the moments are sharded the same way), so the
     # line reports both (DESIGN.md section 6 has the per-rank byte model)
@@ -704,7 +802,6 @@ def main():
         cfg5["sharded_index"] = bench_cfg5_sharded(dev, 10, world)
 
     if rank == 0:
-        samples = world * B * args.steps
         per_step_ms = {k: v[0] / args.steps for k, v in prof.items() if v[1]}
         launches = {k: v[1] / args.steps for k, v in prof.items() if v[1]}
         # every kernel class priced against HBM with the library's per-launch
@@ -750,47 +847,13 @@ def main():
         deep_flop = sum(GEMM_FLOP.values()) * B
         g_ms, g_cnt, _ = prof["gather_cross"]
         gather_gbs = GATHER_BYTES * B * args.steps / g_cnt / (g_ms / g_cnt / 1e3) / 1e9
-        out = {
-            "metric": "fwd+bwd samples/sec (DCN-R train step) + scored (user,hotel) pairs/sec",
-            "value": samples / el,
-            "unit": "samples/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": el / args.steps * 1e3,
+        out = headline()
+        out.update({
             "ms_per_step_instrumented": el_prof / args.steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": args.precision,
-            "data": "synthetic (uniform ids, U[0,1) dense, Bernoulli labels; a distinct batch per "
-                    "step, generated on the device before the timed region; weights seed 42, "
-                    "torch default init)",
-            "config": {"workload": "DCN-R train step: fwd (train BN, dropout 0.6) + BCE + bwd + "
-                                   "AdamW (+grad all-reduce), BASELINE configs[2]/[3]",
-                       "batch_per_gpu": B, "global_batch": world * B,
-                       "tables": "1M x 32 users, 100k x 32 hotels, 12 x 1000 x 32 cat, 8 dense",
-                       "deep": "3 cross + 4 x 512 residual", "parallelism": f"dp{world}",
-                       "backend": dist.get_backend() if world > 1 else None,
-                       "rank_devices": None if world == 1 else
-                       [f'{r["device"]} bus {r["pci_bus_id"]}' for r in ranks_info],
-                       "exchange": "none" if world == 1 else (
-                           "dense params: all-reduce started in the backward (overlapped); "
-                           "user/item tables: touched rows all_to_all to the shard owners + "
-                           "sharded AdamW + all-gather; categorical tables: all-reduce"
-                           if args.exchange == "sparse"
-                           else "dense params: all-reduce started in the backward (overlapped); "
-                                "tables: reduce-scatter + sharded AdamW + all-gather, "
-                                f"pipelined in {trainer.chunks} chunks"),
-                       "exchange_chunks": trainer.chunks if world > 1 else None},
-            "distributed": None if world == 1 else {
-                "backend": dist.get_backend(), "world_size": world, "ranks": ranks_info,
-                "distinct_devices": len({(r["pci_bus_id"], r["uuid"], r["local_rank"]) for r in ranks_info})},
             "scored_pairs_per_sec": pairs_per_s,
             "scored_pairs_roofline": eval_roof,
             "other_exchange": other_exchange,
             "exchange_window_after_backward": exchange_window,
-            "final_loss": final_loss,
             "roofline": roof,
             "roofline_by_class": table,
             "deep_tower_mfma": {"gemm_ms_per_step": deep_ms, "flop_per_step": deep_flop,
@@ -810,7 +873,7 @@ def main():
             "configs4": cfg5,
             "kernel_ms_per_step": per_step_ms,
             "kernel_launches_per_step": launches,
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         if rehearse:

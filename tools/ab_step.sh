@@ -5,7 +5,7 @@
 set -o pipefail
 R=gpurun_out/$1; V=$2; N=${3:-2}
 mkdir -p $R
-A="--steps 20 --warmup 5 --no-cpu-baseline --no-serving --no-fp32 --no-zipf"
+A="--full --steps 20 --warmup 5 --no-cpu-baseline --no-serving --no-fp32 --no-zipf"
 for i in $(seq $N); do
   timeout -k 10 300 python3 -u bench.py $A > $R/base_$i.log 2>&1 || exit 1
   DCNR_LIB=$PWD/tools/lab_bin/libdcnr_$V.so timeout -k 10 300 python3 -u bench.py $A > $R/${V}_$i.log 2>&1 || exit 1

@@ -6,7 +6,7 @@ runs, dispatches serialised by the profiler) see every dispatch of the run;
 the step is the dispatches after the (N-1)-th `adam_kernel` up to the N-th.
 FETCH_SIZE is doubled on gfx950, WRITE_SIZE taken as is (MI355X_MICROARCH.md,
 HBM section; the same corrections as tools/pmc_traffic.py).  Algorithmic
-bytes per class come from the bench JSON line of a run of the same tree
+bytes per class come from the `bench.py --full` JSON line of a run of the same tree
 (`roofline_by_class[*].bytes_per_launch` x `launches_per_step`: inputs read
 once, outputs written once, counted by the library at each launch).
 

@@ -11,7 +11,7 @@ R=${1:-r03}
 OUT=gpurun_out/$R/sq
 mkdir -p $OUT
 export TMPDIR=/tmp
-ARGS="--steps 2 --warmup 1 --eval-steps 1 --no-cpu-baseline --no-serving --no-fp32 --no-zipf"
+ARGS="--full --steps 2 --warmup 1 --eval-steps 1 --no-cpu-baseline --no-serving --no-fp32 --no-zipf"
 P1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE"
 P2="SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES GRBM_GUI_ACTIVE"
 i=0

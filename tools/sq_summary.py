@@ -86,7 +86,7 @@ def main():
             per[g][c].append(v)
         if dur:
             per[g]["_dur_" + key[0]].append(dur)
-    print("SQ counters per production kernel (averages per dispatch; bench.py --steps 2 "
+    print("SQ counters per production kernel (averages per dispatch; bench.py --full --steps 2 "
           "--warmup 1 --eval-steps 1 under rocprofv3 --pmc, two passes)")
     print("mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / (1024 SIMDs x GRBM_GUI_ACTIVE/8); "
           "lds_wait = SQ_WAIT_INST_LDS / SQ_WAVE_CYCLES; bank_conf = SQ_LDS_BANK_CONFLICT / "

@@ -1,6 +1,6 @@
 """Per-pass averages of one kernel from a rocprofv3 kernel trace of bench.py.
 
-bench.py times K plain steps (the reported value), then the same K steps
+bench.py --full times K plain steps (the reported value), then the same K steps
 with every launch bracketed by HIP events (the roofline pass).  In the plain
 pass the bf16 weight-gradient GEMMs run on the side stream, concurrently
 with the main stream's dX GEMMs and BN passes; in the instrumented pass the
