@@ -90,19 +90,19 @@ namespace {
     dcnr_status st_ = (x);           \
     if (st_ != DCNR_OK) return st_;  \
   } while (0)
-// TRY with the launch attributed to a kernel class (stream `s` in scope)
-#define TRYP(cat, x)                 \
-  do {                               \
-    ProfScope ps_(cat, s);           \
-    dcnr_status st_ = (x);           \
-    if (st_ != DCNR_OK) return st_;  \
+// TRY with the launch timed on `stream` and attributed to a kernel class
+#define TRYP(cat, stream, x)            \
+  do {                                  \
+    ProfScope ps_(cat, stream);         \
+    dcnr_status st_ = (x);              \
+    if (st_ != DCNR_OK) return st_;     \
   } while (0)
 // ... and its algorithmic bytes
-#define TRYB(cat, nbytes, x)                 \
-  do {                                       \
-    ProfScope ps_(cat, s, (double)(nbytes)); \
-    dcnr_status st_ = (x);                   \
-    if (st_ != DCNR_OK) return st_;          \
+#define TRYB(cat, stream, nbytes, x)              \
+  do {                                            \
+    ProfScope ps_(cat, stream, (double)(nbytes)); \
+    dcnr_status st_ = (x);                        \
+    if (st_ != DCNR_OK) return st_;               \
   } while (0)
 
 // Flags of the fork/join events between the caller's stream and the side
@@ -272,17 +272,6 @@ double gather_row_b(const Dims& d, int n_num) {
 double w_b(const Dims& d, int K) { return (double)d.Hp * K * d.es; }
 
 // ------------------------------------------------------------- workspace
-struct Bump {
-  char* base; size_t off = 0;
-  explicit Bump(void* b) : base((char*)b) {}
-  void* take(size_t bytes) {
-    off = (off + 255) & ~(size_t)255;
-    void* p = base ? base + off : nullptr;
-    off += bytes;
-    return p;
-  }
-};
-
 struct BnBufs { float *scale, *shift, *mean, *invstd; };
 
 struct Layout {
@@ -296,16 +285,15 @@ struct Layout {
   void* a1;                 // eval: BN1/ReLU output scratch; train: backward scratch (dt1)
   void* a1s[MAX_RES];       // train: each block's dropout(relu(BN1(t1))), saved for dW2
   float* zc; float* zdeep;
-  float* headp;             // eval: [head parts][B] deep-head partial dots (null: row_dot)
-  char* twp;                // eval, fused tower: the packed weight slices (null: layer by layer)
+  float* headp;             // eval (Plan::eval_headp): [head parts][B] deep-head partial dots
+  char* twp;                // eval (Plan::tower): the packed weight slices
   BnBufs bn[2 * MAX_RES];
   float* part; double* sums; float* coef;
   double* red2; int* red_cnt;   // reduce_fused scratch (counters zeroed by pack_all)
   // backward
   void* G; void* dt2; void* du; void* da;
-  void* dt2b; void* dt1b;   // second dt2 / dt1 set (bf16 train, odd blocks); null: one set
-  // per-block backward buffers: all alias G/dt2/du/da/a1 unless
-  // DCNR_FLAG_KEEP_INTERMEDIATES gives each block its own
+  // per-block backward buffers: all alias dt2/du/da/a1 unless DCNR_FLAG_KEEP_INTERMEDIATES
+  // gives each block its own (Plan::own_dt: dt2k / dt1k a set per block)
   void* duk[MAX_RES]; void* dt2k[MAX_RES]; void* dak[MAX_RES]; void* dt1k[MAX_RES];
   float* dx0;                 // deep part of dL/dx0, [B][Dq] (Dq = Dp rounded up to 32)
   float* slab; int64_t slab_elems;
@@ -313,8 +301,8 @@ struct Layout {
   float* sc;                 // forward -> backward cross scalars [B][2L+1]
   float* xcoef; float* xalpha;  // [B][L+1] each (cross_bwd.hip)
   void* cscratch; size_t cscratch_bytes;
-  // 1-bit keep masks for the backward GEMM epilogues (bf16, Hp % 32 == 0):
-  // mask_a1[j] = [a1_j != 0], mask_h[j] = [h_j > 0] (j >= 1)
+  // 1-bit keep masks for the backward GEMM epilogues (Plan::masks):
+  // mask_a1[j] = [a1_j != 0], mask_h[j] = [h_j > 0] (j >= 1; j = R: Plan::rank1)
   uint8_t* mask_a1[MAX_RES]; uint8_t* mask_h[MAX_RES + 1];
   EmbSortBufs emb;                              // deterministic embedding backward
   double* bce_part;
@@ -322,23 +310,24 @@ struct Layout {
   size_t total;
 };
 
-// the backward GEMM epilogues read 1-bit keep masks (bf16 path, mask rows of
-// whole 32-bit words) instead of the bf16 activations
-bool masks_ok(const Dims& d) { return d.prec == DCNR_PREC_BF16 && d.Hp % 32 == 0; }
 // leading dimension of the deep dx0: 32-float (128-B) rows so that each
 // embedding table's segment of a row is line-aligned for embed_bwd.hip
 int dq_of(const Dims& d) { return (int)rup(d.Dp, 32); }
-bool keep_of(const dcnr_model_desc* desc) { return (desc->flags & DCNR_FLAG_KEEP_INTERMEDIATES) != 0; }
 
-// bf16 train: the last block's head pass does not store h_R; the backward's
-// BN2 statistics pass rebuilds it from t2, h_{R-1} and the BN2 affine
-// (KEEP_INTERMEDIATES still stores it for the stage tests)
-bool head_rebuild(const Dims& d, bool train) {
-  return train && d.prec == DCNR_PREC_BF16 && bn_add_relu_head_supported(d.prec, d.Hp);
-}
+// ------------------------------------------------------------------ plan
+// The predicates below are called from make_plan alone.
+// the backward GEMM epilogues read 1-bit keep masks (bf16 path, mask rows of
+// whole 32-bit words) instead of the bf16 activations
+bool masks_ok(const Dims& d) { return d.prec == DCNR_PREC_BF16 && d.Hp % 32 == 0; }
+// Stats epilogues of the streaming GEMM (BN column partials produced by the
+// GEMM that writes the BN input / the BN output gradient) -- bf16 only.
+bool epi_stats_ok(const Dims& d) { return masks_ok(d) && gemm_ws_supported(d.Hp, d.Hp); }
+// Eval forward with BatchNorm (running statistics) + ReLU (+ residual) in the
+// streaming GEMM's epilogue: no t1/t2 round trip through HBM and no rowwise
+// passes (bf16, gemm_ws shapes).
 bool eval_fuse_ok(const Dims& d) { return d.prec == DCNR_PREC_BF16 && gemm_ws_supported(d.Hp, d.Hp); }
 
-// The eval forward's deep tower as one persistent launch (tower.hip): bf16,
+// The eval forward's deep tower as one persistent launch (tower.hip): eval, bf16,
 // the shapes it covers (input width <= 512, hidden <= 512), not when the
 // stage tests ask for every intermediate, and from TOWER_MIN_B samples (or
 // with DCNR_FLAG_FUSED_TOWER): one 128-sample tile per CU walks all 2R+1
@@ -346,22 +335,76 @@ bool eval_fuse_ok(const Dims& d) { return d.prec == DCNR_PREC_BF16 && gemm_ws_su
 // layer-by-layer path spreads each layer over the chip (bench model: 179 vs
 // 139 us at 4096 samples, 622 vs 806 us at 131072).
 constexpr int64_t TOWER_MIN_B = 16384;
-bool tower_ok(const Dims& d, bool train, uint32_t flags, int64_t B) {
+bool tower_ok(const Dims& d, uint32_t flags, int64_t B) {
   const bool size_ok = B >= TOWER_MIN_B || (flags & DCNR_FLAG_FUSED_TOWER);
-  return !train && !(flags & DCNR_FLAG_KEEP_INTERMEDIATES) && size_ok && d.prec == DCNR_PREC_BF16 &&
+  return !(flags & DCNR_FLAG_KEEP_INTERMEDIATES) && size_ok && d.prec == DCNR_PREC_BF16 &&
          tower_supported(d.Dp, d.H, d.R);
 }
 
-Layout make_layout(const Dims& d, int64_t B, int mode, void* ws, uint32_t flags = 0) {
-  const bool keep = (flags & DCNR_FLAG_KEEP_INTERMEDIATES) != 0;
+// Which kernels a call runs, decided once from (model, flags, mode, B).  The
+// layout (what gets a buffer), the forward (what is written) and the backward
+// (what is read) follow these fields and nothing else, so they cannot disagree.
+struct Plan {
+  bool train, keep;  // mode; DCNR_FLAG_KEEP_INTERMEDIATES
+  // ---- eval
+  bool tower;        // the fused deep tower: x0, zc and the packed slices are the whole layout
+  bool eval_epi;     // BN + ReLU (+ residual) in the GEMM epilogues
+  bool eval_headp;   // ... the last GEMM ending in the deep head's partial dots (no h_R)
+  // ---- the layer-by-layer forward (train, and eval without the epilogues)
+  bool head_fused;   // the last block's BN2 apply + residual + ReLU + head dot + logits in one pass
+  // ---- train
+  bool masks;        // the forward stores the 1-bit keep masks
+  bool stats_epi;    // BN column partials from the forward and dX GEMM epilogues
+  bool xbn;          // ... and the BN backward's row passes folded into them (256 < Hp <= 512)
+  bool rebuild_hR;   // the backward's BN2 statistics pass rebuilds h_R from t2, h_{R-1} and the
+                     // BN2 affine; the head pass stores h_R only with `keep` (stage tests)
+  bool rank1;        // the head pass stores [h_R > 0]; the last BN2 apply is the rank-1 form over it
+  bool own_dt;       // every block its own dt2 / dt1 buffers (else one shared set)
+  bool rowmap;       // DCNR_FLAG_ROW_MAP
+  int dw_lag;        // DwPipe: the main stream waits for the dW GEMM this many calls back (1 << 30: never)
+};
+
+Plan make_plan(const Dims& d, uint32_t flags, int mode, int64_t B) {
+  Plan p{};
+  const bool bf16p = d.prec == DCNR_PREC_BF16;
+  p.train = mode == DCNR_TRAIN;
+  p.keep = (flags & DCNR_FLAG_KEEP_INTERMEDIATES) != 0;
+  p.head_fused = bn_add_relu_head_supported(d.prec, d.Hp);
+  if (!p.train) {
+    p.tower = tower_ok(d, flags, B);
+    p.eval_epi = !p.tower && eval_fuse_ok(d);
+    // (32-bit buffer offsets into the head partials: at Hp = 512 up to ~33M
+    // rows; larger batches take the unfused, M-chunked tail)
+    p.eval_headp = p.eval_epi && !p.keep &&
+                   (int64_t)B * gemm_ws_head_parts(d.Hp) * 4 < (int64_t(1) << 31);
+    return p;
+  }
+  p.masks = masks_ok(d);
+  p.stats_epi = epi_stats_ok(d);
+  p.xbn = p.stats_epi && gemm_ws_xbn_supported(NT_EPI_DROP_BN, d.Hp, d.Hp);
+  p.rebuild_hR = bf16p && p.head_fused;
+  p.rank1 = p.masks && p.head_fused;
+  // bf16: every residual block has its own dt2 / dt1 buffers: the side
+  // stream's weight-gradient GEMMs read them while the main stream goes on,
+  // and the main stream never waits for the side stream inside the backward
+  // (4.029-4.044 vs 4.068-4.075 ms per step with two sets alternating by
+  // block parity and a wait for call n-3, same box, profiles/lab/r04s_dt_per_block_ab.txt;
+  // +0.54 GB of workspace at the bench shape)
+  p.own_dt = !p.keep && bf16p && d.R > 1;
+  p.rowmap = (flags & DCNR_FLAG_ROW_MAP) != 0;
+  p.dw_lag = p.keep || p.own_dt ? 1 << 30 : 1;
+  return p;
+}
+
+Layout make_layout(const Dims& d, int64_t B, const Plan& pl, void* ws) {
   Layout L;
   memset(&L, 0, sizeof(L));
   Bump b(ws);
-  const bool train = mode == DCNR_TRAIN;
+  const bool train = pl.train, keep = pl.keep;
   const size_t es = d.es;
   const size_t act = (size_t)B * d.Hp * es;
   L.err = (int*)b.take(256);
-  if (tower_ok(d, train, flags, B)) {   // x0, zc, the packed slices: nothing of the tower in HBM
+  if (pl.tower) {   // x0, zc, the packed slices: nothing of the tower in HBM
     L.x0 = b.take((size_t)B * d.Dp * es);
     L.zc = (float*)b.take(B * 4);
     L.twp = (char*)b.take((size_t)tower_ws_bytes(d.H, d.R));
@@ -393,20 +436,15 @@ Layout make_layout(const Dims& d, int64_t B, int mode, void* ws, uint32_t flags 
   L.a1 = b.take(act);
   if (train)
     for (int j = 0; j < d.R; ++j) L.a1s[j] = b.take(act);
-  if (train && masks_ok(d)) {
+  if (pl.masks) {
     const size_t mb = (size_t)B * d.Hp / 8;
     for (int j = 0; j < d.R; ++j) L.mask_a1[j] = (uint8_t*)b.take(mb);
     for (int j = 1; j < d.R; ++j) L.mask_h[j] = (uint8_t*)b.take(mb);
-    if (bn_add_relu_head_supported(d.prec, d.Hp))   // [h_R > 0] for the last block's BN2 apply
-      L.mask_h[d.R] = (uint8_t*)b.take(mb);
+    if (pl.rank1) L.mask_h[d.R] = (uint8_t*)b.take(mb);
   }
   L.zc = (float*)b.take(B * 4);
   L.zdeep = (float*)b.take(B * 4);
-  // the last eval GEMM's head partials (32-bit buffer offsets: at Hp = 512
-  // up to ~33M rows; larger batches take the unfused, M-chunked tail)
-  if (!train && !keep && eval_fuse_ok(d) && d.R >= 1 &&
-      (int64_t)B * gemm_ws_head_parts(d.Hp) * 4 < (int64_t(1) << 31))
-    L.headp = (float*)b.take((size_t)B * gemm_ws_head_parts(d.Hp) * 4);
+  if (pl.eval_headp) L.headp = (float*)b.take((size_t)B * gemm_ws_head_parts(d.Hp) * 4);
   for (int i = 0; i < 2 * d.R; ++i) {
     L.bn[i].scale = (float*)b.take(d.Hp * 4);
     L.bn[i].shift = (float*)b.take(d.Hp * 4);
@@ -446,29 +484,22 @@ Layout make_layout(const Dims& d, int64_t B, int mode, void* ws, uint32_t flags 
       L.emb.tmp_bytes = emb_sort_tmp_bytes(d.rows, d.widths, 2 + d.K, B);
       L.emb.tmp = b.take(L.emb.tmp_bytes);
     }
-    // bf16: every residual block has its own dt2 / dt1 buffers (blocks 0
-    // and 1 take the shared set and dt2b / dt1b): the side stream's
-    // weight-gradient GEMMs read them while the main stream goes on, and the
-    // main stream never waits for the side stream inside the backward
-    // (4.029-4.044 vs 4.068-4.075 ms per step with two sets alternating by
-    // block parity and a wait for call n-3, same box, profiles/lab/r04s_dt_per_block_ab.txt;
-    // +0.54 GB of workspace at the bench shape)
-    const bool own_dt = !keep && d.prec == DCNR_PREC_BF16 && d.R > 1;
-    if (own_dt) {
-      L.dt2b = b.take(act);
-      L.dt1b = b.take(act);
+    // own_dt: blocks 0 and 1 take the shared set and a second one, later blocks a fresh set
+    void *dt2b = nullptr, *dt1b = nullptr;
+    if (pl.own_dt) {
+      dt2b = b.take(act);
+      dt1b = b.take(act);
     }
     for (int j = 0; j < d.R; ++j) {
-      const bool fresh = own_dt && j > 1;
+      const bool fresh = pl.own_dt && j > 1;
       L.duk[j] = keep ? b.take(act) : L.du;
-      L.dt2k[j] = keep || fresh ? b.take(act) : own_dt && j == 1 ? L.dt2b : L.dt2;
+      L.dt2k[j] = keep || fresh ? b.take(act) : pl.own_dt && j == 1 ? dt2b : L.dt2;
       L.dak[j] = keep ? b.take(act) : L.da;
-      L.dt1k[j] = keep || fresh ? b.take(act) : own_dt && j == 1 ? L.dt1b : L.a1;
+      L.dt1k[j] = keep || fresh ? b.take(act) : pl.own_dt && j == 1 ? dt1b : L.a1;
     }
-
   }
   L.bce_part = (double*)b.take(bce_ws_bytes());
-  if (train && (flags & DCNR_FLAG_ROW_MAP)) {   // last: every other offset as without the flag
+  if (pl.rowmap) {   // last: every other offset as without the flag
     int64_t rows = 0;
     for (int t = 0; t < 2 + d.K; ++t) rows += d.rows[t];
     L.rowmap_bytes = (size_t)rup(rows, 256);
@@ -591,7 +622,7 @@ dcnr_status pack_all(const Dims& d, const Params& P, const Layout& L, bool train
     PackBatch pb;
     pb.n = (int)std::min<size_t>(MAX_PACK, v.size() - o);
     for (int i = 0; i < pb.n; ++i) pb.d[i] = v[o + i];
-    TRYP(DCNR_K_PACK, pack_weights(d.prec, pb, s));
+    TRYP(DCNR_K_PACK, s, pack_weights(d.prec, pb, s));
   }
   return DCNR_OK;
 }
@@ -622,14 +653,6 @@ dcnr_status linear_fwd(const Dims& d, const void* A, int lda, const void* W, int
   g.M = B; g.N = d.Hp; g.K = K; g.k_per_split = K;
   return gemm_nn(d.prec, EPI_STORE, g, 1, s);
 }
-
-// Stats epilogues of the streaming GEMM (BN column partials produced by the
-// GEMM that writes the BN input / the BN output gradient) -- bf16 only.
-bool epi_stats_ok(const Dims& d) { return masks_ok(d) && gemm_ws_supported(d.Hp, d.Hp); }
-
-// Eval forward with BatchNorm (running statistics) + ReLU (+ residual) in the
-// streaming GEMM's epilogue: no t1/t2 round trip through HBM and no rowwise
-// passes (bf16, gemm_ws shapes).
 
 // out = relu((A W^T + b) * bn.scale + bn.shift [+ R]); with rs (the layer's
 // gamma, beta, running mean, running var) the kernel makes scale / shift
@@ -694,9 +717,10 @@ dcnr_status linear_dx_bn(const Dims& d, const Layout& L, int epi, const void* X,
 // dW[N][Kc] = sum_b dY[b][n] X[b][k]   (real extents Nr x Kr written to out)
 // bf16: the 256x256 LDS-DMA weight-gradient kernel (gemm_dw.hip), S batch
 // splits, fp32 slabs summed by splitk_reduce
-dcnr_status wgrad_bf16(const void* dY, int64_t ldy, int N, const void* X, int64_t ldx, int Kc,
-                       int64_t B, float* slab, int64_t slab_elems, float* out, int Nr, int Kr,
-                       int accumulate, hipStream_t s) {
+dcnr_status dw_args(const void* dY, int64_t ldy, int N, const void* X, int64_t ldx, int Kc, int64_t B,
+                    float* slab, int64_t slab_elems, DwArgs* out) {
+  // (the full-chip split count: 32 / 16 splits, leaving CUs to the main
+  // stream and halving the slab, measured 2 % / 21 % slower per step)
   const int S = gemm_dw_splits(N, Kc, B);
   if ((int64_t)S * N * Kc > slab_elems) {
     set_error("wgrad: slab too small");
@@ -708,9 +732,17 @@ dcnr_status wgrad_bf16(const void* dY, int64_t ldy, int N, const void* X, int64_
   a.C = slab; a.ldc = N; a.slab_stride = (int64_t)N * Kc;   // transposed slab [Kc][N]
   a.Btot = B; a.k_per_split = rup(cdiv(B, S), 64);
   a.N = N; a.K = Kc; a.splits = S;
-  TRYB(DCNR_K_GEMM_DW, 2.0 * B * (N + Kc) + 4.0 * Nr * Kr * (accumulate ? 2 : 1), gemm_dw(a, s));
-  TRYB(DCNR_K_REDUCE, 4.0 * S * N * Kc + 4.0 * Nr * Kr * (accumulate ? 2 : 1),
-       splitk_reduce_t(slab, S, (int64_t)N * Kc, N, Nr, Kr, out, accumulate, s));
+  *out = a;
+  return DCNR_OK;
+}
+dcnr_status wgrad_bf16(const void* dY, int64_t ldy, int N, const void* X, int64_t ldx, int Kc,
+                       int64_t B, float* slab, int64_t slab_elems, float* out, int Nr, int Kr,
+                       int accumulate, hipStream_t s) {
+  DwArgs a;
+  TRY(dw_args(dY, ldy, N, X, ldx, Kc, B, slab, slab_elems, &a));
+  TRYB(DCNR_K_GEMM_DW, s, 2.0 * B * (N + Kc) + 4.0 * Nr * Kr * (accumulate ? 2 : 1), gemm_dw(a, s));
+  TRYB(DCNR_K_REDUCE, s, 4.0 * a.splits * N * Kc + 4.0 * Nr * Kr * (accumulate ? 2 : 1),
+       splitk_reduce_t(slab, a.splits, (int64_t)N * Kc, N, Nr, Kr, out, accumulate, s));
   return DCNR_OK;
 }
 
@@ -742,9 +774,8 @@ struct DwPipe {
     if (!pend.slab) return DCNR_OK;
     const Combine c = pend;
     pend = Combine{};
-    hipStream_t s = side;   // TRYB launches and times on the side stream
-    TRYB(DCNR_K_REDUCE, 4.0 * c.S * c.stride + 4.0 * c.Nr * c.Kr * (c.acc ? 2 : 1),
-         splitk_reduce_t(c.slab, c.S, c.stride, c.ld, c.Nr, c.Kr, c.out, c.acc, s));
+    TRYB(DCNR_K_REDUCE, side, 4.0 * c.S * c.stride + 4.0 * c.Nr * c.Kr * (c.acc ? 2 : 1),
+         splitk_reduce_t(c.slab, c.S, c.stride, c.ld, c.Nr, c.Kr, c.out, c.acc, side));
     return DCNR_OK;
   }
   dcnr_status init(hipStream_t side_stream, int lag_calls) {
@@ -769,21 +800,9 @@ struct DwPipe {
                     int Kc, int64_t B, float* out, int Nr, int Kr, int accumulate, hipStream_t main_s) {
     TRY(enter(main_s));
     const int call = calls++;
-    hipStream_t s = side;   // TRYB launches and times on the side stream
-    // (the full-chip split count: 32 / 16 splits, leaving CUs to the main
-    // stream and halving the slab, measured 2 % / 21 % slower per step)
-    const int S = gemm_dw_splits(N, Kc, B);
-    if ((int64_t)S * N * Kc > L.slab_elems) {
-      set_error("wgrad: slab too small");
-      return DCNR_WORKSPACE_TOO_SMALL;
-    }
     float* slab = (call & 1) ? L.slab2 : L.slab;
     DwArgs a;
-    memset(&a, 0, sizeof(a));
-    a.A = (const bf16*)dY; a.lda = ldy; a.B = (const bf16*)X; a.ldb = ldx;
-    a.C = slab; a.ldc = N; a.slab_stride = (int64_t)N * Kc;   // transposed slab [Kc][N]
-    a.Btot = B; a.k_per_split = rup(cdiv(B, S), 64);
-    a.N = N; a.K = Kc; a.splits = S;
+    TRY(dw_args(dY, ldy, N, X, ldx, Kc, B, slab, L.slab_elems, &a));
     double rbytes = 0;
     if (pend.slab) {   // the previous call's combine, in this launch's tail
       a.rslab = pend.slab; a.rsplits = pend.S; a.rstride = pend.stride; a.rld = pend.ld;
@@ -796,9 +815,10 @@ struct DwPipe {
         return DCNR_UNSUPPORTED_SHAPE;
       }
     }
-    TRYB(DCNR_K_GEMM_DW, 2.0 * B * (N + Kc) + 4.0 * Nr * Kr * (accumulate ? 2 : 1) + rbytes, gemm_dw(a, s));
-    DCNR_HIP(hipEventRecord(dw_ev[call % RING], s));
-    pend = Combine{slab, S, (int64_t)N * Kc, N, Nr, Kr, out, accumulate};
+    TRYB(DCNR_K_GEMM_DW, side, 2.0 * B * (N + Kc) + 4.0 * Nr * Kr * (accumulate ? 2 : 1) + rbytes,
+         gemm_dw(a, side));
+    DCNR_HIP(hipEventRecord(dw_ev[call % RING], side));
+    pend = Combine{slab, a.splits, (int64_t)N * Kc, N, Nr, Kr, out, accumulate};
     return DCNR_OK;
   }
   dcnr_status join(hipStream_t main_s) {
@@ -846,8 +866,8 @@ dcnr_status linear_dw(const Dims& d, const Layout& L, const void* dY, int ldy, i
   g.A = dY; g.lda = ldy; g.B = X; g.ldb = ldx;
   g.C = L.slab; g.ldc = Kc;
   g.M = N; g.N = Kc; g.K = B; g.k_per_split = kps; g.slab_stride = (int64_t)N * Kc;
-  TRYB(DCNR_K_GEMM_DW, (double)d.es * B * (N + Kc) + 4.0 * Nr * Kr, gemm(d.prec, true, true, EPI_SPLITK, g, (int)S, s));
-  TRYB(DCNR_K_REDUCE, 4.0 * S * N * Kc + 4.0 * Nr * Kr * (accumulate ? 2 : 1),
+  TRYB(DCNR_K_GEMM_DW, s, (double)d.es * B * (N + Kc) + 4.0 * Nr * Kr, gemm(d.prec, true, true, EPI_SPLITK, g, (int)S, s));
+  TRYB(DCNR_K_REDUCE, s, 4.0 * S * N * Kc + 4.0 * Nr * Kr * (accumulate ? 2 : 1),
        splitk_reduce(L.slab, (int)S, (int64_t)N * Kc, Kc, Nr, Kr, out, accumulate, s));
   return DCNR_OK;
 }
@@ -870,7 +890,6 @@ RedFinal red_init(const Layout& L, int mode, double count, int accumulate) {
   return rf;
 }
 
-
 RedFinal bn_bwd_rf(const Layout& L, int64_t B, const float* gamma, const float* invstd,
                    float* dgamma, float* dbeta, float* dwf, float* dbias_pre, int accumulate) {
   RedFinal rf = red_init(L, RED_BN_BWD, (double)B, accumulate);
@@ -891,20 +910,20 @@ dcnr_status bn_layer_fwd(const dcnr_model_desc* desc, const Dims& d, const Layou
   if (train) {
     int nc = nc_pre;
     const void* shift = nc_pre ? nullptr : t;
-    if (!nc_pre) TRYB(DCNR_K_ROWWISE, act_b(d, B), col_stats(d.prec, t, B, d.Hp, d.Hp, L.part, &nc, s));
+    if (!nc_pre) TRYB(DCNR_K_ROWWISE, s, act_b(d, B), col_stats(d.prec, t, B, d.Hp, d.Hp, L.part, &nc, s));
     if (!desc->bn_allreduce) {  // local BN: reduce + finalize in one launch
       RedFinal rf = red_init(L, RED_BN_FWD, (double)B, 0);
       rf.f = f;
       rf.shiftf = shiftf;
-      TRYP(DCNR_K_REDUCE, reduce_fused(d.prec, L.part, nc, 2, d.Hp, d.H, shift, rf, s));
+      TRYP(DCNR_K_REDUCE, s, reduce_fused(d.prec, L.part, nc, 2, d.Hp, d.H, shift, rf, s));
       return DCNR_OK;
     }
     RedFinal rf = red_init(L, RED_SUMS, (double)B, 0);
     rf.shiftf = shiftf;
-    TRYP(DCNR_K_REDUCE, reduce_fused(d.prec, L.part, nc, 2, d.Hp, d.H, shift, rf, s));
+    TRYP(DCNR_K_REDUCE, s, reduce_fused(d.prec, L.part, nc, 2, d.Hp, d.H, shift, rf, s));
     TRY(hook(desc, d, L, s));
   }
-  TRYP(DCNR_K_REDUCE, bn_finalize2(L.sums, d.Hp, d.H, train ? 1 : 0, f, s));
+  TRYP(DCNR_K_REDUCE, s, bn_finalize2(L.sums, d.Hp, d.H, train ? 1 : 0, f, s));
   return DCNR_OK;
 }
 
@@ -918,17 +937,17 @@ dcnr_status bn_bwd_reduce(const dcnr_model_desc* desc, const Dims& d, const Layo
   const int Hp = d.Hp, H = d.H;
   if (!desc->bn_allreduce) {
     RedFinal rf = bn_bwd_rf(L, B, gamma, invstd, dgamma, dbeta, dwf, dbias_pre, accumulate);
-    TRYP(DCNR_K_REDUCE, reduce_fused(DCNR_PREC_FP32, L.part, nc, NK, Hp, H, nullptr, rf, s));
+    TRYP(DCNR_K_REDUCE, s, reduce_fused(DCNR_PREC_FP32, L.part, nc, NK, Hp, H, nullptr, rf, s));
     return DCNR_OK;
   }
   RedFinal rf = red_init(L, RED_SUMS, (double)B, 0);
-  TRYP(DCNR_K_REDUCE, reduce_fused(DCNR_PREC_FP32, L.part, nc, NK, Hp, H, nullptr, rf, s));
-  if (dwf) TRYP(DCNR_K_REDUCE, sums_to_grad(L.sums + 2 * Hp, H, dwf, accumulate, s));
-  TRYP(DCNR_K_REDUCE, sums_to_grad(L.sums + Hp, H, dgamma, accumulate, s));
-  TRYP(DCNR_K_REDUCE, sums_to_grad(L.sums, H, dbeta, accumulate, s));
+  TRYP(DCNR_K_REDUCE, s, reduce_fused(DCNR_PREC_FP32, L.part, nc, NK, Hp, H, nullptr, rf, s));
+  if (dwf) TRYP(DCNR_K_REDUCE, s, sums_to_grad(L.sums + 2 * Hp, H, dwf, accumulate, s));
+  TRYP(DCNR_K_REDUCE, s, sums_to_grad(L.sums + Hp, H, dgamma, accumulate, s));
+  TRYP(DCNR_K_REDUCE, s, sums_to_grad(L.sums, H, dbeta, accumulate, s));
   TRY(hook(desc, d, L, s));
-  TRYP(DCNR_K_REDUCE, bn_bwd_coef(L.sums, Hp, H, gamma, invstd, L.coef, 1, s));
-  if (!accumulate) TRYP(DCNR_K_PACK, fill_zero(dbias_pre, (size_t)H * 4, s));   // exactly 0 (see finalize)
+  TRYP(DCNR_K_REDUCE, s, bn_bwd_coef(L.sums, Hp, H, gamma, invstd, L.coef, 1, s));
+  if (!accumulate) TRYP(DCNR_K_PACK, s, fill_zero(dbias_pre, (size_t)H * 4, s));   // exactly 0 (see finalize)
   return DCNR_OK;
 }
 
@@ -937,9 +956,322 @@ dcnr_status bias_reduce(const Dims& d, const Layout& L, int nc, float* grad, int
                         hipStream_t s, int NK = 1) {
   RedFinal rf = red_init(L, RED_BIAS, 0.0, accumulate);
   rf.grad = grad;
-  TRYP(DCNR_K_REDUCE, reduce_fused(DCNR_PREC_FP32, L.part, nc, NK, d.Hp, d.H, nullptr, rf, s));
+  TRYP(DCNR_K_REDUCE, s, reduce_fused(DCNR_PREC_FP32, L.part, nc, NK, d.Hp, d.H, nullptr, rf, s));
   return DCNR_OK;
 }
+
+// C = X Wt^T [+ R] for the backward's plain dX GEMMs (all [B][Hp], square Hp)
+dcnr_status linear_dx(const Dims& d, const void* X, const void* Wt, const void* R, void* C, int64_t B,
+                      hipStream_t s) {
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A = X; g.lda = d.Hp; g.B = Wt; g.ldb = d.Hp; g.C = C; g.ldc = d.Hp;
+  g.resid = R; g.ldr = R ? d.Hp : 0;
+  g.M = B; g.N = d.Hp; g.K = d.Hp; g.k_per_split = d.Hp;
+  TRYB(DCNR_K_GEMM_DX, s, (R ? 3 : 2) * act_b(d, B) + w_b(d, d.Hp),
+       gemm_nn(d.prec, R ? EPI_STORE_RESID : EPI_STORE, g, 1, s));
+  return DCNR_OK;
+}
+
+// ------------------------------------------------------------- forward
+// One forward call's operands, and the tails the plan chooses between.
+struct Fwd {
+  const dcnr_model_desc* desc; const Dims& d; const Plan& pl; const Layout& L; const Params& P;
+  const int64_t *user_ids, *item_ids, *cat_features; const float* num_features;
+  int64_t B; float* logits; hipStream_t s; int check;   // check: DCNR_FLAG_CHECK_INDICES
+  GatherDesc g; CrossParams cp;
+
+  // eval, Plan::tower: gather + cross (x0 bf16, zc) -> the fused deep tower + head
+  dcnr_status tower() const {
+    TowerPack tp;
+    memset(&tp, 0, sizeof(tp));
+    tp.W0 = P.W0; tp.D = d.D; tp.b0 = P.b0;
+    for (int j = 0; j < d.R; ++j) {
+      const auto& Bk = P.blk[j];
+      tp.w1[j] = Bk.w1; tp.b1[j] = Bk.b1; tp.g1[j] = Bk.g1; tp.be1[j] = Bk.be1; tp.rm1[j] = Bk.rm1; tp.rv1[j] = Bk.rv1;
+      tp.w2[j] = Bk.w2; tp.b2[j] = Bk.b2; tp.g2[j] = Bk.g2; tp.be2[j] = Bk.be2; tp.rm2[j] = Bk.rm2; tp.rv2[j] = Bk.rv2;
+    }
+    tp.wf = P.wf; tp.H = d.H; tp.R = d.R; tp.out = L.twp; tp.err = check ? L.err : nullptr;
+    TRYP(DCNR_K_PACK, s, tower_pack(tp, s));
+    const GcOut o{nullptr, L.x0, L.zc, 0, d.Dp, nullptr};
+    TRYB(DCNR_K_GATHER_CROSS, s, (double)B * (gather_row_b(d, desc->n_num) + (double)d.Dp * d.es + 4.0),
+         gather_cross_out(g, cp, user_ids, item_ids, cat_features, num_features, B, o, 1, L.err, check, s));
+    TowerArgs ta;
+    memset(&ta, 0, sizeof(ta));
+    ta.x0 = (const bf16*)L.x0; ta.ldx = d.Dp; ta.M = B; ta.Dp = d.Dp; ta.H = d.H; ta.R = d.R;
+    ta.wp = L.twp; ta.zc = L.zc; ta.bias = P.bf; ta.logits = logits; ta.err = L.err;
+    ta.err_mirror = check ? desc->error_mirror : nullptr;   // (the tower stores the mirror itself)
+    // algorithmic bytes: the x0 rows + zc in, the logits out (the packed
+    // weights are L2-resident: every CU streams the same 4.7 MB)
+    TRYB(DCNR_K_TOWER, s, (double)B * (d.Dp * d.es + 8.0), eval_tower(ta, s));
+    return DCNR_OK;
+  }
+
+  // The two layer-wise paths' front: weight pack, gather + cross, initial Linear.
+  // Train: the weight packing (bf16 copies + transposes of the deep tower's
+  // weights) is not read by the gather/cross kernel, so it runs on the side
+  // stream under it and the first GEMM waits for it alone (same box, two
+  // runs each: 4.033 / 4.045 vs 4.071 / 4.055 ms/step, DESIGN.md; eval keeps it on the
+  // stream: its fork/join cost ~1 % of the eval forward). The embedding
+  // backward's id sort needs the ids alone, so it follows there, under this
+  // forward (dcnr_forward joins `sj` after the tail, so the caller's id
+  // tensors are free to go once the forward's work is done).
+  dcnr_status front(SideJoin& sj) const {
+    const bool train = pl.train;
+    if (train) {
+      TRY(sj.fork(s));
+      TRY(pack_all(d, P, L, train, sj.side));
+      TRY(sj.mark());
+    } else {
+      TRY(pack_all(d, P, L, train, s, check != 0));
+    }
+    // (train: the pack runs on the side stream beside the gather, so the
+    // error word is zeroed here, before it)
+    if (check && train) TRYP(DCNR_K_PACK, s, fill_zero(L.err, 4, s));
+    if (train) {
+      EmbBwdDesc eb;
+      memset(&eb, 0, sizeof(eb));
+      eb.n_tab = g.n_tab;
+      for (int t = 0; t < g.n_tab; ++t) { eb.rows[t] = g.rows[t]; eb.width[t] = g.width[t]; }
+      TRYB(DCNR_K_EMB_SORT, sj.side, 2.0 * 8.0 * g.n_tab * B + 8.0 * B * (2 + d.K) + 4.0 * B * 2,
+           emb_sort(eb, user_ids, item_ids, cat_features, B, L.emb, sj.side));
+      TRY(sj.record());
+    }
+    const GcOut o{nullptr, L.x0, L.zc, 0, d.Dp, train ? L.sc : nullptr};
+    TRYB(DCNR_K_GATHER_CROSS, s, (double)B * (gather_row_b(d, desc->n_num) + (double)d.Dp * d.es + 4.0),
+         gather_cross_out(g, cp, user_ids, item_ids, cat_features, num_features, B, o,
+                          d.prec == DCNR_PREC_BF16, L.err, check, s));
+    if (train) TRY(sj.wait_mark(s));   // packed weights, biases, zeroed reduction counters
+    TRYB(DCNR_K_GEMM_FWD, s, (double)B * d.Dp * d.es + act_b(d, B) + w_b(d, d.Dp),
+         linear_fwd(d, L.x0, d.Dp, L.W0p, d.Dp, L.b0p, L.h[0], B, s));
+    return DCNR_OK;
+  }
+
+  // eval, Plan::eval_epi: BatchNorm (running statistics) + ReLU (+ residual) in
+  // the GEMM epilogues.  eval_headp: each GEMM makes its layer's running-stat
+  // affine itself and the last block's GEMM ends in the deep head dot (no h_R),
+  // summed with zc + bf; else every layer's affine in one launch first
+  dcnr_status eval_epi() const {
+    const bool hp = pl.eval_headp;
+    if (!hp) {
+      BnEvalBatch eb;
+      memset(&eb, 0, sizeof(eb));
+      eb.n = 2 * d.R; eb.N = d.Hp; eb.Nr = d.H;
+      for (int j = 0; j < d.R; ++j) {
+        const auto& Bk = P.blk[j];
+        const BnBufs& b1 = L.bn[2 * j];
+        const BnBufs& b2 = L.bn[2 * j + 1];
+        eb.f[2 * j] = BnFinal{Bk.g1, Bk.be1, Bk.rm1, Bk.rv1, Bk.nbt1, b1.scale, b1.shift, b1.mean, b1.invstd};
+        eb.f[2 * j + 1] = BnFinal{Bk.g2, Bk.be2, Bk.rm2, Bk.rv2, Bk.nbt2, b2.scale, b2.shift, b2.mean, b2.invstd};
+      }
+      TRYP(DCNR_K_REDUCE, s, bn_eval_finalize(eb, s));
+    }
+    const int np = gemm_ws_head_parts(d.Hp);
+    for (int j = 0; j < d.R; ++j) {
+      const auto& Bk = P.blk[j];
+      const float* rs1[4] = {Bk.g1, Bk.be1, Bk.rm1, Bk.rv1};
+      const float* rs2[4] = {Bk.g2, Bk.be2, Bk.rm2, Bk.rv2};
+      const bool last = hp && j == d.R - 1;
+      TRYB(DCNR_K_GEMM_FWD, s, 2 * act_b(d, B) + w_b(d, d.Hp),
+           linear_bn_relu(d, L.h[j], L.W1p[j], L.b1p[j], L.bn[2 * j], nullptr, L.a1, B, s, hp ? rs1 : nullptr));
+      TRYB(DCNR_K_GEMM_FWD, s, (last ? 2 * act_b(d, B) + 4.0 * B * np : 3 * act_b(d, B)) + w_b(d, d.Hp),
+           linear_bn_relu(d, L.a1, L.W2p[j], L.b2p[j], L.bn[2 * j + 1], L.h[j], last ? nullptr : L.h[j + 1],
+                          B, s, hp ? rs2 : nullptr, last ? P.wf : nullptr, last ? L.headp : nullptr));
+    }
+    if (!hp) return unfused_head();
+    TRYB(DCNR_K_HEAD, s, (4.0 * np + 8.0) * B, head_parts(L.headp, np, L.zc, P.bf, B, logits, s));
+    return DCNR_OK;
+  }
+
+  dcnr_status unfused_head() const {
+    TRYB(DCNR_K_HEAD, s, act_b(d, B) + 4.0 * B, row_dot(d.prec, L.h[d.R], d.Hp, d.H, P.wf, B, L.zdeep, s));
+    TRYB(DCNR_K_HEAD, s, 12.0 * B, head_logits(L.zdeep, L.zc, P.bf, B, logits, s));
+    return DCNR_OK;
+  }
+
+  // t = A W^T + b and the BatchNorm of t (Plan::stats_epi: its column
+  // partials from the GEMM's epilogue, else from a pass over t)
+  dcnr_status linear_bn(const void* A, const void* W, const float* bias, void* t, const float* gamma,
+                        const float* beta, float* rm, float* rv, int64_t* nbt, const BnBufs& bn) const {
+    int nc = 0;
+    if (pl.stats_epi)
+      TRYB(DCNR_K_GEMM_FWD, s, 2 * act_b(d, B) + w_b(d, d.Hp),
+           linear_fwd_stats(d, L, A, d.Hp, W, d.Hp, bias, t, B, &nc, s));
+    else
+      TRYB(DCNR_K_GEMM_FWD, s, 2 * act_b(d, B) + w_b(d, d.Hp), linear_fwd(d, A, d.Hp, W, d.Hp, bias, t, B, s));
+    return bn_layer_fwd(desc, d, L, t, B, pl.train, gamma, beta, rm, rv, nbt, bn, s, nc,
+                        pl.stats_epi ? bias : nullptr);
+  }
+
+  // train, and eval without the epilogues: layer by layer
+  dcnr_status layers(uint64_t dropout_seed) const {
+    const bool train = pl.train;
+    const float p = train ? d.dropout : 0.f;
+    for (int j = 0; j < d.R; ++j) {
+      const auto& Bk = P.blk[j];
+      const BnBufs& bn1 = L.bn[2 * j];
+      const BnBufs& bn2 = L.bn[2 * j + 1];
+      TRY(linear_bn(L.h[j], L.W1p[j], L.b1p[j], L.t1[j], Bk.g1, Bk.be1, Bk.rm1, Bk.rv1, Bk.nbt1, bn1));
+      void* a1 = train ? L.a1s[j] : L.a1;
+      TRYB(DCNR_K_ROWWISE, s, 2 * act_b(d, B) + (train ? mask_b(d, B) : 0),
+           bn_relu_drop(d.prec, L.t1[j], a1, B, d.Hp, d.Hp, bn1.scale, bn1.shift, p, dropout_seed, j, s,
+                        L.mask_a1[j]));
+      TRY(linear_bn(a1, L.W2p[j], L.b2p[j], L.t2[j], Bk.g2, Bk.be2, Bk.rm2, Bk.rv2, Bk.nbt2, bn2));
+      if (j == d.R - 1 && pl.head_fused) {
+        // last block: residual + ReLU + deep head dot + logits in one pass
+        const bool store_hR = !pl.rebuild_hR || pl.keep;
+        TRYB(DCNR_K_ROWWISE, s, (store_hR ? 3 : 2) * act_b(d, B) + 12.0 * B,
+             bn_add_relu_head(d.prec, L.t2[j], L.h[j], store_hR ? L.h[j + 1] : nullptr, B, d.Hp, d.Hp,
+                              bn2.scale, bn2.shift, P.wf, d.H, L.zc, P.bf, logits, s, L.mask_h[d.R]));
+      } else {
+        const bool bits = train && j + 1 < d.R;
+        TRYB(DCNR_K_ROWWISE, s, 3 * act_b(d, B) + (bits ? mask_b(d, B) : 0),
+             bn_add_relu2(d.prec, L.t2[j], L.h[j], L.h[j + 1], B, d.Hp, d.Hp, bn2.scale, bn2.shift, s,
+                          bits ? L.mask_h[j + 1] : nullptr));
+      }
+    }
+    return pl.head_fused ? DCNR_OK : unfused_head();
+  }
+};
+
+// ------------------------------------------------------------ backward
+// One backward call's operands, what one residual block hands to the next
+// (the blocks run last to first), and a block's backward on either path.
+struct Bwd {
+  const dcnr_model_desc* desc; const Dims& d; const Plan& pl; const Layout& L;
+  const Params& P; const Grads& Gr;
+  int64_t B; const float* dz; uint64_t dropout_seed; int accumulate; hipStream_t s; DwPipe* pipe;
+  const void* Gin = nullptr;   // gradient wrt the current block's output (null: rank-1 dz * wf)
+  int nc_du = 0;               // > 0: this block's du and its BN2 partials were made by the previous dX GEMM
+  bool b0_done = false;        // the initial layer's bias gradient came with G (NT_EPI_RESID_SUM)
+
+  // dW2 = dt2^T a1 and dW1 = dt1^T h_j, enqueued where they are called
+  dcnr_status dw2(int j) const {
+    return linear_dw(d, L, L.dt2k[j], d.Hp, d.Hp, L.a1s[j], d.Hp, d.Hp, B, Gr.blk[j].w2, d.H, d.H, accumulate, s, pipe);
+  }
+  dcnr_status dw1(int j) const {
+    return linear_dw(d, L, L.dt1k[j], d.Hp, d.Hp, L.h[j], d.Hp, d.Hp, B, Gr.blk[j].w1, d.H, d.H, accumulate, s, pipe);
+  }
+  // the BN backward's reductions: dgamma, dbeta (+ dW_f[:H]) and the apply pass's coefficients
+  dcnr_status bn2_reduce(int j, int nc, int NK, float* dwf) const {
+    return bn_bwd_reduce(desc, d, L, nc, NK, B, P.blk[j].g2, L.bn[2 * j + 1].invstd, Gr.blk[j].g2,
+                         Gr.blk[j].be2, dwf, Gr.blk[j].b2, accumulate, s);
+  }
+  dcnr_status bn1_reduce(int j, int nc) const {
+    return bn_bwd_reduce(desc, d, L, nc, 2, B, P.blk[j].g1, L.bn[2 * j].invstd, Gr.blk[j].g1, Gr.blk[j].be1,
+                         nullptr, Gr.blk[j].b1, accumulate, s);
+  }
+
+  // out = relu(BN2(t2) + h_j): du = g * [out > 0], then the BN2 apply that
+  // makes dt2 unless `fold` leaves it to the dX GEMM (last block with
+  // Plan::rank1: from the head pass's [h_R > 0] bits instead of du)
+  dcnr_status bn2_backward(int j, bool fold) {
+    const BnBufs& bn2 = L.bn[2 * j + 1];
+    const bool last = !Gin && j == d.R - 1;
+    int nc = 0;
+    if (nc_du) {   // du and its partials came with the previous block's dX GEMM
+      TRY(bn2_reduce(j, nc_du, 2, nullptr));
+    } else {
+      TRYB(DCNR_K_ROWWISE, s, 3 * act_b(d, B) + (Gin ? act_b(d, B) : 4.0 * B),
+           bwd_bn2_stats3(d.prec, Gin, dz, P.wf, L.h[j + 1], L.t2[j], bn2.mean, bn2.invstd, B, d.Hp, d.Hp,
+                          L.duk[j], L.part, &nc, s, last && pl.rebuild_hR ? L.h[j] : nullptr, bn2.scale,
+                          bn2.shift));
+      // dbeta2, dgamma2 and (last block only) dW_f[:H]
+      TRY(bn2_reduce(j, nc, 3, Gin ? nullptr : Gr.wf));
+    }
+    if (last && pl.rank1)
+      TRYB(DCNR_K_ROWWISE, s, 2 * act_b(d, B) + mask_b(d, B) + 4.0 * B,
+           bwd_bn2_apply_rank1(L.mask_h[d.R], dz, P.wf, L.t2[j], bn2.mean, bn2.invstd, L.coef, B, d.Hp, d.Hp,
+                               L.dt2k[j], s));
+    else if (!fold)
+      TRYB(DCNR_K_ROWWISE, s, 3 * act_b(d, B),
+           bwd_bn2_apply2(d.prec, L.duk[j], L.t2[j], bn2.mean, bn2.invstd, L.coef, B, d.Hp, d.Hp, L.dt2k[j],
+                          L.part, &nc, s));
+    return DCNR_OK;
+  }
+
+  // One block with plain GEMMs and row passes (fp32, or bf16 where the GEMM
+  // epilogues do not apply), in launch order.
+  dcnr_status block_plain(int j) {
+    const BnBufs& bn1 = L.bn[2 * j];
+    void *da = L.dak[j], *dt1 = L.dt1k[j];
+    int nc = 0;
+    TRY(bn2_backward(j, false));
+    // ---- layer2: dW2 = dt2^T a1 ; da = dt2 W2
+    TRY(dw2(j));
+    TRY(linear_dx(d, L.dt2k[j], L.W2t[j], nullptr, da, B, s));
+    // ---- relu/dropout + BN1 backward
+    TRYB(DCNR_K_ROWWISE, s, 3 * act_b(d, B),
+         bwd_bn1_stats(d.prec, da, L.t1[j], bn1.scale, bn1.shift, bn1.mean, bn1.invstd, B, d.Hp, d.Hp,
+                       d.dropout, dropout_seed, j, L.part, &nc, s));
+    TRY(bn1_reduce(j, nc));
+    TRYB(DCNR_K_ROWWISE, s, 3 * act_b(d, B),
+         bwd_bn1_apply2(d.prec, da, L.t1[j], bn1.mean, bn1.invstd, L.coef, B, d.Hp, d.Hp, dt1, L.part, &nc, s));
+    // ---- layer1: dW1 = dt1^T h_j ; G = dt1 W1 + du
+    TRY(dw1(j));
+    TRY(linear_dx(d, dt1, L.W1t[j], L.duk[j], L.G, B, s));
+    Gin = L.G;
+    return DCNR_OK;
+  }
+
+  // One block through the dX GEMM epilogues (keep masks instead of
+  // activations, BN partials from the GEMMs), in launch order.  xbn: the BN
+  // backward's row passes are folded into those GEMMs as well -- a GEMM then
+  // takes du / da and makes dt2 / dt1 itself, and the weight gradient that
+  // reads that dt follows the GEMM instead of preceding it.
+  dcnr_status block_epi(int j, bool xbn) {
+    const BnBufs& bn1 = L.bn[2 * j];
+    const BnBufs& bn2 = L.bn[2 * j + 1];
+    void *du = L.duk[j], *dt2 = L.dt2k[j], *da = L.dak[j], *dt1 = L.dt1k[j];
+    int nc = 0;
+    const bool xbn2 = xbn && !(j == d.R - 1 && pl.rank1);   // the BN2 apply folded into the DROP_BN GEMM
+    TRY(bn2_backward(j, xbn2));
+    // ---- layer2: dW2 = dt2^T a1 ; dy1 = (dt2 W2) * [a1 != 0] / (1-p): relu and
+    // dropout masks from the saved activation's bits, BN1 partials in the same pass
+    if (!xbn2) TRY(dw2(j));
+    const XbnOperand xo2{L.t2[j], &bn2, dt2};
+    TRYB(DCNR_K_GEMM_DX, s, (xbn2 ? 5 : 3) * act_b(d, B) + mask_b(d, B) + w_b(d, d.Hp),
+         linear_dx_bn(d, L, NT_EPI_DROP_BN, xbn2 ? du : dt2, L.W2t[j], nullptr, da, L.mask_a1[j],
+                      d.dropout > 0.f ? 1.f / (1.f - d.dropout) : 1.f, L.t1[j], bn1, B, &nc, s,
+                      xbn2 ? &xo2 : nullptr));
+    if (xbn2) TRY(dw2(j));
+    TRY(bn1_reduce(j, nc));   // ---- BN1 backward
+    if (!xbn) {
+      TRYB(DCNR_K_ROWWISE, s, 3 * act_b(d, B),
+           bwd_bn1_apply2(d.prec, da, L.t1[j], bn1.mean, bn1.invstd, L.coef, B, d.Hp, d.Hp, dt1, L.part, &nc, s));
+      TRY(dw1(j));
+    }
+    // ---- layer1: dW1 = dt1^T h_j ; G = dt1 W1 + du
+    const XbnOperand xo1{L.t1[j], &bn1, dt1};
+    if (j > 0) {
+      // G is only consumed by block j-1's BN2 backward: emit its du = G * [h_j > 0]
+      // (in place over this block's du, the residual operand, unless
+      // KEEP_INTERMEDIATES) and the partials
+      TRYB(DCNR_K_GEMM_DX, s, (xbn ? 6 : 4) * act_b(d, B) + mask_b(d, B) + w_b(d, d.Hp),
+           linear_dx_bn(d, L, NT_EPI_RESID_BN, xbn ? da : dt1, L.W1t[j], du, L.duk[j - 1], L.mask_h[j], 1.f,
+                        L.t2[j - 1], L.bn[2 * (j - 1) + 1], B, &nc_du, s, xbn ? &xo1 : nullptr));
+      if (xbn) TRY(dw1(j));
+      Gin = L.duk[j - 1];
+      return DCNR_OK;
+    }
+    if (xbn) {
+      // block 0: G's column sums (the initial layer's bias gradient) in the
+      // epilogue, which reads no mask and no BN input
+      int ncg = 0;
+      TRYB(DCNR_K_GEMM_DX, s, 5 * act_b(d, B) + w_b(d, d.Hp),
+           linear_dx_bn(d, L, NT_EPI_RESID_SUM, da, L.W1t[j], du, L.G, nullptr, 0.f, nullptr, BnBufs{}, B,
+                        &ncg, s, &xo1));
+      TRY(dw1(j));
+      TRY(bias_reduce(d, L, ncg, Gr.b0, accumulate, s, 2));
+      b0_done = true;
+    } else {
+      TRY(linear_dx(d, dt1, L.W1t[j], du, L.G, B, s));
+    }
+    Gin = L.G;
+    nc_du = 0;
+    return DCNR_OK;
+  }
+};
 
 }  // namespace
 }  // namespace dcnr
@@ -961,7 +1293,7 @@ dcnr_status dcnr_workspace_size(const dcnr_model_desc* desc, int64_t B, int mode
   Dims d;
   TRY(make_dims(desc, &d));
   if (!bytes || B < 0) { set_error("bad args"); return DCNR_BAD_ARG; }
-  *bytes = make_layout(d, B, mode, nullptr, desc->flags).total;
+  *bytes = make_layout(d, B, make_plan(d, desc->flags, mode, B), nullptr).total;
   return DCNR_OK;
 }
 
@@ -973,8 +1305,7 @@ dcnr_status dcnr_workspace_offset(const dcnr_model_desc* desc, int64_t B, int mo
   // a null base yields offsets as pointers from 0 (Bump takes nullptr -> nullptr),
   // so lay out against a fake non-null base
   char* base = (char*)(uintptr_t)4096;
-  Layout L = make_layout(d, B, mode, base, desc->flags);
-  const bool train = mode == DCNR_TRAIN;
+  Layout L = make_layout(d, B, make_plan(d, desc->flags, mode, B), base);
   const int R = d.R;
   auto blk = [&](int n) { return index >= 0 && index < n; };
   const void* p = nullptr;
@@ -983,22 +1314,22 @@ dcnr_status dcnr_workspace_offset(const dcnr_model_desc* desc, int64_t B, int mo
     case DCNR_WS_H: if (blk(R + 1)) p = L.h[index]; break;
     case DCNR_WS_T1: if (blk(R)) p = L.t1[index]; break;
     case DCNR_WS_T2: if (blk(R)) p = L.t2[index]; break;
-    case DCNR_WS_A1: if (blk(R) && train) p = L.a1s[index]; break;
+    case DCNR_WS_A1: if (blk(R)) p = L.a1s[index]; break;
     case DCNR_WS_MASK_A1: if (blk(R)) p = L.mask_a1[index]; break;
     case DCNR_WS_MASK_H: if (blk(R)) p = L.mask_h[index]; break;
     case DCNR_WS_BN_MEAN: if (blk(2 * R)) p = L.bn[index].mean; break;
     case DCNR_WS_BN_INVSTD: if (blk(2 * R)) p = L.bn[index].invstd; break;
     case DCNR_WS_BN_SCALE: if (blk(2 * R)) p = L.bn[index].scale; break;
     case DCNR_WS_BN_SHIFT: if (blk(2 * R)) p = L.bn[index].shift; break;
-    case DCNR_WS_DU: if (blk(R) && train) p = L.duk[index]; break;
-    case DCNR_WS_DT2: if (blk(R) && train) p = L.dt2k[index]; break;
-    case DCNR_WS_DA: if (blk(R) && train) p = L.dak[index]; break;
-    case DCNR_WS_DT1: if (blk(R) && train) p = L.dt1k[index]; break;
-    case DCNR_WS_G: if (train) p = L.G; break;
-    case DCNR_WS_DX0: if (train) p = L.dx0; break;
+    case DCNR_WS_DU: if (blk(R)) p = L.duk[index]; break;
+    case DCNR_WS_DT2: if (blk(R)) p = L.dt2k[index]; break;
+    case DCNR_WS_DA: if (blk(R)) p = L.dak[index]; break;
+    case DCNR_WS_DT1: if (blk(R)) p = L.dt1k[index]; break;
+    case DCNR_WS_G: p = L.G; break;
+    case DCNR_WS_DX0: p = L.dx0; break;
     case DCNR_WS_ZC: p = L.zc; break;
-    case DCNR_WS_XCOEF: if (train) p = L.xcoef; break;
-    case DCNR_WS_SC: if (train) p = L.sc; break;
+    case DCNR_WS_XCOEF: p = L.xcoef; break;
+    case DCNR_WS_SC: p = L.sc; break;
     case DCNR_WS_ROW_MAP: p = L.rowmap; break;
   }
   *offset = p ? (int64_t)((const char*)p - base) : -1;
@@ -1029,210 +1360,47 @@ dcnr_status dcnr_gather_cross(const dcnr_model_desc* desc, void* const* params,
   CrossParams cp = make_cross(d, P);
   const GcOut o{cross_out, x0, nullptr, (int)ld_cross, (int)ld_x0};
   const int check = oob_flag != nullptr;
-  TRYB(DCNR_K_GATHER_CROSS, (double)B * (gather_row_b(d, desc->n_num) + 4.0 * d.D * ((x0 ? 1 : 0) + (cross_out ? 1 : 0))),
+  TRYB(DCNR_K_GATHER_CROSS, s, (double)B * (gather_row_b(d, desc->n_num) + 4.0 * d.D * ((x0 ? 1 : 0) + (cross_out ? 1 : 0))),
        gather_cross_out(g, cp, user_ids, item_ids, cat_features, num_features, B, o, 0, oob_flag, check, s));
   return DCNR_OK;
 }
-
-static dcnr_status forward_body(const dcnr_model_desc* desc, void* const* params,
-                                const int64_t* user_ids, const int64_t* item_ids,
-                                const int64_t* cat_features, const float* num_features, int64_t B,
-                                int mode, uint64_t dropout_seed, float* logits, void* ws,
-                                size_t ws_bytes, dcnr_stream_t stream, bool* mirrored);
 
 dcnr_status dcnr_forward(const dcnr_model_desc* desc, void* const* params,
                          const int64_t* user_ids, const int64_t* item_ids,
                          const int64_t* cat_features, const float* num_features, int64_t B,
                          int mode, uint64_t dropout_seed, float* logits, void* ws,
                          size_t ws_bytes, dcnr_stream_t stream) {
-  bool mirrored = false;
-  TRY(forward_body(desc, params, user_ids, item_ids, cat_features, num_features, B, mode, dropout_seed,
-                   logits, ws, ws_bytes, stream, &mirrored));
-  // the id-check word to the caller's mirror (the fused eval tower stores it
-  // itself); after the forward's last kernel on the stream
-  if (B > 0 && !mirrored && desc->error_mirror && (desc->flags & DCNR_FLAG_CHECK_INDICES)) {
-    hipStream_t s = (hipStream_t)stream;
-    TRYP(DCNR_K_PACK, mirror_word((const int*)ws, desc->error_mirror, s));
-  }
-  return DCNR_OK;
-}
-
-static dcnr_status forward_body(const dcnr_model_desc* desc, void* const* params,
-                                const int64_t* user_ids, const int64_t* item_ids,
-                                const int64_t* cat_features, const float* num_features, int64_t B,
-                                int mode, uint64_t dropout_seed, float* logits, void* ws,
-                                size_t ws_bytes, dcnr_stream_t stream, bool* mirrored) {
   Dims d;
   TRY(make_dims(desc, &d));
   hipStream_t s = (hipStream_t)stream;
-  const bool train = mode == DCNR_TRAIN;
   if (!params || !logits || !ws || B < 0 || (B > 0 && (!user_ids || !item_ids)) ||
       (d.K > 0 && B > 0 && !cat_features) || (desc->n_num > 0 && B > 0 && !num_features)) {
     set_error("dcnr_forward: null argument");
     return DCNR_BAD_ARG;
   }
-  if (train && B < 2) {
+  if (mode == DCNR_TRAIN && B < 2) {
     set_error("Expected more than 1 value per channel when training");
     return DCNR_BAD_ARG;
   }
-  Layout L = make_layout(d, B, mode, ws, desc->flags);
+  const Plan pl = make_plan(d, desc->flags, mode, B);
+  const Layout L = make_layout(d, B, pl, ws);
   if (ws_bytes < L.total) {
     set_error("workspace too small: %zu < %zu", ws_bytes, L.total);
     return DCNR_WORKSPACE_TOO_SMALL;
   }
   if (B == 0) return DCNR_OK;
-  Params P = map_params(d, params);
+  const Params P = map_params(d, params);
   const int check = (desc->flags & DCNR_FLAG_CHECK_INDICES) ? 1 : 0;
-  GatherDesc g = make_gather(d, P, desc->n_num);
-  CrossParams cp = make_cross(d, P);
-  // Train: the weight packing (bf16 copies + transposes of the deep tower's
-  // weights) is not read by the gather/cross kernel, so it runs on the side
-  // stream under it and the first GEMM waits for it alone (same box, two
-  // runs each: 4.033 / 4.045 vs 4.071 / 4.055 ms/step, DESIGN.md; eval keeps it on the
-  // stream: its fork/join cost ~1 % of the eval forward). The embedding
-  // backward's id sort needs the ids alone, so it follows there, under this
-  // forward (joined before returning, so the caller's id tensors are free to
-  // go once the forward's work is done).
-  if (L.twp) {
-    // eval: gather + cross (x0 bf16, zc) -> the fused deep tower + head
-    TowerPack tp;
-    memset(&tp, 0, sizeof(tp));
-    tp.W0 = P.W0; tp.D = d.D; tp.b0 = P.b0;
-    for (int j = 0; j < d.R; ++j) {
-      const auto& Bk = P.blk[j];
-      tp.w1[j] = Bk.w1; tp.b1[j] = Bk.b1; tp.g1[j] = Bk.g1; tp.be1[j] = Bk.be1; tp.rm1[j] = Bk.rm1; tp.rv1[j] = Bk.rv1;
-      tp.w2[j] = Bk.w2; tp.b2[j] = Bk.b2; tp.g2[j] = Bk.g2; tp.be2[j] = Bk.be2; tp.rm2[j] = Bk.rm2; tp.rv2[j] = Bk.rv2;
-    }
-    tp.wf = P.wf; tp.H = d.H; tp.R = d.R; tp.out = L.twp; tp.err = check ? L.err : nullptr;
-    TRYP(DCNR_K_PACK, tower_pack(tp, s));
-    const GcOut o{nullptr, L.x0, L.zc, 0, d.Dp, nullptr};
-    TRYB(DCNR_K_GATHER_CROSS, (double)B * (gather_row_b(d, desc->n_num) + (double)d.Dp * d.es + 4.0),
-         gather_cross_out(g, cp, user_ids, item_ids, cat_features, num_features, B, o, 1, L.err, check, s));
-    TowerArgs ta;
-    memset(&ta, 0, sizeof(ta));
-    ta.x0 = (const bf16*)L.x0; ta.ldx = d.Dp; ta.M = B; ta.Dp = d.Dp; ta.H = d.H; ta.R = d.R;
-    ta.wp = L.twp; ta.zc = L.zc; ta.bias = P.bf; ta.logits = logits;
-    ta.err = L.err;
-    ta.err_mirror = check ? desc->error_mirror : nullptr;
-    *mirrored = true;
-    // algorithmic bytes: the x0 rows + zc in, the logits out (the packed
-    // weights are L2-resident: every CU streams the same 4.7 MB)
-    TRYB(DCNR_K_TOWER, (double)B * (d.Dp * d.es + 8.0), eval_tower(ta, s));
-    return DCNR_OK;
-  }
+  const Fwd f{desc, d, pl, L, P, user_ids, item_ids, cat_features, num_features, B, logits, s, check,
+              make_gather(d, P, desc->n_num), make_cross(d, P)};
+  if (pl.tower) return f.tower();
   SideJoin sj;
-  if (train) {
-    TRY(sj.fork(s));
-    hipStream_t s = sj.side;
-    TRY(pack_all(d, P, L, train, s));
-    TRY(sj.mark());
-  } else {
-    TRY(pack_all(d, P, L, train, s, check != 0));
-  }
-  // (train: the pack runs on the side stream beside the gather, so the
-  // error word is zeroed here, before it)
-  if (check && train) TRYP(DCNR_K_PACK, fill_zero(L.err, 4, s));
-  if (train) {
-    EmbBwdDesc eb;
-    memset(&eb, 0, sizeof(eb));
-    eb.n_tab = g.n_tab;
-    for (int t = 0; t < g.n_tab; ++t) { eb.rows[t] = g.rows[t]; eb.width[t] = g.width[t]; }
-    hipStream_t s = sj.side;   // TRYB launches and times on the side stream
-    TRYB(DCNR_K_EMB_SORT, 2.0 * 8.0 * g.n_tab * B + 8.0 * B * (2 + d.K) + 4.0 * B * 2,
-         emb_sort(eb, user_ids, item_ids, cat_features, B, L.emb, s));
-    TRY(sj.record());
-  }
-  {
-    const GcOut o{nullptr, L.x0, L.zc, 0, d.Dp, train ? L.sc : nullptr};
-    TRYB(DCNR_K_GATHER_CROSS, (double)B * (gather_row_b(d, desc->n_num) + (double)d.Dp * d.es + 4.0),
-         gather_cross_out(g, cp, user_ids, item_ids, cat_features, num_features, B, o,
-                          d.prec == DCNR_PREC_BF16, L.err, check, s));
-  }
-  if (train) TRY(sj.wait_mark(s));   // packed weights, biases, zeroed reduction counters
-  TRYB(DCNR_K_GEMM_FWD, (double)B * d.Dp * d.es + act_b(d, B) + w_b(d, d.Dp),
-       linear_fwd(d, L.x0, d.Dp, L.W0p, d.Dp, L.b0p, L.h[0], B, s));
-  if (!train && eval_fuse_ok(d)) {
-    if (L.headp) {
-      // each GEMM makes its layer's running-stat affine itself; the last
-      // block's GEMM ends in the deep head dot (no h_R), summed with zc + bf
-      for (int j = 0; j < d.R; ++j) {
-        const auto& Bk = P.blk[j];
-        const float* rs1[4] = {Bk.g1, Bk.be1, Bk.rm1, Bk.rv1};
-        const float* rs2[4] = {Bk.g2, Bk.be2, Bk.rm2, Bk.rv2};
-        const bool last = j == d.R - 1;
-        TRYB(DCNR_K_GEMM_FWD, 2 * act_b(d, B) + w_b(d, d.Hp),
-             linear_bn_relu(d, L.h[j], L.W1p[j], L.b1p[j], L.bn[2 * j], nullptr, L.a1, B, s, rs1));
-        TRYB(DCNR_K_GEMM_FWD, (last ? 2 * act_b(d, B) + 4.0 * B * gemm_ws_head_parts(d.Hp) : 3 * act_b(d, B)) + w_b(d, d.Hp),
-             linear_bn_relu(d, L.a1, L.W2p[j], L.b2p[j], L.bn[2 * j + 1], L.h[j], last ? nullptr : L.h[j + 1],
-                            B, s, rs2, last ? P.wf : nullptr, last ? L.headp : nullptr));
-      }
-      const int np = gemm_ws_head_parts(d.Hp);
-      TRYB(DCNR_K_HEAD, (4.0 * np + 8.0) * B, head_parts(L.headp, np, L.zc, P.bf, B, logits, s));
-      return DCNR_OK;
-    }
-    // every layer's running-stat affine in one launch
-    BnEvalBatch eb;
-    memset(&eb, 0, sizeof(eb));
-    eb.n = 2 * d.R; eb.N = d.Hp; eb.Nr = d.H;
-    for (int j = 0; j < d.R; ++j) {
-      const auto& Bk = P.blk[j];
-      const BnBufs& b1 = L.bn[2 * j];
-      const BnBufs& b2 = L.bn[2 * j + 1];
-      eb.f[2 * j] = BnFinal{Bk.g1, Bk.be1, Bk.rm1, Bk.rv1, Bk.nbt1, b1.scale, b1.shift, b1.mean, b1.invstd};
-      eb.f[2 * j + 1] = BnFinal{Bk.g2, Bk.be2, Bk.rm2, Bk.rv2, Bk.nbt2, b2.scale, b2.shift, b2.mean, b2.invstd};
-    }
-    TRYP(DCNR_K_REDUCE, bn_eval_finalize(eb, s));
-    for (int j = 0; j < d.R; ++j) {
-      TRYB(DCNR_K_GEMM_FWD, 2 * act_b(d, B) + w_b(d, d.Hp),
-           linear_bn_relu(d, L.h[j], L.W1p[j], L.b1p[j], L.bn[2 * j], nullptr, L.a1, B, s));
-      TRYB(DCNR_K_GEMM_FWD, 3 * act_b(d, B) + w_b(d, d.Hp),
-           linear_bn_relu(d, L.a1, L.W2p[j], L.b2p[j], L.bn[2 * j + 1], L.h[j], L.h[j + 1], B, s));
-    }
-    TRYB(DCNR_K_HEAD, act_b(d, B) + 4.0 * B, row_dot(d.prec, L.h[d.R], d.Hp, d.H, P.wf, B, L.zdeep, s));
-    TRYB(DCNR_K_HEAD, 12.0 * B, head_logits(L.zdeep, L.zc, P.bf, B, logits, s));
-    return DCNR_OK;   // (eval: nothing forked)
-  }
-  const float p = train ? d.dropout : 0.f;
-  for (int j = 0; j < d.R; ++j) {
-    const auto& Bk = P.blk[j];
-    const bool fuse = train && epi_stats_ok(d);   // BN partials from the GEMM epilogue
-    int nc = 0;
-    if (fuse)
-      TRYB(DCNR_K_GEMM_FWD, 2 * act_b(d, B) + w_b(d, d.Hp),
-           linear_fwd_stats(d, L, L.h[j], d.Hp, L.W1p[j], d.Hp, L.b1p[j], L.t1[j], B, &nc, s));
-    else
-      TRYB(DCNR_K_GEMM_FWD, 2 * act_b(d, B) + w_b(d, d.Hp),
-           linear_fwd(d, L.h[j], d.Hp, L.W1p[j], d.Hp, L.b1p[j], L.t1[j], B, s));
-    TRY(bn_layer_fwd(desc, d, L, L.t1[j], B, train, Bk.g1, Bk.be1, Bk.rm1, Bk.rv1, Bk.nbt1,
-                     L.bn[2 * j], s, nc, fuse ? L.b1p[j] : nullptr));
-    void* a1 = train ? L.a1s[j] : L.a1;
-    TRYB(DCNR_K_ROWWISE, 2 * act_b(d, B) + (train ? mask_b(d, B) : 0), bn_relu_drop(d.prec, L.t1[j], a1, B, d.Hp, d.Hp, L.bn[2 * j].scale, L.bn[2 * j].shift, p,
-                     dropout_seed, j, s, train ? L.mask_a1[j] : nullptr));
-    if (fuse)
-      TRYB(DCNR_K_GEMM_FWD, 2 * act_b(d, B) + w_b(d, d.Hp),
-           linear_fwd_stats(d, L, a1, d.Hp, L.W2p[j], d.Hp, L.b2p[j], L.t2[j], B, &nc, s));
-    else
-      TRYB(DCNR_K_GEMM_FWD, 2 * act_b(d, B) + w_b(d, d.Hp),
-           linear_fwd(d, a1, d.Hp, L.W2p[j], d.Hp, L.b2p[j], L.t2[j], B, s));
-    TRY(bn_layer_fwd(desc, d, L, L.t2[j], B, train, Bk.g2, Bk.be2, Bk.rm2, Bk.rv2, Bk.nbt2,
-                     L.bn[2 * j + 1], s, nc, fuse ? L.b2p[j] : nullptr));
-    const bool head = j == d.R - 1 && bn_add_relu_head_supported(d.prec, d.Hp);
-    if (head)   // last block: residual + ReLU + deep head dot + logits in one pass
-      TRYB(DCNR_K_ROWWISE, (head_rebuild(d, train) && !keep_of(desc) ? 2 : 3) * act_b(d, B) + 12.0 * B,
-           bn_add_relu_head(d.prec, L.t2[j], L.h[j],
-                            head_rebuild(d, train) && !keep_of(desc) ? nullptr : L.h[j + 1], B, d.Hp, d.Hp,
-                                            L.bn[2 * j + 1].scale, L.bn[2 * j + 1].shift, P.wf,
-                                            d.H, L.zc, P.bf, logits, s, train ? L.mask_h[d.R] : nullptr));
-    else
-      TRYB(DCNR_K_ROWWISE, 3 * act_b(d, B) + (train && j + 1 < d.R ? mask_b(d, B) : 0), bn_add_relu2(d.prec, L.t2[j], L.h[j], L.h[j + 1], B, d.Hp, d.Hp,
-                                        L.bn[2 * j + 1].scale, L.bn[2 * j + 1].shift, s,
-                                        train && j + 1 < d.R ? L.mask_h[j + 1] : nullptr));
-  }
-  if (!bn_add_relu_head_supported(d.prec, d.Hp)) {
-    TRYB(DCNR_K_HEAD, act_b(d, B) + 4.0 * B, row_dot(d.prec, L.h[d.R], d.Hp, d.H, P.wf, B, L.zdeep, s));
-    TRYB(DCNR_K_HEAD, 12.0 * B, head_logits(L.zdeep, L.zc, P.bf, B, logits, s));
-  }
-  if (train) TRY(sj.join(s));   // the sorted ids (workspace) for dcnr_backward
+  TRY(f.front(sj));
+  TRY(pl.eval_epi ? f.eval_epi() : f.layers(dropout_seed));
+  if (pl.train) TRY(sj.join(s));   // the sorted ids (workspace) for dcnr_backward
+  // the id-check word to the caller's mirror, after the forward's last kernel
+  // on the stream
+  if (desc->error_mirror && check) TRYP(DCNR_K_PACK, s, mirror_word((const int*)ws, desc->error_mirror, s));
   return DCNR_OK;
 }
 
@@ -1248,18 +1416,16 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
     set_error("dcnr_backward: bad argument");
     return DCNR_BAD_ARG;
   }
-  Layout L = make_layout(d, B, DCNR_TRAIN, ws, desc->flags);
+  const Plan pl = make_plan(d, desc->flags, DCNR_TRAIN, B);
+  const Layout L = make_layout(d, B, pl, ws);
   if (ws_bytes < L.total) {
     set_error("workspace too small: %zu < %zu", ws_bytes, L.total);
     return DCNR_WORKSPACE_TOO_SMALL;
   }
-  Params P = map_params(d, params);
-  Grads Gr = map_grads(d, grads);
-  const float* dz = dlogits;
+  const Params P = map_params(d, params);
+  const Grads Gr = map_grads(d, grads);
   const int Hp = d.Hp, H = d.H;
-  const float p = d.dropout;
-  const bool rowmap = (desc->flags & DCNR_FLAG_ROW_MAP) != 0;
-  if (rowmap && (accumulate || !L.rowmap)) {
+  if (pl.rowmap && accumulate) {
     set_error("dcnr_backward: DCNR_FLAG_ROW_MAP needs accumulate = 0");
     return DCNR_BAD_ARG;
   }
@@ -1268,15 +1434,15 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
   // tower instead: 3.99-4.00 vs 3.98-3.99 ms/step, same box; kept here.)
   // DCNR_FLAG_ROW_MAP: only the row map is zeroed; the sums mark the rows
   // they write and the optimizer reads unmarked rows as 0.
-  if (rowmap) {
-    TRYB(DCNR_K_PACK, (double)L.rowmap_bytes, fill_zero(L.rowmap, L.rowmap_bytes, s));
+  if (pl.rowmap) {
+    TRYB(DCNR_K_PACK, s, (double)L.rowmap_bytes, fill_zero(L.rowmap, L.rowmap_bytes, s));
   } else if (!accumulate) {
     void* zp[2 + MAX_CAT];
     int64_t zn[2 + MAX_CAT];
     for (int t = 0; t < 2 + d.K; ++t) { zp[t] = Gr.tab[t]; zn[t] = d.rows[t] * d.widths[t] * 4; }
     double zb = 0;
     for (int t = 0; t < 2 + d.K; ++t) zb += (double)zn[t];
-    TRYB(DCNR_K_PACK, zb, fill_zero_multi(2 + d.K, zp, zn, s));
+    TRYB(DCNR_K_PACK, s, zb, fill_zero_multi(2 + d.K, zp, zn, s));
   }
 
   // embedding backward, part 1 (the stable sort of the (table row, sample)
@@ -1285,7 +1451,7 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
   EmbBwdDesc eb;
   memset(&eb, 0, sizeof(eb));
   eb.n_tab = g.n_tab;
-  eb.touched = rowmap ? L.rowmap : nullptr;
+  eb.touched = L.rowmap;   // (null without DCNR_FLAG_ROW_MAP)
   for (int t = 0; t < g.n_tab; ++t) {
     eb.grad[t] = Gr.tab[t]; eb.rows[t] = g.rows[t]; eb.width[t] = g.width[t]; eb.off[t] = g.off[t];
   }
@@ -1295,8 +1461,6 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
   SideJoin sj;
   TRY(sj.fork(s));
   const CrossParams cpx = make_cross(d, P);
-  {
-  hipStream_t s = sj.side;   // TRYB launches and times on the side stream
   // ---- cross network + head bias (low-rank form, from the forward's
   // per-sample scalars, dz and the stored x0 alone; cross_bwd.hip)
   CrossGrads cg;
@@ -1304,138 +1468,22 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
   for (int l = 0; l < d.L; ++l) { cg.dw[l] = Gr.cw[l]; cg.db[l] = Gr.cb[l]; }
   cg.dwf_cross = Gr.wf + H;
   cg.dbf = Gr.bf;
-  TRYB(DCNR_K_CROSS_BWD, (double)B * (4.0 * (2 * d.L + 1) + 4.0 + 8.0 * (d.L + 1)) +
-                             (double)B * d.Dp * d.es,
-       cross_backward(cpx, d.D, L.sc, dz, L.x0, d.prec == DCNR_PREC_BF16, d.Dp, B, cg, L.xcoef,
-                      L.xalpha, L.cscratch, L.cscratch_bytes, accumulate, s));
-  }
+  TRYB(DCNR_K_CROSS_BWD, sj.side, (double)B * (4.0 * (2 * d.L + 1) + 4.0 + 8.0 * (d.L + 1)) + (double)B * d.Dp * d.es,
+       cross_backward(cpx, d.D, L.sc, dlogits, L.x0, d.prec == DCNR_PREC_BF16, d.Dp, B, cg, L.xcoef,
+                      L.xalpha, L.cscratch, L.cscratch_bytes, accumulate, sj.side));
   TRY(sj.record());
   DwPipe dwp;
   DwPipe* pipe = nullptr;
-  // (not while kernel classes are being timed: there every launch is priced
-  // alone, on the main stream, as before the overlap -- except in profile
-  // mode 2, which times the side stream's gemm_dw launches in place)
+  // (a run-time choice, not a plan field: not while kernel classes are being
+  // timed, where every launch is priced alone, on the main stream -- except
+  // in profile mode 2, which times the side stream's gemm_dw launches in place)
   if (d.prec == DCNR_PREC_BF16 && (!g_prof || g_prof_mode == 2)) {
-    // with a dt2 / dt1 set per block the main stream never waits for the
-    // side stream before the join (one shared set: after the previous call)
-    TRY(dwp.init(sj.side, keep_of(desc) || L.dt2b ? 1 << 30 : 1));
+    TRY(dwp.init(sj.side, pl.dw_lag));
     pipe = &dwp;
   }
 
-  const void* Gin = nullptr;  // gradient wrt the current block output (null: rank-1 dz*wf)
-  const bool fuse = epi_stats_ok(d);   // BN partials from the dX GEMM epilogues
-  // the BN backward's row passes folded into those GEMMs (bf16, K = Hp in (256, 512])
-  const bool xbn_ok = fuse && d.prec == DCNR_PREC_BF16 && gemm_ws_xbn_supported(NT_EPI_DROP_BN, d.Hp, d.Hp);
-  int nc_du = 0;   // > 0: L.du and its BN2 partials were made by the previous dX GEMM
-  bool b0_done = false;   // the initial layer's bias gradient came with G (NT_EPI_RESID_SUM)
-  for (int j = d.R - 1; j >= 0; --j) {
-    const auto& Bk = P.blk[j];
-    auto& Gk = Gr.blk[j];
-    const BnBufs& bn1 = L.bn[2 * j];
-    const BnBufs& bn2 = L.bn[2 * j + 1];
-    int nc = 0;
-    // this block's backward buffers (one shared set unless KEEP_INTERMEDIATES)
-    void* du = L.duk[j];
-    void* dt2 = L.dt2k[j];
-    void* da = L.dak[j];
-    void* dt1 = L.dt1k[j];
-    // ---- out = relu(BN2(t2) + h_j):  du, BN2 backward
-    if (nc_du) {
-      TRY(bn_bwd_reduce(desc, d, L, nc_du, 2, B, Bk.g2, bn2.invstd, Gk.g2, Gk.be2, nullptr,
-                        Gk.b2, accumulate, s));
-    } else {
-      const bool rebuild = !Gin && j == d.R - 1 && head_rebuild(d, true);
-      TRYB(DCNR_K_ROWWISE, 3 * act_b(d, B) + (Gin ? act_b(d, B) : 4.0 * B), bwd_bn2_stats3(d.prec, Gin, dz, P.wf, L.h[j + 1], L.t2[j], bn2.mean,
-                                          bn2.invstd, B, Hp, Hp, du, L.part, &nc, s,
-                                          rebuild ? L.h[j] : nullptr, bn2.scale, bn2.shift));
-      // dbeta2, dgamma2 and (last block only) dW_f[:H]
-      TRY(bn_bwd_reduce(desc, d, L, nc, 3, B, Bk.g2, bn2.invstd, Gk.g2, Gk.be2,
-                        Gin ? nullptr : Gr.wf, Gk.b2, accumulate, s));
-    }
-    const bool rank1 = !Gin && j == d.R - 1 && L.mask_h[d.R] && d.prec == DCNR_PREC_BF16;
-    // the BN2 backward's row pass folded into the DROP_BN dX GEMM (du and t2
-    // in, dt2 out for dW2) where that GEMM runs the fused epilogue
-    const bool xbn2 = fuse && !rank1 && xbn_ok;
-    if (rank1)
-      TRYB(DCNR_K_ROWWISE, 2 * act_b(d, B) + mask_b(d, B) + 4.0 * B,
-           bwd_bn2_apply_rank1(L.mask_h[d.R], dz, P.wf, L.t2[j], bn2.mean, bn2.invstd, L.coef, B, Hp, Hp,
-                               dt2, s));
-    else if (!xbn2)
-      TRYB(DCNR_K_ROWWISE, 3 * act_b(d, B), bwd_bn2_apply2(d.prec, du, L.t2[j], bn2.mean, bn2.invstd, L.coef, B, Hp, Hp,
-                         dt2, L.part, &nc, s));
-    // ---- layer2: dW2 = dt2^T a1 ; da = dt2 W2 (the weight gradient after
-    // the GEMM that makes dt2 when the row pass is folded in)
-    if (!xbn2) TRY(linear_dw(d, L, dt2, Hp, Hp, L.a1s[j], Hp, Hp, B, Gk.w2, H, H, accumulate, s, pipe));
-    if (fuse) {
-      // dy1 = (dt2 W2) * [a1 != 0] / (1-p): relu and dropout masks from the
-      // saved activation, BN1 partials in the same pass
-      const XbnOperand xo{L.t2[j], &bn2, dt2};
-      TRYB(DCNR_K_GEMM_DX, (xbn2 ? 5 : 3) * act_b(d, B) + mask_b(d, B) + w_b(d, d.Hp),
-           linear_dx_bn(d, L, NT_EPI_DROP_BN, xbn2 ? du : dt2, L.W2t[j], nullptr, da, L.mask_a1[j],
-                        p > 0.f ? 1.f / (1.f - p) : 1.f, L.t1[j], bn1, B, &nc, s, xbn2 ? &xo : nullptr));
-      if (xbn2) TRY(linear_dw(d, L, dt2, Hp, Hp, L.a1s[j], Hp, Hp, B, Gk.w2, H, H, accumulate, s, pipe));
-    } else {
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.A = dt2; g.lda = Hp; g.B = L.W2t[j]; g.ldb = Hp; g.C = da; g.ldc = Hp;
-      g.M = B; g.N = Hp; g.K = Hp; g.k_per_split = Hp;
-      TRYB(DCNR_K_GEMM_DX, 2 * act_b(d, B) + w_b(d, d.Hp), gemm_nn(d.prec, EPI_STORE, g, 1, s));
-      // ---- relu/dropout + BN1 backward
-      TRYB(DCNR_K_ROWWISE, 3 * act_b(d, B), bwd_bn1_stats(d.prec, da, L.t1[j], bn1.scale, bn1.shift, bn1.mean,
-                                         bn1.invstd, B, Hp, Hp, p, dropout_seed, j, L.part, &nc, s));
-    }
-    TRY(bn_bwd_reduce(desc, d, L, nc, 2, B, Bk.g1, bn1.invstd, Gk.g1, Gk.be1, nullptr, Gk.b1,
-                        accumulate, s));
-    // the BN1 backward's row pass folded into the RESID_BN dX GEMM likewise
-    // (block 0: into the RESID GEMM that makes G)
-    const bool xbn1 = fuse && xbn_ok;
-    if (!xbn1) {
-      TRYB(DCNR_K_ROWWISE, 3 * act_b(d, B), bwd_bn1_apply2(d.prec, da, L.t1[j], bn1.mean, bn1.invstd, L.coef, B, Hp, Hp, dt1,
-                         L.part, &nc, s));
-      // ---- layer1: dW1 = dt1^T h_j ; G = dt1 W1 + du
-      TRY(linear_dw(d, L, dt1, Hp, Hp, L.h[j], Hp, Hp, B, Gk.w1, H, H, accumulate, s, pipe));
-    }
-    if (fuse && j > 0) {
-      // G is only consumed by block j-1's BN2 backward: emit its du = G * [h_j > 0]
-      // (in place over this block's du, the residual operand, unless
-      // KEEP_INTERMEDIATES) and the partials
-      const BnBufs& bp = L.bn[2 * (j - 1) + 1];
-      const XbnOperand xo{L.t1[j], &bn1, dt1};
-      TRYB(DCNR_K_GEMM_DX, (xbn1 ? 6 : 4) * act_b(d, B) + mask_b(d, B) + w_b(d, d.Hp),
-           linear_dx_bn(d, L, NT_EPI_RESID_BN, xbn1 ? da : dt1, L.W1t[j], du, L.duk[j - 1], L.mask_h[j], 1.f,
-                        L.t2[j - 1], bp, B, &nc_du, s, xbn1 ? &xo : nullptr));
-      if (xbn1) TRY(linear_dw(d, L, dt1, Hp, Hp, L.h[j], Hp, Hp, B, Gk.w1, H, H, accumulate, s, pipe));
-      Gin = L.duk[j - 1];
-    } else if (xbn1) {   // G = dt1 W1 + du, dt1 made from da and t1 in the GEMM,
-                         // G's column sums (the initial layer's bias gradient) in its epilogue
-      NtArgs a;
-      memset(&a, 0, sizeof(a));
-      a.Tx = (const bf16*)L.t1[j];
-      a.xmean = bn1.mean; a.xinvstd = bn1.invstd; a.xcoef = L.coef;
-      a.dt = (bf16*)dt1;
-      a.X = (const bf16*)da; a.ldx = Hp; a.M = B; a.K = Hp;
-      a.W = (const bf16*)L.W1t[j]; a.ldw = Hp; a.N = Hp;
-      a.C = L.G; a.ldc = Hp;
-      a.R = du; a.ldr = Hp;
-      a.part = L.part;
-      int ncg = 0;
-      TRYB(DCNR_K_GEMM_DX, 5 * act_b(d, B) + w_b(d, d.Hp), gemm_ws(NT_EPI_RESID_SUM, a, s, &ncg));
-      TRY(linear_dw(d, L, dt1, Hp, Hp, L.h[j], Hp, Hp, B, Gk.w1, H, H, accumulate, s, pipe));
-      TRY(bias_reduce(d, L, ncg, Gr.b0, accumulate, s, 2));
-      b0_done = true;
-      Gin = L.G;
-      nc_du = 0;
-    } else {
-      GemmArgs g;
-      memset(&g, 0, sizeof(g));
-      g.A = dt1; g.lda = Hp; g.B = L.W1t[j]; g.ldb = Hp; g.C = L.G; g.ldc = Hp;
-      g.resid = du; g.ldr = Hp;
-      g.M = B; g.N = Hp; g.K = Hp; g.k_per_split = Hp;
-      TRYB(DCNR_K_GEMM_DX, 3 * act_b(d, B) + w_b(d, d.Hp), gemm_nn(d.prec, EPI_STORE_RESID, g, 1, s));
-      Gin = L.G;
-      nc_du = 0;
-    }
-  }
+  Bwd c{desc, d, pl, L, P, Gr, B, dlogits, dropout_seed, accumulate, s, pipe};
+  for (int j = d.R - 1; j >= 0; --j) TRY(pl.stats_epi ? c.block_epi(j, pl.xbn) : c.block_plain(j));
   // ---- initial layer: the weight gradient on the side stream (after block
   // 0's); the bias gradient came with G (b0_done) or is a column-sum pass
   // here on the main stream, ahead of the dx0 GEMM.  The side stream's queue
@@ -1443,9 +1491,9 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
   // waited 135 us for it while the main stream was done
   // (profiles/r06fin_step_timeline.txt)
   TRY(linear_dw(d, L, L.G, Hp, Hp, L.x0, d.Dp, d.Dp, B, Gr.W0, H, d.D, accumulate, s, pipe));
-  if (!b0_done) {
+  if (!c.b0_done) {
     int nc = 0;
-    TRYB(DCNR_K_ROWWISE, act_b(d, B), col_sum(d.prec, L.G, B, Hp, Hp, L.part, &nc, s));
+    TRYB(DCNR_K_ROWWISE, s, act_b(d, B), col_sum(d.prec, L.G, B, Hp, Hp, L.part, &nc, s));
     TRY(bias_reduce(d, L, nc, Gr.b0, accumulate, s));
   }
   TRY(sj.join(s));   // the side stream's cross gradients, coefficients and sorted ids
@@ -1453,13 +1501,11 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
   // optimizer, so they join at the end (under the dx0 GEMM and embedding sums)
   if (desc->grad_ready) TRY(dwp.join(s));
   TRY(grads_ready(desc, DCNR_GRADS_DENSE, s));   // every non-embedding gradient is enqueued
-  {
-    GemmArgs g;
-    memset(&g, 0, sizeof(g));
-    g.A = L.G; g.lda = Hp; g.B = L.W0t; g.ldb = Hp; g.C = L.dx0; g.ldc = dq_of(d); g.out_f32 = 1;
-    g.M = B; g.N = d.Dp; g.K = Hp; g.k_per_split = Hp;
-    TRYB(DCNR_K_GEMM_DX, act_b(d, B) + 4.0 * B * d.Dp + w_b(d, d.Dp), gemm_nn(d.prec, EPI_STORE, g, 1, s));
-  }
+  GemmArgs gx;
+  memset(&gx, 0, sizeof(gx));
+  gx.A = L.G; gx.lda = Hp; gx.B = L.W0t; gx.ldb = Hp; gx.C = L.dx0; gx.ldc = dq_of(d); gx.out_f32 = 1;
+  gx.M = B; gx.N = d.Dp; gx.K = Hp; gx.k_per_split = Hp;
+  TRYB(DCNR_K_GEMM_DX, s, act_b(d, B) + 4.0 * B * d.Dp + w_b(d, d.Dp), gemm_nn(d.prec, EPI_STORE, gx, 1, s));
   // ---- embedding backward part 2: sorted (table row, sample) pairs -> per row
   // sum of the deep dx0 segments + sum of the cross coefficients
   double ew = 0;
@@ -1467,7 +1513,7 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
   eb.nv = d.L + 1;
   for (int l = 0; l < d.L; ++l) eb.V[l] = cpx.w[l];
   eb.V[d.L] = cpx.wf_cross;
-  TRYB(DCNR_K_EMB_SUM, (double)B * (4.0 * ew + (8.0 + 4.0 * (d.L + 1)) * g.n_tab),
+  TRYB(DCNR_K_EMB_SUM, s, (double)B * (4.0 * ew + (8.0 + 4.0 * (d.L + 1)) * g.n_tab),
        emb_segment_sum(eb, L.emb, B, L.dx0, dq_of(d), L.xcoef, accumulate, s));
   if (!desc->grad_ready) TRY(dwp.join(s));
   TRY(grads_ready(desc, DCNR_GRADS_EMBEDDING, s));
@@ -1482,7 +1528,7 @@ dcnr_status dcnr_gather_rows(const int64_t* idx, int64_t n, int64_t n_src, int32
     set_error("dcnr_gather_rows: null argument");
     return DCNR_BAD_ARG;
   }
-  TRYP(DCNR_K_SERVE, gather_rows(idx, n, n_src, n_arrays, src, dst, row_bytes, s));
+  TRYP(DCNR_K_SERVE, s, gather_rows(idx, n, n_src, n_arrays, src, dst, row_bytes, s));
   return DCNR_OK;
 }
 
@@ -1495,7 +1541,7 @@ dcnr_status dcnr_candidate_union(const int64_t* positives, int64_t Q, const int6
     return DCNR_BAD_ARG;
   }
   if (Q == 0) return DCNR_OK;
-  TRYP(DCNR_K_SERVE, candidate_union(positives, Q, knn_idx, k, out_rows, out_count, s));
+  TRYP(DCNR_K_SERVE, s, candidate_union(positives, Q, knn_idx, k, out_rows, out_count, s));
   return DCNR_OK;
 }
 
@@ -1511,7 +1557,7 @@ dcnr_status dcnr_ranking_batch(const int64_t* item_rows, int64_t n, int64_t user
     set_error("dcnr_ranking_batch: bad argument");
     return DCNR_BAD_ARG;
   }
-  TRYP(DCNR_K_SERVE, ranking_batch(item_rows, n, user_row, item_cat, n_cat, item_num, n_num,
+  TRYP(DCNR_K_SERVE, s, ranking_batch(item_rows, n, user_row, item_cat, n_cat, item_num, n_num,
                                    n_items, user_ids, item_ids, cat_features, num_features, s));
   return DCNR_OK;
 }
@@ -1523,7 +1569,7 @@ dcnr_status dcnr_rank_by_score(const float* scores, int64_t n, int64_t* order,
     set_error("dcnr_rank_by_score: bad argument");
     return DCNR_BAD_ARG;
   }
-  TRYP(DCNR_K_SERVE, rank_desc(scores, n, order, s));
+  TRYP(DCNR_K_SERVE, s, rank_desc(scores, n, order, s));
   return DCNR_OK;
 }
 
@@ -1537,7 +1583,7 @@ dcnr_status dcnr_mmr_rerank(const float* table, const float* inv_norms, int32_t 
     set_error("dcnr_mmr_rerank: bad argument");
     return DCNR_BAD_ARG;
   }
-  TRYP(DCNR_K_SERVE, mmr_rerank(table, inv_norms, d, rows, scores, n, lambda_param, top_k,
+  TRYP(DCNR_K_SERVE, s, mmr_rerank(table, inv_norms, d, rows, scores, n, lambda_param, top_k,
                                 out_pos, out_count, s));
   return DCNR_OK;
 }
@@ -1556,7 +1602,7 @@ dcnr_status dcnr_emb_touched_rows(const dcnr_model_desc* desc, const void* ws, s
     set_error("dcnr_emb_touched_rows: bad argument");
     return DCNR_BAD_ARG;
   }
-  Layout L = make_layout(d, B, DCNR_TRAIN, (void*)ws, desc->flags);
+  Layout L = make_layout(d, B, make_plan(d, desc->flags, DCNR_TRAIN, B), (void*)ws);
   if (ws_bytes < L.total) {
     set_error("workspace too small: %zu < %zu", ws_bytes, L.total);
     return DCNR_WORKSPACE_TOO_SMALL;
@@ -1592,7 +1638,7 @@ dcnr_status dcnr_sparse_pack(const float* grad, const int64_t* offsets, int64_t 
     return DCNR_BAD_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
-  TRYP(DCNR_K_SERVE, sparse_pack(grad, offsets, ld, table_counts, n_tables, width, out_offsets, out_rows, s));
+  TRYP(DCNR_K_SERVE, s, sparse_pack(grad, offsets, ld, table_counts, n_tables, width, out_offsets, out_rows, s));
   return DCNR_OK;
 }
 
@@ -1615,7 +1661,7 @@ dcnr_status dcnr_sparse_accumulate(float* shard, int64_t shard_lo, int64_t shard
     return DCNR_BAD_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
-  TRYP(DCNR_K_SERVE, sparse_accumulate(shard, shard_lo, shard_elems, width, offsets, rows, source_counts,
+  TRYP(DCNR_K_SERVE, s, sparse_accumulate(shard, shard_lo, shard_elems, width, offsets, rows, source_counts,
                                        n_sources, s));
   return DCNR_OK;
 }
@@ -1632,7 +1678,7 @@ dcnr_status dcnr_bce_with_logits(const float* logits, const float* labels, int64
     return DCNR_WORKSPACE_TOO_SMALL;
   }
   hipStream_t s = (hipStream_t)stream;
-  TRYP(DCNR_K_HEAD, bce(logits, labels, B, loss, dlogits, grad_scale, (double*)ws, s));
+  TRYP(DCNR_K_HEAD, s, bce(logits, labels, B, loss, dlogits, grad_scale, (double*)ws, s));
   return DCNR_OK;
 }
 
@@ -1648,7 +1694,7 @@ dcnr_status dcnr_adam_step(int32_t n_tensors, float* const* params, const float*
   hipStream_t s = (hipStream_t)stream;
   double nparam = 0;
   for (int i = 0; i < n_tensors; ++i) nparam += (double)numel[i];
-  TRYB(DCNR_K_ADAM, 28.0 * nparam, adam(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2,
+  TRYB(DCNR_K_ADAM, s, 28.0 * nparam, adam(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2,
                          eps, weight_decay, step, decoupled, s));
   return DCNR_OK;
 }
@@ -1677,7 +1723,7 @@ dcnr_status dcnr_adam_step_rows(int32_t n_tensors, float* const* params, const f
               (row_map[i] ? (double)numel[i] / row_width[i] : 0.0);
   }
   hipStream_t s = (hipStream_t)stream;
-  TRYB(DCNR_K_ADAM, nbytes, adam(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2,
+  TRYB(DCNR_K_ADAM, s, nbytes, adam(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2,
                                  eps, weight_decay, step, decoupled, s, row_map, row_width));
   return DCNR_OK;
 }
@@ -1720,7 +1766,7 @@ dcnr_status dcnr_cosine_topk_packed(const float* table, const float* inv_norms, 
     return DCNR_BAD_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
-  TRYB(DCNR_K_KNN, (double)N * (4.0 * d + 4.0),
+  TRYB(DCNR_K_KNN, s, (double)N * (4.0 * d + 4.0),
        cosine_topk(table, inv_norms, (const bf16*)packed, N, d, queries, Q, k, idx, dist, ws, ws_bytes, s));
   return DCNR_OK;
 }
@@ -1739,7 +1785,7 @@ dcnr_status dcnr_topk_merge(const float* dist, const int64_t* idx, int32_t lists
     return DCNR_BAD_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
-  TRYB(DCNR_K_KNN, (double)lists * Q * k * 12.0 + Q * k * 12.0,
+  TRYB(DCNR_K_KNN, s, (double)lists * Q * k * 12.0 + Q * k * 12.0,
        topk_merge(dist, idx, lists, Q, k, out_idx, out_dist, s));
   return DCNR_OK;
 }
@@ -1756,7 +1802,7 @@ dcnr_status dcnr_linear_bf16(const void* X, int64_t ldx, int64_t M, int32_t K, c
   memset(&g, 0, sizeof(g));
   g.A = X; g.lda = ldx; g.B = W; g.ldb = ldw; g.C = C; g.ldc = ldc; g.bias = bias;
   g.M = M; g.N = N; g.K = K; g.k_per_split = K; g.out_f32 = out_f32 ? 1 : 0;
-  TRYP(DCNR_K_GEMM_FWD, gemm_nn(DCNR_PREC_BF16, EPI_STORE, g, 1, s));
+  TRYP(DCNR_K_GEMM_FWD, s, gemm_nn(DCNR_PREC_BF16, EPI_STORE, g, 1, s));
   return DCNR_OK;
 }
 

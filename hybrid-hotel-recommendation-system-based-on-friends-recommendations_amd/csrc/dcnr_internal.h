@@ -53,6 +53,19 @@ dcnr_status set_max_dyn_lds(const void* kernel, size_t bytes);
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t rup(int64_t a, int64_t b) { return cdiv(a, b) * b; }
 
+// Carves a caller-owned workspace: each region starts at the next multiple of
+// `align` bytes.  With a null base every pointer is null and `off` is the size.
+struct Bump {
+  char* base; size_t off = 0;
+  explicit Bump(void* b) : base((char*)b) {}
+  void* take(size_t bytes, size_t align = 256) {
+    off = (off + align - 1) / align * align;
+    void* p = base ? base + off : nullptr;
+    off += bytes;
+    return p;
+  }
+};
+
 // ------------------------------------------------------------- storage T
 template <typename T> struct St;
 template <> struct St<float> {
@@ -251,16 +264,6 @@ __device__ __forceinline__ float wave_sum_dpp(float v) {
   t = __uint_as_float(r[0]) + __uint_as_float(r[1]);
   return row16_sum(t);
 }
-// two independent 64-lane sums at once (wave-uniform results)
-__device__ __forceinline__ void wave_sum2(float a, float b, float& sa, float& sb) {
-  auto p = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  const float t = __uint_as_float(p[0]) + __uint_as_float(p[1]);     // lanes 0-31: a, 32-63: b
-  const unsigned ut = __float_as_uint(t);
-  auto r = __builtin_amdgcn_permlane16_swap(ut, ut, false, false);
-  const float u = row16_sum(__uint_as_float(r[0]) + __uint_as_float(r[1]));  // rows: a, a, b, b
-  sa = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), 0));
-  sb = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(u), 32));
-}
 // four independent 64-lane sums at once (wave-uniform results)
 __device__ __forceinline__ void wave_sum4(float a, float b, float c, float d, float& sa, float& sb,
                                           float& sc, float& sd) {
@@ -377,7 +380,6 @@ struct RedFinal {
   float* grad;                                 // RED_BIAS
   const float* shiftf;                         // f32 shift of the stats partials (or null)
 };
-
 
 constexpr float BN_EPS = 1e-5f;
 constexpr double BN_MOM = 0.1;
@@ -578,11 +580,6 @@ struct CrossParams {
   const float* wf_cross; // final_linear.weight + H  ([D])
 };
 
-dcnr_status gather_cross_fwd(int precision, const GatherDesc& g, const CrossParams& cp,
-                             const int64_t* user, const int64_t* item, const int64_t* cat,
-                             const float* num, int64_t B, void* x0, int ldx, float* zc,
-                             int* err, int check, hipStream_t s);
-
 // 16-byte-lane forward (gather_cross.hip): any subset of x0 (fp32 or bf16),
 // the cross output x_L (fp32, BASELINE configs[1]) and the head partial zc.
 struct GcOut {
@@ -656,7 +653,6 @@ dcnr_status sparse_accumulate(float* shard, int64_t lo, int64_t elems, int width
 dcnr_status emb_segment_sum(const EmbBwdDesc& e, const EmbSortBufs& sb, int64_t B,
                             const float* dx0_deep, int ld, const float* coef, int accumulate,
                             hipStream_t s);
-
 
 // Column reductions: partial sums per row-chunk, part[nchunks][NK][N] (f32),
 // reduced in fixed order into sums[3][N] (f64; components >= NK zeroed) with

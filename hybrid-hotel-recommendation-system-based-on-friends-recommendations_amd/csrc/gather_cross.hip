@@ -704,15 +704,14 @@ constexpr int FWD_SPW = 4;   // samples per wave per tile (forward)
 template <typename T, int RM>
 dcnr_status launch_fwd(const GatherDesc& g, const CrossParams& cp, const int64_t* user,
                        const int64_t* item, const int64_t* cat, const float* num, int64_t B,
-                       void* x0, int ldx, float* zc, int* err, int check, hipStream_t s,
-                       float* cross = nullptr, int ldc = 0, float* sc = nullptr) {
+                       const GcOut& o, int* err, int check, hipStream_t s) {
   constexpr int S = FWD_SPW * WPB;
   size_t lds = (size_t)(((2 * cp.L + 1) * g.D + S * g.n_tab + 3) & ~3) * sizeof(float) +
                (size_t)WPB * RM * WAVE * sizeof(bf16);
   int64_t blocks = std::min<int64_t>(cdiv(B, S), 256 * 8);
   hipLaunchKernelGGL((gather_cross_fwd_kernel<T, RM, FWD_SPW>), dim3((unsigned)blocks), dim3(NT),
-                     lds, s, g, cp, user, item, cat, num, B, (T*)x0, ldx, zc, err, check, cross, ldc,
-                     sc);
+                     lds, s, g, cp, user, item, cat, num, B, (T*)o.x0, o.ld_x0, o.zc, err, check, o.cross,
+                     o.ld_cross, o.sc);
   DCNR_LAUNCH_CHECK();
   return DCNR_OK;
 }
@@ -778,26 +777,7 @@ bool v4_ok(const GatherDesc& g, const float* num, const GcOut& o) {
   return true;
 }
 
-
 }  // namespace
-
-
-dcnr_status gather_cross_fwd(int precision, const GatherDesc& g, const CrossParams& cp,
-                             const int64_t* user, const int64_t* item, const int64_t* cat,
-                             const float* num, int64_t B, void* x0, int ldx, float* zc, int* err,
-                             int check, hipStream_t s) {
-  if (B <= 0) return DCNR_OK;
-  if (g.D > 16 * WAVE || cp.L > 8 || g.n_tab > MAX_TABLES) {
-    set_error("gather: unsupported D=%d / n_cross=%d / tables=%d", g.D, cp.L, g.n_tab);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  bool small = g.D <= 8 * WAVE && ldx <= 8 * WAVE;
-  if (precision == DCNR_PREC_BF16)
-    return small ? launch_fwd<bf16, 8>(g, cp, user, item, cat, num, B, x0, ldx, zc, err, check, s)
-                 : launch_fwd<bf16, 16>(g, cp, user, item, cat, num, B, x0, ldx, zc, err, check, s);
-  return small ? launch_fwd<float, 8>(g, cp, user, item, cat, num, B, x0, ldx, zc, err, check, s)
-               : launch_fwd<float, 16>(g, cp, user, item, cat, num, B, x0, ldx, zc, err, check, s);
-}
 
 dcnr_status gather_cross_out(const GatherDesc& g, const CrossParams& cp, const int64_t* user,
                              const int64_t* item, const int64_t* cat, const float* num, int64_t B,
@@ -815,14 +795,10 @@ dcnr_status gather_cross_out(const GatherDesc& g, const CrossParams& cp, const i
     const bool small = g.D <= 8 * WAVE && (!o.x0 || o.ld_x0 <= 8 * WAVE) &&
                        (!o.cross || o.ld_cross <= 8 * WAVE);
     if (x0_bf16)
-      return small ? launch_fwd<bf16, 8>(g, cp, user, item, cat, num, B, o.x0, o.ld_x0, o.zc, err,
-                                         check, s, o.cross, o.ld_cross, o.sc)
-                   : launch_fwd<bf16, 16>(g, cp, user, item, cat, num, B, o.x0, o.ld_x0, o.zc,
-                                          err, check, s, o.cross, o.ld_cross, o.sc);
-    return small ? launch_fwd<float, 8>(g, cp, user, item, cat, num, B, o.x0, o.ld_x0, o.zc, err,
-                                        check, s, o.cross, o.ld_cross, o.sc)
-                 : launch_fwd<float, 16>(g, cp, user, item, cat, num, B, o.x0, o.ld_x0, o.zc, err,
-                                         check, s, o.cross, o.ld_cross, o.sc);
+      return small ? launch_fwd<bf16, 8>(g, cp, user, item, cat, num, B, o, err, check, s)
+                   : launch_fwd<bf16, 16>(g, cp, user, item, cat, num, B, o, err, check, s);
+    return small ? launch_fwd<float, 8>(g, cp, user, item, cat, num, B, o, err, check, s)
+                 : launch_fwd<float, 16>(g, cp, user, item, cat, num, B, o, err, check, s);
   }
   const bool r1 = g.D <= 4 * WAVE && (!o.x0 || o.ld_x0 <= 4 * WAVE) &&
                   (!o.cross || o.ld_cross <= 4 * WAVE);

@@ -47,9 +47,6 @@ typedef bf16 bf16x2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack2(float a, float b) {
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(f2v{a, b}, bf16x2v));
 }
-__device__ __forceinline__ f2v unpack2(uint32_t w) {
-  return f2v{__uint_as_float(w << 16), __uint_as_float(w & 0xffff0000u)};
-}
 template <int H, int CTRL>
 __device__ __forceinline__ void bfly(float (&x)[16], bool hi) {
 #pragma unroll

@@ -1887,29 +1887,42 @@ bool use_v4(int64_t N, int64_t Q, int d, int k) {
   return use_v2(d, k) && Q >= 1 && d % 32 == 0 && (Q > 1 || N >= V4_Q1_N);
 }
 
-// v4 scratch after the v2 layout (cands | qn [Q][d] | thr0 [Q]): bf16
-// queries [Q][d] | per-query counts [Q] | admitted rows [Q][V4_CAP]
-// | their exact distances [Q][V4_CAP] | the bound's block minima
-// [Q][B5_G]
-// the split fallback's k-lists (k <= 32: scan v4's range), for Q <= V4_FQ
-size_t v4_split_bytes(int64_t Q) {
-  const int L = v4_lists(Q);
-  return L > 1 ? rup((size_t)Q * L * 32 * 4, 256) + (size_t)Q * L * 32 * 8 : 0;
-}
-size_t v4_extra(int64_t Q, int d) {
-  return rup((size_t)Q * d * 2, 256) + rup((size_t)Q * 8 + 48, 256) + 2 * (size_t)Q * V4_CAP * 4 +
-         rup((size_t)Q * B5_G * 4, 256) + v4_split_bytes(Q) + 256;
-}
-
-size_t topk_ws_d(int64_t N, int64_t Q, int k, int d) {
-  int ns; int64_t rps;
-  if (use_v2(d, k)) {
-    plan2(N, &ns, &rps);
-    const size_t v2 = rup((size_t)Q * ns * k * sizeof(Cand), 256) + (size_t)Q * (d + 1) * 4;
-    return use_v4(N, Q, d, k) ? rup(v2, 256) + v4_extra(Q, d) : v2;
-  }
-  plan(N, Q, k, &ns, &rps);
-  return (size_t)Q * ns * k * sizeof(Cand);
+// The scratch of one search, carved once (null base: `total` is the size).
+// Scan v1: the per-slice k-lists.  v2 / v3: cands | qn [Q][d] | thr0 [Q].
+// v4 after those: bf16 queries [Q][d] | qcnt: [Q] list counts, the overflow
+// word, [Q] fallback arrival counters, a spare word, the batched fallback's
+// 8 queue heads | admitted rows [Q][V4_CAP] | their exact distances | the
+// bound's block minima [Q][B5_G] | the fallbacks' k-lists (k <= 32)
+struct TopkWs {
+  int ns; int64_t rps;   // the scan's row slices
+  Cand* cands;
+  float *qn, *thr0;
+  bf16* qb; int* qcnt; int* rows; float* dists; float* bmins; float* split_d; int64_t* split_i;
+  size_t total;
+};
+TopkWs carve_topk(void* ws, int64_t N, int64_t Q, int k, int d) {
+  TopkWs w{};
+  Bump b(ws);
+  const bool v2 = use_v2(d, k);
+  if (v2) plan2(N, &w.ns, &w.rps);
+  else plan(N, Q, k, &w.ns, &w.rps);
+  w.cands = (Cand*)b.take((size_t)Q * w.ns * k * sizeof(Cand));
+  w.total = b.off;
+  if (!v2) return w;
+  w.qn = (float*)b.take((size_t)Q * d * 4);
+  w.thr0 = (float*)b.take((size_t)Q * 4, 4);   // (right behind qn)
+  w.total = b.off;
+  if (!use_v4(N, Q, d, k)) return w;
+  const size_t lists = (size_t)Q * v4_lists(Q) * 32;   // (v4_lists >= 8 for every Q >= 1)
+  w.qb = (bf16*)b.take((size_t)Q * d * 2);
+  w.qcnt = (int*)b.take((size_t)Q * 8 + 48);
+  w.rows = (int*)b.take((size_t)Q * V4_CAP * 4);
+  w.dists = (float*)b.take((size_t)Q * V4_CAP * 4);
+  w.bmins = (float*)b.take((size_t)Q * B5_G * 4);
+  w.split_d = (float*)b.take(lists * 4);
+  w.split_i = (int64_t*)b.take(lists * 8);
+  w.total = b.off + 256;
+  return w;
 }
 
 // Final merge of the per-block k-lists, one block per query.  Measured at
@@ -1925,11 +1938,10 @@ dcnr_status merge_lists(const Cand* cands, int64_t Q, int ns, int k, int64_t* id
   return DCNR_OK;
 }
 
-// enough for every d (the v2 path keeps Q x d <= Q x 64 normalised queries)
+// enough for every d (the v2 path keeps Q x d <= Q x 64 normalised queries;
+// wider rows take scan v1)
 size_t topk_ws(int64_t N, int64_t Q, int k) {
-  int ns; int64_t rps;
-  plan(N, Q, k, &ns, &rps);
-  return std::max(topk_ws_d(N, Q, k, 64), (size_t)Q * ns * k * sizeof(Cand));
+  return std::max(carve_topk(nullptr, N, Q, k, 64).total, carve_topk(nullptr, N, Q, k, 256).total);
 }
 
 dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_t N, int d,
@@ -1941,40 +1953,16 @@ dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_
     return DCNR_UNSUPPORTED_SHAPE;
   }
   if (Q <= 0) return DCNR_OK;
-  if (ws_bytes < topk_ws_d(N, Q, k, d)) {
+  const auto [ns, rps, cands, qn, thr0, qb, qcnt, rows, dists, bmins, split_d, split_i, total] =
+      carve_topk(ws, N, Q, k, d);
+  if (ws_bytes < total) {
     set_error("cosine_topk: workspace too small");
     return DCNR_WORKSPACE_TOO_SMALL;
   }
-  int ns; int64_t rps;
-  Cand* cands = (Cand*)ws;
   if (use_v2(d, k)) {
-    plan2(N, &ns, &rps);
-    float* qn = (float*)((char*)ws + rup((size_t)Q * ns * k * sizeof(Cand), 256));
     // normalised queries + admission bounds, one block per query (v4 makes
     // its own, from a larger sample, below)
-    float* thr0 = qn + Q * d;
     const bool v4 = use_v4(N, Q, d, k);
-    bf16* qb = nullptr;
-    int *qcnt = nullptr, *rows = nullptr;   // v4 scratch
-    float* dists = nullptr;
-    float* bmins = nullptr;             // v4 bound: block minima
-    float* split_d = nullptr;           // v4 split fallback: k-lists
-    int64_t* split_i = nullptr;
-    if (v4) {
-      char* x = (char*)ws + rup(rup((size_t)Q * ns * k * sizeof(Cand), 256) + (size_t)Q * (d + 1) * 4, 256);
-      qb = (bf16*)x;
-      x += rup((size_t)Q * d * 2, 256);
-      qcnt = (int*)x;   // [Q] list counts, the overflow word, [Q] fallback arrival counters,
-                        // a spare word, the batched fallback's 8 queue heads
-      x += rup((size_t)Q * 8 + 48, 256);
-      rows = (int*)x;
-      dists = (float*)(rows + Q * V4_CAP);
-      x += 2 * (size_t)Q * V4_CAP * 4;
-      bmins = (float*)x;
-      x += rup((size_t)Q * B5_G * 4, 256);
-      split_d = (float*)x;
-      split_i = (int64_t*)(x + rup((size_t)Q * v4_lists(Q) * 32 * 4, 256));
-    }
     if (!v4) {
       switch (d / 4) {
 #define CASEK(n)                                                                             \
@@ -2088,17 +2076,13 @@ dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_
     DCNR_LAUNCH_CHECK();
     return merge_lists(cands, Q, ns, k, idx, dist, s);
   }
-  plan(N, Q, k, &ns, &rps);
   dim3 grid(ns, (unsigned)cdiv(Q, QT));
   if (d <= 64)
     hipLaunchKernelGGL(scan_kernel<16>, grid, dim3(NT), 0, s, t, inv, N, d, q, Q, k, rps, cands);
   else
     hipLaunchKernelGGL(scan_kernel<64>, grid, dim3(NT), 0, s, t, inv, N, d, q, Q, k, rps, cands);
   DCNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(merge_kernel, dim3((unsigned)Q), dim3(NT), 0, s, cands, ns, k, idx, dist, 1,
-                     nullptr);
-  DCNR_LAUNCH_CHECK();
-  return DCNR_OK;
+  return merge_lists(cands, Q, ns, k, idx, dist, s);
 }
 
 dcnr_status topk_merge(const float* dist, const int64_t* idx, int lists, int64_t Q, int k,
