@@ -1316,7 +1316,7 @@ dcnr_status dcnr_workspace_offset(const dcnr_model_desc* desc, int64_t B, int mo
     case DCNR_WS_T2: if (blk(R)) p = L.t2[index]; break;
     case DCNR_WS_A1: if (blk(R)) p = L.a1s[index]; break;
     case DCNR_WS_MASK_A1: if (blk(R)) p = L.mask_a1[index]; break;
-    case DCNR_WS_MASK_H: if (blk(R)) p = L.mask_h[index]; break;
+    case DCNR_WS_MASK_H: if (blk(R + 1)) p = L.mask_h[index]; break;   // (j = R: Plan::rank1)
     case DCNR_WS_BN_MEAN: if (blk(2 * R)) p = L.bn[index].mean; break;
     case DCNR_WS_BN_INVSTD: if (blk(2 * R)) p = L.bn[index].invstd; break;
     case DCNR_WS_BN_SCALE: if (blk(2 * R)) p = L.bn[index].scale; break;

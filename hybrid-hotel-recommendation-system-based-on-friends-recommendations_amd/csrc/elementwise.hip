@@ -370,8 +370,11 @@ template <typename T> struct Bwd1StatsOp {
       q.a[v] = pre > 0.f ? q.a[v] : 0.f;
     }
     if (drop) apply_dropout<VE<T>>(seed, layer, r, c, thresh, inv_keep, q.a);
+    // the sums use the stored (storage type) value, the one the apply pass
+    // reads back -- as Bwd2StatsOp's and the dX GEMM epilogues' do
 #pragma unroll
     for (int v = 0; v < VE<T>; ++v) {
+      q.a[v] = (float)(T)q.a[v];
       float xh = (q.t[v] - k.mu[v]) * k.is[v];
       acc[0][v] += q.a[v];
       acc[1][v] += q.a[v] * xh;
