@@ -1682,6 +1682,30 @@ dcnr_status dcnr_bce_with_logits(const float* logits, const float* labels, int64
   return DCNR_OK;
 }
 
+size_t dcnr_eval_metrics_workspace_size(int64_t n) { return metrics_ws_bytes(n); }
+
+dcnr_status dcnr_eval_metrics(const float* logits, const float* labels, int64_t n, dcnr_metrics* out,
+                              void* ws, size_t ws_bytes, dcnr_stream_t stream) {
+  if (n < 0 || n >= ((int64_t)1 << 31) || !out || (n > 0 && (!logits || !labels))) {
+    set_error("dcnr_eval_metrics: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  const size_t need = metrics_ws_bytes(n);
+  if (ws_bytes < need) {
+    set_error("dcnr_eval_metrics: workspace too small: %zu < %zu", ws_bytes, need);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  if (need && !ws) {
+    set_error("dcnr_eval_metrics: null workspace");
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // algorithmic bytes: the inputs once, the keys written and read once per sort pass
+  TRYB(DCNR_K_HEAD, s, 8.0 * (double)n + 3.0 * 16.0 * (double)n,
+       eval_metrics(logits, labels, n, out, ws, s));
+  return DCNR_OK;
+}
+
 dcnr_status dcnr_adam_step(int32_t n_tensors, float* const* params, const float* const* grads,
                            float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
                            float lr, float beta1, float beta2, float eps, float weight_decay,

@@ -736,6 +736,11 @@ size_t bce_ws_bytes();
 dcnr_status bce(const float* z, const float* y, int64_t B, float* loss, float* dz, float scale,
                 double* part, hipStream_t s);
 
+// validation metrics (metrics.hip): logloss, exact AUC, RMSE over n logits
+size_t metrics_ws_bytes(int64_t n);
+dcnr_status eval_metrics(const float* z, const float* y, int64_t n, dcnr_metrics* out, void* ws,
+                         hipStream_t s);
+
 // optimizer
 dcnr_status adam(int n, float* const* p, const float* const* g, float* const* m, float* const* v,
                  const int64_t* numel, float lr, float b1, float b2, float eps, float wd,

@@ -7,7 +7,12 @@ System-Based-on-Friends-Recommendations):
   BCEWithLogitsLoss                  train.py:206
   AdamW, Adam                        train.py:201-204
   NearestNeighbors (cosine, brute)   main.py:268-270
-  FusedTrainer                       the train.py:219-226 inner-loop step
+  FusedTrainer                       the train.py:219-226 inner-loop step;
+                                     .fit: the epoch loop, train.py:216-253
+  PlateauLR                          ReduceLROnPlateau (train.py:208-213, 235)
+  eval_metrics, roc_auc_score,       BCEWithLogitsLoss / roc_auc_score / RMSE of
+  evaluate                           the validation pass (train.py:228-233,
+                                     255-265, 366-387)
   DeviceLoader                       TensorDataset + DataLoader (train.py:195-196)
   serving.rerank_with_mmr            main.py:133-169
   serving.RankingPipeline            the /recommendations + /similar_items core
@@ -20,7 +25,8 @@ All compute runs in libdcnr.so (C ABI: include/dcnr.h) on the HIP device.
 from .model import CrossLayer, DCN_RecSys, ResBlock  # noqa: F401
 from .ops import Adam, AdamW, BCEWithLogitsLoss, bce_with_logits  # noqa: F401
 from .knn import NearestNeighbors, ShardedNearestNeighbors  # noqa: F401
-from .train import FusedTrainer  # noqa: F401
+from .train import FusedTrainer, PlateauLR  # noqa: F401
+from .metrics import Metrics, eval_metrics, evaluate, roc_auc_score  # noqa: F401
 from . import serving  # noqa: F401
 from .data import DeviceLoader  # noqa: F401
 from .serving import RankingPipeline, rerank_with_mmr  # noqa: F401

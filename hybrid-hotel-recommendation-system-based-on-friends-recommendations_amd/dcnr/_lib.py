@@ -59,6 +59,21 @@ class ModelDesc(ctypes.Structure):
     ]
 
 
+class MetricsStruct(ctypes.Structure):
+    """dcnr_metrics (written to device memory by dcnr_eval_metrics)."""
+    _fields_ = [
+        ("logloss", ctypes.c_double),
+        ("auc", ctypes.c_double),
+        ("rmse", ctypes.c_double),
+        ("n", ctypes.c_int64),
+        ("n_pos", ctypes.c_int64),
+        ("n_neg", ctypes.c_int64),
+        ("auc_u2", ctypes.c_int64),
+        ("n_bad_label", ctypes.c_int64),
+        ("n_nan", ctypes.c_int64),
+    ]
+
+
 # exported symbol -> (restype, argtypes); must match include/dcnr.h
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -85,6 +100,8 @@ _SIGS = {
     "dcnr_bce_workspace_size": (ctypes.c_size_t, []),
     "dcnr_bce_with_logits": (ctypes.c_int, [_P, _P, _I64, _P, _P, ctypes.c_float, _P,
                                             ctypes.c_size_t, _P]),
+    "dcnr_eval_metrics_workspace_size": (ctypes.c_size_t, [_I64]),
+    "dcnr_eval_metrics": (ctypes.c_int, [_P, _P, _I64, _P, _P, ctypes.c_size_t, _P]),
     "dcnr_adam_step": (ctypes.c_int, [ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_float,
                                       ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                       ctypes.c_float, _I64, ctypes.c_int, _P]),

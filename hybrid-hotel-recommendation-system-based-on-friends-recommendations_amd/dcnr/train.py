@@ -66,6 +66,38 @@ from .model import DCN_RecSys, dropout_seed, run_backward, run_forward
 from .ops import bce_with_logits
 
 
+class PlateauLR:
+    """``torch.optim.lr_scheduler.ReduceLROnPlateau(opt, 'min', patience=,
+    factor=)`` (train.py:208-213, 235) at torch's other defaults (relative
+    threshold 1e-4, no cooldown, min_lr 0, eps 1e-8) over a plain float:
+    ``step(val_loss)`` returns the learning rate to use from now on."""
+
+    threshold = 1e-4
+    eps = 1e-8
+
+    def __init__(self, lr, patience=10, factor=0.1):
+        if factor >= 1.0:
+            raise ValueError("Factor should be < 1.0.")
+        self.lr = float(lr)
+        self.patience, self.factor = patience, factor
+        self.best = math.inf
+        self.num_bad_epochs = 0
+
+    def step(self, val_loss) -> float:
+        current = float(val_loss)
+        if current < self.best * (1.0 - self.threshold):
+            self.best = current
+            self.num_bad_epochs = 0
+        else:
+            self.num_bad_epochs += 1
+        if self.num_bad_epochs > self.patience:
+            new_lr = max(self.lr * self.factor, 0.0)
+            if self.lr - new_lr > self.eps:
+                self.lr = new_lr
+            self.num_bad_epochs = 0
+        return self.lr
+
+
 class FusedTrainer:
     """The reference's training step (train.py:219-226) as native calls; see
     the module docstring.  ``dense_table_grads=False`` (default) at world 1
@@ -221,6 +253,55 @@ class FusedTrainer:
             e1.record()
             marks.append((e0, e1))
         return (loss, logits) if return_logits else loss
+
+    def fit(self, train_loader, val, n_epochs=50, patience=5, lr_scheduler_patience=10,
+            lr_scheduler_factor=0.1, checkpoint_path=None, on_epoch=None):
+        """The reference's epoch loop (train.py:216-253, without Optuna).
+
+        Each epoch: ``step()`` over ``train_loader`` (an iterable of
+        ``(collab, cat, num, y)`` batches, e.g. a DeviceLoader; train.py:218-226),
+        ``evaluate`` on ``val = (collab, cat, num, y)`` (the whole split as one
+        set, train.py:228-233), the learning rate from ``PlateauLR`` on the
+        validation logloss (train.py:235), ``model.state_dict()`` saved to
+        ``checkpoint_path`` on a strictly better logloss (train.py:240-245),
+        and a stop after ``patience`` epochs without one (train.py:251-253).
+        ``on_epoch(epoch, metrics)`` is called last in the epoch (history and
+        checkpoint up to date); a truthy return stops the loop -- the place of
+        the reference's pruner (train.py:236-238).
+
+        Returns ``{"epochs": [{"epoch", "metrics", "lr"}, ...], "best_epoch",
+        "best_val_loss", "stopped_early"}``; ``lr`` is the rate the schedule set
+        after that epoch's validation.  World 1 only."""
+        if self.world > 1:
+            raise NotImplementedError(
+                "FusedTrainer.fit runs at world 1 only: a data-parallel epoch loop (sharded "
+                "validation, one checkpoint writer) is not implemented; drive step() and "
+                "dcnr.evaluate per rank instead")
+        from .metrics import evaluate
+        sched = PlateauLR(self.lr, patience=lr_scheduler_patience, factor=lr_scheduler_factor)
+        history = {"epochs": [], "best_epoch": None, "best_val_loss": math.inf,
+                   "stopped_early": False}
+        no_improve = 0
+        for epoch in range(n_epochs):
+            for batch in train_loader:   # (a host DataLoader's batches are moved, train.py:220-221)
+                collab, cat, num, y = (t.to(self.flat.device) for t in batch)
+                self.step(collab[:, 0], collab[:, 1], cat, num, y)
+            m = evaluate(self.model, *val)
+            self.lr = sched.step(m.logloss)
+            history["epochs"].append({"epoch": epoch, "metrics": m, "lr": self.lr})
+            if m.logloss < history["best_val_loss"]:
+                history["best_val_loss"], history["best_epoch"] = m.logloss, epoch
+                no_improve = 0
+                if checkpoint_path is not None:
+                    torch.save(self.model.state_dict(), checkpoint_path)
+            else:
+                no_improve += 1
+            if on_epoch is not None and on_epoch(epoch, m):
+                break
+            if no_improve >= patience:
+                history["stopped_early"] = True
+                break
+        return history
 
     def materialize_table_grads(self):
         """Zero the table-gradient rows the last row-map step did not write.

@@ -26,6 +26,8 @@
  *   dcnr_ranking_batch    preprocess_for_ranking              main.py:215-230
  *   dcnr_rank_by_score    sorted(zip(scores, ids), reverse=True) main.py:325
  *   dcnr_mmr_rerank       rerank_with_mmr                     main.py:133-169
+ *   dcnr_eval_metrics     roc_auc_score / BCEWithLogitsLoss / sqrt(mean_squared_error)
+ *                         over the validation logits          train.py:255-265, 366-387
  *
  * Conventions
  *  - All tensor pointers are DEVICE pointers owned by the caller; the
@@ -284,6 +286,41 @@ size_t dcnr_bce_workspace_size(void);
 dcnr_status dcnr_bce_with_logits(const float* logits, const float* labels, int64_t B,
                                  float* loss, float* dlogits, float grad_scale, void* ws,
                                  size_t ws_bytes, dcnr_stream_t stream);
+
+/* The reference's validation metrics (train.py:255-265, 366-387) over n
+ * logits and labels, all n in one set as the reference's single validation
+ * batch: BCEWithLogitsLoss, sklearn's roc_auc_score(y, z) and
+ * sqrt(mean_squared_error(y, sigmoid(z))).  The struct is written to DEVICE
+ * memory, stream-ordered; a caller copies its 72 bytes when it wants them. */
+typedef struct {
+  double logloss;       /* mean(max(z,0) - z*y + log1p(exp(-|z|))), terms and sum in fp64 */
+  double auc;           /* (double)auc_u2 / (2.0 * n_pos * n_neg); NaN if n_pos * n_neg == 0 */
+  double rmse;          /* sqrt(mean((y - p)^2)), p = (float)(1/(1+exp(-(double)z))), sum fp64 */
+  int64_t n, n_pos, n_neg; /* n_pos: labels == 1.0f; n_neg = n - n_pos */
+  int64_t auc_u2;       /* 2U, exact: sum over positives i of
+                           2 * #{neg j: z_j < z_i} + #{neg j: z_j == z_i} */
+  int64_t n_bad_label;  /* labels that are neither 0.0f nor 1.0f */
+  int64_t n_nan;        /* NaN logits */
+} dcnr_metrics;
+
+/* Workspace bytes of dcnr_eval_metrics for n logits (0 for n <= 0): two
+ * 8-byte keys per logit for the sort plus its counters,
+ *   16 n + 4 * 2048 * (3 + U) + 40 * P + 40 * A   (+ < 2 KiB of alignment),
+ * U = min(1024, ceil(n / 4096)), P = min(1024, ceil(n / 8192)),
+ * A = ceil(n / max(2048, ceil(n / 1024) rounded up to 256)). */
+size_t dcnr_eval_metrics_workspace_size(int64_t n);
+
+/* AUC is exact: the midrank Mann-Whitney statistic (algebraically the
+ * trapezoid area sklearn integrates) from a full stable sort of the scores;
+ * equality is IEEE equality (-0.0 == +0.0; +-inf are ordinary values), and
+ * auc_u2 is an integer, the same whatever the kernels' order.  logloss and
+ * rmse are fixed-order fp64 reductions: the same input gives the same bits.
+ * NaN logits and labels other than 0 / 1 are counted (n_nan, n_bad_label);
+ * the metrics of such an input are unspecified (sklearn raises there; the
+ * Python layer does too).  0 <= n < 2^31; n = 0 writes a zeroed struct with
+ * NaN metrics and reads neither input nor workspace. */
+dcnr_status dcnr_eval_metrics(const float* logits, const float* labels, int64_t n,
+                              dcnr_metrics* out, void* ws, size_t ws_bytes, dcnr_stream_t stream);
 
 /* One torch.optim.AdamW (decoupled = 1) or Adam (decoupled = 0) step over
  * n_tensors tensors (host arrays of device pointers + element counts).
