@@ -44,10 +44,14 @@ __device__ __forceinline__ bool cless(float da, int ia, float db, int ib) {
   return da < db || (da == db && (unsigned)ia < (unsigned)ib);
 }
 
-// bitonic sort of n2 (a power of two) entries in LDS, ascending by (d, i);
-// all NTB threads of the block participate
-template <int NTB = NT>
-__device__ void bitonic(float* cd, int* ci, int n2 = CAP) {
+struct CandLess {
+  __device__ bool operator()(float da, int ia, float db, int ib) const { return cless(da, ia, db, ib); }
+};
+
+// bitonic sort of n2 (a power of two) entries in LDS, ascending by less (by
+// default (d, i)); all NTB threads of the block participate
+template <int NTB = NT, class I = int, class Less = CandLess>
+__device__ void bitonic(float* cd, I* ci, int n2 = CAP, Less less = Less{}) {
   for (int k2 = 2; k2 <= n2; k2 <<= 1) {
     for (int j = k2 >> 1; j > 0; j >>= 1) {
       for (int t = threadIdx.x; t < n2 / 2; t += NTB) {
@@ -55,12 +59,31 @@ __device__ void bitonic(float* cd, int* ci, int n2 = CAP) {
         const int p = i + j;
         const bool asc = (i & k2) == 0;
         const float a = cd[i], b = cd[p];
-        const int ia = ci[i], ib = ci[p];
-        const bool sw = asc ? cless(b, ib, a, ia) : cless(a, ia, b, ib);
+        const I ia = ci[i], ib = ci[p];
+        const bool sw = asc ? less(b, ib, a, ia) : less(a, ia, b, ib);
         if (sw) { cd[i] = b; cd[p] = a; ci[i] = ib; ci[p] = ia; }
       }
       __syncthreads();
     }
+  }
+}
+
+// The k best of nv candidates in LDS (room for the next power of two), sorted,
+// to idx / dist; slots past nv read (-1, FLT_MAX) (merge_kernel's rule;
+// rescore_kernel, which wrote ci / cd as they stood, always has nv >= k: at
+// least k of its n >= k distances lie at or under the k-th's bin).  All NTB
+// threads.
+template <int NTB>
+__device__ void sort_emit(float* cd, int* ci, int nv, int k, int64_t* idx, float* dist) {
+  int n2 = 2;
+  while (n2 < nv) n2 <<= 1;
+  for (int t = nv + threadIdx.x; t < n2; t += NTB) { cd[t] = FLT_MAX; ci[t] = INT_MAX; }
+  __syncthreads();
+  bitonic<NTB>(cd, ci, n2);
+  for (int t = threadIdx.x; t < k; t += NTB) {
+    const bool ok = t < nv;
+    idx[t] = ok ? (int64_t)ci[t] : -1;
+    dist[t] = ok ? cd[t] : FLT_MAX;
   }
 }
 
@@ -107,6 +130,27 @@ __device__ __forceinline__ float cos_dist(float s, float ir) {
   return fminf(fmaxf(fmaf(-s, ir, 1.f), 0.f), 2.f);
 }
 
+// one table row (d = 4 DV) as float4 chunks: its DV loads in flight together
+template <int DV>
+__device__ __forceinline__ void load_row(const float* __restrict__ tab, int64_t r, float4 (&x)[DV]) {
+  const float4* rp = reinterpret_cast<const float4*>(tab + r * DV * 4);
+#pragma unroll
+  for (int v = 0; v < DV; ++v) x[v] = rp[v];
+}
+// scan v2's exact distance of one row (x, its inverse norm ir) to one
+// normalised query (qv): the one expression every exact path uses, so they
+// agree bit for bit
+template <int DV>
+__device__ __forceinline__ float exact_dist(const float4 (&x)[DV], const float4* qv, float ir) {
+  float s = 0.f;
+#pragma unroll
+  for (int v = 0; v < DV; ++v) {
+    const float4 q = qv[v];
+    s += dot4(x[v], q);
+  }
+  return cos_dist(s, ir);
+}
+
 template <int MAXV>
 __global__ __launch_bounds__(NT) void scan_kernel(const float* __restrict__ tab,
                                                   const float* __restrict__ inv, int64_t N, int d,
@@ -117,15 +161,12 @@ __global__ __launch_bounds__(NT) void scan_kernel(const float* __restrict__ tab,
   __shared__ int ci[QT][CAP];
   __shared__ int cnt[QT];
   __shared__ float thr[QT];
-  __shared__ int need;
   const int slice = blockIdx.x;
   const int64_t q0 = (int64_t)blockIdx.y * QT;
   const int nq = (int)min<int64_t>(QT, Q - q0);
   // normalised queries (sklearn normalize(): zero norm -> unchanged)
   for (int i = threadIdx.x; i < QT * MAXV * 4; i += NT) (&qs[0][0])[i] = 0.f;
   __syncthreads();
-  if (threadIdx.x < 64 * QT) {
-  }
   for (int qq = threadIdx.x >> 6; qq < nq; qq += NT / 64) {
     const int lane = threadIdx.x & 63;
     float s = 0.f;
@@ -170,7 +211,6 @@ __global__ __launch_bounds__(NT) void scan_kernel(const float* __restrict__ tab,
       if (cnt[qq] > CAP - NT) compact(cd[qq], ci[qq], &cnt[qq], &thr[qq], k);
     }
   }
-  (void)need;
   for (int qq = 0; qq < nq; ++qq) {
     compact(cd[qq], ci[qq], &cnt[qq], &thr[qq], k);
     Cand* o = out + ((q0 + qq) * gridDim.x + slice) * k;
@@ -233,6 +273,74 @@ __device__ __forceinline__ int wave_compact(float* cd, int* ci, int c, int k, in
   return c < k ? c : k;
 }
 
+// admit (dd, r) into one wave's k-list (K2_CAP LDS slots, compacted when
+// full) while strictly under its k-th best: the per-wave list protocol of
+// scan v2 and the exact fallbacks
+__device__ __forceinline__ void wave_admit(float* lcd, int* lci, int& c, float& th, int k, int lane,
+                                           bool ok, float dd, int64_t r) {
+  bool pass = ok && dd < th;
+  uint64_t m = __ballot(pass);
+  while (m) {
+    const int room = K2_CAP - c;
+    if (room == 0) {
+      c = wave_compact(lcd, lci, c, k, lane, &th);
+      pass = pass && dd < th;
+      m = __ballot(pass);
+      continue;
+    }
+    const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+    if (pass && rank < room) {
+      lcd[c + rank] = dd;
+      lci[c + rank] = (int)r;
+    }
+    const int n = __popcll(m);
+    c += n < room ? n : room;
+    pass = pass && rank >= room;
+    m = __ballot(pass);
+  }
+}
+
+// merge NW sorted k-lists held in LDS (list ww at cd / ci + ww * lstride, its
+// count at cnt[ww * cstride]) in one wave, two lists per 64-lane sort
+// (k <= 32): the k best by (distance, row) in lanes [0, k)
+template <int NW>
+__device__ __forceinline__ void wave_merge_lists(const float* cd, const int* ci, const int* cnt, int lstride,
+                                                 int cstride, int k, int lane, float& d, int& i) {
+  d = FLT_MAX;
+  i = INT_MAX;
+  for (int ww = 0; ww < NW; ++ww) {
+    const int cw = cnt[ww * cstride];
+    const int sl = ww == 0 ? lane : lane - k;
+    if (ww == 0 || lane >= k) {
+      const bool has = sl >= 0 && sl < k && sl < cw;
+      d = has ? cd[ww * lstride + sl] : FLT_MAX;
+      i = has ? ci[ww * lstride + sl] : INT_MAX;
+    }
+    if (ww > 0) wave_sort64(d, i, lane);
+  }
+}
+
+// the same merge over nl k-lists of one query in global memory (list l at
+// pd / pi + l * k; a list of fewer than k rows is padded with FLT_MAX, whose
+// row id reads as INT_MAX)
+__device__ __forceinline__ Cand wave_merge_global_lists(const float* pd, const int64_t* pi, int64_t l0, int nl,
+                                                        int k, int lane) {
+  float d = FLT_MAX;
+  int i = INT_MAX;
+  for (int l = 0; l < nl; ++l) {
+    const int sl = l == 0 ? lane : lane - k;
+    if (l == 0 || lane >= k) {
+      const bool has = sl >= 0 && sl < k;
+      const float dv = has ? pd[(l0 + l) * k + sl] : FLT_MAX;
+      const int64_t iv = has ? pi[(l0 + l) * k + sl] : (int64_t)INT_MAX;
+      d = dv;
+      i = dv == FLT_MAX ? INT_MAX : (int)iv;
+    }
+    if (l > 0) wave_sort64(d, i, lane);
+  }
+  return Cand{d, i};
+}
+
 template <int DV>
 __global__ __launch_bounds__(K2_NT) void scan2_kernel(const float* __restrict__ tab,
                                                       const float* __restrict__ inv, int64_t N,
@@ -265,45 +373,16 @@ __global__ __launch_bounds__(K2_NT) void scan2_kernel(const float* __restrict__ 
     const bool ok = r < r1;
     const int64_t rc = ok ? r : r0;
     float4 x[DV];
-    const float4* rp = reinterpret_cast<const float4*>(tab + rc * DV * 4);
-#pragma unroll
-    for (int v = 0; v < DV; ++v) x[v] = rp[v];
+    load_row<DV>(tab, rc, x);
     const float ir = inv[rc];
     for (int qq = 0; qq < nq; ++qq) {
-      float s = 0.f;
-#pragma unroll
-      for (int v = 0; v < DV; ++v) {
-        const float4 q = qv[qq * DV + v];
-        s += dot4(x[v], q);
-      }
-      const float dist = cos_dist(s, ir);
+      const float dist = exact_dist<DV>(x, qv + qq * DV, ir);
       float th = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(thrv), qq));
       const float b0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bound0), qq));
-      bool pass = ok && dist < th && dist <= b0;
-      uint64_t m = __ballot(pass);
-      if (!m) continue;
+      const bool cand = ok && dist <= b0;
+      if (!__ballot(cand && dist < th)) continue;   // (nothing to append: the usual case)
       int c = __builtin_amdgcn_readlane(cntv, qq);
-      float* lcd = cd[w][qq];
-      int* lci = ci[w][qq];
-      while (m) {
-        const int room = K2_CAP - c;
-        if (room == 0) {
-          c = wave_compact(lcd, lci, c, k, lane, &th);
-          pass = pass && dist < th;
-          m = __ballot(pass);
-          continue;
-        }
-        const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                                   __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-        if (pass && rank < room) {
-          lcd[c + rank] = dist;
-          lci[c + rank] = (int)r;
-        }
-        const int n = __popcll(m);
-        c += n < room ? n : room;
-        pass = pass && rank >= room;
-        m = __ballot(pass);
-      }
+      wave_admit(cd[w][qq], ci[w][qq], c, th, k, lane, cand, dist, r);
       cntv = lane == qq ? c : cntv;
       thrv = lane == qq ? th : thrv;
     }
@@ -318,18 +397,9 @@ __global__ __launch_bounds__(K2_NT) void scan2_kernel(const float* __restrict__ 
   }
   __syncthreads();
   for (int qq = w; qq < nq; qq += K2_WPB) {
-    float d = FLT_MAX;
-    int i = INT_MAX;
-    for (int ww = 0; ww < K2_WPB; ++ww) {
-      const int c = cntl[ww][qq];
-      const int sl = ww == 0 ? lane : lane - k;
-      if (ww == 0 || lane >= k) {
-        const bool has = sl >= 0 && sl < k && sl < c;
-        d = has ? cd[ww][qq][sl] : FLT_MAX;
-        i = has ? ci[ww][qq][sl] : INT_MAX;
-      }
-      if (ww > 0) wave_sort64(d, i, lane);
-    }
+    float d;
+    int i;
+    wave_merge_lists<K2_WPB>(cd[0][qq], ci[0][qq], &cntl[0][qq], K2_QT * K2_CAP, K2_QT, k, lane, d, i);
     Cand* o = out + ((q0 + qq) * nslices + slice) * (int64_t)k;
     if (lane < k) o[lane] = Cand{d, i};
   }
@@ -458,18 +528,9 @@ __global__ __launch_bounds__(K2_NT) void scan3_kernel(const float* __restrict__ 
     }
   __syncthreads();
   for (int qq = w; qq < nq; qq += K2_WPB) {
-    float d = FLT_MAX;
-    int i = INT_MAX;
-    for (int ww = 0; ww < K2_WPB; ++ww) {
-      const int c = cntl[ww][qq];
-      const int sl = ww == 0 ? lane : lane - k;
-      if (ww == 0 || lane >= k) {
-        const bool has = sl >= 0 && sl < k && sl < c;
-        d = has ? cd[ww][qq][sl] : FLT_MAX;
-        i = has ? ci[ww][qq][sl] : INT_MAX;
-      }
-      if (ww > 0) wave_sort64(d, i, lane);
-    }
+    float d;
+    int i;
+    wave_merge_lists<K2_WPB>(cd[0][qq], ci[0][qq], &cntl[0][qq], K3_QT * K2_CAP, K3_QT, k, lane, d, i);
     Cand* o = out + ((q0 + qq) * nslices + slice) * (int64_t)k;
     if (lane < k) o[lane] = Cand{d, i};
   }
@@ -484,57 +545,22 @@ __global__ __launch_bounds__(K2_NT) void scan3_kernel(const float* __restrict__ 
 constexpr int TH_S = 512;   // sample rows: the bound sits near quantile k / TH_S
 constexpr float TH_MARGIN = 1e-5f;
 
-// Block qq: normalises query qq (sklearn normalize(): zero norm -> unchanged;
-// written to qn for the scan) and takes the k-th smallest sample distance by
-// a 2-pass radix select over the distances' bits (exponent + 7 mantissa
-// bits): the upper edge of the selected bin, an upper bound within 2^-7
-// relative of the exact k-th value.
-template <int DV, int NTB = 256>
-__global__ __launch_bounds__(NTB) void kth_bound_kernel(const float* __restrict__ tab,
-                                                        const float* __restrict__ inv, int64_t N,
-                                                        const float* __restrict__ q, float* qn,
-                                                        int k, float* thr0) {
-  constexpr int PT = TH_S / NTB;
-  constexpr int d = DV * 4;   // <= 64: one element per lane
+// k-th smallest of a block's keys -- the bits of non-negative floats, which
+// order like the values -- by a 2-pass radix select over exponent + 7
+// mantissa bits: returns the upper edge of the selected bin (>= the exact
+// k-th value, within 2^-7 relative), or 0xffffffff when the block holds
+// nkeys < k keys (block-uniform; as the callers' own checks said before).
+// count(hist, mask, prefix, sh) adds the calling thread's keys with
+// (key & mask) == prefix to hist[(key >> sh) & 255]: the callers hold their
+// keys differently (registers, LDS) and count them accordingly.
+// Every thread of a block of at least 256 threads (the bins are zeroed one
+// per thread) calls it.  The LDS words are static: one set per kernel, shared
+// by every call in it, so the barrier at the end lets a kernel call it again.
+template <class Count>
+__device__ __forceinline__ unsigned radix_select_kth(int k, int nkeys, Count count) {
   __shared__ unsigned hist[256];
   __shared__ unsigned sel_prefix, sel_need;
-  __shared__ int sel_fail;
-  __shared__ __attribute__((aligned(16))) float qs[d];
-  const int64_t qq = blockIdx.x;
-  if (threadIdx.x < 64) {
-    const int lane = threadIdx.x;
-    const float v = lane < d ? q[qq * d + lane] : 0.f;
-    const float ss = wave_sum(v * v);
-    const float in = ss > 0.f ? 1.f / sqrtf(ss) : 1.f;
-    if (lane < d) {
-      qs[lane] = v * in;
-      qn[qq * d + lane] = v * in;
-    }
-  }
-  __syncthreads();
-  const float4* qv = reinterpret_cast<const float4*>(qs);
-  const int S = (int)min<int64_t>(N, TH_S);
-  unsigned key[PT];
-#pragma unroll 4
-  for (int j = 0; j < PT; ++j) {
-    const int t = threadIdx.x + j * NTB;
-    float dist = FLT_MAX;
-    if (t < S) {
-      const float4* rp = reinterpret_cast<const float4*>(tab + (int64_t)t * DV * 4);
-      float4 x[DV];
-#pragma unroll
-      for (int v = 0; v < DV; ++v) x[v] = rp[v];
-      float s = 0.f;
-#pragma unroll
-      for (int v = 0; v < DV; ++v) {
-        const float4 q = qv[v];
-        s += dot4(x[v], q);
-      }
-      dist = cos_dist(s, inv[t]);
-    }
-    key[j] = __float_as_uint(dist) & 0x7fffffffu;   // >= 0: bits order like values
-  }
-  if (threadIdx.x == 0) { sel_prefix = 0; sel_need = (unsigned)k; sel_fail = S < k; }
+  if (threadIdx.x == 0) { sel_prefix = 0; sel_need = (unsigned)k; }
   unsigned mask = 0;
 #pragma unroll
   for (int pass = 0; pass < 2; ++pass) {
@@ -542,10 +568,10 @@ __global__ __launch_bounds__(NTB) void kth_bound_kernel(const float* __restrict_
     if (threadIdx.x < 256) hist[threadIdx.x] = 0;
     __syncthreads();
     const unsigned prefix = sel_prefix;
-#pragma unroll
-    for (int j = 0; j < PT; ++j)
-      if ((key[j] & mask) == prefix) atomicAdd(&hist[(key[j] >> sh) & 255u], 1u);
+    count(hist, mask, prefix, sh);
     __syncthreads();
+    // wave 0 scans the bins (4 per lane), picks the one holding the need-th
+    // key and narrows prefix / need to it
     if (threadIdx.x < 64) {
       const int lane = threadIdx.x;
       const unsigned need = sel_need;
@@ -574,9 +600,66 @@ __global__ __launch_bounds__(NTB) void kth_bound_kernel(const float* __restrict_
     mask |= 255u << sh;
     __syncthreads();
   }
+  const unsigned r = nkeys < k ? 0xffffffffu : (sel_prefix | 0xffffu);
+  __syncthreads();
+  return r;
+}
+
+// Block qq: normalises query qq (sklearn normalize(): zero norm -> unchanged;
+// written to qn for the scan) and takes the k-th smallest sample distance
+// (radix_select_kth: an upper bound within 2^-7 relative of the exact k-th
+// value; a sample of fewer than k rows has the bound +inf).
+template <int DV, int NTB = 256>
+__global__ __launch_bounds__(NTB) void kth_bound_kernel(const float* __restrict__ tab,
+                                                        const float* __restrict__ inv, int64_t N,
+                                                        const float* __restrict__ q, float* qn,
+                                                        int k, float* thr0) {
+  constexpr int PT = TH_S / NTB;
+  constexpr int d = DV * 4;   // <= 64: one element per lane
+  __shared__ __attribute__((aligned(16))) float qs[d];
+  const int64_t qq = blockIdx.x;
+  if (threadIdx.x < 64) {
+    const int lane = threadIdx.x;
+    const float v = lane < d ? q[qq * d + lane] : 0.f;
+    const float ss = wave_sum(v * v);
+    const float in = ss > 0.f ? 1.f / sqrtf(ss) : 1.f;
+    if (lane < d) {
+      qs[lane] = v * in;
+      qn[qq * d + lane] = v * in;
+    }
+  }
+  __syncthreads();
+  const float4* qv = reinterpret_cast<const float4*>(qs);
+  const int S = (int)min<int64_t>(N, TH_S);
+  unsigned key[PT];
+#pragma unroll 4
+  for (int j = 0; j < PT; ++j) {
+    const int t = threadIdx.x + j * NTB;
+    float dist = FLT_MAX;
+    if (t < S) {
+      float4 x[DV];
+      load_row<DV>(tab, t, x);
+      // exact_dist's expression, written out: through the call -- the
+      // inverse norm loaded before the dot or after it -- the kernel took up
+      // to 98 VGPRs for 66 (occupancy 4 for 7 at DV = 16)
+      float s = 0.f;
+#pragma unroll
+      for (int v = 0; v < DV; ++v) {
+        const float4 q = qv[v];
+        s += dot4(x[v], q);
+      }
+      dist = cos_dist(s, inv[t]);
+    }
+    key[j] = __float_as_uint(dist) & 0x7fffffffu;   // >= 0: bits order like values
+  }
+  const unsigned tk = radix_select_kth(k, S, [&](unsigned* hist, unsigned mask, unsigned prefix, int sh) {
+#pragma unroll
+    for (int j = 0; j < PT; ++j)
+      if ((key[j] & mask) == prefix) atomicAdd(&hist[(key[j] >> sh) & 255u], 1u);
+  });
   if (threadIdx.x == 0) {
-    const float kth = __uint_as_float(sel_prefix | 0xffffu);
-    thr0[qq] = (sel_fail || !(kth < 2.5f)) ? FLT_MAX : kth + TH_MARGIN;
+    const float kth = __uint_as_float(tk);   // (NaN: S < k)
+    thr0[qq] = !(kth < 2.5f) ? FLT_MAX : kth + TH_MARGIN;
   }
 }
 
@@ -622,23 +705,12 @@ inline int v4_rpb(int nqb, int64_t N) {
 constexpr int64_t V4_Q1_N = 800000;   // a single query takes scan v2 below this many rows
                                       // (from Q = 2: 60-66 us for Q <= 8 against 65-98 on scan v2)
 
-// k-th smallest of n distances (>= 0) held in LDS, by a 2-pass radix select
-// over their bits (exponent + 7 mantissa bits): returns the upper edge of the
-// selected bin (>= the exact k-th value, within 2^-7 relative), or
-// 0xffffffff when n < k.  Every thread of the block calls it.
+// k-th smallest of n distances (>= 0) held in LDS (radix_select_kth: the
+// upper edge of the k-th's bin, or 0xffffffff when n < k).  Every thread of
+// the block calls it.
 template <int NTB>
 __device__ unsigned block_select_kth(const float* v, int n, int k) {
-  __shared__ unsigned hist[256];
-  __shared__ unsigned sel_prefix, sel_need;
-  __shared__ int sel_fail;
-  if (threadIdx.x == 0) { sel_prefix = 0; sel_need = (unsigned)k; sel_fail = n < k; }
-  unsigned mask = 0;
-#pragma unroll
-  for (int pass = 0; pass < 2; ++pass) {
-    const int sh = 24 - 8 * pass;
-    if (threadIdx.x < 256) hist[threadIdx.x] = 0;
-    __syncthreads();
-    const unsigned prefix = sel_prefix;
+  return radix_select_kth(k, n, [&](unsigned* hist, unsigned mask, unsigned prefix, int sh) {
     // distances crowd into a few bins (one exponent spans a factor of 2), so
     // equal bins of a wave are counted with one atomic (up to 4 bins per
     // wave-instruction; the rest of the lanes add one each): plain per-lane
@@ -659,37 +731,7 @@ __device__ unsigned block_select_kth(const float* v, int n, int k) {
       }
       if ((act >> lane) & 1ull) atomicAdd(&hist[bin], 1u);
     }
-    __syncthreads();
-    if (threadIdx.x < 64) {
-      const unsigned need = sel_need;
-      unsigned h[4], sum = 0;
-#pragma unroll
-      for (int b = 0; b < 4; ++b) { h[b] = hist[4 * lane + b]; sum += h[b]; }
-      unsigned incl = sum;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const unsigned x = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += x;
-      }
-      unsigned cum = incl - sum;
-      if (cum < need && need <= incl) {
-#pragma unroll
-        for (int b = 0; b < 4; ++b) {
-          if (cum + h[b] >= need) {
-            sel_prefix = prefix | ((unsigned)(4 * lane + b) << sh);
-            sel_need = need - cum;
-            break;
-          }
-          cum += h[b];
-        }
-      }
-    }
-    mask |= 255u << sh;
-    __syncthreads();
-  }
-  const unsigned r = sel_fail ? 0xffffffffu : (sel_prefix | 0xffffu);
-  __syncthreads();
-  return r;
+  });
 }
 
 constexpr int B4_T = 1024;   // threads of the per-query v4 kernels
@@ -1163,65 +1205,6 @@ __global__ __launch_bounds__(256, NQB > 4 ? V4_WPS : 1) void scan4_kernel(const 
 // the waves' sorted k-lists.  The same (distance, row) order as every other
 // scan, so a query that lands here returns what scan v2 returns.  Needs
 // k <= 32 (two k-lists per 64-lane merge step) and 16 * 64 * 8 B of LDS.
-// scan v2's exact distance of one row (x, its inverse norm ir) to one
-// normalised query (wave-uniform qv): the one expression every exact path
-// uses, so they agree bit for bit
-template <int DV>
-__device__ __forceinline__ float exact_dist(const float4 (&x)[DV], const float4* qv, float ir) {
-  float s = 0.f;
-#pragma unroll
-  for (int v = 0; v < DV; ++v) {
-    const float4 q = qv[v];
-    s += dot4(x[v], q);
-  }
-  return cos_dist(s, ir);
-}
-
-// admit (dd, r) into one wave's k-list (64 LDS slots, compacted when full)
-// while strictly under its k-th best: scan v2's per-wave list protocol
-__device__ __forceinline__ void wave_admit(float* lcd, int* lci, int& c, float& th, int k, int lane,
-                                           bool ok, float dd, int64_t r) {
-  bool pass = ok && dd < th;
-  uint64_t m = __ballot(pass);
-  while (m) {
-    const int room = 64 - c;
-    if (room == 0) {
-      c = wave_compact(lcd, lci, c, k, lane, &th);
-      pass = pass && dd < th;
-      m = __ballot(pass);
-      continue;
-    }
-    const int rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-    if (pass && rank < room) {
-      lcd[c + rank] = dd;
-      lci[c + rank] = (int)r;
-    }
-    const int n = __popcll(m);
-    c += n < room ? n : room;
-    pass = pass && rank >= room;
-    m = __ballot(pass);
-  }
-}
-
-// merge NW sorted wave k-lists (wave ww's at cd[ww * 64], ci[ww * 64], counts
-// cnt[ww]) in one wave: the k best by (distance, row) in lanes [0, k)
-template <int NW>
-__device__ __forceinline__ void wave_merge_lists(const float* cd, const int* ci, const int* cnt, int k,
-                                                 int lane, float& d, int& i) {
-  d = FLT_MAX;
-  i = INT_MAX;
-  for (int ww = 0; ww < NW; ++ww) {
-    const int cw = cnt[ww];
-    const int sl = ww == 0 ? lane : lane - k;
-    if (ww == 0 || lane >= k) {
-      const bool has = sl >= 0 && sl < k && sl < cw;
-      d = has ? cd[ww * 64 + sl] : FLT_MAX;
-      i = has ? ci[ww * 64 + sl] : INT_MAX;
-    }
-    if (ww > 0) wave_sort64(d, i, lane);
-  }
-}
-
 template <int DV>
 __device__ void exact_query_topk(const float* __restrict__ tab, const float* __restrict__ inv, int64_t lo,
                                  int64_t N, const float* __restrict__ qrow, int k, float* lds, int64_t* idx,
@@ -1240,9 +1223,7 @@ __device__ void exact_query_topk(const float* __restrict__ tab, const float* __r
     const bool ok = r < N;
     const int64_t rc = ok ? r : 0;
     float4 x[DV];
-    const float4* rp = reinterpret_cast<const float4*>(tab + rc * DV * 4);
-#pragma unroll
-    for (int v = 0; v < DV; ++v) x[v] = rp[v];
+    load_row<DV>(tab, rc, x);
     const float dd = exact_dist<DV>(x, qv, inv[rc]);
     wave_admit(lcd, lci, c, th, k, lane, ok, dd, r);
   }
@@ -1252,7 +1233,7 @@ __device__ void exact_query_topk(const float* __restrict__ tab, const float* __r
   if (w == 0) {
     float d;
     int i;
-    wave_merge_lists<NW>(lds, reinterpret_cast<const int*>(lds + NW * 64), cntl, k, lane, d, i);
+    wave_merge_lists<NW>(lds, reinterpret_cast<const int*>(lds + NW * 64), cntl, 64, 1, k, lane, d, i);
     if (lane < k) {
       idx[lane] = (int64_t)i;
       dist[lane] = d;
@@ -1349,7 +1330,7 @@ __device__ void exact_batch_item(const float* __restrict__ tab, const float* __r
     if (!((act >> qi) & 1u)) continue;
     float d;
     int i;
-    wave_merge_lists<NW>(bcd + qi * NW * 64, bci + qi * NW * 64, bcnt + qi * NW, k, lane, d, i);
+    wave_merge_lists<NW>(bcd + qi * NW * 64, bci + qi * NW * 64, bcnt + qi * NW, 64, 1, k, lane, d, i);
     if (lane < k) {
       pd[qi * lstride + lane] = d;
       pi[qi * lstride + lane] = (int64_t)i;
@@ -1403,22 +1384,10 @@ __device__ __attribute__((noinline)) void batch_fallback_pool(
       for (int qi = w; qi < V4_BQ; qi += NW) {
         if (!((act >> qi) & 1u)) continue;
         const int64_t qq = q0 + qi;
-        float d = FLT_MAX;
-        int i = INT_MAX;
-        for (int ff = 0; ff < FB; ++ff) {
-          const int sl = ff == 0 ? lane : lane - k;
-          if (ff == 0 || lane >= k) {
-            const bool has = sl >= 0 && sl < k;
-            const float dv = has ? pd[(qq * FB + ff) * k + sl] : FLT_MAX;
-            const int64_t iv = has ? pi[(qq * FB + ff) * k + sl] : (int64_t)INT_MAX;
-            d = dv;
-            i = dv == FLT_MAX ? INT_MAX : (int)iv;
-          }
-          if (ff > 0) wave_sort64(d, i, lane);
-        }
+        const Cand c = wave_merge_global_lists(pd, pi, qq * FB, FB, k, lane);
         if (lane < k) {
-          idx[qq * k + lane] = (int64_t)i;
-          dist[qq * k + lane] = d;
+          idx[qq * k + lane] = (int64_t)c.i;
+          dist[qq * k + lane] = c.d;
         }
       }
     }
@@ -1502,22 +1471,10 @@ __global__ __launch_bounds__(B4_T) void rescore_kernel(const float* __restrict__
     if (!last_arriver(pcnt + qq, F, &last)) return;
     if (threadIdx.x < 64) {
       const int lane = threadIdx.x;
-      float d = FLT_MAX;
-      int i = INT_MAX;
-      for (int ff = 0; ff < F; ++ff) {
-        const int sl = ff == 0 ? lane : lane - k;
-        if (ff == 0 || lane >= k) {
-          const bool has = sl >= 0 && sl < k;
-          const float dv = has ? pd[(qq * F + ff) * k + sl] : FLT_MAX;
-          const int64_t iv = has ? pi[(qq * F + ff) * k + sl] : (int64_t)INT_MAX;
-          d = dv;
-          i = dv == FLT_MAX ? INT_MAX : (int)iv;   // (a range shorter than k: FLT_MAX / INT_MAX pads)
-        }
-        if (ff > 0) wave_sort64(d, i, lane);
-      }
+      const Cand c = wave_merge_global_lists(pd, pi, qq * F, F, k, lane);
       if (lane < k) {
-        idx[qq * k + lane] = (int64_t)i;
-        dist[qq * k + lane] = d;
+        idx[qq * k + lane] = (int64_t)c.i;
+        dist[qq * k + lane] = c.d;
       }
     }
   };
@@ -1569,15 +1526,7 @@ __global__ __launch_bounds__(B4_T) void rescore_kernel(const float* __restrict__
     if (pool) join_pool();
     return;
   }
-  int n2 = 2;
-  while (n2 < nv) n2 <<= 1;
-  for (int t = nv + threadIdx.x; t < n2; t += B4_T) { cd[t] = FLT_MAX; ci[t] = INT_MAX; }
-  __syncthreads();
-  bitonic<B4_T>(cd, ci, n2);
-  for (int t = threadIdx.x; t < k; t += B4_T) {
-    idx[qq * k + t] = (int64_t)ci[t];
-    dist[qq * k + t] = cd[t];
-  }
+  sort_emit<B4_T>(cd, ci, nv, k, idx + qq * k, dist + qq * k);
   if (pool) join_pool();
 }
 
@@ -1586,31 +1535,24 @@ __global__ __launch_bounds__(B4_T) void rescore_kernel(const float* __restrict__
 // running k-th best and compacted in LDS.
 constexpr int MT = 16;
 constexpr int FT = 24;   // fast path: candidates loaded per thread per round
-// groups > 1: block (query, group) merges lists [g*lpg, (g+1)*lpg) of its
-// query into gout[query][group] (a first stage); groups == 1: the final
-// stage writes idx / dist.
-__global__ __launch_bounds__(NT) void merge_kernel(const Cand* in, int nslices, int k,
-                                                   int64_t* idx, float* dist, int groups,
-                                                   Cand* gout) {
+__global__ __launch_bounds__(NT) void merge_kernel(const Cand* in, int nl, int k, int64_t* idx,
+                                                   float* dist) {
   __shared__ float cd[CAP];
   __shared__ int ci[CAP];
   __shared__ int cnt;
   __shared__ float thr;
-  const int64_t qq = blockIdx.x / groups;
-  const int grp = blockIdx.x % groups;
-  const int lpg = (nslices + groups - 1) / groups;
-  const int l0 = grp * lpg, nl = max(0, min(lpg, nslices - l0));
-  const Cand* c = in + (qq * (int64_t)nslices + l0) * k;
+  const int64_t qq = blockIdx.x;
+  const Cand* c = in + qq * (int64_t)nl * k;
   const int total = nl * k;
-  // fast path 0 (final stage, one load round, up to 4 lists per thread): the
-  // k-th smallest of the lists' minima bounds the k-th best overall (k lists
-  // each hold a candidate at or under it), so only the candidates at or under
-  // that bound -- found by a 2-pass radix select over the minima -- are sorted.
-  // Same result as sorting them all: every candidate of the k best passes.
-  if (groups == 1 && total <= NT * FT && nl <= 4 * NT) {
-    __shared__ unsigned hist[256];
-    __shared__ unsigned sel_prefix, sel_need;
-    __shared__ int sel_fail;
+  idx += qq * k;
+  dist += qq * k;
+  // fast path 0 (one load round, up to 4 lists per thread): the k-th smallest
+  // of the lists' minima bounds the k-th best overall (k lists each hold a
+  // candidate at or under it), so only the candidates at or under that bound
+  // -- radix_select_kth over the nl minima, which fails with fewer than k
+  // lists -- are sorted.  Same result as sorting them all: every candidate of
+  // the k best passes.
+  if (total <= NT * FT && nl <= 4 * NT) {
     Cand e[FT];
 #pragma unroll
     for (int j = 0; j < FT; ++j) {
@@ -1628,51 +1570,13 @@ __global__ __launch_bounds__(NT) void merge_kernel(const Cand* in, int nslices, 
         for (int j = 0; j < k; ++j) m = fminf(m, c[(int64_t)l * k + j].d);
       mk[r] = l < nl ? key(m) : 0xffffffffu;
     }
-    if (threadIdx.x == 0) { sel_prefix = 0; sel_need = (unsigned)k; sel_fail = 0; }
-    unsigned mask = 0;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-      const int sh = 24 - 8 * pass;
-      for (int b = threadIdx.x; b < 256; b += NT) hist[b] = 0;
-      __syncthreads();
-      const unsigned prefix = sel_prefix;
+    if (threadIdx.x == 0) cnt = 0;   // (the select's barriers order it before the appends)
+    const unsigned tk = radix_select_kth(k, nl, [&](unsigned* hist, unsigned mask, unsigned prefix, int sh) {
 #pragma unroll
       for (int r = 0; r < 4; ++r)
         if (mk[r] != 0xffffffffu && (mk[r] & mask) == prefix) atomicAdd(&hist[(mk[r] >> sh) & 255u], 1u);
-      __syncthreads();
-      if (threadIdx.x < 64) {
-        const int lane = threadIdx.x;
-        const unsigned need = sel_need;
-        unsigned h[4], sum = 0;
-#pragma unroll
-        for (int b = 0; b < 4; ++b) { h[b] = hist[4 * lane + b]; sum += h[b]; }
-        unsigned incl = sum;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-          const unsigned v = __shfl_up(incl, off, 64);
-          if (lane >= off) incl += v;
-        }
-        unsigned cum = incl - sum;
-        if (cum < need && need <= incl) {
-#pragma unroll
-          for (int b = 0; b < 4; ++b) {
-            if (cum + h[b] >= need) {
-              sel_prefix = prefix | ((unsigned)(4 * lane + b) << sh);
-              sel_need = need - cum;
-              break;
-            }
-            cum += h[b];
-          }
-        }
-        if (lane == 63 && incl < need) sel_fail = 1;   // fewer than k lists hold candidates
-      }
-      mask |= 255u << sh;
-      __syncthreads();
-    }
-    if (!sel_fail) {
-      const unsigned tk = sel_prefix | 0xffffu;
-      if (threadIdx.x == 0) cnt = 0;
-      __syncthreads();
+    });
+    if (tk != 0xffffffffu) {
       constexpr int SCAP = 128;
 #pragma unroll
       for (int j = 0; j < FT; ++j)
@@ -1683,16 +1587,7 @@ __global__ __launch_bounds__(NT) void merge_kernel(const Cand* in, int nslices, 
       __syncthreads();
       const int nv = cnt;
       if (nv <= SCAP) {
-        int n2 = 2;
-        while (n2 < nv) n2 <<= 1;
-        for (int t = nv + threadIdx.x; t < n2; t += NT) { cd[t] = FLT_MAX; ci[t] = INT_MAX; }
-        __syncthreads();
-        bitonic(cd, ci, n2);
-        for (int t = threadIdx.x; t < k; t += NT) {
-          const bool ok = t < nv;
-          idx[qq * k + t] = ok ? (int64_t)ci[t] : -1;
-          dist[qq * k + t] = ok ? cd[t] : FLT_MAX;
-        }
+        sort_emit<NT>(cd, ci, nv, k, idx, dist);
         return;
       }
     }
@@ -1719,20 +1614,7 @@ __global__ __launch_bounds__(NT) void merge_kernel(const Cand* in, int nslices, 
   __syncthreads();
   const int nv = cnt;
   if (nv <= CAP) {
-    int n2 = 2;
-    while (n2 < nv) n2 <<= 1;
-    for (int t = nv + threadIdx.x; t < n2; t += NT) { cd[t] = FLT_MAX; ci[t] = INT_MAX; }
-    __syncthreads();
-    bitonic(cd, ci, n2);
-    for (int t = threadIdx.x; t < k; t += NT) {
-      const bool ok = t < nv;
-      if (groups > 1) {
-        gout[(qq * groups + grp) * k + t] = Cand{ok ? cd[t] : FLT_MAX, ok ? ci[t] : INT_MAX};
-      } else {
-        idx[qq * k + t] = ok ? (int64_t)ci[t] : -1;
-        dist[qq * k + t] = ok ? cd[t] : FLT_MAX;
-      }
-    }
+    sort_emit<NT>(cd, ci, nv, k, idx, dist);
     return;
   }
   __syncthreads();
@@ -1758,13 +1640,9 @@ __global__ __launch_bounds__(NT) void merge_kernel(const Cand* in, int nslices, 
   }
   compact(cd, ci, &cnt, &thr, k);
   for (int t = threadIdx.x; t < k; t += NT) {
-    bool ok = t < cnt;
-    if (groups > 1) {
-      gout[(qq * groups + grp) * k + t] = Cand{ok ? cd[t] : FLT_MAX, ok ? ci[t] : INT_MAX};
-    } else {
-      idx[qq * k + t] = ok ? (int64_t)ci[t] : -1;
-      dist[qq * k + t] = ok ? cd[t] : FLT_MAX;
-    }
+    const bool ok = t < cnt;
+    idx[t] = ok ? (int64_t)ci[t] : -1;
+    dist[t] = ok ? cd[t] : FLT_MAX;
   }
 }
 
@@ -1792,21 +1670,9 @@ __global__ __launch_bounds__(NT) void topk_merge_kernel(const float* dist, const
     }
   }
   __syncthreads();
-  for (int k2 = 2; k2 <= n2; k2 <<= 1) {
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      for (int t = threadIdx.x; t < n2 / 2; t += NT) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-        const int p = i + j;
-        const bool asc = (i & k2) == 0;
-        const float a = cd[i], b = cd[p];
-        const uint64_t ia = ci[i], ib = ci[p];
-        const bool bl = b < a || (b == a && ib < ia);
-        const bool al = a < b || (a == b && ia < ib);
-        if (asc ? bl : al) { cd[i] = b; cd[p] = a; ci[i] = ib; ci[p] = ia; }
-      }
-      __syncthreads();
-    }
-  }
+  bitonic<NT>(cd, ci, n2, [](float da, uint64_t ia, float db, uint64_t ib) {
+    return da < db || (da == db && ia < ib);
+  });
   for (int t = threadIdx.x; t < k; t += NT) {
     out_idx[qq * k + t] = (int64_t)ci[t];
     out_dist[qq * k + t] = cd[t];
@@ -1824,7 +1690,7 @@ __global__ void inv_norm_kernel(const float* t, int64_t N, int d, float* out) {
   }
 }
 
-void plan(int64_t N, int64_t Q, int k, int* nslices, int64_t* rows_per_slice) {
+void plan(int64_t N, int64_t Q, int* nslices, int64_t* rows_per_slice) {
   int64_t qtiles = cdiv(Q, QT);
   int64_t want = std::max<int64_t>(1, 2048 / qtiles);
   int64_t ns = std::min<int64_t>(want, std::max<int64_t>(1, cdiv(N, 2048)));
@@ -1905,7 +1771,7 @@ TopkWs carve_topk(void* ws, int64_t N, int64_t Q, int k, int d) {
   Bump b(ws);
   const bool v2 = use_v2(d, k);
   if (v2) plan2(N, &w.ns, &w.rps);
-  else plan(N, Q, k, &w.ns, &w.rps);
+  else plan(N, Q, &w.ns, &w.rps);
   w.cands = (Cand*)b.take((size_t)Q * w.ns * k * sizeof(Cand));
   w.total = b.off;
   if (!v2) return w;
@@ -1932,10 +1798,30 @@ TopkWs carve_topk(void* ws, int64_t N, int64_t Q, int k, int d) {
 // merge 50 us -- the block barriers of a one-block kernel dominate all of them.
 dcnr_status merge_lists(const Cand* cands, int64_t Q, int ns, int k, int64_t* idx, float* dist,
                         hipStream_t s) {
-  hipLaunchKernelGGL(merge_kernel, dim3((unsigned)Q), dim3(NT), 0, s, cands, ns, k, idx, dist, 1,
-                     nullptr);
+  hipLaunchKernelGGL(merge_kernel, dim3((unsigned)Q), dim3(NT), 0, s, cands, ns, k, idx, dist);
   DCNR_LAUNCH_CHECK();
   return DCNR_OK;
+}
+
+// The kernels' compile-time shapes, each chosen in one place: f is called
+// with the shape as std::integral_constant arguments.
+template <int V> using ic = std::integral_constant<int, V>;
+// d / 4 in [1, 16] (scan v2's widths)
+template <int DV = 1, class F>
+void with_dv(int dv, F f) {
+  if (dv == DV) f(ic<DV>{});
+  else if constexpr (DV < 16) with_dv<DV + 1>(dv, f);
+}
+// scan v4: KS = d / 32 (1 or 2), and whether the fit-time bf16 copy is read
+template <class F>
+void with_v4_rows(int d, bool packed, F f) {
+  if (d == 32) packed ? f(ic<1>{}, std::true_type{}) : f(ic<1>{}, std::false_type{});
+  else packed ? f(ic<2>{}, std::true_type{}) : f(ic<2>{}, std::false_type{});
+}
+// ... and the 16-query blocks per scan4 block (2, 4, 8 or 16)
+template <class F>
+void with_v4_nqb(int nqb, F f) {
+  nqb == 2 ? f(ic<2>{}) : nqb == 4 ? f(ic<4>{}) : nqb == 8 ? f(ic<8>{}) : f(ic<16>{});
 }
 
 // enough for every d (the v2 path keeps Q x d <= Q x 64 normalised queries;
@@ -1953,136 +1839,96 @@ dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_
     return DCNR_UNSUPPORTED_SHAPE;
   }
   if (Q <= 0) return DCNR_OK;
-  const auto [ns, rps, cands, qn, thr0, qb, qcnt, rows, dists, bmins, split_d, split_i, total] =
-      carve_topk(ws, N, Q, k, d);
-  if (ws_bytes < total) {
+  const TopkWs w = carve_topk(ws, N, Q, k, d);
+  if (ws_bytes < w.total) {
     set_error("cosine_topk: workspace too small");
     return DCNR_WORKSPACE_TOO_SMALL;
   }
-  if (use_v2(d, k)) {
-    // normalised queries + admission bounds, one block per query (v4 makes
-    // its own, from a larger sample, below)
-    const bool v4 = use_v4(N, Q, d, k);
-    if (!v4) {
-      switch (d / 4) {
-#define CASEK(n)                                                                             \
-  case n:                                                                                    \
-    hipLaunchKernelGGL(kth_bound_kernel<n>, dim3((unsigned)Q), dim3(256), 0, s, t, inv, N, q, qn, k, \
-                       thr0);                                                                          \
-    break;
-        CASEK(1) CASEK(2) CASEK(3) CASEK(4) CASEK(5) CASEK(6) CASEK(7) CASEK(8)
-        CASEK(9) CASEK(10) CASEK(11) CASEK(12) CASEK(13) CASEK(14) CASEK(15) CASEK(16)
-#undef CASEK
-      }
-      DCNR_LAUNCH_CHECK();
-    }
-    if (v4) {
-      // query blocks of 16: NQB per launch row (the table is read once per
-      // NQB * 16 queries)
-      const int nqb = (int)std::min<int64_t>(cdiv(Q, 16), V4_QC / 16);
-      const int NQ = nqb <= 2 ? 2 : nqb <= 4 ? 4 : nqb <= 8 ? 8 : 16;
-      const int rpb = v4_rpb(NQ, N);
-      const dim3 g4((unsigned)cdiv(N, rpb), (unsigned)cdiv(Q, NQ * 16));
-      // the admission bound from the first V4_S rows (bound5_kernel), its
-      // minima merged by scan4 itself up to V4_MQ queries
-      const int ng = (int)cdiv(std::min<int64_t>(N, V4_S), B5_C);
-      const bool merge4 = Q <= V4_MQ;
-      {
-        const int qg = merge4 ? 1 : B5_QG;
-        const dim3 gb((unsigned)ng, (unsigned)cdiv(Q, 16 * qg));
-#define BOUND5(ks, pk)                                                                                         \
-  do {                                                                                                         \
-    if (merge4)                                                                                                \
-      hipLaunchKernelGGL((bound5_kernel<ks, pk, 1>), gb, dim3(256), 0, s, t, inv, tb, N, q, Q, qn, qb, qcnt, bmins); \
-    else                                                                                                       \
-      hipLaunchKernelGGL((bound5_kernel<ks, pk, B5_QG>), gb, dim3(256), 0, s, t, inv, tb, N, q, Q, qn, qb, qcnt,     \
-                         bmins);                                                                               \
-  } while (0)
-        if (d == 32) {
-          if (tb) BOUND5(1, true);
-          else BOUND5(1, false);
-        } else {
-          if (tb) BOUND5(2, true);
-          else BOUND5(2, false);
-        }
-#undef BOUND5
-        DCNR_LAUNCH_CHECK();
-        if (!merge4) {
-          hipLaunchKernelGGL(bound5_merge_kernel, dim3((unsigned)cdiv(Q, 4)), dim3(256), 0, s, bmins, ng, Q, k,
-                             thr0);
-          DCNR_LAUNCH_CHECK();
-        }
-      }
-#define SCAN4(ks, nq, pk, g, n, rp)                                                                    \
-  hipLaunchKernelGGL((scan4_kernel<ks, nq, pk>), g, dim3(256), 0, s, t, inv, tb, n, rp, qb, thr0, qn, \
-                     Q, qcnt, rows, dists, merge4 ? bmins : nullptr, ng, k)
-#define CASE4(ks, nq, sel, g, n, rp)                                  \
-  if (d == 32 * ks && sel == nq) {                                    \
-    if (tb) SCAN4(ks, nq, true, g, n, rp);                            \
-    else SCAN4(ks, nq, false, g, n, rp);                              \
-  }
-#define CASES4(sel, g, n, rp)                                                             \
-  CASE4(1, 2, sel, g, n, rp) CASE4(1, 4, sel, g, n, rp) CASE4(1, 8, sel, g, n, rp)         \
-  CASE4(1, 16, sel, g, n, rp) CASE4(2, 2, sel, g, n, rp) CASE4(2, 4, sel, g, n, rp)        \
-  CASE4(2, 8, sel, g, n, rp) CASE4(2, 16, sel, g, n, rp)
-      CASES4(NQ, g4, N, rpb)
-      DCNR_LAUNCH_CHECK();
-      // (a query whose list overflowed: the split fallback for Q <= V4_FQ,
-      // else the batched fallback's pool, inside these blocks)
-      const int F = v4_fallback_split(Q);
-      const int FB = v4_batch_chunks(Q);
-      const unsigned nb = (unsigned)(Q * F);
-      if (d == 32)
-        hipLaunchKernelGGL(rescore_kernel<8>, dim3(nb), dim3(B4_T), 0, s, dists, qcnt, rows, k,
-                           idx, dist, t, inv, N, qn, Q, F, FB, split_d, split_i, qcnt + Q + 1);
-      else
-        hipLaunchKernelGGL(rescore_kernel<16>, dim3(nb), dim3(B4_T), 0, s, dists, qcnt, rows, k,
-                           idx, dist, t, inv, N, qn, Q, F, FB, split_d, split_i, qcnt + Q + 1);
-      DCNR_LAUNCH_CHECK();
-#undef CASES4
-#undef CASE4
-#undef SCAN4
-      return DCNR_OK;
-    }
-    if (!v4 && Q >= MFMA_MIN_Q && d % 16 == 0) {
-      const int qtiles = (int)cdiv(Q, K3_QT);
-      const int64_t blocks = rup(ns, 8) * qtiles;
-      switch (d / 16) {
-#define CASE3(n)                                                                                   \
-  case n:                                                                                          \
-    hipLaunchKernelGGL(scan3_kernel<4 * n>, dim3((unsigned)blocks), dim3(K2_NT), 0, s, t, inv, N,  \
-                       qn, Q, k, rps, ns, qtiles, cands, thr0);                              \
-    break;
-        CASE3(1) CASE3(2) CASE3(3) CASE3(4)
-#undef CASE3
-      }
-      DCNR_LAUNCH_CHECK();
-      return merge_lists(cands, Q, ns, k, idx, dist, s);
-    }
-    // scan v2: the exact VALU scan (the same distance arithmetic as v4's
-    // rescoring and its per-query fallback)
-    const int qtiles = (int)cdiv(Q, K2_QT);
-    const int64_t blocks = rup(ns, 8) * qtiles;
-    switch (d / 4) {
-#define CASE(n)                                                                                  \
-  case n:                                                                                        \
-    hipLaunchKernelGGL(scan2_kernel<n>, dim3((unsigned)blocks), dim3(K2_NT), 0, s, t, inv, N, qn, \
-                       Q, k, rps, ns, qtiles, cands, thr0);                                \
-    break;
-      CASE(1) CASE(2) CASE(3) CASE(4) CASE(5) CASE(6) CASE(7) CASE(8)
-      CASE(9) CASE(10) CASE(11) CASE(12) CASE(13) CASE(14) CASE(15) CASE(16)
-#undef CASE
-    }
+  if (!use_v2(d, k)) {   // scan v1
+    const dim3 grid(w.ns, (unsigned)cdiv(Q, QT));
+    if (d <= 64)
+      hipLaunchKernelGGL(scan_kernel<16>, grid, dim3(NT), 0, s, t, inv, N, d, q, Q, k, w.rps, w.cands);
+    else
+      hipLaunchKernelGGL(scan_kernel<64>, grid, dim3(NT), 0, s, t, inv, N, d, q, Q, k, w.rps, w.cands);
     DCNR_LAUNCH_CHECK();
-    return merge_lists(cands, Q, ns, k, idx, dist, s);
+    return merge_lists(w.cands, Q, w.ns, k, idx, dist, s);
   }
-  dim3 grid(ns, (unsigned)cdiv(Q, QT));
-  if (d <= 64)
-    hipLaunchKernelGGL(scan_kernel<16>, grid, dim3(NT), 0, s, t, inv, N, d, q, Q, k, rps, cands);
-  else
-    hipLaunchKernelGGL(scan_kernel<64>, grid, dim3(NT), 0, s, t, inv, N, d, q, Q, k, rps, cands);
+  if (use_v4(N, Q, d, k)) {
+    // query blocks of 16: NQB per launch row (the table is read once per
+    // NQB * 16 queries)
+    const int nqb = (int)std::min<int64_t>(cdiv(Q, 16), V4_QC / 16);
+    const int NQ = nqb <= 2 ? 2 : nqb <= 4 ? 4 : nqb <= 8 ? 8 : 16;
+    const int rpb = v4_rpb(NQ, N);
+    const dim3 g4((unsigned)cdiv(N, rpb), (unsigned)cdiv(Q, NQ * 16));
+    // the admission bound from the first V4_S rows (bound5_kernel, which also
+    // normalises the queries), its minima merged by scan4 itself up to V4_MQ
+    // queries
+    const int ng = (int)cdiv(std::min<int64_t>(N, V4_S), B5_C);
+    const bool merge4 = Q <= V4_MQ;
+    const dim3 gb((unsigned)ng, (unsigned)cdiv(Q, 16 * (merge4 ? 1 : B5_QG)));
+    with_v4_rows(d, tb != nullptr, [&](auto ks, auto pk) {
+      constexpr int KS = decltype(ks)::value;
+      constexpr bool PK = decltype(pk)::value;
+      if (merge4)
+        hipLaunchKernelGGL((bound5_kernel<KS, PK, 1>), gb, dim3(256), 0, s, t, inv, tb, N, q, Q, w.qn, w.qb,
+                           w.qcnt, w.bmins);
+      else
+        hipLaunchKernelGGL((bound5_kernel<KS, PK, B5_QG>), gb, dim3(256), 0, s, t, inv, tb, N, q, Q, w.qn, w.qb,
+                           w.qcnt, w.bmins);
+    });
+    DCNR_LAUNCH_CHECK();
+    if (!merge4) {
+      hipLaunchKernelGGL(bound5_merge_kernel, dim3((unsigned)cdiv(Q, 4)), dim3(256), 0, s, w.bmins, ng, Q, k,
+                         w.thr0);
+      DCNR_LAUNCH_CHECK();
+    }
+    with_v4_rows(d, tb != nullptr, [&](auto ks, auto pk) {
+      with_v4_nqb(NQ, [&](auto nq) {
+        hipLaunchKernelGGL((scan4_kernel<decltype(ks)::value, decltype(nq)::value, decltype(pk)::value>), g4,
+                           dim3(256), 0, s, t, inv, tb, N, rpb, w.qb, w.thr0, w.qn, Q, w.qcnt, w.rows, w.dists,
+                           merge4 ? w.bmins : nullptr, ng, k);
+      });
+    });
+    DCNR_LAUNCH_CHECK();
+    // (a query whose list overflowed: the split fallback for Q <= V4_FQ,
+    // else the batched fallback's pool, inside these blocks)
+    const int F = v4_fallback_split(Q);
+    const int FB = v4_batch_chunks(Q);
+    const unsigned nb = (unsigned)(Q * F);
+    if (d == 32)
+      hipLaunchKernelGGL(rescore_kernel<8>, dim3(nb), dim3(B4_T), 0, s, w.dists, w.qcnt, w.rows, k, idx, dist, t,
+                         inv, N, w.qn, Q, F, FB, w.split_d, w.split_i, w.qcnt + Q + 1);
+    else
+      hipLaunchKernelGGL(rescore_kernel<16>, dim3(nb), dim3(B4_T), 0, s, w.dists, w.qcnt, w.rows, k, idx, dist, t,
+                         inv, N, w.qn, Q, F, FB, w.split_d, w.split_i, w.qcnt + Q + 1);
+    DCNR_LAUNCH_CHECK();
+    return DCNR_OK;
+  }
+  // scans v2 / v3: normalised queries + admission bounds, one block per query
+  with_dv(d / 4, [&](auto dv) {
+    hipLaunchKernelGGL(kth_bound_kernel<decltype(dv)::value>, dim3((unsigned)Q), dim3(256), 0, s, t, inv, N, q,
+                       w.qn, k, w.thr0);
+  });
   DCNR_LAUNCH_CHECK();
-  return merge_lists(cands, Q, ns, k, idx, dist, s);
+  const bool v3 = Q >= MFMA_MIN_Q && d % 16 == 0;
+  const int qtiles = (int)cdiv(Q, v3 ? K3_QT : K2_QT);
+  const dim3 blocks((unsigned)(rup(w.ns, 8) * qtiles));
+  // scan v3 where it applies, else scan v2: the exact VALU scan (the same
+  // distance arithmetic as v4's rescoring and its per-query fallback)
+  with_dv(d / 4, [&](auto dv) {
+    constexpr int DV = decltype(dv)::value;
+    if constexpr (DV % 4 == 0) {
+      if (v3) {
+        hipLaunchKernelGGL(scan3_kernel<DV>, blocks, dim3(K2_NT), 0, s, t, inv, N, w.qn, Q, k, w.rps, w.ns, qtiles,
+                           w.cands, w.thr0);
+        return;
+      }
+    }
+    hipLaunchKernelGGL(scan2_kernel<DV>, blocks, dim3(K2_NT), 0, s, t, inv, N, w.qn, Q, k, w.rps, w.ns, qtiles,
+                       w.cands, w.thr0);
+  });
+  DCNR_LAUNCH_CHECK();
+  return merge_lists(w.cands, Q, w.ns, k, idx, dist, s);
 }
 
 dcnr_status topk_merge(const float* dist, const int64_t* idx, int lists, int64_t Q, int k,

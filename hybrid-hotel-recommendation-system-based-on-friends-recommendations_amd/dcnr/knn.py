@@ -16,8 +16,9 @@ import torch
 
 from . import _lib
 
-# the batched scan (knn.hip scan v4) serves d = 32 / 64 over tables larger
-# than its 32768-row sample; only those get the fit-time bf16 copy
+# the batched scan (knn.hip scan v4) serves d = 32 / 64; its admission bound
+# samples the first V4_S = 65536 rows.  Tables of more than PACKED_MIN_ROWS
+# rows get the fit-time bf16 copy
 PACKED_D = (32, 64)
 PACKED_MIN_ROWS = 32768
 

@@ -6,9 +6,10 @@ The merge kernel (``dcnr_topk_merge``) is checked against a numpy lexsort on
 lists with planted distance ties and padding; the sharded index runs as two
 processes sharing cuda:0 over gloo (RCCL refuses two ranks on one device; the
 exchange is backend-agnostic) and must return exactly the single-process
-``NearestNeighbors`` result -- the scan2 path (Q < 32) and the MFMA scan3 path
-(Q >= 32), duplicate rows split across the two shards, and a table whose
-shards hold fewer than k rows each.
+``NearestNeighbors`` result -- few and many queries (at d = 64 both take scan
+v4, bf16-MFMA admission + exact rescoring; the exact scans v1 - v3 have their
+own cases in test_knn_paths_gpu.py), duplicate rows split across the two
+shards, and a table whose shards hold fewer than k rows each.
 """
 import os
 import socket
