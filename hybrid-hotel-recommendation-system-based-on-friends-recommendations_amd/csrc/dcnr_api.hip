@@ -1588,6 +1588,123 @@ dcnr_status dcnr_mmr_rerank(const float* table, const float* inv_norms, int32_t 
   return DCNR_OK;
 }
 
+// ---- a batch of requests (serving.hip's req_* kernels).  Shapes the kernels
+// do not take: more requests than DCNR_REQ_MAX_R (one workgroup each), k above
+// the top-k's 64, a set CSR of 2^31 rows or more.
+namespace {
+constexpr int64_t DCNR_REQ_MAX_R = int64_t(1) << 22;
+
+// the checks the three entry points share; DCNR_OK: launch
+dcnr_status requests_shape(const char* who, int64_t R, int32_t cap) {
+  if (R < 0 || cap < 1 || cap > requests_cap_max()) {
+    set_error("%s: R=%lld (>= 0), cap=%d (1..%d)", who, (long long)R, cap, requests_cap_max());
+    return DCNR_BAD_ARG;
+  }
+  if (R > DCNR_REQ_MAX_R) {
+    set_error("%s: R=%lld exceeds %lld requests per call", who, (long long)R,
+              (long long)DCNR_REQ_MAX_R);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  return DCNR_OK;
+}
+}  // namespace
+
+size_t dcnr_requests_workspace_size(int64_t R, int64_t Q_total, int32_t k, int32_t cap) {
+  if (R <= 0 || R > DCNR_REQ_MAX_R || Q_total < 0 || k < 1 || cap < 1 || cap > requests_cap_max())
+    return 0;
+  return requests_ws_bytes(R, cap) + 256;
+}
+
+dcnr_status dcnr_requests_candidates(const int64_t* positives, const int64_t* pos_offsets,
+                                     int64_t R, int64_t Q_total, const int64_t* knn_idx, int32_t k,
+                                     const int64_t* set_rows, int64_t n_set_rows,
+                                     const int64_t* set_offsets, int32_t S, const int32_t* allowed,
+                                     const int32_t* excluded, const int32_t* fallback,
+                                     int32_t min_candidates, int64_t n_items, int32_t cap,
+                                     int64_t* out_rows, int32_t* out_count, int32_t* status,
+                                     int64_t* offsets, int64_t* host_offsets,
+                                     int32_t* host_status, dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TRY(requests_shape("dcnr_requests_candidates", R, cap));
+  if (Q_total < 0 || k < 1 || S < 0 || n_set_rows < 0 || n_items < 1) {
+    set_error("dcnr_requests_candidates: Q_total=%lld, k=%d, S=%d, n_set_rows=%lld, n_items=%lld",
+              (long long)Q_total, k, S, (long long)n_set_rows, (long long)n_items);
+    return DCNR_BAD_ARG;
+  }
+  if (R > 0 && (!pos_offsets || !out_rows || !out_count || !status || !offsets ||
+                (Q_total > 0 && (!positives || !knn_idx)) || (S > 0 && !set_offsets) ||
+                (n_set_rows > 0 && !set_rows) ||
+                (S == 0 && (allowed || excluded || fallback)))) {
+    set_error("dcnr_requests_candidates: null argument (or set indices without sets)");
+    return DCNR_BAD_ARG;
+  }
+  if (k > 64 || n_set_rows > INT32_MAX) {
+    set_error("dcnr_requests_candidates: k=%d (max 64), n_set_rows=%lld (max 2^31 - 1)", k,
+              (long long)n_set_rows);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  if (R == 0) return DCNR_OK;
+  RequestsIn in{positives, pos_offsets, R, Q_total, knn_idx, k, set_rows, n_set_rows,
+                set_offsets, S, allowed, excluded, fallback};
+  TRYP(DCNR_K_SERVE, s, requests_candidates(in, min_candidates, n_items, cap, out_rows, out_count,
+                                            status, offsets, host_offsets, host_status, s));
+  return DCNR_OK;
+}
+
+dcnr_status dcnr_requests_ranking_batch(const int64_t* cand_rows, int32_t cap,
+                                        const int64_t* offsets, int64_t R, int64_t n,
+                                        const int64_t* user_rows, const int64_t* item_cat,
+                                        int32_t n_cat, const float* item_num, int32_t n_num,
+                                        int64_t n_items, int64_t* user_ids, int64_t* item_ids,
+                                        int64_t* cat_features, float* num_features,
+                                        dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TRY(requests_shape("dcnr_requests_ranking_batch", R, cap));
+  if (n < 0 || n > R * cap || n_items < 1 || n_cat < 0 || n_num < 0 ||
+      (n > 0 && (!cand_rows || !offsets || !user_rows || !user_ids || !item_ids ||
+                 (n_cat && (!item_cat || !cat_features)) ||
+                 (n_num && (!item_num || !num_features))))) {
+    set_error("dcnr_requests_ranking_batch: bad argument (n=%lld of at most R*cap=%lld)",
+              (long long)n, (long long)(R * cap));
+    return DCNR_BAD_ARG;
+  }
+  if (R == 0) return DCNR_OK;
+  TRYP(DCNR_K_SERVE, s, requests_batch(cand_rows, cap, offsets, R, n, user_rows, item_cat, n_cat,
+                                       item_num, n_num, n_items, user_ids, item_ids,
+                                       cat_features, num_features, s));
+  return DCNR_OK;
+}
+
+dcnr_status dcnr_requests_rank_mmr(const float* logits, int64_t n, const int64_t* cand_rows,
+                                   int32_t cap, const int64_t* offsets, int64_t R,
+                                   const float* table, const float* inv_norms, int32_t d,
+                                   int64_t n_items, const float* lambda_param,
+                                   const int32_t* top_k, int64_t* out_rows, float* out_logits,
+                                   int32_t* out_count, int32_t* status, void* ws, size_t ws_bytes,
+                                   dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TRY(requests_shape("dcnr_requests_rank_mmr", R, cap));
+  if (n < 0 || n > R * cap || d < 1 || d > 256 || n_items < 1 ||
+      (R > 0 && (!cand_rows || !offsets || !table || !inv_norms || !lambda_param || !top_k ||
+                 !out_count || !status || !ws || (n > 0 && (!logits || !out_rows || !out_logits))))) {
+    set_error("dcnr_requests_rank_mmr: bad argument (n=%lld of at most R*cap=%lld, d=%d of 1..256)",
+              (long long)n, (long long)(R * cap), d);
+    return DCNR_BAD_ARG;
+  }
+  if (R == 0) return DCNR_OK;
+  const size_t need = requests_ws_bytes(R, cap) + 256;
+  if (ws_bytes < need) {
+    set_error("dcnr_requests_rank_mmr: workspace too small: %zu < %zu", ws_bytes, need);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  Bump b((void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255));
+  const RequestsWs w = requests_ws(b, R, cap);
+  TRYP(DCNR_K_SERVE, s, requests_rank_mmr(logits, n, cand_rows, cap, offsets, R, table, inv_norms, d,
+                                          n_items, lambda_param, top_k, w, out_rows, out_logits,
+                                          out_count, status, s));
+  return DCNR_OK;
+}
+
 size_t dcnr_bce_workspace_size(void) { return bce_ws_bytes() + 256; }
 
 dcnr_status dcnr_emb_touched_rows(const dcnr_model_desc* desc, const void* ws, size_t ws_bytes,

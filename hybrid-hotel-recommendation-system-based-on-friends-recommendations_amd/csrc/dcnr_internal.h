@@ -773,6 +773,32 @@ dcnr_status rank_desc(const float* scores, int64_t n, int64_t* order, hipStream_
 dcnr_status mmr_rerank(const float* table, const float* inv, int d, const int64_t* rows,
                        const float* scores, int64_t n, float lambda, int top_k, int64_t* out_pos,
                        int32_t* out_count, hipStream_t s);
+// the same steps for a batch of R requests, one workgroup each, over CSR
+// segments (dcnr_requests_*)
+struct RequestsIn {
+  const int64_t* pos; const int64_t* pos_off; int64_t R, Q_total;   // positives [Q_total], [R + 1]
+  const int64_t* idx; int k;                                       // their neighbours [Q_total][k]
+  const int64_t* set_rows; int64_t n_set_rows; const int64_t* set_off; int S;
+  const int32_t* allowed; const int32_t* excluded; const int32_t* fallback;   // [R] or null
+};
+struct RequestsWs { int64_t* rrows; float* rscores; };   // [R][cap] ranked lists for the MMR
+int requests_cap_max();
+RequestsWs requests_ws(Bump& b, int64_t R, int cap);
+size_t requests_ws_bytes(int64_t R, int cap);
+dcnr_status requests_candidates(const RequestsIn& in, int min_candidates, int64_t n_items, int cap,
+                                int64_t* out_rows, int32_t* out_count, int32_t* status,
+                                int64_t* offsets, int64_t* host_offsets, int32_t* host_status,
+                                hipStream_t s);
+dcnr_status requests_batch(const int64_t* slots, int cap, const int64_t* offsets, int64_t R,
+                           int64_t n, const int64_t* user_rows, const int64_t* item_cat, int K,
+                           const float* item_num, int F, int64_t n_items, int64_t* user_out,
+                           int64_t* item_out, int64_t* cat_out, float* num_out, hipStream_t s);
+dcnr_status requests_rank_mmr(const float* logits, int64_t n, const int64_t* slots, int cap,
+                              const int64_t* offsets, int64_t R, const float* table,
+                              const float* inv, int d, int64_t n_items, const float* lambda,
+                              const int32_t* top_k, const RequestsWs& w, int64_t* out_rows,
+                              float* out_logits, int32_t* out_count, int32_t* status,
+                              hipStream_t s);
 
 dcnr_status fill_zero(void* p, size_t bytes, hipStream_t s);
 // *dst = *src with a system-scope store (dst may be pinned host memory)

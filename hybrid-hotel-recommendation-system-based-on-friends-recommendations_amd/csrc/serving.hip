@@ -16,6 +16,15 @@
 // Each is one workgroup (the sets are tens to thousands of items): the sort is
 // an LDS bitonic sort of (key, position) pairs, so ties resolve by position
 // exactly as Python's stable sort does.
+//
+// A batch of R requests (req_* kernels) is the same work over CSR segments,
+// request r in workgroup r, side by side on the CUs: candidates with the
+// fallback and the allowed / excluded filters (main.py:204-212) as binary
+// searches in resident row sets, the offsets of the compacted batch, its
+// ranking batch, and rank + MMR per segment.  Both forms call one copy of
+// each building block (lds_bitonic, block_compact, union_entry, batch_row,
+// rank_sort, block_argmax, mmr_sim / mmr_value / mmr_better, mmr_table /
+// mmr_lds), so a request's answer is the same bits either way.
 #include "dcnr_internal.h"
 
 #include <cfloat>
@@ -50,6 +59,58 @@ __device__ void lds_bitonic(K* key, int* val, int n2) {
   }
 }
 
+// Stable compaction by the whole workgroup: for t < n in order, where
+// flag(t, v) holds (it also hands over the element's value v), write(p, v)
+// with p = the number of flagged elements before t (ballot prefix per wave,
+// wave totals through LDS).  Every value is taken before the chunk's barrier
+// and written after it, to p <= t, so write may store into the array flag
+// reads.  Returns the number of flagged elements, in every thread.
+template <typename V, typename F, typename W>
+__device__ int block_compact(int n, int* wsum, F flag, W write) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int running = 0;
+  for (int base = 0; base < n; base += SV_NT) {
+    const int t = base + threadIdx.x;
+    V v = V();
+    const bool f = t < n && flag(t, v);
+    const uint64_t m = __ballot(f);
+    const int pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
+                                              __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+    if (lane == 0) wsum[w] = __popcll(m);
+    __syncthreads();
+    int off = running, tot = 0;
+    for (int i = 0; i < SV_NT / 64; ++i) {
+      off += i < w ? wsum[i] : 0;
+      tot += wsum[i];
+    }
+    if (f) write(off + pre, v);
+    running += tot;
+    __syncthreads();
+  }
+  return running;
+}
+
+// entry t of a request's staged list: positives[q] at j = 0, else the
+// neighbour idx[q][j] (t = q * k + j); rows < 0 are skipped (INT64_MAX)
+__device__ __forceinline__ int64_t union_entry(const int64_t* pos, const int64_t* idx, int k, int t) {
+  const int64_t q = t / k, j = t % k;
+  const int64_t r = j == 0 ? pos[q] : idx[q * k + j];
+  return r < 0 ? INT64_MAX : r;
+}
+
+// key[0 .. n2) sorted ascending (INT64_MAX last): the first occurrence of
+// every row, compacted through write; returns their number
+template <typename W>
+__device__ int distinct_rows(const int64_t* key, int n2, int* wsum, W write) {
+  return block_compact<int64_t>(
+      n2, wsum,
+      [&](int t, int64_t& v) {
+        v = key[t];
+        return v != INT64_MAX && (t == 0 || v != key[t - 1]);
+      },
+      write);
+}
+
 // union of positives[Q] and idx[Q][k][1:] (rows < 0 skipped) -> ascending
 // unique rows; out_count[0] = number of rows
 __global__ __launch_bounds__(SV_NT) void union_kernel(const int64_t* pos, int64_t Q,
@@ -62,60 +123,234 @@ __global__ __launch_bounds__(SV_NT) void union_kernel(const int64_t* pos, int64_
   int n2 = 1;
   while (n2 < n) n2 <<= 1;
   for (int t = threadIdx.x; t < n2; t += SV_NT) {
-    int64_t r = INT64_MAX;
-    if (t < n) {
-      const int64_t q = t / k, j = t % k;
-      r = j == 0 ? pos[q] : idx[q * k + j];
-      if (r < 0) r = INT64_MAX;
-    }
-    key[t] = r;
+    key[t] = t < n ? union_entry(pos, idx, k, t) : INT64_MAX;
     val[t] = t;
   }
   __syncthreads();
   lds_bitonic(key, val, n2);
-  // compact the first occurrence of every id (ballot prefix per wave, wave
-  // totals through LDS)
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int running = 0;
-  for (int base = 0; base < n2; base += SV_NT) {
-    const int t = base + threadIdx.x;
-    const bool f = t < n2 && key[t] != INT64_MAX && (t == 0 || key[t] != key[t - 1]);
-    const uint64_t m = __ballot(f);
-    const int pre = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
-                                              __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
-    if (lane == 0) wsum[w] = __popcll(m);
+  const int cnt = distinct_rows(key, n2, wsum, [&](int p, int64_t v) { out[p] = v; });
+  if (threadIdx.x == 0) *out_count = cnt;
+}
+
+// is v in the ascending distinct set[0 .. len)?
+__device__ __forceinline__ bool set_contains(const int64_t* set, int64_t len, int64_t v) {
+  int64_t lo = 0, hi = len;
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (set[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo < len && set[lo] == v;
+}
+
+// The row sets a batch of requests names (the city's hotels, its popular
+// hotels, a user's negative reviews ...): a CSR of S ascending distinct sets
+// and three indices per request, -1 = none (a null index array = none at all)
+struct ReqSets {
+  const int64_t* rows; int64_t n_rows;
+  const int64_t* off; int S;
+  const int32_t* allowed; const int32_t* excluded; const int32_t* fallback;
+};
+
+constexpr int32_t REQ_OVERFLOW = 1, REQ_BAD_DATA = 2;   // dcnr.h: DCNR_REQ_*
+
+// set `which[r]` of the CSR as (first row, length); false: an index or an
+// offset pair outside the CSR
+__device__ bool req_set(const ReqSets& st, const int32_t* which, int64_t r, const int64_t*& rows,
+                        int64_t& len) {
+  rows = nullptr;
+  len = -1;   // none
+  const int32_t s = which ? which[r] : -1;
+  if (s == -1) return true;
+  if (s < -1 || s >= st.S) return false;
+  const int64_t lo = st.off[s], hi = st.off[s + 1];
+  if (lo < 0 || hi < lo || hi > st.n_rows || hi - lo > INT_MAX) return false;
+  rows = st.rows + lo;
+  len = hi - lo;
+  return true;
+}
+
+// The candidates of request r = blockIdx.x (main.py:196-212 on hotel rows):
+// union of its positives and their neighbours; the fallback set joined when
+// fewer than min_cand rows resulted; the allowed / excluded filters; the
+// surviving rows ascending in out[r][0 .. cap), their number in out_count[r].
+// status[r]: REQ_OVERFLOW when the staged list, the union or the result does
+// not fit (count 0), REQ_BAD_DATA when the request's offsets, set indices or
+// rows lie outside the lengths passed by value (count 0).  Every index formed
+// here is checked against one of those lengths first.
+__global__ __launch_bounds__(SV_NT) void req_candidates_kernel(
+    const int64_t* pos, const int64_t* pos_off, int64_t R, int64_t Q_total, const int64_t* idx,
+    int k, ReqSets st, int min_cand, int64_t n_items, int cap, int64_t* out, int32_t* out_count,
+    int32_t* status) {
+  __shared__ int64_t key[SV_MAX];
+  __shared__ int val[SV_MAX];
+  __shared__ int wsum[SV_NT / 64];
+  __shared__ int bad;
+  const int64_t r = blockIdx.x;
+  if (r >= R) return;
+  // (everything that decides an exit below is uniform over the workgroup)
+  auto finish = [&](int cnt, int32_t stt) {
+    if (threadIdx.x == 0) { out_count[r] = cnt; status[r] = stt; }
+  };
+  const int64_t q0 = pos_off[r], q1 = pos_off[r + 1];
+  const int64_t *arows, *erows, *frows;
+  int64_t alen, elen, flen;
+  const bool a_ok = req_set(st, st.allowed, r, arows, alen);
+  const bool e_ok = req_set(st, st.excluded, r, erows, elen);
+  const bool f_ok = req_set(st, st.fallback, r, frows, flen);
+  const bool sets_ok = a_ok && e_ok && f_ok;
+  if (q0 < 0 || q1 < q0 || q1 > Q_total || !sets_ok) return finish(0, REQ_BAD_DATA);
+  // ascending sets: the ends bound every row of a filter set (its rows are
+  // compared, never used as an index; fallback rows are checked one by one)
+  if ((alen > 0 && (arows[0] < 0 || arows[alen - 1] >= n_items)) ||
+      (elen > 0 && (erows[0] < 0 || erows[elen - 1] >= n_items)))
+    return finish(0, REQ_BAD_DATA);
+  if ((q1 - q0) * k > SV_MAX) return finish(0, REQ_OVERFLOW);
+  const int n = (int)((q1 - q0) * k);
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
+  int n2 = 1;
+  while (n2 < n) n2 <<= 1;
+  for (int t = threadIdx.x; t < n2; t += SV_NT) {
+    int64_t v = INT64_MAX;
+    if (t < n) {
+      v = union_entry(pos + q0, idx + q0 * k, k, t);
+      if (v != INT64_MAX && v >= n_items) { bad = 1; v = INT64_MAX; }
+    }
+    key[t] = v;
+    val[t] = t;
+  }
+  __syncthreads();
+  if (bad) return finish(0, REQ_BAD_DATA);
+  lds_bitonic(key, val, n2);
+  // distinct rows, compacted in place: key[0 .. m)
+  int m = distinct_rows(key, n2, wsum, [&](int p, int64_t v) { key[p] = v; });
+  if (flen >= 0 && m < min_cand) {
+    // the fallback rows not among them, appended (while room), then one more sort
+    const int n1 = m;
+    const int extra = block_compact<int64_t>(
+        (int)flen, wsum,
+        [&](int t, int64_t& v) {
+          v = frows[t];
+          if (v < 0 || v >= n_items) { bad = 1; return false; }
+          return !set_contains(key, n1, v);
+        },
+        [&](int p, int64_t v) { if (n1 + p < SV_MAX) key[n1 + p] = v; });
+    if (bad) return finish(0, REQ_BAD_DATA);
+    if ((int64_t)n1 + extra > SV_MAX) return finish(0, REQ_OVERFLOW);
+    m = n1 + extra;
+    n2 = 1;
+    while (n2 < m) n2 <<= 1;
+    for (int t = threadIdx.x; t < n2; t += SV_NT) {
+      if (t >= m) key[t] = INT64_MAX;
+      val[t] = t;
+    }
     __syncthreads();
-    int off = running, tot = 0;
+    lds_bitonic(key, val, n2);
+  }
+  int64_t* slot = out + r * cap;
+  const int cnt = block_compact<int64_t>(
+      m, wsum,
+      [&](int t, int64_t& v) {
+        v = key[t];
+        return (alen < 0 || set_contains(arows, alen, v)) &&
+               !(elen > 0 && set_contains(erows, elen, v));
+      },
+      [&](int p, int64_t v) { if (p < cap) slot[p] = v; });
+  if (cnt > cap) return finish(0, REQ_OVERFLOW);
+  finish(cnt, 0);
+}
+
+// offsets[r] = sum of count[0 .. r) (counts clamped to 0 .. cap), r <= R, by
+// one workgroup; mirrored to host_off, and status [R] to host_status (pinned
+// host memory, or null), with system-scope stores, visible to the host once
+// the stream has reached here
+__global__ __launch_bounds__(SV_NT) void req_offsets_kernel(const int32_t* count,
+                                                            const int32_t* status, int64_t R,
+                                                            int cap, int64_t* offsets,
+                                                            int64_t* host_off,
+                                                            int32_t* host_status) {
+  __shared__ int wsum[SV_NT / 64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int64_t running = 0;
+  auto put = [&](int64_t i, int64_t v) {
+    offsets[i] = v;
+    if (host_off) __hip_atomic_store(host_off + i, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  };
+  for (int64_t base = 0; base < R; base += SV_NT) {
+    const int64_t t = base + threadIdx.x;
+    const int c = t < R ? min(max(count[t], 0), cap) : 0;
+    int inc = c;   // inclusive scan over the wave
+    for (int o = 1; o < 64; o <<= 1) {
+      const int up = __shfl_up(inc, o, 64);
+      if (lane >= o) inc += up;
+    }
+    if (lane == 63) wsum[w] = inc;
+    __syncthreads();
+    int off = 0, tot = 0;
     for (int i = 0; i < SV_NT / 64; ++i) {
       off += i < w ? wsum[i] : 0;
       tot += wsum[i];
     }
-    if (f) out[off + pre] = key[t];
+    if (t < R) {
+      put(t, running + off + inc - c);
+      if (host_status)
+        __hip_atomic_store(host_status + t, status[t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
     running += tot;
     __syncthreads();
   }
-  if (threadIdx.x == 0) *out_count = running;
+  if (threadIdx.x == 0) put(R, running);
 }
 
-// ranking batch for one user: user_out[i] = user_row, item_out[i] = rows[i],
-// cat_out[i][:] = item_cat[rows[i]][:], num_out[i][:] = item_num[rows[i]][:]
+// one row of a ranking batch: user_out[i] = user_row, item_out[i] = row,
+// cat_out[i][:] = item_cat[row][:], num_out[i][:] = item_num[row][:] (the
+// gathers clamp the row into the tables), by the blockDim.x threads of row i
+__device__ __forceinline__ void batch_row(int64_t i, int64_t row, int64_t user_row,
+                                          const int64_t* item_cat, int K, const float* item_num,
+                                          int F, int64_t n_items, int64_t* user_out,
+                                          int64_t* item_out, int64_t* cat_out, float* num_out) {
+  const int64_t r = row < 0 ? 0 : (row >= n_items ? n_items - 1 : row);
+  if (threadIdx.x == 0) { user_out[i] = user_row; item_out[i] = row; }
+  for (int c = threadIdx.x; c < K; c += blockDim.x) cat_out[i * K + c] = item_cat[r * K + c];
+  for (int c = threadIdx.x; c < F; c += blockDim.x) num_out[i * F + c] = item_num[r * F + c];
+}
+
+// ranking batch for one user over rows[n]
 __global__ void batch_kernel(const int64_t* rows, int64_t n, int64_t user_row,
                              const int64_t* item_cat, int K, const float* item_num, int F,
                              int64_t n_items, int64_t* user_out, int64_t* item_out,
                              int64_t* cat_out, float* num_out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.y + threadIdx.y;
   if (i >= n) return;
-  int64_t r = rows[i];
-  r = r < 0 ? 0 : (r >= n_items ? n_items - 1 : r);
-  if (threadIdx.x == 0) { user_out[i] = user_row; item_out[i] = rows[i]; }
-  for (int c = threadIdx.x; c < K; c += blockDim.x) cat_out[i * K + c] = item_cat[r * K + c];
-  for (int c = threadIdx.x; c < F; c += blockDim.x) num_out[i * F + c] = item_num[r * F + c];
+  batch_row(i, rows[i], user_row, item_cat, K, item_num, F, n_items, user_out, item_out, cat_out,
+            num_out);
 }
 
-// order[i] = position of the i-th highest score (ties: lower position first)
-__global__ __launch_bounds__(SV_NT) void rank_kernel(const float* scores, int n, int64_t* order) {
-  __shared__ float key[SV_MAX];
-  __shared__ int val[SV_MAX];
+// ranking batch of a whole batch of requests: row i < n of the compacted
+// batch belongs to the request whose segment [offsets[r], offsets[r + 1])
+// holds it and is candidate i - offsets[r] of slots[r][cap] (a position the
+// offsets put outside the slot reads as row 0)
+__global__ void req_batch_kernel(const int64_t* slots, int cap, const int64_t* offsets, int64_t R,
+                                 int64_t n, const int64_t* user_rows, const int64_t* item_cat,
+                                 int K, const float* item_num, int F, int64_t n_items,
+                                 int64_t* user_out, int64_t* item_out, int64_t* cat_out,
+                                 float* num_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.y + threadIdx.y;
+  if (i >= n) return;
+  int64_t lo = 0, hi = R - 1;   // the last request with offsets[r] <= i
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo + 1) >> 1);
+    if (offsets[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  const int64_t j = i - offsets[lo];
+  const int64_t row = j >= 0 && j < cap ? slots[lo * cap + j] : 0;
+  batch_row(i, row, user_rows[lo], item_cat, K, item_num, F, n_items, user_out, item_out, cat_out,
+            num_out);
+}
+
+// val[0 .. n) = positions of scores[0 .. n) in descending score order (ties:
+// lower position first), through key / val [n rounded up to a power of two]
+__device__ void rank_sort(const float* scores, int n, float* key, int* val) {
   int n2 = 1;
   while (n2 < n) n2 <<= 1;
   for (int t = threadIdx.x; t < n2; t += SV_NT) {
@@ -124,6 +359,13 @@ __global__ __launch_bounds__(SV_NT) void rank_kernel(const float* scores, int n,
   }
   __syncthreads();
   lds_bitonic(key, val, n2);
+}
+
+// order[i] = position of the i-th highest score (ties: lower position first)
+__global__ __launch_bounds__(SV_NT) void rank_kernel(const float* scores, int n, int64_t* order) {
+  __shared__ float key[SV_MAX];
+  __shared__ int val[SV_MAX];
+  rank_sort(scores, n, key, val);
   for (int t = threadIdx.x; t < n; t += SV_NT) order[t] = val[t];
 }
 
@@ -151,18 +393,43 @@ __device__ void block_argmax(float v, int p, float* sv, int* sp, float& bv, int&
 // (zero-norm rows -> 0, as sklearn's normalize + dot).  The first candidate is
 // always taken; then up to min(top_k, n) - 1 more while some candidate is
 // eligible.  Max-similarity is 0 while no selected item has an embedding.
-__global__ __launch_bounds__(SV_NT) void mmr_kernel(const float* table, const float* inv, int d,
-                                                    const int64_t* rows, const float* scores,
-                                                    int n, float lambda, int top_k,
-                                                    int64_t* out_pos, int32_t* out_count) {
-  __shared__ float maxsim[SV_MAX];
-  __shared__ unsigned char taken[SV_MAX];
+//
+// The building blocks of both forms (candidates' rows re-read from the table,
+// or staged in LDS) and of both callers (one request, a batch of them):
+
+// cosine similarity of a candidate (raw row, inverse norm rinv) to the
+// selected item (raw row sel, inverse norm is): the sum in c order of
+// row[c] * (sel[c] * is), then * rinv
+__device__ __forceinline__ float mmr_sim(const float* row, float rinv, const float* sel, float is,
+                                         int d) {
+  float s = 0.f;
+  for (int c = 0; c < d; ++c) s += row[c] * (sel[c] * is);
+  return s * rinv;
+}
+
+// the MMR value of a candidate; its max similarity counts as 0 while no
+// selected item has an embedding (sel false)
+__device__ __forceinline__ float mmr_value(float lambda, float score, bool sel, float maxsim) {
+  return lambda * score - (1.f - lambda) * (sel ? maxsim : 0.f);
+}
+
+// a thread's running best (v, p): higher value first, lower position on ties
+__device__ __forceinline__ void mmr_better(float m, int t, float& v, int& p) {
+  if (p == INT_MAX || m > v || (m == v && t < p)) { v = m; p = t; }
+}
+
+// The table-reading form.  maxsim [n], taken [n], selv [d] are workgroup
+// scratch in LDS; emit(i, p), called by thread 0, records that the i-th item
+// of the result is candidate p.  Returns the number of items, in every thread.
+template <typename Emit>
+__device__ int mmr_table(const float* table, const float* inv, int d, const int64_t* rows,
+                         const float* scores, int n, float lambda, int top_k, float* maxsim,
+                         unsigned char* taken, float* selv, Emit emit) {
   __shared__ float sv[SV_NT / 64];
   __shared__ int sp[SV_NT / 64];
-  __shared__ float selv[256];
   __shared__ int any_sel;
   for (int t = threadIdx.x; t < n; t += SV_NT) { maxsim[t] = -FLT_MAX; taken[t] = 0; }
-  if (threadIdx.x == 0) { any_sel = 0; taken[0] = 1; out_pos[0] = 0; }
+  if (threadIdx.x == 0) { any_sel = 0; taken[0] = 1; emit(0, 0); }   // (thread 0 owns t = 0)
   __syncthreads();
   const int want = min(top_k, n);
   int cnt = 1, last = 0;
@@ -171,15 +438,12 @@ __global__ __launch_bounds__(SV_NT) void mmr_kernel(const float* table, const fl
     const int64_t sr = rows[last];
     if (sr >= 0) {
       const float is = inv[sr];
-      for (int t = threadIdx.x; t < d; t += SV_NT) selv[t] = table[sr * d + t] * is;
+      for (int t = threadIdx.x; t < d; t += SV_NT) selv[t] = table[sr * d + t];
       __syncthreads();
       for (int t = threadIdx.x; t < n; t += SV_NT) {
         const int64_t r = rows[t];
         if (r < 0 || taken[t]) continue;
-        float s = 0.f;
-        for (int c = 0; c < d; ++c) s += table[r * d + c] * selv[c];
-        s *= inv[r];
-        maxsim[t] = fmaxf(maxsim[t], s);
+        maxsim[t] = fmaxf(maxsim[t], mmr_sim(table + r * d, inv[r], selv, is, d));
       }
       if (threadIdx.x == 0) any_sel = 1;
       __syncthreads();
@@ -190,18 +454,29 @@ __global__ __launch_bounds__(SV_NT) void mmr_kernel(const float* table, const fl
     const bool sel = any_sel != 0;
     for (int t = threadIdx.x; t < n; t += SV_NT) {
       if (taken[t] || rows[t] < 0) continue;
-      const float m = lambda * scores[t] - (1.f - lambda) * (sel ? maxsim[t] : 0.f);
-      if (p == INT_MAX || m > v || (m == v && t < p)) { v = m; p = t; }
+      mmr_better(mmr_value(lambda, scores[t], sel, maxsim[t]), t, v, p);
     }
     float bv;
     int bp;
     block_argmax(v, p, sv, sp, bv, bp);
     if (bp == INT_MAX) break;
-    if (threadIdx.x == 0) { taken[bp] = 1; out_pos[cnt] = bp; }
+    if (threadIdx.x == 0) { taken[bp] = 1; emit(cnt, bp); }
     __syncthreads();
     ++cnt;
     last = bp;
   }
+  return cnt;
+}
+
+__global__ __launch_bounds__(SV_NT) void mmr_kernel(const float* table, const float* inv, int d,
+                                                    const int64_t* rows, const float* scores,
+                                                    int n, float lambda, int top_k,
+                                                    int64_t* out_pos, int32_t* out_count) {
+  __shared__ float maxsim[SV_MAX];
+  __shared__ unsigned char taken[SV_MAX];
+  __shared__ float selv[256];
+  const int cnt = mmr_table(table, inv, d, rows, scores, n, lambda, top_k, maxsim, taken, selv,
+                            [&](int i, int p) { out_pos[i] = p; });
   for (int t = threadIdx.x + cnt; t < top_k; t += SV_NT) out_pos[t] = -1;
   if (threadIdx.x == 0) *out_count = cnt;
 }
@@ -211,17 +486,16 @@ __global__ __launch_bounds__(SV_NT) void mmr_kernel(const float* table, const fl
 // and inverse norms in LDS, each thread's candidates (t = tid + j*SV_NT) --
 // validity, score, max similarity, taken -- in registers, so a round is one
 // dot product per candidate and a block argmax (its two barriers), with no
-// global loads.  Arithmetic as in mmr_kernel: s = sum_c row[c] * (sel[c] * is)
-// in c order, then * inv.
-__global__ __launch_bounds__(SV_NT) void mmr_lds_kernel(const float* table, const float* inv, int d,
-                                                    const int64_t* rows, const float* scores,
-                                                    int n, float lambda, int top_k,
-                                                    int64_t* out_pos, int32_t* out_count) {
+// global loads.  Arithmetic as in mmr_table (mmr_sim, mmr_value, mmr_better).
+// lds_rows [n (d + 1) + n] floats and vld [n] are workgroup scratch in LDS;
+// emit and the result as in mmr_table.
+template <typename Emit>
+__device__ int mmr_lds(const float* table, const float* inv, int d, const int64_t* rows,
+                       const float* scores, int n, float lambda, int top_k, float* lds_rows,
+                       unsigned char* vld, Emit emit) {
   constexpr int MR = SV_MAX / SV_NT;   // candidates per thread
   __shared__ float sv[SV_NT / 64];
   __shared__ int sp[SV_NT / 64];
-  __shared__ unsigned char vld[SV_MAX];
-  extern __shared__ float lds_rows[];
   float* invs = lds_rows + (size_t)n * (d + 1);
   for (int e = threadIdx.x; e < n * d; e += SV_NT) {
     const int t = e / d, c = e - t * d;
@@ -243,7 +517,7 @@ __global__ __launch_bounds__(SV_NT) void mmr_lds_kernel(const float* table, cons
       vld[t] = r >= 0;
     }
   }
-  if (threadIdx.x == 0) out_pos[0] = 0;
+  if (threadIdx.x == 0) emit(0, 0);
   __syncthreads();
   const int want = min(top_k, n);
   int cnt = 1, last = 0;
@@ -257,11 +531,7 @@ __global__ __launch_bounds__(SV_NT) void mmr_lds_kernel(const float* table, cons
       for (int j = 0; j < MR; ++j) {
         const int t = threadIdx.x + j * SV_NT;
         if (t >= n || !ok[j] || tk[j]) continue;
-        const float* rw = lds_rows + t * (d + 1);
-        float s = 0.f;
-        for (int c = 0; c < d; ++c) s += rw[c] * (sr[c] * is);
-        s *= invs[t];
-        ms[j] = fmaxf(ms[j], s);
+        ms[j] = fmaxf(ms[j], mmr_sim(lds_rows + t * (d + 1), invs[t], sr, is, d));
       }
       sel = true;
     }
@@ -272,20 +542,116 @@ __global__ __launch_bounds__(SV_NT) void mmr_lds_kernel(const float* table, cons
     for (int j = 0; j < MR; ++j) {
       const int t = threadIdx.x + j * SV_NT;
       if (t >= n || tk[j] || !ok[j]) continue;
-      const float m = lambda * sc[j] - (1.f - lambda) * (sel ? ms[j] : 0.f);
-      if (p == INT_MAX || m > v || (m == v && t < p)) { v = m; p = t; }
+      mmr_better(mmr_value(lambda, sc[j], sel, ms[j]), t, v, p);
     }
     float bv;
     int bp;
     block_argmax(v, p, sv, sp, bv, bp);
     if (bp == INT_MAX) break;
     if (bp % SV_NT == (int)threadIdx.x) tk[bp / SV_NT] = true;   // the owner thread
-    if (threadIdx.x == 0) out_pos[cnt] = bp;
+    if (threadIdx.x == 0) emit(cnt, bp);
     ++cnt;
     last = bp;
   }
+  return cnt;
+}
+
+__global__ __launch_bounds__(SV_NT) void mmr_lds_kernel(const float* table, const float* inv, int d,
+                                                    const int64_t* rows, const float* scores,
+                                                    int n, float lambda, int top_k,
+                                                    int64_t* out_pos, int32_t* out_count) {
+  __shared__ unsigned char vld[SV_MAX];
+  extern __shared__ float lds_rows[];
+  const int cnt = mmr_lds(table, inv, d, rows, scores, n, lambda, top_k, lds_rows, vld,
+                          [&](int i, int p) { out_pos[i] = p; });
   for (int t = threadIdx.x + cnt; t < top_k; t += SV_NT) out_pos[t] = -1;
   if (threadIdx.x == 0) *out_count = cnt;
+}
+
+// does the LDS-resident form hold n candidates of width d?
+__host__ __device__ inline size_t mmr_lds_bytes(int64_t n, int d) {
+  return ((size_t)n * (d + 1) + (size_t)n) * sizeof(float);
+}
+
+// Rank + MMR of request r = blockIdx.x over its segment [offsets[r],
+// offsets[r + 1]) of the compacted batch: the segment's logits sorted
+// descending (ties by position); lambda[r] >= 1: the whole ranked list; else
+// the greedy MMR over it with top_k[r], in the LDS-resident form when the
+// segment fits it, the table-reading form otherwise.  Ranked rows and their
+// logits go to the segment's start of out_rows / out_logits, their number to
+// out_count[r].  rrows / rscores [R][cap] (workspace) hold the ranked list the
+// MMR reads.  Everything in LDS but 4 KiB is dynamic (MMR_LDS_MAX), carved per
+// stage: the sort's keys, then either form's scratch.  A segment the offsets
+// put outside the batch or the slot, a top_k < 1, a row >= n_items or a logit
+// without a rank (-inf, NaN): count 0 and REQ_BAD_DATA in status[r].
+__global__ __launch_bounds__(SV_NT) void req_rank_mmr_kernel(
+    const float* logits, int64_t n_total, const int64_t* slots, int cap, const int64_t* offsets,
+    int64_t R, const float* table, const float* inv, int d, int64_t n_items, const float* lambda,
+    const int32_t* top_k, int64_t* rrows, float* rscores, int64_t* out_rows, float* out_logits,
+    int32_t* out_count, int32_t* status) {
+  __shared__ unsigned char flags[SV_MAX];   // vld (LDS form) / taken (table form)
+  __shared__ int bad;
+  extern __shared__ float dyn[];
+  const int64_t r = blockIdx.x;
+  if (r >= R) return;
+  const int64_t o0 = offsets[r], o1 = offsets[r + 1];
+  const float lam = lambda[r];
+  const int tk = top_k[r];
+  if (o0 < 0 || o1 < o0 || o1 > n_total || o1 - o0 > cap || (lam < 1.f && tk < 1)) {
+    if (threadIdx.x == 0) { out_count[r] = 0; status[r] |= REQ_BAD_DATA; }
+    return;
+  }
+  const int n = (int)(o1 - o0);
+  if (n == 0) {
+    if (threadIdx.x == 0) out_count[r] = 0;
+    return;
+  }
+  const int64_t* slot = slots + r * cap;
+  const float* z = logits + o0;
+  float* key = dyn;
+  int* val = (int*)(dyn + SV_MAX);
+  if (threadIdx.x == 0) bad = 0;
+  rank_sort(z, n, key, val);
+  // a logit that does not order below the padding (-inf, NaN) leaves a
+  // padding position among the first n: no position is used unchecked
+  const bool mmr = lam < 1.f;
+  int64_t* rr = rrows + r * cap;
+  float* rs = rscores + r * cap;
+  for (int t = threadIdx.x; t < n; t += SV_NT) {
+    const int p = val[t];
+    if (p < 0 || p >= n) { bad = 1; continue; }
+    const int64_t row = slot[p];
+    const float zp = z[p];
+    if (!(zp >= -FLT_MAX)) bad = 1;   // -inf, NaN (a NaN may leave the padding in place)
+    if (!mmr) {   // main.py:325-326: the sorted list is the answer
+      out_rows[o0 + t] = row;
+      out_logits[o0 + t] = zp;
+    } else {
+      if (row >= n_items) bad = 1;
+      rr[t] = row;
+      rs[t] = zp;
+    }
+  }
+  __syncthreads();   // the ranked list is in memory; the sort's LDS is free
+  if (bad) {
+    // the whole segment marked (rows -1, logits NaN), so that a caller who does
+    // not read the status back never takes stale memory for an answer
+    for (int t = threadIdx.x; t < n; t += SV_NT) {
+      out_rows[o0 + t] = -1;
+      out_logits[o0 + t] = __int_as_float(0x7fc00000);
+    }
+    if (threadIdx.x == 0) { out_count[r] = 0; status[r] |= REQ_BAD_DATA; }
+    return;
+  }
+  if (!mmr) {
+    if (threadIdx.x == 0) out_count[r] = n;
+    return;
+  }
+  auto emit = [&](int i, int p) { out_rows[o0 + i] = rr[p]; out_logits[o0 + i] = rs[p]; };
+  const int cnt = mmr_lds_bytes(n, d) <= MMR_LDS_MAX
+                      ? mmr_lds(table, inv, d, rr, rs, n, lam, tk, dyn, flags, emit)
+                      : mmr_table(table, inv, d, rr, rs, n, lam, tk, dyn, flags, dyn + SV_MAX, emit);
+  if (threadIdx.x == 0) out_count[r] = cnt;
 }
 
 // Batch assembly of a device-resident dataset (the DataLoader of
@@ -385,7 +751,7 @@ dcnr_status mmr_rerank(const float* table, const float* inv, int d, const int64_
   if (n <= 0) return DCNR_OK;
   // candidate rows staged in LDS when they fit (the same arithmetic, in the
   // same order, as the kernel that re-reads them from the table)
-  const size_t lds = ((size_t)n * (d + 1) + (size_t)n) * sizeof(float);
+  const size_t lds = mmr_lds_bytes(n, d);
   if (lds <= MMR_LDS_MAX) {
     TRY_ST(set_max_dyn_lds((const void*)mmr_lds_kernel, MMR_LDS_MAX));
     hipLaunchKernelGGL(mmr_lds_kernel, dim3(1), dim3(SV_NT), lds, s, table, inv, d, rows, scores, (int)n,
@@ -394,6 +760,64 @@ dcnr_status mmr_rerank(const float* table, const float* inv, int d, const int64_
     hipLaunchKernelGGL(mmr_kernel, dim3(1), dim3(SV_NT), 0, s, table, inv, d, rows, scores, (int)n,
                        lambda, top_k, out_pos, out_count);
   }
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
+// ---- a batch of R requests: one workgroup per request
+int requests_cap_max() { return SV_MAX; }
+
+size_t requests_ws_bytes(int64_t R, int cap) {
+  Bump b(nullptr);
+  requests_ws(b, R, cap);
+  return b.off;
+}
+
+RequestsWs requests_ws(Bump& b, int64_t R, int cap) {
+  RequestsWs w;
+  w.rrows = (int64_t*)b.take((size_t)R * cap * sizeof(int64_t));
+  w.rscores = (float*)b.take((size_t)R * cap * sizeof(float));
+  return w;
+}
+
+dcnr_status requests_candidates(const RequestsIn& in, int min_candidates, int64_t n_items, int cap,
+                                int64_t* out_rows, int32_t* out_count, int32_t* status,
+                                int64_t* offsets, int64_t* host_offsets, int32_t* host_status,
+                                hipStream_t s) {
+  ReqSets st{in.set_rows, in.n_set_rows, in.set_off, in.S, in.allowed, in.excluded, in.fallback};
+  hipLaunchKernelGGL(req_candidates_kernel, dim3((unsigned)in.R), dim3(SV_NT), 0, s, in.pos,
+                     in.pos_off, in.R, in.Q_total, in.idx, in.k, st, min_candidates, n_items, cap,
+                     out_rows, out_count, status);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(req_offsets_kernel, dim3(1), dim3(SV_NT), 0, s, out_count, status, in.R, cap,
+                     offsets, host_offsets, host_status);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
+dcnr_status requests_batch(const int64_t* slots, int cap, const int64_t* offsets, int64_t R,
+                           int64_t n, const int64_t* user_rows, const int64_t* item_cat, int K,
+                           const float* item_num, int F, int64_t n_items, int64_t* user_out,
+                           int64_t* item_out, int64_t* cat_out, float* num_out, hipStream_t s) {
+  if (n <= 0) return DCNR_OK;
+  dim3 blk(16, 16);
+  hipLaunchKernelGGL(req_batch_kernel, dim3((unsigned)cdiv(n, 16)), blk, 0, s, slots, cap, offsets,
+                     R, n, user_rows, item_cat, K, item_num, F, n_items, user_out, item_out,
+                     cat_out, num_out);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
+dcnr_status requests_rank_mmr(const float* logits, int64_t n, const int64_t* slots, int cap,
+                              const int64_t* offsets, int64_t R, const float* table,
+                              const float* inv, int d, int64_t n_items, const float* lambda,
+                              const int32_t* top_k, const RequestsWs& w, int64_t* out_rows,
+                              float* out_logits, int32_t* out_count, int32_t* status,
+                              hipStream_t s) {
+  TRY_ST(set_max_dyn_lds((const void*)req_rank_mmr_kernel, MMR_LDS_MAX));
+  hipLaunchKernelGGL(req_rank_mmr_kernel, dim3((unsigned)R), dim3(SV_NT), MMR_LDS_MAX, s, logits, n,
+                     slots, cap, offsets, R, table, inv, d, n_items, lambda, top_k, w.rrows,
+                     w.rscores, out_rows, out_logits, out_count, status);
   DCNR_LAUNCH_CHECK();
   return DCNR_OK;
 }

@@ -123,6 +123,16 @@ _SIGS = {
     "dcnr_rank_by_score": (ctypes.c_int, [_P, _I64, _P, _P]),
     "dcnr_mmr_rerank": (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, _I64, ctypes.c_float,
                                        ctypes.c_int32, _P, _P, _P]),
+    "dcnr_requests_workspace_size": (ctypes.c_size_t, [_I64, _I64, ctypes.c_int32, ctypes.c_int32]),
+    "dcnr_requests_candidates": (ctypes.c_int, [_P, _P, _I64, _I64, _P, ctypes.c_int32, _P, _I64,
+                                                _P, ctypes.c_int32, _P, _P, _P, ctypes.c_int32,
+                                                _I64, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "dcnr_requests_ranking_batch": (ctypes.c_int, [_P, ctypes.c_int32, _P, _I64, _I64, _P, _P,
+                                                   ctypes.c_int32, _P, ctypes.c_int32, _I64, _P,
+                                                   _P, _P, _P, _P]),
+    "dcnr_requests_rank_mmr": (ctypes.c_int, [_P, _I64, _P, ctypes.c_int32, _P, _I64, _P, _P,
+                                              ctypes.c_int32, _I64, _P, _P, _P, _P, _P, _P, _P,
+                                              ctypes.c_size_t, _P]),
     "dcnr_check_errors": (ctypes.c_int, [_P, ctypes.c_size_t, _P]),
     "dcnr_linear_bf16": (ctypes.c_int, [_P, _I64, _I64, ctypes.c_int32, _P, _I64, ctypes.c_int32,
                                         _P, _P, _I64, ctypes.c_int, _P]),

@@ -22,9 +22,16 @@ values); mapping external ids stays with the caller, as in main.py.  The
 pandas filters of _generate_candidates (city, negative reviews, popular-hotel
 fill-up, main.py:204-212) are host set operations and take ``allowed`` /
 ``excluded`` row sets here.
+
+``RankingPipeline.recommend_many`` answers a batch of requests in one device
+pass (dcnr_requests_*: one workgroup per request, the filters as binary
+searches in row sets kept on the device by ``register_sets``, one forward over
+all candidates, one host wait); ``similar_items_many`` is its /similar_items
+companion.
 """
 from __future__ import annotations
 
+import threading
 from typing import Any, Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
@@ -36,6 +43,18 @@ from .knn import NearestNeighbors
 ml_artifacts: Dict[str, Any] = {}
 
 SV_MAX = 4096   # csrc/serving.hip: candidates per union / rank / MMR call
+REQ_OVERFLOW, REQ_BAD_DATA = 1, 2   # DCNR_REQ_* status bits of the batched calls
+
+
+def _row_set(rows, n_rows, what) -> np.ndarray:
+    """A row set as the kernels read it: int64, ascending, distinct, inside the table."""
+    if torch.is_tensor(rows):
+        rows = rows.cpu().numpy()
+    a = np.unique(np.asarray(list(rows) if not isinstance(rows, np.ndarray) else rows,
+                             dtype=np.int64).reshape(-1))
+    if a.size and (a[0] < 0 or a[-1] >= n_rows):
+        raise ValueError(f"{what}: row outside [0, {n_rows})")
+    return a
 
 def _dev_table(emb, device):
     """(table fp32 [n, d] on device, inverse row norms [n]) cached per source array."""
@@ -130,6 +149,15 @@ class RankingPipeline:
         self.n_neighbors = n_neighbors
         if self.item_num.shape[0] != self.n_items:
             raise ValueError("item_cat and item_num must have one row per item")
+        # hotel rows every table holds (index, item_cat, item_num): what a
+        # batched request may name
+        self.n_rows = min(self.n_items, self.index._table.shape[0])
+        # register_sets: (rows on the device, host offsets [S + 1]); replaced
+        # as a whole, so a call in flight keeps the pair it started with
+        self._no_rows = torch.empty(0, dtype=torch.int64, device=dev)
+        self._sets = (self._no_rows, np.zeros(1, np.int64))
+        self._sets_lock = threading.Lock()
+        self._tls = threading.local()
 
     # ---------------------------------------------------------- /similar_items
     def similar_items(self, item_row: int, n: int = 10) -> torch.Tensor:
@@ -238,3 +266,268 @@ class RankingPipeline:
                                 lambda_param, top_k)
             return ranked[pos], rscores[pos]
         return ranked, rscores
+
+    # ------------------------------------------------- a batch of requests
+    def similar_items_many(self, item_rows, n: int = 10) -> torch.Tensor:
+        """R /similar_items queries (main.py:294-303) in one top-k call:
+        int64 [R, n], row r what ``similar_items(item_rows[r], n)`` returns."""
+        rows = np.asarray(item_rows, dtype=np.int64).reshape(-1)
+        if rows.size and (rows.min() < 0 or rows.max() >= self.index._table.shape[0]):
+            raise ValueError("similar_items_many: item row outside the index")
+        if rows.size == 0:
+            return torch.empty((0, n), dtype=torch.int64, device=self.device)
+        q = self.index._table[torch.from_numpy(rows).to(self.device)]
+        _, idx = self.index.kneighbors_device(q, n + 1)
+        return idx[:, 1:]
+
+    def register_sets(self, sets) -> List[int]:
+        """Upload row sets (a city's hotels, its most reviewed hotels ...) once,
+        sorted and distinct, and return their indices for ``recommend_many``'s
+        ``allowed`` / ``excluded`` / ``fallback``.  A later call appends; indices
+        stay valid."""
+        new = [_row_set(s, self.n_rows, "register_sets") for s in sets]
+        with self._sets_lock:
+            rows, off = self._sets
+            first = off.size - 1
+            if new:
+                add = torch.from_numpy(np.concatenate(new)).to(self.device)
+                lens = np.array([a.size for a in new], np.int64)
+                rows = torch.cat([rows, add])
+                # published only once written: a call on another stream may read it at once
+                torch.cuda.current_stream(self.device).synchronize()
+                self._sets = (rows, np.concatenate([off, off[-1] + np.cumsum(lens)]))
+        return list(range(first, first + len(new)))
+
+    @torch.no_grad()
+    def recommend_many(self, user_rows, positive_rows, lambda_param=1.0, top_k=20,
+                       allowed=None, excluded=None, fallback=None, min_candidates: int = 20):
+        """``recommend()`` for R requests in one device pass: returns a list of
+        R pairs (ranked rows, their logits), each equal to what ``recommend``
+        returns for that request alone, as views into two result tensors.
+
+        user_rows      R user rows
+        positive_rows  R sequences of hotel rows (may be empty)
+        lambda_param, top_k   a scalar or R values
+        allowed, excluded, fallback   None, or R entries, each None, an index
+                       from ``register_sets`` or an iterable of rows (uploaded
+                       for this call)
+
+        One packed, pinned, non-blocking copy carries every host input; one
+        top-k call serves all positives; each request's set work runs in its
+        own workgroup; one forward scores all candidates.  The call waits for
+        the device ONCE: after the candidate kernels, to read the forward's
+        batch size (the last of the request offsets the device mirrors into
+        pinned memory).  Rows are validated on the host before anything is
+        launched (ValueError).  A request whose candidates exceed the batched
+        kernels' capacity (SV_MAX) is answered by ``recommend()`` and spliced
+        in, never truncated.
+
+        The index and the feature tables must hold the same hotels (equal row
+        counts; ValueError otherwise -- ``recommend()`` clamps there).  Nothing
+        is read back after the forward, so a request whose logits hold a NaN
+        or -inf (they have no rank; ``recommend()`` is undefined there too) is
+        not reported: the device marks its whole answer, rows -1 and logits
+        NaN."""
+        lib = _lib.load()
+        dev = self.device
+        if self.index._table.shape[0] != self.n_items:
+            raise ValueError(f"recommend_many: the index holds {self.index._table.shape[0]} rows, "
+                             f"item_cat / item_num {self.n_items}")
+        users = np.asarray(user_rows, dtype=np.int64).reshape(-1)
+        R = users.size
+        if len(positive_rows) != R:
+            raise ValueError("recommend_many: one positive list per user row")
+        if R == 0:
+            return []
+        ins, info = self._pack_requests(users, positive_rows, lambda_param, top_k, allowed,
+                                        excluded, fallback)
+        pos, lam, topk, cap, S, n_adhoc = (info[k_] for k_ in ("pos", "lam", "topk", "cap", "S",
+                                                               "n_adhoc"))
+        k = self.n_neighbors
+        # ---- every host input in one pinned buffer, one non-blocking copy; the
+        # device's mirrors of the offsets and the status words behind them
+        at, total = {}, 0
+        for name, a in ins:
+            at[name] = total
+            total += (a.nbytes + 7) & ~7
+        o_off = total
+        o_st = o_off + 8 * (R + 1)
+        pin, host = self._pinned(o_st + ((4 * R + 7) & ~7))
+        for name, a in ins:
+            host[at[name]:at[name] + a.nbytes] = a.view(np.uint8)
+        dbuf = pin[:total].to(dev, non_blocking=True)
+        d_at = lambda name: dbuf.data_ptr() + at[name] if name in at else None
+        reg_rows = info["reg_rows"]
+        if n_adhoc:   # the per-call sets behind the registered ones: one CSR
+            o = at["adhoc_rows"]
+            reg_rows = torch.cat([reg_rows, dbuf[o:o + 8 * n_adhoc].view(torch.int64)])
+        stream = _lib.stream_ptr(dev)
+        Q = pos.size
+        idx = None
+        if Q:   # one top-k call for all requests' positives
+            d_pos = dbuf[at["pos"]:at["pos"] + 8 * Q].view(torch.int64)
+            _, idx = self.index.kneighbors_device(self.index._table[d_pos], k)
+        slots = torch.empty((R, cap), dtype=torch.int64, device=dev)
+        offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        words = torch.empty(3 * R, dtype=torch.int32, device=dev)   # count, status, out_count
+        count, status, out_count = (words.data_ptr() + 4 * R * j for j in range(3))
+        _lib.check(lib.dcnr_requests_candidates(
+            d_at("pos") if Q else None, d_at("pos_off"), R, Q, idx.data_ptr() if Q else None, k,
+            reg_rows.data_ptr() if reg_rows.numel() else None, reg_rows.numel(),
+            d_at("set_off"), S, d_at("allowed"), d_at("excluded"), d_at("fallback"),
+            int(min_candidates), self.n_rows, cap, slots.data_ptr(), count, status,
+            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream),
+            "dcnr_requests_candidates")
+        # (allocated while the device works, not after the wait)
+        nb = int(lib.dcnr_requests_workspace_size(R, Q, k, cap))
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()   # the call's one wait
+        seg = host[o_off:o_st].view(np.int64)
+        n = int(seg[R])
+        st = host[o_st:o_st + 4 * R].view(np.int32)
+        if (st & REQ_BAD_DATA).any():
+            raise RuntimeError("recommend_many: the device rejected validated input")
+        out_rows = out_logits = None
+        if n:
+            K, F = self.item_cat.shape[1], self.item_num.shape[1]
+            u = torch.empty(n, dtype=torch.int64, device=dev)
+            i = torch.empty(n, dtype=torch.int64, device=dev)
+            c = torch.empty((n, K), dtype=torch.int64, device=dev)
+            x = torch.empty((n, F), dtype=torch.float32, device=dev)
+            _lib.check(lib.dcnr_requests_ranking_batch(
+                slots.data_ptr(), cap, offsets.data_ptr(), R, n, d_at("users"),
+                self.item_cat.data_ptr() if K else None, K,
+                self.item_num.data_ptr() if F else None, F, self.n_items, u.data_ptr(),
+                i.data_ptr(), c.data_ptr() if K else None, x.data_ptr() if F else None, stream),
+                "dcnr_requests_ranking_batch")
+            logits = self.model(u, i, c, x).reshape(-1).to(torch.float32).contiguous()
+            out_rows = torch.empty(n, dtype=torch.int64, device=dev)
+            out_logits = torch.empty(n, dtype=torch.float32, device=dev)
+            table, inv = self.index._table, self.index._inv
+            _lib.check(lib.dcnr_requests_rank_mmr(
+                logits.data_ptr(), n, slots.data_ptr(), cap, offsets.data_ptr(), R,
+                table.data_ptr(), inv.data_ptr(), table.shape[1], table.shape[0],
+                d_at("lam"), d_at("topk"), out_rows.data_ptr(), out_logits.data_ptr(),
+                out_count, status, ws.data_ptr(), nb, stream),
+                "dcnr_requests_rank_mmr")
+        if not n:
+            out_rows = torch.empty(0, dtype=torch.int64, device=dev)
+            out_logits = torch.empty(0, dtype=torch.float32, device=dev)
+        # recommend() decides "lambda < 1" on the Python double and computes with its
+        # float32: a lambda that rounds to 1.0f from below goes its way
+        lam64 = info["lam64"]
+        odd = (lam64 < 1.0) != (lam < 1.0)
+        res = []
+        for r in range(R):
+            # above the batched kernels' capacity (or such a lambda): the one-request path
+            if st[r] & REQ_OVERFLOW or odd[r]:
+                pick = lambda v: None if v is None else v[r]
+                p_r = pos[info["pos_off"][r]:info["pos_off"][r + 1]]
+                res.append(self.recommend(int(users[r]), p_r, float(lam64[r]), int(topk[r]),
+                                          allowed=self._set_arg(pick(allowed)),
+                                          excluded=self._set_arg(pick(excluded)),
+                                          fallback=self._set_arg(pick(fallback)),
+                                          min_candidates=min_candidates))
+                continue
+            n_r = int(seg[r + 1] - seg[r])
+            # every candidate is a table row, so the MMR finds min(top_k, n_r) items
+            c_r = min(int(topk[r]), n_r) if lam[r] < 1.0 else n_r
+            o = int(seg[r])
+            res.append((out_rows[o:o + c_r], out_logits[o:o + c_r]))
+        return res
+
+    def _pack_requests(self, users, positive_rows, lambda_param, top_k, allowed, excluded,
+                       fallback):
+        """The host half of ``recommend_many``: validates the rows and returns
+        ([(name, array)] to upload, info).  Without set arguments nothing about
+        sets is built or uploaded (the index arrays go as null: no filters)."""
+        # (few numpy calls: at R = 1 this host work is latency the device waits for.
+        # A row read as unsigned is in range iff it is below the table's length)
+        R = users.size
+        n_users = self.model.user_embedding.weight.shape[0]
+        if users.view(np.uint64).max() >= n_users:
+            raise ValueError(f"recommend_many: user row outside [0, {n_users})")
+        pos = [np.asarray(p.cpu() if torch.is_tensor(p) else p, dtype=np.int64).reshape(-1)
+               for p in positive_rows]
+        lens = [p.size for p in pos]
+        pos_off = np.zeros(R + 1, np.int64)
+        if R == 1:
+            pos_all, pos_off[1] = pos[0], lens[0]
+        else:
+            pos_all = np.concatenate(pos)
+            np.cumsum(lens, out=pos_off[1:])
+        if pos_all.size and pos_all.view(np.uint64).max() >= self.n_rows:
+            raise ValueError(f"recommend_many: positive row outside [0, {self.n_rows})")
+        lam64 = np.full(R, lambda_param, np.float64) if np.isscalar(lambda_param) else \
+            np.array(lambda_param, np.float64).reshape(R)
+        lam = lam64.astype(np.float32)   # what the kernels (and dcnr_mmr_rerank) compute with
+        topk = np.full(R, top_k, np.int32) if np.isscalar(top_k) else \
+            np.array(top_k, np.int32).reshape(R)
+        if (top_k if np.isscalar(top_k) else topk.min()) < 1:
+            raise ValueError("recommend_many: top_k must be at least 1")
+        k = self.n_neighbors
+        ins = [("pos", pos_all), ("pos_off", pos_off), ("users", users), ("lam", lam),
+               ("topk", topk)]
+        info = dict(pos=pos_all, pos_off=pos_off, lam=lam, lam64=lam64, topk=topk, S=0, n_adhoc=0,
+                    reg_rows=self._no_rows)
+        need = np.array(lens, np.int64) * k   # a request's slot: its staged list (+ its fallback set)
+        if allowed is not None or excluded is not None or fallback is not None:
+            # registered sets by index, per-call ones appended to the CSR
+            reg_rows, reg_off = self._sets
+            n_reg = reg_off.size - 1
+            adhoc: List[np.ndarray] = []
+
+            def set_indices(entries, what):
+                out = np.full(R, -1, np.int32)
+                if entries is None:
+                    return out
+                if len(entries) != R:
+                    raise ValueError(f"recommend_many: {what} needs one entry per request")
+                for r, e in enumerate(entries):
+                    if e is None:
+                        continue
+                    if isinstance(e, (int, np.integer)):
+                        if not 0 <= e < n_reg:
+                            raise ValueError(f"recommend_many: {what}[{r}] = {e} is not a "
+                                             "registered set")
+                        out[r] = e
+                    else:
+                        adhoc.append(_row_set(e, self.n_rows, f"recommend_many: {what}[{r}]"))
+                        out[r] = n_reg + len(adhoc) - 1
+                return out
+
+            a_idx = set_indices(allowed, "allowed")
+            e_idx = set_indices(excluded, "excluded")
+            f_idx = set_indices(fallback, "fallback")
+        else:
+            a_idx = e_idx = f_idx = None
+        # lists whose entries are all None name no set: nothing about sets is uploaded
+        if a_idx is not None and (a_idx.max() >= 0 or e_idx.max() >= 0 or f_idx.max() >= 0):
+            adhoc_rows = np.concatenate(adhoc) if adhoc else np.zeros(0, np.int64)
+            set_off = np.concatenate([reg_off, reg_off[-1] + np.cumsum([a.size for a in adhoc],
+                                                                         dtype=np.int64)])
+            set_len = np.append(np.diff(set_off), 0)   # [-1] = 0: no fallback named
+            need = need + set_len[f_idx]
+            ins += [("set_off", set_off), ("adhoc_rows", adhoc_rows), ("allowed", a_idx),
+                    ("excluded", e_idx), ("fallback", f_idx)]
+            info.update(S=set_off.size - 1, n_adhoc=adhoc_rows.size, reg_rows=reg_rows)
+        info["cap"] = int(min(SV_MAX, max(1, int(need.max()))))
+        return ins, info
+
+    def _pinned(self, nbytes):
+        """This thread's pinned staging buffer (tensor, numpy view), grown as
+        needed.  One per thread: a call has waited for the device before it
+        returns, so nothing of it is in flight when the thread's next call
+        writes the buffer."""
+        buf = getattr(self._tls, "pin", None)
+        if buf is None or buf[0].numel() < nbytes:
+            t = torch.empty(max(4096, 2 * nbytes), dtype=torch.uint8, pin_memory=True)
+            buf = self._tls.pin = (t, t.numpy())
+        return buf
+
+    def _set_arg(self, e):
+        """A recommend_many set entry as ``recommend()`` takes it (rows)."""
+        if e is None or not isinstance(e, (int, np.integer)):
+            return e
+        rows, off = self._sets
+        return rows[int(off[e]):int(off[e + 1])].tolist()

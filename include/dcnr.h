@@ -26,6 +26,8 @@
  *   dcnr_ranking_batch    preprocess_for_ranking              main.py:215-230
  *   dcnr_rank_by_score    sorted(zip(scores, ids), reverse=True) main.py:325
  *   dcnr_mmr_rerank       rerank_with_mmr                     main.py:133-169
+ *   dcnr_requests_*       the same four steps for a batch of requests, one
+ *                         workgroup per request               main.py:309-332
  *   dcnr_eval_metrics     roc_auc_score / BCEWithLogitsLoss / sqrt(mean_squared_error)
  *                         over the validation logits          train.py:255-265, 366-387
  *
@@ -430,6 +432,97 @@ dcnr_status dcnr_mmr_rerank(const float* table, const float* inv_norms, int32_t 
                             const int64_t* rows, const float* scores, int64_t n,
                             float lambda_param, int32_t top_k, int64_t* out_pos,
                             int32_t* out_count, dcnr_stream_t stream);
+
+/* ---- serving, a batch of R requests in one pass (main.py:309-332 for each) ----
+ * The same steps over CSR-style segments, one workgroup per request, so that
+ * R requests cost one top-k call, one launch per step, one forward over all
+ * their candidates and ONE host wait (for the forward's batch size).  Per
+ * request the results are exactly those of the single-request calls above.
+ *
+ *   cosine_topk over all requests' positives  (Q_total queries, k neighbours)
+ *   dcnr_requests_candidates     -> cand_rows [R][cap], count, status, offsets
+ *   (host: wait, n = offsets[R] from the pinned mirror)
+ *   dcnr_requests_ranking_batch  -> the forward's inputs for the n rows
+ *   dcnr_forward (eval)          -> logits [n]
+ *   dcnr_requests_rank_mmr       -> ranked rows / logits per segment
+ *
+ * Row sets (a city's hotels, its most reviewed hotels, a user's negative
+ * reviews ...) are one CSR of S sets, set_rows [n_set_rows] with set_offsets
+ * [S + 1], each set ascending and distinct; a request names its allowed,
+ * excluded and fallback set by index (int32 [R], -1 = none; a NULL array =
+ * none for every request).  An allowed set that is empty allows nothing.
+ *
+ * status [R] (device int32) bits: */
+#define DCNR_REQ_OVERFLOW 1  /* the request's staged list (Q_r * k entries), its union (before
+                                or after the fallback) or its result exceeds 4096 rows, or the
+                                result exceeds cap: count 0; serve it with the single calls */
+#define DCNR_REQ_BAD_DATA 2  /* offsets not monotone or outside [0, Q_total] / [0, n]; a set
+                                index >= S or set offsets outside the CSR; a positive,
+                                neighbour or set row >= n_items (a set row < 0); top_k < 1;
+                                a logit of -inf or NaN (it has no rank): count 0.  No access is made outside the buffers: every index
+                                is checked against a length passed by value */
+/* Other requests of the batch are unaffected by one that overflows or has bad
+ * data.  Argument errors are rejected before any launch: DCNR_BAD_ARG (R < 0,
+ * k < 1, cap outside 1..4096, d outside 1..256, a null pointer with R > 0),
+ * DCNR_UNSUPPORTED_SHAPE (R > 2^22, k > 64, n_set_rows >= 2^31),
+ * DCNR_WORKSPACE_TOO_SMALL.  R = 0 returns DCNR_OK without a launch. */
+
+/* Workspace bytes of dcnr_requests_rank_mmr: each request's ranked rows and
+ * logits, 12 * R * cap (+ alignment); 0 for R <= 0 or arguments the calls
+ * reject.  Q_total and k are validated only: the union is staged in LDS. */
+size_t dcnr_requests_workspace_size(int64_t R, int64_t Q_total, int32_t k, int32_t cap);
+
+/* Candidates of every request: request r owns positives[pos_offsets[r] ..
+ * pos_offsets[r + 1]) and the matching rows of knn_idx [Q_total][k].  In order:
+ * the union of dcnr_candidate_union; if it has fewer than min_candidates rows
+ * and the request names a fallback set, that set joined in (distinct rows
+ * ascending, as torch.unique(cat) gives); rows outside its allowed set and
+ * rows in its excluded set dropped.  out_rows [R][cap]: the surviving rows
+ * ascending in row r's slot; out_count [R]; status [R] (written, see above).
+ * Then offsets [R + 1] = the exclusive sum of out_count in request order, also
+ * stored to host_offsets, and status to host_status [R] (pinned, device-visible
+ * host memory, or NULL), with system-scope stores: valid on the host once the
+ * stream has reached here. */
+dcnr_status dcnr_requests_candidates(const int64_t* positives, const int64_t* pos_offsets,
+                                     int64_t R, int64_t Q_total, const int64_t* knn_idx, int32_t k,
+                                     const int64_t* set_rows, int64_t n_set_rows,
+                                     const int64_t* set_offsets, int32_t S, const int32_t* allowed,
+                                     const int32_t* excluded, const int32_t* fallback,
+                                     int32_t min_candidates, int64_t n_items, int32_t cap,
+                                     int64_t* out_rows, int32_t* out_count, int32_t* status,
+                                     int64_t* offsets, int64_t* host_offsets,
+                                     int32_t* host_status, dcnr_stream_t stream);
+
+/* dcnr_ranking_batch over the compacted batch of n = offsets[R] rows: row i
+ * belongs to the request r whose segment [offsets[r], offsets[r + 1]) holds
+ * it, its item is cand_rows[r][i - offsets[r]], its user user_rows[r]. */
+dcnr_status dcnr_requests_ranking_batch(const int64_t* cand_rows, int32_t cap,
+                                        const int64_t* offsets, int64_t R, int64_t n,
+                                        const int64_t* user_rows, const int64_t* item_cat,
+                                        int32_t n_cat, const float* item_num, int32_t n_num,
+                                        int64_t n_items, int64_t* user_ids, int64_t* item_ids,
+                                        int64_t* cat_features, float* num_features,
+                                        dcnr_stream_t stream);
+
+/* dcnr_rank_by_score, then (lambda_param[r] < 1) dcnr_mmr_rerank with
+ * top_k[r], of every request's segment of logits [n]; rows of `table`
+ * [n_items][d] are the candidates themselves (cand_rows; a row < 0 has no
+ * embedding).  The ranked rows and their logits are written from the start
+ * of the request's segment of out_rows / out_logits [n]: out_count[r] of
+ * them, the whole segment when lambda_param[r] >= 1, at most min(top_k[r],
+ * segment length) otherwise.  status [R] must hold what
+ * dcnr_requests_candidates wrote (or zeros): DCNR_REQ_BAD_DATA is OR-ed in.
+ * A request whose logits hold -inf or NaN, or whose MMR meets a row >= n_items,
+ * also gets its whole segment of out_rows set to -1 and of out_logits to NaN,
+ * so a caller that derives the counts itself and reads nothing back (the
+ * Python layer) cannot take unwritten memory for an answer. */
+dcnr_status dcnr_requests_rank_mmr(const float* logits, int64_t n, const int64_t* cand_rows,
+                                   int32_t cap, const int64_t* offsets, int64_t R,
+                                   const float* table, const float* inv_norms, int32_t d,
+                                   int64_t n_items, const float* lambda_param,
+                                   const int32_t* top_k, int64_t* out_rows, float* out_logits,
+                                   int32_t* out_count, int32_t* status, void* ws, size_t ws_bytes,
+                                   dcnr_stream_t stream);
 
 /* The deep tower's Linear layer as a standalone bf16 call (nn.Linear forward,
  * train.py:143,105,109): C[M,N] = X[M,K] . W[N,K]^T + bias, X/W bf16
