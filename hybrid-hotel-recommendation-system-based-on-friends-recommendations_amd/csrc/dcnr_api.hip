@@ -1705,6 +1705,78 @@ dcnr_status dcnr_requests_rank_mmr(const float* logits, int64_t n, const int64_t
   return DCNR_OK;
 }
 
+// ---- requests by user.  The store's lengths are checked here; what lies in
+// device memory (offsets, rows) the kernels check against them.
+namespace {
+constexpr int64_t DCNR_STORE_MAX_ITEMS = int64_t(1) << 29;   // hotel row * 4 + class bits in 32
+
+dcnr_status store_shape(const char* who, const dcnr_interactions* st, int64_t n_items) {
+  if (!st || st->n_reviewers < 0 || st->n_friend_rows < 0 || st->n_reviews < 0 || n_items < 1 ||
+      !st->friend_offsets || !st->review_offsets || (st->n_friend_rows > 0 && !st->friend_rows) ||
+      (st->n_reviews > 0 && (!st->review_items || !st->review_rows))) {
+    set_error("%s: null or negative store field, or n_items < 1", who);
+    return DCNR_BAD_ARG;
+  }
+  if (n_items > DCNR_STORE_MAX_ITEMS || st->n_reviewers >= INT32_MAX ||
+      st->n_reviews > INT32_MAX || st->n_friend_rows > INT32_MAX) {
+    set_error("%s: n_items=%lld (max 2^29), n_reviewers=%lld, n_reviews=%lld, n_friend_rows=%lld "
+              "(max 2^31 - 1)", who, (long long)n_items, (long long)st->n_reviewers,
+              (long long)st->n_reviews, (long long)st->n_friend_rows);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  return DCNR_OK;
+}
+}  // namespace
+
+dcnr_status dcnr_requests_sources(const dcnr_interactions* store, const int32_t* reviewers,
+                                  const int32_t* modes, int64_t R, int64_t n_items,
+                                  const int64_t* pos_offsets, int64_t Q_total, int64_t* positives,
+                                  const int64_t* neg_offsets, int64_t neg_lo, int64_t neg_hi,
+                                  int64_t* neg_rows, int32_t* counts, int32_t* status,
+                                  int32_t* host_counts, int32_t* host_status,
+                                  dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TRY(requests_shape("dcnr_requests_sources", R, 1));
+  TRY(store_shape("dcnr_requests_sources", store, n_items));
+  if (Q_total < 0 || neg_lo < 0 || neg_hi < neg_lo ||
+      (R > 0 && (!reviewers || !modes || !pos_offsets || !neg_offsets || !counts || !status ||
+                 (Q_total > 0 && !positives) || (neg_hi > neg_lo && !neg_rows)))) {
+    set_error("dcnr_requests_sources: bad argument (Q_total=%lld, negatives [%lld, %lld))",
+              (long long)Q_total, (long long)neg_lo, (long long)neg_hi);
+    return DCNR_BAD_ARG;
+  }
+  if (R == 0) return DCNR_OK;
+  TRYP(DCNR_K_SERVE, s, requests_sources(*store, reviewers, modes, R, n_items, pos_offsets, Q_total,
+                                         positives, neg_offsets, neg_lo, neg_hi, neg_rows, counts,
+                                         status, host_counts, host_status, s));
+  return DCNR_OK;
+}
+
+dcnr_status dcnr_requests_recommended_by(const dcnr_interactions* store, const int32_t* reviewers,
+                                         int64_t R, int64_t n_items, const int64_t* out_rows,
+                                         int64_t n, const int64_t* offsets,
+                                         const int32_t* out_count, const int64_t* list_offsets,
+                                         int64_t n_list_rows, int32_t* lists, int32_t* by_count,
+                                         int64_t* by_offsets, int32_t* by_reviewers,
+                                         int32_t* status, dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TRY(requests_shape("dcnr_requests_recommended_by", R, 1));
+  TRY(store_shape("dcnr_requests_recommended_by", store, n_items));
+  if (n < 0 || n > R * requests_cap_max() || n_list_rows < 0 ||
+      (R > 0 && (!reviewers || !offsets || !out_count || !list_offsets || !by_offsets || !status ||
+                 (n > 0 && (!out_rows || !by_count)) ||
+                 (n_list_rows > 0 && (!lists || !by_reviewers))))) {
+    set_error("dcnr_requests_recommended_by: bad argument (n=%lld, n_list_rows=%lld)",
+              (long long)n, (long long)n_list_rows);
+    return DCNR_BAD_ARG;
+  }
+  if (R == 0) return DCNR_OK;
+  TRYP(DCNR_K_SERVE, s, requests_recommended_by(*store, reviewers, R, n_items, out_rows, n, offsets,
+                                                out_count, list_offsets, n_list_rows, lists,
+                                                by_count, by_offsets, by_reviewers, status, s));
+  return DCNR_OK;
+}
+
 size_t dcnr_bce_workspace_size(void) { return bce_ws_bytes() + 256; }
 
 dcnr_status dcnr_emb_touched_rows(const dcnr_model_desc* desc, const void* ws, size_t ws_bytes,

@@ -799,6 +799,21 @@ dcnr_status requests_rank_mmr(const float* logits, int64_t n, const int64_t* slo
                               const int32_t* top_k, const RequestsWs& w, int64_t* out_rows,
                               float* out_logits, int32_t* out_count, int32_t* status,
                               hipStream_t s);
+// requests by user: the positives / negatives in front of requests_candidates,
+// the recommended_by lists behind requests_rank_mmr (dcnr_requests_sources,
+// dcnr_requests_recommended_by)
+dcnr_status requests_sources(const dcnr_interactions& store, const int32_t* reviewers,
+                             const int32_t* modes, int64_t R, int64_t n_items,
+                             const int64_t* pos_off, int64_t Q_total, int64_t* pos,
+                             const int64_t* neg_off, int64_t neg_lo, int64_t neg_hi, int64_t* neg,
+                             int32_t* counts, int32_t* status, int32_t* host_counts,
+                             int32_t* host_status, hipStream_t s);
+dcnr_status requests_recommended_by(const dcnr_interactions& store, const int32_t* reviewers,
+                                    int64_t R, int64_t n_items, const int64_t* out_rows, int64_t n,
+                                    const int64_t* offsets, const int32_t* out_count,
+                                    const int64_t* list_off, int64_t L_total, int32_t* lists,
+                                    int32_t* by_count, int64_t* by_off, int32_t* by_reviewers,
+                                    int32_t* status, hipStream_t s);
 
 dcnr_status fill_zero(void* p, size_t bytes, hipStream_t s);
 // *dst = *src with a system-scope store (dst may be pinned host memory)

@@ -654,6 +654,318 @@ __global__ __launch_bounds__(SV_NT) void req_rank_mmr_kernel(
   if (threadIdx.x == 0) out_count[r] = cnt;
 }
 
+// ---- requests by user: the interaction store (dcnr.InteractionStore) on the
+// device, the steps of /recommendations that read it (get_friends_for_user,
+// main.py:172-178; the positives and negatives of _generate_candidates,
+// main.py:187-194; the recommended_by lists, main.py:336-351)
+//
+// Two CSRs over the U reviewers: friends (symmetric, distinct) and reviews
+// (within a reviewer in main_df order): rv_item = hotel row * 4 + class bits
+// (1: rating >= 8, 2: rating <= 4), rv_row = the review's main_df row.
+struct ReqStore {
+  int64_t U;
+  const int64_t* fr_off; const int32_t* fr_idx; int64_t n_fr;
+  const int64_t* rv_off; const int32_t* rv_item; const int32_t* rv_row; int64_t M;
+};
+
+constexpr int REQ_FRIENDS = 0, REQ_PERSONAL = 1;   // dcnr.h: DCNR_MODE_*
+constexpr int64_t SRC_NEG = int64_t(1) << 40;      // staged key of a negative row: row + SRC_NEG
+
+// the friend list of reviewer u (0 <= u < U) as (first, length); false:
+// offsets outside the CSR
+__device__ bool store_friends(const ReqStore& st, int64_t u, const int32_t*& fr, int64_t& nf) {
+  const int64_t lo = st.fr_off[u], hi = st.fr_off[u + 1];
+  fr = nullptr;
+  nf = 0;
+  if (lo < 0 || hi < lo || hi > st.n_fr) return false;
+  fr = st.fr_idx + lo;
+  nf = hi - lo;
+  return true;
+}
+
+// the review segment [lo, hi) of reviewer f; false: f outside [0, U) or
+// offsets outside the CSR
+__device__ bool store_reviews(const ReqStore& st, int64_t f, int64_t& lo, int64_t& hi) {
+  lo = hi = 0;
+  if (f < 0 || f >= st.U) return false;
+  lo = st.rv_off[f];
+  hi = st.rv_off[f + 1];
+  return lo >= 0 && hi >= lo && hi <= st.M;
+}
+
+// Sum of the review rows of the nf sources of a request (src(i): source i),
+// one wave per source, into *total (LDS, zeroed by the caller before a
+// barrier); *bad set when a source or its offsets lie outside the store
+template <typename Src>
+__device__ void store_count_rows(const ReqStore& st, int64_t nf, Src src,
+                                 unsigned long long* total, int* bad) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int64_t i = w; i < nf; i += SV_NT / 64) {
+    int64_t lo, hi;
+    if (!store_reviews(st, src(i), lo, hi)) { *bad = 1; continue; }
+    if (lane == 0) atomicAdd(total, (unsigned long long)(hi - lo));
+  }
+}
+
+// first position of key[0 .. n) (ascending) not below v
+template <typename K>
+__device__ __forceinline__ int lower_bound(const K* key, int n, K v) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (key[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+// The positives and negatives of request r = blockIdx.x (main.py:187-194 on
+// hotel rows): the reviews of its sources -- the friends of reviewers[r]
+// (REQ_FRIENDS) or the reviewer alone (REQ_PERSONAL); -1 = unknown user, no
+// sources -- staged in LDS as row (rating >= 8) or row + SRC_NEG (rating <= 4),
+// sorted, made distinct.  The request owns pos[pos_off[r] .. pos_off[r + 1])
+// and neg[neg_off[r] .. neg_off[r + 1]) (lengths the host knows as bounds of
+// the counts): its distinct positives ascending, then the last repeated to
+// the segment's end; likewise its negatives, which makes the segment a set
+// req_candidates_kernel's binary search takes as `excluded`.  counts[2r],
+// counts[2r + 1] = the distinct numbers.  status[r]: REQ_OVERFLOW when the
+// friends or the staged review rows exceed SV_MAX, REQ_BAD_DATA when a
+// reviewer, mode, offset, friend or hotel row lies outside the lengths passed
+// by value, or a segment is shorter than its count or non-empty with count 0;
+// both leave counts 0 and the segments filled with -1 (no positive; a set
+// req_candidates_kernel rejects).  counts and status are mirrored to pinned
+// host memory (or null) with system-scope stores, as req_offsets_kernel does.
+__global__ __launch_bounds__(SV_NT) void req_sources_kernel(
+    ReqStore st, const int32_t* reviewers, const int32_t* modes, int64_t R, int64_t n_items,
+    const int64_t* pos_off, int64_t Q_total, int64_t* pos, const int64_t* neg_off, int64_t neg_lo,
+    int64_t neg_hi, int64_t* neg, int32_t* counts, int32_t* status, int32_t* host_counts,
+    int32_t* host_status) {
+  __shared__ int64_t key[SV_MAX];
+  __shared__ int val[SV_MAX];
+  __shared__ int wsum[SV_NT / 64];
+  __shared__ int bad, n_st;
+  __shared__ unsigned long long total;
+  const int64_t r = blockIdx.x;
+  if (r >= R) return;
+  // (everything that decides an exit below is uniform over the workgroup)
+  const int64_t p0 = pos_off[r], p1 = pos_off[r + 1], g0 = neg_off[r], g1 = neg_off[r + 1];
+  const bool seg_ok = p0 >= 0 && p1 >= p0 && p1 <= Q_total && p1 - p0 <= SV_MAX && g0 >= neg_lo &&
+                      g1 >= g0 && g1 <= neg_hi && g1 - g0 <= SV_MAX;
+  const int np = seg_ok ? (int)(p1 - p0) : 0, ng = seg_ok ? (int)(g1 - g0) : 0;
+  auto finish = [&](int npos, int nneg, int32_t stt) {
+    if (stt) {   // nothing of the segments stays unwritten
+      for (int t = threadIdx.x; t < np; t += SV_NT) pos[p0 + t] = -1;
+      for (int t = threadIdx.x; t < ng; t += SV_NT) neg[g0 + t] = -1;
+    }
+    if (threadIdx.x == 0) {
+      counts[2 * r] = npos; counts[2 * r + 1] = nneg; status[r] = stt;
+      if (host_counts) {
+        __hip_atomic_store(host_counts + 2 * r, npos, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        __hip_atomic_store(host_counts + 2 * r + 1, nneg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
+      if (host_status)
+        __hip_atomic_store(host_status + r, stt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  };
+  const int64_t u = reviewers[r];
+  const int mode = modes[r];
+  if (!seg_ok || u < -1 || u >= st.U || (mode != REQ_FRIENDS && mode != REQ_PERSONAL))
+    return finish(0, 0, REQ_BAD_DATA);
+  const int32_t* fr = nullptr;
+  int64_t nf = 0;
+  if (u >= 0 && mode == REQ_PERSONAL) nf = 1;
+  else if (u >= 0 && !store_friends(st, u, fr, nf)) return finish(0, 0, REQ_BAD_DATA);
+  if (nf > SV_MAX) return finish(0, 0, REQ_OVERFLOW);
+  auto src = [&](int64_t i) -> int64_t { return fr ? fr[i] : u; };
+  if (threadIdx.x == 0) { bad = 0; n_st = 0; total = 0; }
+  __syncthreads();
+  store_count_rows(st, nf, src, &total, &bad);
+  __syncthreads();
+  if (bad) return finish(0, 0, REQ_BAD_DATA);
+  if (total > (unsigned long long)SV_MAX) return finish(0, 0, REQ_OVERFLOW);
+  // stage the classed reviews, one wave per source; the order in the list is
+  // of no account (it is sorted next), so a slot is claimed with an LDS atomic
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int64_t i = w; i < nf; i += SV_NT / 64) {
+    int64_t lo, hi;
+    if (!store_reviews(st, src(i), lo, hi)) { bad = 1; continue; }
+    for (int64_t j = lo + lane; j < hi; j += 64) {
+      const int32_t wd = st.rv_item[j];
+      const int cls = wd & 3;
+      if (wd < 0 || (wd >> 2) >= n_items || cls == 3) { bad = 1; continue; }
+      if (cls == 0) continue;
+      const int p = atomicAdd(&n_st, 1);
+      if (p >= SV_MAX) { bad = 1; continue; }   // (total <= SV_MAX: not reached)
+      key[p] = (int64_t)(wd >> 2) + (cls == 2 ? SRC_NEG : 0);
+      val[p] = 0;
+    }
+  }
+  __syncthreads();
+  if (bad) return finish(0, 0, REQ_BAD_DATA);
+  const int n = n_st;
+  int n2 = 1;
+  while (n2 < n) n2 <<= 1;
+  for (int t = n + threadIdx.x; t < n2 || t < 1; t += SV_NT) { key[t] = INT64_MAX; val[t] = 0; }
+  __syncthreads();
+  lds_bitonic(key, val, n2);
+  // distinct keys, compacted in place: positives key[0 .. npos), negatives behind
+  const int m = distinct_rows(key, n2, wsum, [&](int p, int64_t v) { key[p] = v; });
+  const int npos = lower_bound<int64_t>(key, m, SRC_NEG), nneg = m - npos;
+  if (npos > np || nneg > ng || (npos == 0) != (np == 0) || (nneg == 0) != (ng == 0))
+    return finish(0, 0, REQ_BAD_DATA);
+  for (int t = threadIdx.x; t < np; t += SV_NT) pos[p0 + t] = key[min(t, npos - 1)];
+  for (int t = threadIdx.x; t < ng; t += SV_NT) neg[g0 + t] = key[npos + min(t, nneg - 1)] - SRC_NEG;
+  finish(npos, nneg, 0);
+}
+
+struct ByPair { int64_t k; int v; };
+
+// The recommended_by lists of request r = blockIdx.x (main.py:336-351), after
+// req_rank_mmr_kernel: for each returned position i < out_count[r] of its
+// segment [offsets[r], offsets[r + 1]) of out_rows, the distinct friends of
+// reviewers[r] (whatever the request's mode) with a rating >= 8 review of that
+// hotel, in the order of their first such review's main_df row.  The returned
+// rows sorted in LDS are the map hotel -> position; the matching reviews are
+// staged as (position, reviewer, review row) and sorted, the first of every
+// (position, reviewer) kept, and those sorted by (position, review row).  The
+// reviewers go, position by position, to lists[list_off[r] .. list_off[r + 1])
+// (a length the host knows as a bound; the rest -1), their number per
+// position to by_count[offsets[r] + i] (0 from out_count[r] on).  status[r]:
+// REQ_OVERFLOW (friends or their review rows above SV_MAX) and REQ_BAD_DATA
+// (an offset, count, reviewer, friend, hotel or review row outside the
+// lengths passed by value; more reviewers than the list segment holds) leave
+// every count of the request 0.
+__global__ __launch_bounds__(SV_NT) void req_recommended_by_kernel(
+    ReqStore st, const int32_t* reviewers, int64_t R, int64_t n_items, const int64_t* out_rows,
+    int64_t n_total, const int64_t* offsets, const int32_t* out_count, const int64_t* list_off,
+    int64_t L_total, int32_t* lists, int32_t* by_count, int32_t* status) {
+  __shared__ int mkey[SV_MAX];
+  __shared__ int mval[SV_MAX];
+  __shared__ int64_t key[SV_MAX];
+  __shared__ int val[SV_MAX];
+  __shared__ int wsum[SV_NT / 64];
+  __shared__ int bad, n_st;
+  __shared__ unsigned long long total;
+  const int64_t r = blockIdx.x;
+  if (r >= R) return;
+  const int64_t o0 = offsets[r], o1 = offsets[r + 1], l0 = list_off[r], l1 = list_off[r + 1];
+  const bool seg_ok = o0 >= 0 && o1 >= o0 && o1 <= n_total && o1 - o0 <= SV_MAX;
+  const bool list_ok = l0 >= 0 && l1 >= l0 && l1 <= L_total;
+  const int n = seg_ok ? (int)(o1 - o0) : 0;
+  const int64_t nl = list_ok ? l1 - l0 : 0;
+  // a request without lists: every count 0, its list segment -1
+  auto finish = [&](int32_t stt) {
+    for (int t = threadIdx.x; t < n; t += SV_NT) by_count[o0 + t] = 0;
+    for (int64_t t = threadIdx.x; t < nl; t += SV_NT) lists[l0 + t] = -1;
+    if (threadIdx.x == 0) status[r] = stt;
+  };
+  const int c = out_count[r];
+  const int64_t u = reviewers[r];
+  if (!seg_ok || !list_ok || c < 0 || c > n || u < -1 || u >= st.U) return finish(REQ_BAD_DATA);
+  if (c == 0 || u < 0) return finish(0);
+  const int32_t* fr;
+  int64_t nf;
+  if (!store_friends(st, u, fr, nf)) return finish(REQ_BAD_DATA);
+  if (nf > SV_MAX) return finish(REQ_OVERFLOW);
+  auto src = [&](int64_t i) -> int64_t { return fr[i]; };
+  if (threadIdx.x == 0) { bad = 0; n_st = 0; total = 0; }
+  __syncthreads();
+  store_count_rows(st, nf, src, &total, &bad);
+  __syncthreads();
+  if (bad) return finish(REQ_BAD_DATA);
+  if (total > (unsigned long long)SV_MAX) return finish(REQ_OVERFLOW);
+  // hotel row -> position among the c returned rows (a row outside the table,
+  // the -1 of a marked answer: never found)
+  int c2 = 1;
+  while (c2 < c) c2 <<= 1;
+  for (int t = threadIdx.x; t < c2; t += SV_NT) {
+    const int64_t row = t < c ? out_rows[o0 + t] : -1;
+    mkey[t] = row >= 0 && row < n_items ? (int)row : INT_MAX;
+    mval[t] = t;
+  }
+  __syncthreads();
+  lds_bitonic(mkey, mval, c2);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int64_t i = w; i < nf; i += SV_NT / 64) {
+    const int64_t f = fr[i];
+    int64_t lo, hi;
+    if (!store_reviews(st, f, lo, hi)) { bad = 1; continue; }
+    for (int64_t j = lo + lane; j < hi; j += 64) {
+      const int32_t wd = st.rv_item[j];
+      const int32_t row = st.rv_row[j];
+      if (wd < 0 || (wd >> 2) >= n_items || row < 0 || row >= st.M) { bad = 1; continue; }
+      if (!(wd & 1)) continue;
+      const int q = lower_bound<int>(mkey, c2, wd >> 2);
+      if (q >= c2 || mkey[q] != (wd >> 2)) continue;
+      const int p = atomicAdd(&n_st, 1);
+      if (p >= SV_MAX) { bad = 1; continue; }   // (total <= SV_MAX: not reached)
+      key[p] = ((int64_t)mval[q] << 32) | (uint32_t)f;
+      val[p] = row;
+    }
+  }
+  __syncthreads();
+  if (bad) return finish(REQ_BAD_DATA);
+  const int ns = n_st;
+  int n2 = 1;
+  while (n2 < ns) n2 <<= 1;
+  for (int t = ns + threadIdx.x; t < n2 || t < 1; t += SV_NT) { key[t] = INT64_MAX; val[t] = 0; }
+  __syncthreads();
+  lds_bitonic(key, val, n2);   // by (position, reviewer), then review row
+  // a reviewer's repeats dropped: the first of every (position, reviewer), in place
+  const int m = block_compact<ByPair>(
+      n2, wsum,
+      [&](int t, ByPair& v) {
+        v.k = key[t];
+        v.v = val[t];
+        return v.k != INT64_MAX && (t == 0 || v.k != key[t - 1]);
+      },
+      [&](int p, ByPair v) { key[p] = v.k; val[p] = v.v; });
+  if (m > nl) return finish(REQ_BAD_DATA);
+  // (position, reviewer | row) -> (position, row | reviewer), each thread its own entries
+  int m2 = 1;
+  while (m2 < m) m2 <<= 1;
+  for (int t = threadIdx.x; t < m2; t += SV_NT) {
+    const int64_t k = key[t];
+    const int row = val[t];
+    key[t] = t < m ? (k & ~(int64_t)0xffffffff) | (uint32_t)row : INT64_MAX;
+    val[t] = t < m ? (int)(uint32_t)k : 0;
+  }
+  __syncthreads();
+  lds_bitonic(key, val, m2);   // by (position, first review row)
+  for (int64_t t = threadIdx.x; t < nl; t += SV_NT) lists[l0 + t] = t < m ? val[t] : -1;
+  for (int t = threadIdx.x; t < n; t += SV_NT)
+    by_count[o0 + t] = t < c ? lower_bound<int64_t>(key, m, (int64_t)(t + 1) << 32) -
+                                   lower_bound<int64_t>(key, m, (int64_t)t << 32)
+                             : 0;
+  if (threadIdx.x == 0) status[r] = 0;
+}
+
+// by_reviewers as one CSR over the n positions of the result (by_off [n + 1]
+// = the exclusive sum of by_count): position i of request r (the segment of
+// offsets holding it) copies its by_count[i] reviewers from the request's
+// list segment, where they follow those of the request's earlier positions;
+// the words behind by_off[n] are set to -1.  A copy that would leave either
+// buffer (L_total words) is not made.
+__global__ void req_by_gather_kernel(const int32_t* lists, const int64_t* list_off, int64_t L_total,
+                                     const int64_t* offsets, int64_t R, int64_t n,
+                                     const int32_t* by_count, const int64_t* by_off,
+                                     int32_t* by_reviewers) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t end = n > 0 ? by_off[n] : 0;
+  if (i >= end && i < L_total) by_reviewers[i] = -1;   // (one thread per word of the tail, too)
+  if (i >= n) return;
+  int64_t lo = 0, hi = R - 1;   // the last request with offsets[r] <= i
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo + 1) >> 1);
+    if (offsets[mid] <= i) lo = mid; else hi = mid - 1;
+  }
+  const int64_t o0 = offsets[lo];
+  if (o0 < 0 || o0 > i) return;
+  const int64_t dst = by_off[i], src = list_off[lo] + (dst - by_off[o0]);
+  const int64_t cnt = by_count[i];
+  if (cnt <= 0 || dst < 0 || src < 0 || dst + cnt > L_total || src + cnt > L_total) return;
+  for (int64_t j = 0; j < cnt; ++j) by_reviewers[dst + j] = lists[src + j];
+}
+
 // Batch assembly of a device-resident dataset (the DataLoader of
 // train.py:195-196): dst_a[i] = src_a[idx[i]] for each array a, whole rows of
 // row_bytes (a multiple of 4) copied as dwords, one wave per (row, array).
@@ -819,6 +1131,51 @@ dcnr_status requests_rank_mmr(const float* logits, int64_t n, const int64_t* slo
                      slots, cap, offsets, R, table, inv, d, n_items, lambda, top_k, w.rrows,
                      w.rscores, out_rows, out_logits, out_count, status);
   DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
+// ---- requests by user (the interaction store on the device)
+static ReqStore req_store(const dcnr_interactions& s) {
+  return ReqStore{s.n_reviewers, s.friend_offsets, s.friend_rows, s.n_friend_rows,
+                  s.review_offsets, s.review_items, s.review_rows, s.n_reviews};
+}
+
+dcnr_status requests_sources(const dcnr_interactions& store, const int32_t* reviewers,
+                             const int32_t* modes, int64_t R, int64_t n_items,
+                             const int64_t* pos_off, int64_t Q_total, int64_t* pos,
+                             const int64_t* neg_off, int64_t neg_lo, int64_t neg_hi, int64_t* neg,
+                             int32_t* counts, int32_t* status, int32_t* host_counts,
+                             int32_t* host_status, hipStream_t s) {
+  hipLaunchKernelGGL(req_sources_kernel, dim3((unsigned)R), dim3(SV_NT), 0, s, req_store(store),
+                     reviewers, modes, R, n_items, pos_off, Q_total, pos, neg_off, neg_lo, neg_hi,
+                     neg, counts, status, host_counts, host_status);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
+dcnr_status requests_recommended_by(const dcnr_interactions& store, const int32_t* reviewers,
+                                    int64_t R, int64_t n_items, const int64_t* out_rows, int64_t n,
+                                    const int64_t* offsets, const int32_t* out_count,
+                                    const int64_t* list_off, int64_t L_total, int32_t* lists,
+                                    int32_t* by_count, int64_t* by_off, int32_t* by_reviewers,
+                                    int32_t* status, hipStream_t s) {
+  // (positions no valid segment covers count 0)
+  if (n > 0) TRY_ST(fill_zero(by_count, (size_t)n * sizeof(int32_t), s));
+  hipLaunchKernelGGL(req_recommended_by_kernel, dim3((unsigned)R), dim3(SV_NT), 0, s,
+                     req_store(store), reviewers, R, n_items, out_rows, n, offsets, out_count,
+                     list_off, L_total, lists, by_count, status);
+  DCNR_LAUNCH_CHECK();
+  // by_off = the exclusive sum of by_count over the n positions
+  hipLaunchKernelGGL(req_offsets_kernel, dim3(1), dim3(SV_NT), 0, s, by_count,
+                     (const int32_t*)nullptr, n, INT_MAX, by_off, (int64_t*)nullptr,
+                     (int32_t*)nullptr);
+  DCNR_LAUNCH_CHECK();
+  const int64_t threads = n > L_total ? n : L_total;
+  if (threads > 0) {
+    hipLaunchKernelGGL(req_by_gather_kernel, dim3((unsigned)cdiv(threads, 256)), dim3(256), 0, s,
+                       lists, list_off, L_total, offsets, R, n, by_count, by_off, by_reviewers);
+    DCNR_LAUNCH_CHECK();
+  }
   return DCNR_OK;
 }
 

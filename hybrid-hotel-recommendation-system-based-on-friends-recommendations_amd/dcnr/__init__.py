@@ -17,6 +17,9 @@ System-Based-on-Friends-Recommendations):
   serving.rerank_with_mmr            main.py:133-169
   serving.RankingPipeline            the /recommendations + /similar_items core
                                      (main.py:196-230, 294-332)
+  InteractionStore                   main_df's reviews + friendships_df as the
+                                     request path reads them (main.py:172-194,
+                                     336-351); RankingPipeline.recommend_users
   artifacts.save_artifacts /         final_dcn_model.pth + item_embeddings.npy
   artifacts.load_artifacts           (train.py:391-394, main.py:256-270)
 
@@ -30,6 +33,7 @@ from .metrics import Metrics, eval_metrics, evaluate, roc_auc_score  # noqa: F40
 from . import serving  # noqa: F401
 from .data import DeviceLoader  # noqa: F401
 from .serving import RankingPipeline, rerank_with_mmr  # noqa: F401
+from .interactions import InteractionStore  # noqa: F401
 from . import artifacts  # noqa: F401
 
 __version__ = "0.1.0"

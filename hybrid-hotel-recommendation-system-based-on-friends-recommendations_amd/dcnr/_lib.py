@@ -74,6 +74,20 @@ class MetricsStruct(ctypes.Structure):
     ]
 
 
+class Interactions(ctypes.Structure):
+    """dcnr_interactions: the device CSRs of a dcnr.InteractionStore."""
+    _fields_ = [
+        ("n_reviewers", ctypes.c_int64),
+        ("friend_offsets", ctypes.c_void_p),
+        ("friend_rows", ctypes.c_void_p),
+        ("n_friend_rows", ctypes.c_int64),
+        ("review_offsets", ctypes.c_void_p),
+        ("review_items", ctypes.c_void_p),
+        ("review_rows", ctypes.c_void_p),
+        ("n_reviews", ctypes.c_int64),
+    ]
+
+
 # exported symbol -> (restype, argtypes); must match include/dcnr.h
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -133,6 +147,11 @@ _SIGS = {
     "dcnr_requests_rank_mmr": (ctypes.c_int, [_P, _I64, _P, ctypes.c_int32, _P, _I64, _P, _P,
                                               ctypes.c_int32, _I64, _P, _P, _P, _P, _P, _P, _P,
                                               ctypes.c_size_t, _P]),
+    "dcnr_requests_sources": (ctypes.c_int, [ctypes.POINTER(Interactions), _P, _P, _I64, _I64, _P,
+                                             _I64, _P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
+    "dcnr_requests_recommended_by": (ctypes.c_int, [ctypes.POINTER(Interactions), _P, _I64, _I64,
+                                                    _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P,
+                                                    _P, _P]),
     "dcnr_check_errors": (ctypes.c_int, [_P, ctypes.c_size_t, _P]),
     "dcnr_linear_bf16": (ctypes.c_int, [_P, _I64, _I64, ctypes.c_int32, _P, _I64, ctypes.c_int32,
                                         _P, _P, _I64, ctypes.c_int, _P]),

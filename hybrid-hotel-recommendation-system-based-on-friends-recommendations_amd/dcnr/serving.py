@@ -27,7 +27,10 @@ fill-up, main.py:204-212) are host set operations and take ``allowed`` /
 pass (dcnr_requests_*: one workgroup per request, the filters as binary
 searches in row sets kept on the device by ``register_sets``, one forward over
 all candidates, one host wait); ``similar_items_many`` is its /similar_items
-companion.
+companion.  ``RankingPipeline.recommend_users`` is the same pass from user
+ids: the positives, the negatives and the ``recommended_by`` lists (main.py:
+172-194, 336-351) come from a ``dcnr.InteractionStore`` on the device
+(dcnr_requests_sources, dcnr_requests_recommended_by).
 """
 from __future__ import annotations
 
@@ -122,6 +125,44 @@ def rerank_with_mmr(ranked_items_with_scores: List[Tuple[float, int]], lambda_pa
     scores = torch.tensor(np.asarray([s for s, _ in ranked_items_with_scores], dtype=np.float32))
     pos = mmr_positions(table, inv, rows, scores, lambda_param, top_k).cpu().tolist()
     return [ids[p] for p in pos]
+
+
+class UserAnswers(list):
+    """What ``RankingPipeline.recommend_users`` returns: a list of R (ranked
+    rows, logits) pairs, views into ``rows`` / ``logits`` [n] as
+    ``recommend_many``'s are, and the recommended_by lists of every position of
+    those two tensors, on the device:
+
+      by_offsets [n + 1], by_reviewers   a CSR over the positions: position i
+                   was recommended by by_reviewers[by_offsets[i] : by_offsets[i + 1]]
+                   (store reviewer indices, in the reference's order); positions
+                   behind a request's answer have empty lists
+      by_count [n], lists                the same lists where the host can find
+                   them without reading by_offsets: request r's reviewers,
+                   position by position, from lists[list offset of r] on
+
+    ``to_lists(r)`` turns answer r into Python lists with one copy to the
+    host.  A request that was answered on the host (``on_host[r]``) has no
+    positions in the tensors; ``to_lists`` serves it from the store's host
+    copies.  ``n_positives`` / ``positives_bound``: per request the distinct
+    positives the device found and the padded length they were searched at."""
+
+    def to_lists(self, r: int):
+        """(hotel rows, logits, recommended_by lists) of answer r."""
+        rows, logits = self[r]
+        if self.on_host[r]:
+            rows = rows.cpu()
+            return (rows.tolist(), logits.cpu().tolist(),
+                    self._store.recommended_by_host(int(self._rv[r]), rows))
+        o, c = int(self._seg[r]), int(self._cnt[r])
+        l0, l1 = int(self._list_off[r]), int(self._list_off[r + 1])
+        pack = torch.cat([rows, logits.view(torch.int32).to(torch.int64),
+                          self.by_count[o:o + c].to(torch.int64),
+                          self.lists[l0:l1].to(torch.int64)]).cpu().numpy()
+        ends = np.cumsum(pack[2 * c:3 * c])
+        who = pack[3 * c:]
+        by = [who[e - m:e].tolist() for e, m in zip(ends, pack[2 * c:3 * c])]
+        return (pack[:c].tolist(), pack[c:2 * c].astype(np.int32).view(np.float32).tolist(), by)
 
 
 class RankingPipeline:
@@ -387,32 +428,9 @@ class RankingPipeline:
         st = host[o_st:o_st + 4 * R].view(np.int32)
         if (st & REQ_BAD_DATA).any():
             raise RuntimeError("recommend_many: the device rejected validated input")
-        out_rows = out_logits = None
-        if n:
-            K, F = self.item_cat.shape[1], self.item_num.shape[1]
-            u = torch.empty(n, dtype=torch.int64, device=dev)
-            i = torch.empty(n, dtype=torch.int64, device=dev)
-            c = torch.empty((n, K), dtype=torch.int64, device=dev)
-            x = torch.empty((n, F), dtype=torch.float32, device=dev)
-            _lib.check(lib.dcnr_requests_ranking_batch(
-                slots.data_ptr(), cap, offsets.data_ptr(), R, n, d_at("users"),
-                self.item_cat.data_ptr() if K else None, K,
-                self.item_num.data_ptr() if F else None, F, self.n_items, u.data_ptr(),
-                i.data_ptr(), c.data_ptr() if K else None, x.data_ptr() if F else None, stream),
-                "dcnr_requests_ranking_batch")
-            logits = self.model(u, i, c, x).reshape(-1).to(torch.float32).contiguous()
-            out_rows = torch.empty(n, dtype=torch.int64, device=dev)
-            out_logits = torch.empty(n, dtype=torch.float32, device=dev)
-            table, inv = self.index._table, self.index._inv
-            _lib.check(lib.dcnr_requests_rank_mmr(
-                logits.data_ptr(), n, slots.data_ptr(), cap, offsets.data_ptr(), R,
-                table.data_ptr(), inv.data_ptr(), table.shape[1], table.shape[0],
-                d_at("lam"), d_at("topk"), out_rows.data_ptr(), out_logits.data_ptr(),
-                out_count, status, ws.data_ptr(), nb, stream),
-                "dcnr_requests_rank_mmr")
-        if not n:
-            out_rows = torch.empty(0, dtype=torch.int64, device=dev)
-            out_logits = torch.empty(0, dtype=torch.float32, device=dev)
+        out_rows, out_logits = self._score_and_rank(R, cap, n, slots, offsets, d_at("users"),
+                                                    d_at("lam"), d_at("topk"), out_count, status,
+                                                    ws, nb, stream)
         # recommend() decides "lambda < 1" on the Python double and computes with its
         # float32: a lambda that rounds to 1.0f from below goes its way
         lam64 = info["lam64"]
@@ -434,6 +452,228 @@ class RankingPipeline:
             c_r = min(int(topk[r]), n_r) if lam[r] < 1.0 else n_r
             o = int(seg[r])
             res.append((out_rows[o:o + c_r], out_logits[o:o + c_r]))
+        return res
+
+    def _score_and_rank(self, R, cap, n, slots, offsets, d_users, d_lam, d_topk, out_count, status,
+                        ws, nb, stream):
+        """The batched calls' half behind the wait: the ranking batch of the n
+        candidates, one forward, rank + MMR per segment -> (rows, logits) [n]."""
+        lib = _lib.load()
+        dev = self.device
+        if not n:
+            return (torch.empty(0, dtype=torch.int64, device=dev),
+                    torch.empty(0, dtype=torch.float32, device=dev))
+        K, F = self.item_cat.shape[1], self.item_num.shape[1]
+        u = torch.empty(n, dtype=torch.int64, device=dev)
+        i = torch.empty(n, dtype=torch.int64, device=dev)
+        c = torch.empty((n, K), dtype=torch.int64, device=dev)
+        x = torch.empty((n, F), dtype=torch.float32, device=dev)
+        _lib.check(lib.dcnr_requests_ranking_batch(
+            slots.data_ptr(), cap, offsets.data_ptr(), R, n, d_users,
+            self.item_cat.data_ptr() if K else None, K,
+            self.item_num.data_ptr() if F else None, F, self.n_items, u.data_ptr(),
+            i.data_ptr(), c.data_ptr() if K else None, x.data_ptr() if F else None, stream),
+            "dcnr_requests_ranking_batch")
+        logits = self.model(u, i, c, x).reshape(-1).to(torch.float32).contiguous()
+        out_rows = torch.empty(n, dtype=torch.int64, device=dev)
+        out_logits = torch.empty(n, dtype=torch.float32, device=dev)
+        table, inv = self.index._table, self.index._inv
+        _lib.check(lib.dcnr_requests_rank_mmr(
+            logits.data_ptr(), n, slots.data_ptr(), cap, offsets.data_ptr(), R,
+            table.data_ptr(), inv.data_ptr(), table.shape[1], table.shape[0],
+            d_lam, d_topk, out_rows.data_ptr(), out_logits.data_ptr(),
+            out_count, status, ws.data_ptr(), nb, stream),
+            "dcnr_requests_rank_mmr")
+        return out_rows, out_logits
+
+    # --------------------------------------------- a batch of requests by user
+    @torch.no_grad()
+    def recommend_users(self, store, user_rows, reviewers, modes, lambda_param=1.0, top_k=20,
+                        allowed=None, fallback=None, min_candidates: int = 20,
+                        recommended_by: bool = True):
+        """``recommend_many`` from user ids: each request's positives, its
+        excluded set (the negatives, main.py:193-194, 211) and the
+        ``recommended_by`` lists of its answer (main.py:336-351) come from a
+        ``dcnr.InteractionStore`` on the device.
+
+        store       dcnr.InteractionStore over this pipeline's hotel rows
+        user_rows   R model user rows (main.py:217 stays the caller's)
+        reviewers   R store indices, -1 for a user the store does not know
+        modes       'friends' / 'personal', one value or R
+        lambda_param, top_k, allowed, fallback, min_candidates
+                    as in ``recommend_many`` (``excluded`` is the negatives)
+
+        Returns a ``UserAnswers``: a list of R (ranked rows, logits) pairs,
+        each equal to what ``recommend_many`` gives for ``sources_host``'s
+        positives and negatives, with the recommended_by CSR over the result
+        tensor's positions as device tensors and ``to_lists(r)``.
+
+        One packed pinned upload (no positives travel), one wait, as in
+        ``recommend_many``.  The device cannot tell the host how many distinct
+        positives it found without a second wait, so each request gets
+        segments as long as the store's host counts bound them (the sum over
+        its sources of their distinct positives / negatives) and the kernel
+        fills a segment's tail with repeats: the candidate union is a set
+        union and the excluded filter a binary search in an ascending set, so
+        the candidates are those of the distinct rows.  A request whose friends
+        or staged review rows exceed SV_MAX, or whose bound of positives times
+        n_neighbors does (known from the counts before anything is launched),
+        and one the candidate kernel reports as overflowing, is answered by
+        ``sources_host`` + ``recommend()`` + ``recommended_by_host`` and
+        spliced in, never truncated."""
+        from . import interactions as ia
+        lib = _lib.load()
+        dev = self.device
+        if self.index._table.shape[0] != self.n_items:
+            raise ValueError(f"recommend_users: the index holds {self.index._table.shape[0]} "
+                             f"rows, item_cat / item_num {self.n_items}")
+        if store.n_items > self.n_rows:
+            raise ValueError(f"recommend_users: the store names {store.n_items} hotel rows, the "
+                             f"pipeline holds {self.n_rows}")
+        users = np.asarray(user_rows, dtype=np.int64).reshape(-1)
+        R = users.size
+        rv = np.asarray(reviewers, dtype=np.int64).reshape(-1)
+        if rv.size != R:
+            raise ValueError("recommend_users: one reviewer index per user row")
+        if R == 0:
+            return UserAnswers()
+        if rv.min() < -1 or rv.max() >= store.n_reviewers:
+            raise ValueError(f"recommend_users: reviewer outside [-1, {store.n_reviewers})")
+        md = np.full(R, ia.mode_code(modes), np.int32) if isinstance(modes, (str, int, np.integer)) \
+            else np.array([ia.mode_code(m_) for m_ in modes], np.int32)
+        if md.size != R:
+            raise ValueError("recommend_users: one mode, or one per request")
+        # lambda, top_k and the allowed / fallback indices as recommend_many packs them
+        ins, info = self._pack_requests(users, [()] * R, lambda_param, top_k, allowed, None,
+                                        fallback)
+        ins = dict(ins)
+        lam, lam64, topk = info["lam"], info["lam64"], info["topk"]
+        k = self.n_neighbors
+        # ---- what the store's host counts say about each request
+        n_src, staged, pos_b, neg_b, n_fr, fr_rows, by_b = store.bounds(rv, md)
+        on_host = (n_src > SV_MAX) | (staged > SV_MAX) | (pos_b * k > SV_MAX) | \
+            ((lam64 < 1.0) != (lam < 1.0))
+        if recommended_by:
+            on_host |= (n_fr > SV_MAX) | (fr_rows > SV_MAX)
+        else:
+            by_b = np.zeros(R, np.int64)
+        dev_rv = np.where(on_host, -1, rv).astype(np.int32)   # answered on the host: no sources here
+        zero = lambda a: np.where(on_host, 0, a)
+        pos_off, list_off = np.zeros(R + 1, np.int64), np.zeros(R + 1, np.int64)
+        np.cumsum(zero(pos_b), out=pos_off[1:])
+        np.cumsum(zero(by_b), out=list_off[1:])
+        Q, L = int(pos_off[R]), int(list_off[R])
+        # the requests' negatives behind the registered and per-call sets, one CSR
+        set_off = ins.get("set_off", np.zeros(1, np.int64))
+        S0, n0 = set_off.size - 1, int(set_off[-1])
+        neg_b = zero(neg_b)
+        set_off = np.concatenate([set_off, n0 + np.cumsum(neg_b)])
+        NB = int(set_off[-1]) - n0
+        e_idx = np.where(neg_b > 0, S0 + np.arange(R), -1).astype(np.int32)
+        if "fallback" in ins and on_host.any():   # (no fallback either: nothing of theirs is scored)
+            ins["fallback"] = np.where(on_host, -1, ins["fallback"]).astype(np.int32)
+        f_len =np.diff(set_off)[ins["fallback"]] * (ins["fallback"] >= 0) if "fallback" in ins else 0
+        cap = int(min(SV_MAX, max(1, int((zero(pos_b) * k + f_len).max()))))
+        ins.update(pos_off=pos_off, set_off=set_off, list_off=list_off, excluded=e_idx,
+                   reviewers=dev_rv, modes=md)
+        del ins["pos"]
+        # ---- every host input in one pinned buffer, one non-blocking copy; behind
+        # it the device's mirrors: offsets, candidate status, source counts + status
+        at, total = {}, 0
+        for name, a in ins.items():
+            at[name] = total
+            total += (a.nbytes + 7) & ~7
+        o_off = total
+        o_st = o_off + 8 * (R + 1)
+        o_cnt = o_st + ((4 * R + 7) & ~7)
+        o_sst = o_cnt + 8 * R
+        pin, host = self._pinned(o_sst + ((4 * R + 7) & ~7))
+        for name, a in ins.items():
+            host[at[name]:at[name] + a.nbytes] = a.view(np.uint8)
+        dbuf = pin[:total].to(dev, non_blocking=True)
+        d_at = lambda name: dbuf.data_ptr() + at[name] if name in at else None
+        stream = _lib.stream_ptr(dev)
+        sets = [info["reg_rows"]]
+        if info["n_adhoc"]:
+            o = at["adhoc_rows"]
+            sets.append(dbuf[o:o + 8 * info["n_adhoc"]].view(torch.int64))
+        if NB:
+            sets.append(torch.empty(NB, dtype=torch.int64, device=dev))
+        set_rows = torch.cat(sets) if len(sets) > 1 else sets[0]
+        desc, _ = store.on(dev)
+        d_pos = torch.empty(Q, dtype=torch.int64, device=dev)
+        # count, status, out_count of the candidate / rank kernels; the source
+        # kernel's counts [2 R] + status, the recommended_by kernel's status
+        words = torch.empty(7 * R, dtype=torch.int32, device=dev)
+        count, status, out_count, s_cnt, s_st, by_st = (words.data_ptr() + 4 * R * j
+                                                        for j in (0, 1, 2, 3, 5, 6))
+        _lib.check(lib.dcnr_requests_sources(
+            desc, d_at("reviewers"), d_at("modes"), R, self.n_rows, d_at("pos_off"), Q,
+            d_pos.data_ptr() if Q else None, d_at("set_off") + 8 * S0, n0, n0 + NB,
+            set_rows.data_ptr() if NB else None, s_cnt, s_st, pin.data_ptr() + o_cnt,
+            pin.data_ptr() + o_sst, stream), "dcnr_requests_sources")
+        idx = None
+        if Q:   # one top-k call for all requests' (padded) positives
+            _, idx = self.index.kneighbors_device(self.index._table[d_pos], k)
+        slots = torch.empty((R, cap), dtype=torch.int64, device=dev)
+        offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        _lib.check(lib.dcnr_requests_candidates(
+            d_pos.data_ptr() if Q else None, d_at("pos_off"), R, Q,
+            idx.data_ptr() if Q else None, k,
+            set_rows.data_ptr() if set_rows.numel() else None, set_rows.numel(),
+            d_at("set_off"), S0 + R, d_at("allowed"), d_at("excluded"), d_at("fallback"),
+            int(min_candidates), self.n_rows, cap, slots.data_ptr(), count, status,
+            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream),
+            "dcnr_requests_candidates")
+        # (allocated while the device works, not after the wait)
+        nb = int(lib.dcnr_requests_workspace_size(R, Q, k, cap))
+        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        lists = torch.empty(L, dtype=torch.int32, device=dev)
+        by_reviewers = torch.empty(L, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()   # the call's one wait
+        seg = host[o_off:o_st].view(np.int64).copy()
+        n = int(seg[R])
+        st = host[o_st:o_st + 4 * R].view(np.int32).copy()
+        s_counts = host[o_cnt:o_cnt + 8 * R].view(np.int32).reshape(R, 2).copy()
+        sst = host[o_sst:o_sst + 4 * R].view(np.int32)
+        if ((st | sst) & REQ_BAD_DATA).any():
+            raise RuntimeError("recommend_users: the device rejected validated input")
+        on_host = on_host | ((st | sst) & REQ_OVERFLOW).astype(bool)
+        out_rows, out_logits = self._score_and_rank(R, cap, n, slots, offsets, d_at("users"),
+                                                    d_at("lam"), d_at("topk"), out_count, status,
+                                                    ws, nb, stream)
+        by_count = torch.empty(n, dtype=torch.int32, device=dev)
+        by_offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        if recommended_by and n:
+            _lib.check(lib.dcnr_requests_recommended_by(
+                desc, d_at("reviewers"), R, self.n_rows, out_rows.data_ptr(), n,
+                offsets.data_ptr(), out_count, d_at("list_off"), L,
+                lists.data_ptr() if L else None, by_count.data_ptr(), by_offsets.data_ptr(),
+                by_reviewers.data_ptr() if L else None, by_st, stream),
+                "dcnr_requests_recommended_by")
+        elif n:
+            by_count.zero_()
+        n_seg = np.diff(seg)
+        # every candidate is a table row, so the MMR finds min(top_k, n_r) items
+        cnt = np.where(lam < 1.0, np.minimum(topk, n_seg), n_seg)
+        res = UserAnswers()
+        res.by_offsets, res.by_reviewers, res.by_count, res.lists = (by_offsets, by_reviewers,
+                                                                    by_count, lists)
+        res.rows, res.logits = out_rows, out_logits
+        res._seg, res._cnt, res._list_off, res._store, res._rv = seg, cnt, list_off, store, rv
+        res.n_positives, res.positives_bound = s_counts[:, 0], zero(pos_b)
+        res.on_host = on_host
+        for r in range(R):
+            if on_host[r]:   # above the batched kernels' capacity: the one-request path
+                pick = lambda v: None if v is None else v[r]
+                p_r, n_r = store.sources_host(int(rv[r]), int(md[r]))
+                res.append(self.recommend(int(users[r]), p_r, float(lam64[r]), int(topk[r]),
+                                          allowed=self._set_arg(pick(allowed)), excluded=n_r,
+                                          fallback=self._set_arg(pick(fallback)),
+                                          min_candidates=min_candidates))
+                continue
+            o = int(seg[r])
+            res.append((out_rows[o:o + int(cnt[r])], out_logits[o:o + int(cnt[r])]))
         return res
 
     def _pack_requests(self, users, positive_rows, lambda_param, top_k, allowed, excluded,

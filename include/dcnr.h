@@ -28,6 +28,9 @@
  *   dcnr_mmr_rerank       rerank_with_mmr                     main.py:133-169
  *   dcnr_requests_*       the same four steps for a batch of requests, one
  *                         workgroup per request               main.py:309-332
+ *   dcnr_requests_sources, dcnr_requests_recommended_by
+ *                         the friends, positives / negatives and recommended_by
+ *                         lists of those requests    main.py:172-194, 336-351
  *   dcnr_eval_metrics     roc_auc_score / BCEWithLogitsLoss / sqrt(mean_squared_error)
  *                         over the validation logits          train.py:255-265, 366-387
  *
@@ -523,6 +526,77 @@ dcnr_status dcnr_requests_rank_mmr(const float* logits, int64_t n, const int64_t
                                    const int32_t* top_k, int64_t* out_rows, float* out_logits,
                                    int32_t* out_count, int32_t* status, void* ws, size_t ws_bytes,
                                    dcnr_stream_t stream);
+
+/* ---- serving, requests by user: the reviews and the friend graph on the device ----
+ * What /recommendations reads of main_df and friendships_df (get_friends_for_user,
+ * main.py:172-178; the positives and negatives of _generate_candidates, main.py:
+ * 187-194; the recommended_by lists, main.py:336-351), as two CSRs over the
+ * n_reviewers reviewers, in device memory (dcnr.InteractionStore builds them):
+ * the friends of a reviewer, distinct and symmetric (the reviewer itself only
+ * where a (u, u) pair exists), and the reviews of a reviewer in main_df order. */
+typedef struct {
+  int64_t n_reviewers;
+  const int64_t* friend_offsets; /* [n_reviewers + 1] */
+  const int32_t* friend_rows;    /* [n_friend_rows] reviewer indices */
+  int64_t n_friend_rows;
+  const int64_t* review_offsets; /* [n_reviewers + 1] */
+  const int32_t* review_items;   /* [n_reviews] hotel row * 4 + class bits:
+                                    1 = rating_overall >= 8, 2 = rating_overall <= 4 */
+  const int32_t* review_rows;    /* [n_reviews] the review's row in main_df */
+  int64_t n_reviews;
+} dcnr_interactions;
+
+#define DCNR_MODE_FRIENDS 0  /* sources: the reviews of the reviewer's friends */
+#define DCNR_MODE_PERSONAL 1 /* sources: the reviewer's own reviews */
+
+/* The positives and negatives of R requests, one workgroup each, in front of
+ * dcnr_requests_candidates: request r is reviewer reviewers[r] (-1: an unknown
+ * user, no sources) in mode modes[r].  Its distinct positive hotel rows (a
+ * source review with rating >= 8) are written ascending to positives
+ * [pos_offsets[r] .. pos_offsets[r + 1]), the last repeated up to the segment's
+ * end; its distinct negative rows (rating <= 4) likewise to neg_rows
+ * [neg_offsets[r] .. neg_offsets[r + 1]), a segment inside [neg_lo, neg_hi):
+ * an ascending set, so that neg_rows may be the set_rows of
+ * dcnr_requests_candidates and the segment the request's excluded set.  The
+ * segment lengths are the caller's bounds of the two counts (the sum over the
+ * sources of their distinct positives / negatives): at least the count, zero
+ * if and only if the count is.  counts [2 R]: the distinct numbers; status [R]:
+ * DCNR_REQ_OVERFLOW when the friends or the sources' review rows exceed 4096
+ * (answer it on the host), DCNR_REQ_BAD_DATA when a reviewer, mode, offset,
+ * friend or hotel row lies outside the lengths passed by value or a segment
+ * length breaks the rule above; either leaves counts 0 and the request's
+ * segments filled with -1.  Both are also stored to host_counts / host_status
+ * (pinned, device-visible host memory, or NULL) with system-scope stores.
+ * DCNR_BAD_ARG / DCNR_UNSUPPORTED_SHAPE (n_items > 2^29, R > 2^22) before any
+ * launch; R = 0 returns DCNR_OK. */
+dcnr_status dcnr_requests_sources(const dcnr_interactions* store, const int32_t* reviewers,
+                                  const int32_t* modes, int64_t R, int64_t n_items,
+                                  const int64_t* pos_offsets, int64_t Q_total, int64_t* positives,
+                                  const int64_t* neg_offsets, int64_t neg_lo, int64_t neg_hi,
+                                  int64_t* neg_rows, int32_t* counts, int32_t* status,
+                                  int32_t* host_counts, int32_t* host_status,
+                                  dcnr_stream_t stream);
+
+/* The recommended_by lists behind dcnr_requests_rank_mmr: for each of the first
+ * out_count[r] positions of request r's segment of out_rows [n], the distinct
+ * friends of reviewers[r] (in either mode) who reviewed that hotel with rating
+ * >= 8, in the order of their first such review's main_df row.  Result: a CSR
+ * over the n positions, by_offsets [n + 1] and by_reviewers [n_list_rows] (the
+ * words behind by_offsets[n] are -1); by_count [n] = the list lengths.  lists
+ * [n_list_rows] is workspace AND result: request r's reviewers, position by
+ * position, from list_offsets[r] on (the rest of its segment -1), a place the
+ * host knows without reading by_offsets.  A segment's length is the caller's
+ * bound: the sum over the friends of their distinct positives.  status [R]
+ * (words of this call): DCNR_REQ_OVERFLOW (friends or their review rows above
+ * 4096), DCNR_REQ_BAD_DATA (as above; more reviewers than the segment holds):
+ * every list of that request is empty. */
+dcnr_status dcnr_requests_recommended_by(const dcnr_interactions* store, const int32_t* reviewers,
+                                         int64_t R, int64_t n_items, const int64_t* out_rows,
+                                         int64_t n, const int64_t* offsets,
+                                         const int32_t* out_count, const int64_t* list_offsets,
+                                         int64_t n_list_rows, int32_t* lists, int32_t* by_count,
+                                         int64_t* by_offsets, int32_t* by_reviewers,
+                                         int32_t* status, dcnr_stream_t stream);
 
 /* The deep tower's Linear layer as a standalone bf16 call (nn.Linear forward,
  * train.py:143,105,109): C[M,N] = X[M,K] . W[N,K]^T + bias, X/W bf16
