@@ -359,12 +359,17 @@ struct Plan {
   bool rebuild_hR;   // the backward's BN2 statistics pass rebuilds h_R from t2, h_{R-1} and the
                      // BN2 affine; the head pass stores h_R only with `keep` (stage tests)
   bool rank1;        // the head pass stores [h_R > 0]; the last BN2 apply is the rank-1 form over it
+  bool head_stats;   // DCNR_FLAG_HEAD_STATS: dcnr_forward_bce's head pass goes on to dz and the last
+                     // block's BN2-backward partials (left in `part`); the backward runs no
+                     // statistics pass for that block
+  bool r1_resid;     // ... and that block's du is never stored: its dX GEMM (RESID_BN with the
+                     // operand transform, R > 1) rebuilds the rank-1 residual in the epilogue
   bool own_dt;       // every block its own dt2 / dt1 buffers (else one shared set)
   bool rowmap;       // DCNR_FLAG_ROW_MAP
   int dw_lag;        // DwPipe: the main stream waits for the dW GEMM this many calls back (1 << 30: never)
 };
 
-Plan make_plan(const Dims& d, uint32_t flags, int mode, int64_t B) {
+Plan make_plan(const Dims& d, uint32_t flags, int mode, int64_t B, bool sync_bn = false) {
   Plan p{};
   const bool bf16p = d.prec == DCNR_PREC_BF16;
   p.train = mode == DCNR_TRAIN;
@@ -384,6 +389,12 @@ Plan make_plan(const Dims& d, uint32_t flags, int mode, int64_t B) {
   p.xbn = p.stats_epi && gemm_ws_xbn_supported(NT_EPI_DROP_BN, d.Hp, d.Hp);
   p.rebuild_hR = bf16p && p.head_fused;
   p.rank1 = p.masks && p.head_fused;
+  // (not with the stage tests' stored intermediates, which include that
+  // block's du; not with SyncBN, whose hook sums the statistics between the
+  // partials and their use)
+  p.head_stats = (flags & DCNR_FLAG_HEAD_STATS) && p.rank1 && p.rebuild_hR && !p.keep && !sync_bn;
+  // (R = 1: the last block is block 0, whose RESID_SUM GEMM reads the stored du)
+  p.r1_resid = p.head_stats && p.xbn && d.R > 1;
   // bf16: every residual block has its own dt2 / dt1 buffers: the side
   // stream's weight-gradient GEMMs read them while the main stream goes on,
   // and the main stream never waits for the side stream inside the backward
@@ -691,10 +702,13 @@ dcnr_status linear_fwd_stats(const Dims& d, const Layout& L, const void* A, int 
 // dt = bn_bwd_dt(du, xt, xbn mean / invstd, L.coef), also written to dt_out
 // (the row pass folded into this GEMM, gemm_ws.hip XBN)
 struct XbnOperand { const void* xt; const BnBufs* bn; void* dt_out; };
+// r1 (optional, RESID_BN with xbn): R is not read; it is the rank-1
+// bf16(dz (x) wf) under the 1-bit image `bits` (Plan::r1_resid)
+struct Rank1Resid { const float* dz; const float* wf; const uint8_t* bits; };
 dcnr_status linear_dx_bn(const Dims& d, const Layout& L, int epi, const void* X, const void* Wt,
                          const void* R, void* C, const uint8_t* Hbits, float hscale,
                          const void* T, const BnBufs& bn, int64_t B, int* nc, hipStream_t s,
-                         const XbnOperand* xbn = nullptr) {
+                         const XbnOperand* xbn = nullptr, const Rank1Resid* r1 = nullptr) {
   NtArgs a;
   memset(&a, 0, sizeof(a));
   if (xbn) {
@@ -711,6 +725,10 @@ dcnr_status linear_dx_bn(const Dims& d, const Layout& L, int epi, const void* X,
   a.T = (const bf16*)T; a.ldt = d.Hp;
   a.mean = bn.mean; a.invstd = bn.invstd;
   a.part = L.part;
+  if (r1) {
+    a.R = nullptr;
+    a.r1_dz = r1->dz; a.r1_bits = (const uint32_t*)r1->bits; a.wf = r1->wf; a.Nr = d.H;
+  }
   return gemm_ws(epi, a, s, nc);
 }
 
@@ -980,6 +998,8 @@ struct Fwd {
   const int64_t *user_ids, *item_ids, *cat_features; const float* num_features;
   int64_t B; float* logits; hipStream_t s; int check;   // check: DCNR_FLAG_CHECK_INDICES
   GatherDesc g; CrossParams cp;
+  // Plan::head_stats (dcnr_forward_bce): the loss's operands
+  const float* labels = nullptr; float grad_scale = 1.f; float* dz = nullptr;
 
   // eval, Plan::tower: gather + cross (x0 bf16, zc) -> the fused deep tower + head
   dcnr_status tower() const {
@@ -1117,7 +1137,15 @@ struct Fwd {
            bn_relu_drop(d.prec, L.t1[j], a1, B, d.Hp, d.Hp, bn1.scale, bn1.shift, p, dropout_seed, j, s,
                         L.mask_a1[j]));
       TRY(linear_bn(a1, L.W2p[j], L.b2p[j], L.t2[j], Bk.g2, Bk.be2, Bk.rm2, Bk.rv2, Bk.nbt2, bn2));
-      if (j == d.R - 1 && pl.head_fused) {
+      if (j == d.R - 1 && pl.head_stats) {
+        // ... and on to dz and the BN2-backward partials of this block, for
+        // the dcnr_backward that follows on this workspace
+        int nc = 0;
+        TRYB(DCNR_K_ROWWISE, s, (pl.r1_resid ? 2 : 3) * act_b(d, B) + mask_b(d, B) + 20.0 * B,
+             bn_add_relu_head_stats(L.t2[j], L.h[j], B, d.Hp, d.Hp, bn2.scale, bn2.shift, bn2.mean, bn2.invstd,
+                                    P.wf, d.H, L.zc, P.bf, labels, grad_scale, logits, dz, L.mask_h[d.R],
+                                    pl.r1_resid ? nullptr : L.duk[j], L.part, &nc, s));
+      } else if (j == d.R - 1 && pl.head_fused) {
         // last block: residual + ReLU + deep head dot + logits in one pass
         const bool store_hR = !pl.rebuild_hR || pl.keep;
         TRYB(DCNR_K_ROWWISE, s, (store_hR ? 3 : 2) * act_b(d, B) + 12.0 * B,
@@ -1171,6 +1199,8 @@ struct Bwd {
     int nc = 0;
     if (nc_du) {   // du and its partials came with the previous block's dX GEMM
       TRY(bn2_reduce(j, nc_du, 2, nullptr));
+    } else if (last && pl.head_stats) {   // ... with the forward's head pass (dcnr_forward_bce)
+      TRY(bn2_reduce(j, bn2_stats_chunks(B), 3, Gr.wf));
     } else {
       TRYB(DCNR_K_ROWWISE, s, 3 * act_b(d, B) + (Gin ? act_b(d, B) : 4.0 * B),
            bwd_bn2_stats3(d.prec, Gin, dz, P.wf, L.h[j + 1], L.t2[j], bn2.mean, bn2.invstd, B, d.Hp, d.Hp,
@@ -1247,9 +1277,14 @@ struct Bwd {
       // G is only consumed by block j-1's BN2 backward: emit its du = G * [h_j > 0]
       // (in place over this block's du, the residual operand, unless
       // KEEP_INTERMEDIATES) and the partials
-      TRYB(DCNR_K_GEMM_DX, s, (xbn ? 6 : 4) * act_b(d, B) + mask_b(d, B) + w_b(d, d.Hp),
+      // (the last block's du with Plan::r1_resid: rank 1, rebuilt in the epilogue, never stored)
+      const bool r1 = pl.r1_resid && j == d.R - 1;
+      const Rank1Resid rr{dz, P.wf, L.mask_h[d.R]};
+      TRYB(DCNR_K_GEMM_DX, s, (xbn ? 6 : 4) * act_b(d, B) - (r1 ? act_b(d, B) - 4.0 * B : 0) +
+                                  (r1 ? 2 : 1) * mask_b(d, B) + w_b(d, d.Hp),
            linear_dx_bn(d, L, NT_EPI_RESID_BN, xbn ? da : dt1, L.W1t[j], du, L.duk[j - 1], L.mask_h[j], 1.f,
-                        L.t2[j - 1], L.bn[2 * (j - 1) + 1], B, &nc_du, s, xbn ? &xo1 : nullptr));
+                        L.t2[j - 1], L.bn[2 * (j - 1) + 1], B, &nc_du, s, xbn ? &xo1 : nullptr,
+                        r1 ? &rr : nullptr));
       if (xbn) TRY(dw1(j));
       Gin = L.duk[j - 1];
       return DCNR_OK;
@@ -1272,6 +1307,57 @@ struct Bwd {
     return DCNR_OK;
   }
 };
+
+// dcnr_forward (bce null) and dcnr_forward_bce: the forward, then the loss
+struct BceOut { const float* labels; float grad_scale; float* loss; float* dlogits; double* part; };
+
+dcnr_status forward_run(const dcnr_model_desc* desc, void* const* params,
+                        const int64_t* user_ids, const int64_t* item_ids,
+                        const int64_t* cat_features, const float* num_features, int64_t B,
+                        int mode, uint64_t dropout_seed, float* logits, void* ws,
+                        size_t ws_bytes, dcnr_stream_t stream, const BceOut* bce_out) {
+  Dims d;
+  TRY(make_dims(desc, &d));
+  hipStream_t s = (hipStream_t)stream;
+  if (!params || !logits || !ws || B < 0 || (B > 0 && (!user_ids || !item_ids)) ||
+      (d.K > 0 && B > 0 && !cat_features) || (desc->n_num > 0 && B > 0 && !num_features)) {
+    set_error("dcnr_forward: null argument");
+    return DCNR_BAD_ARG;
+  }
+  if (mode == DCNR_TRAIN && B < 2) {
+    set_error("Expected more than 1 value per channel when training");
+    return DCNR_BAD_ARG;
+  }
+  // the head pass's statistics need the loss's operands: dcnr_forward_bce only
+  const uint32_t flags = bce_out ? desc->flags : desc->flags & ~DCNR_FLAG_HEAD_STATS;
+  const Plan pl = make_plan(d, flags, mode, B, desc->bn_allreduce != nullptr);
+  const Layout L = make_layout(d, B, pl, ws);
+  if (ws_bytes < L.total) {
+    set_error("workspace too small: %zu < %zu", ws_bytes, L.total);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  if (B == 0) return DCNR_OK;
+  const Params P = map_params(d, params);
+  const int check = (desc->flags & DCNR_FLAG_CHECK_INDICES) ? 1 : 0;
+  Fwd f{desc, d, pl, L, P, user_ids, item_ids, cat_features, num_features, B, logits, s, check,
+        make_gather(d, P, desc->n_num), make_cross(d, P)};
+  if (bce_out) { f.labels = bce_out->labels; f.grad_scale = bce_out->grad_scale; f.dz = bce_out->dlogits; }
+  if (pl.tower) return f.tower();
+  SideJoin sj;
+  TRY(f.front(sj));
+  TRY(pl.eval_epi ? f.eval_epi() : f.layers(dropout_seed));
+  if (pl.train) TRY(sj.join(s));   // the sorted ids (workspace) for dcnr_backward
+  // the id-check word to the caller's mirror, after the forward's last kernel
+  // on the stream
+  if (desc->error_mirror && check) TRYP(DCNR_K_PACK, s, mirror_word((const int*)ws, desc->error_mirror, s));
+  // the loss value (and dz, unless the head pass made it): the loss kernels
+  // of dcnr_bce_with_logits on the logits, so its bits do not depend on the path
+  if (bce_out)
+    TRYP(DCNR_K_HEAD, s, bce(logits, bce_out->labels, B, bce_out->loss, pl.head_stats ? nullptr : bce_out->dlogits,
+                             bce_out->grad_scale, bce_out->part, s));
+  return DCNR_OK;
+}
+
 
 }  // namespace
 }  // namespace dcnr
@@ -1370,38 +1456,27 @@ dcnr_status dcnr_forward(const dcnr_model_desc* desc, void* const* params,
                          const int64_t* cat_features, const float* num_features, int64_t B,
                          int mode, uint64_t dropout_seed, float* logits, void* ws,
                          size_t ws_bytes, dcnr_stream_t stream) {
-  Dims d;
-  TRY(make_dims(desc, &d));
-  hipStream_t s = (hipStream_t)stream;
-  if (!params || !logits || !ws || B < 0 || (B > 0 && (!user_ids || !item_ids)) ||
-      (d.K > 0 && B > 0 && !cat_features) || (desc->n_num > 0 && B > 0 && !num_features)) {
-    set_error("dcnr_forward: null argument");
+  return forward_run(desc, params, user_ids, item_ids, cat_features, num_features, B, mode, dropout_seed,
+                     logits, ws, ws_bytes, stream, nullptr);
+}
+
+dcnr_status dcnr_forward_bce(const dcnr_model_desc* desc, void* const* params,
+                             const int64_t* user_ids, const int64_t* item_ids,
+                             const int64_t* cat_features, const float* num_features, int64_t B,
+                             uint64_t dropout_seed, const float* labels, float grad_scale,
+                             float* logits, float* loss, float* dlogits, void* bce_ws,
+                             size_t bce_ws_bytes_, void* ws, size_t ws_bytes, dcnr_stream_t stream) {
+  if (!labels || !loss || !dlogits || !bce_ws || B < 2) {
+    set_error("dcnr_forward_bce: bad argument");
     return DCNR_BAD_ARG;
   }
-  if (mode == DCNR_TRAIN && B < 2) {
-    set_error("Expected more than 1 value per channel when training");
-    return DCNR_BAD_ARG;
-  }
-  const Plan pl = make_plan(d, desc->flags, mode, B);
-  const Layout L = make_layout(d, B, pl, ws);
-  if (ws_bytes < L.total) {
-    set_error("workspace too small: %zu < %zu", ws_bytes, L.total);
+  if (bce_ws_bytes_ < bce_ws_bytes()) {
+    set_error("dcnr_forward_bce: loss workspace too small");
     return DCNR_WORKSPACE_TOO_SMALL;
   }
-  if (B == 0) return DCNR_OK;
-  const Params P = map_params(d, params);
-  const int check = (desc->flags & DCNR_FLAG_CHECK_INDICES) ? 1 : 0;
-  const Fwd f{desc, d, pl, L, P, user_ids, item_ids, cat_features, num_features, B, logits, s, check,
-              make_gather(d, P, desc->n_num), make_cross(d, P)};
-  if (pl.tower) return f.tower();
-  SideJoin sj;
-  TRY(f.front(sj));
-  TRY(pl.eval_epi ? f.eval_epi() : f.layers(dropout_seed));
-  if (pl.train) TRY(sj.join(s));   // the sorted ids (workspace) for dcnr_backward
-  // the id-check word to the caller's mirror, after the forward's last kernel
-  // on the stream
-  if (desc->error_mirror && check) TRYP(DCNR_K_PACK, s, mirror_word((const int*)ws, desc->error_mirror, s));
-  return DCNR_OK;
+  const BceOut bo{labels, grad_scale, loss, dlogits, (double*)bce_ws};
+  return forward_run(desc, params, user_ids, item_ids, cat_features, num_features, B, DCNR_TRAIN,
+                     dropout_seed, logits, ws, ws_bytes, stream, &bo);
 }
 
 dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void* const* grads,
@@ -1416,7 +1491,7 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
     set_error("dcnr_backward: bad argument");
     return DCNR_BAD_ARG;
   }
-  const Plan pl = make_plan(d, desc->flags, DCNR_TRAIN, B);
+  const Plan pl = make_plan(d, desc->flags, DCNR_TRAIN, B, desc->bn_allreduce != nullptr);
   const Layout L = make_layout(d, B, pl, ws);
   if (ws_bytes < L.total) {
     set_error("workspace too small: %zu < %zu", ws_bytes, L.total);

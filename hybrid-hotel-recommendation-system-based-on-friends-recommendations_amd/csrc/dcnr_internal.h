@@ -480,6 +480,10 @@ struct NtArgs {
   const float* bn_g; const float* bn_b; const float* bn_rm; const float* bn_rv;
   const float* wf; float* headp; int64_t ldh;      // BN_RESID_RELU_HEAD (wf: Nr entries;
                                                     // headp rows ldh apart, ldh >= M)
+  // RESID_BN with the operand transform, r1_dz != null: R is not read but is
+  // bf16(r1_dz[m] * wf[n]) where bit n%32 of r1_bits word [m][n/32] (row
+  // stride ldhb) is set, else 0 (wf: Nr entries)
+  const float* r1_dz; const uint32_t* r1_bits;
   float* part;                                      // column partials (stats epilogues)
   int Nr;                                           // real columns (eval BN / head: N pads to 8)
   // operand transform (RESID_BN / DROP_BN, Tx != null): X holds a BatchNorm
@@ -732,6 +736,25 @@ dcnr_status head_parts(const float* part, int np, const float* zc, const float* 
                        float* logits, hipStream_t s);
 dcnr_status head_logits(const float* zdeep, const float* zc, const float* bf, int64_t B,
                         float* logits, hipStream_t s);
+// the same pass for a bf16 train step with BCE-with-logits (Plan::head_stats):
+// it goes on from the row's logit to dz[r] = bce_dz(logit, labels[r]) and to
+// the last block's BN2-backward column partials, the floats bwd_bn2_stats3
+// (G null, x non-null) writes into `part` for the same dz: NK = 3 rows per
+// chunk, *nchunks = bn2_stats_chunks(B).  out is not stored; bits as above;
+// du (null: not stored) = bf16(dz (x) wf) * [out > 0]
+dcnr_status bn_add_relu_head_stats(const void* t, const void* x, int64_t B, int N, int ld,
+                                   const float* scale, const float* shift, const float* mean,
+                                   const float* invstd, const float* wf, int Nr, const float* zc,
+                                   const float* bf, const float* labels, float grad_scale,
+                                   float* logits, float* dz, uint8_t* bits, void* du, float* part,
+                                   int* nchunks, hipStream_t s);
+// partial rows (chunks) the rowwise reduction passes write for a batch of B
+int bn2_stats_chunks(int64_t B);
+// d(mean BCE-with-logits)/dz of one sample, times grad_scale: the one copy
+// bce_kernel and the head pass above share
+__device__ __forceinline__ float bce_dz(float z, float y, float scale, int64_t B) {
+  return scale * (1.f / (1.f + expf(-z)) - y) / (float)B;
+}
 size_t bce_ws_bytes();
 dcnr_status bce(const float* z, const float* y, int64_t B, float* loss, float* dz, float scale,
                 double* part, hipStream_t s);

@@ -262,6 +262,57 @@ template <typename T> struct BnAddReluHeadOp {
   }
 };
 
+// the head pass of a train step with BCE-with-logits: after the row's logit
+// it forms dz[r] (bce_dz) and, from the activation it still holds, what
+// Bwd2StatsOp<T, false, REBUILD> would re-read t and x for: du = bf16(dz*wf) *
+// [out > 0] and the column sums [du, du*xhat(t), dz*out], in that op's
+// expressions and (run with NK = 3) its chunks and row order, so `part` holds
+// the same floats.  du_out null: du is not stored (the dX GEMM rebuilds it)
+template <typename T> struct BnAddReluHeadStatsOp {
+  const T* t; const T* x; int ld; const float* sc; const float* sh; const float* mean;
+  const float* invstd; const float* wf; int Nr; const float* zc; const float* bf;
+  const float* y; float scale; int64_t B; float* logits; float* dz; uint8_t* bits; T* du_out;
+  struct Cst { float sc[VE<T>], sh[VE<T>], wf[VE<T>], mu[VE<T>], is[VE<T>]; float bf; };
+  struct Reg { float a[VE<T>], b[VE<T>]; float zc, y; };
+  __device__ void prep(int c, Cst& q) const {
+    ldc(sc + c, q.sc); ldc(sh + c, q.sh); ldc(mean + c, q.mu); ldc(invstd + c, q.is);
+#pragma unroll
+    for (int v = 0; v < VE<T>; ++v) q.wf[v] = c + v < Nr ? wf[c + v] : 0.f;
+    q.bf = bf[0];
+  }
+  __device__ void load(int64_t r, int c, Reg& q) const {
+    ldv<T>(t + r * ld + c, q.a);
+    ldv<T>(x + r * ld + c, q.b);
+    q.zc = zc[r];
+    q.y = y[r];
+  }
+  __device__ void apply(int64_t r, int c, const Cst& k, Reg& q, float (&acc)[3][VE<T>]) const {
+    float o[VE<T>];
+    float d = 0.f;
+#pragma unroll
+    for (int v = 0; v < VE<T>; ++v) {
+      o[v] = (float)(T)bn_fwd_add_relu(q.a[v], k.sc[v], k.sh[v], q.b[v]);
+      d += o[v] * k.wf[v];
+    }
+    if (bits) store_pos_bits<T>(bits, r, ld >> 3, c, o);
+    d = wave_sum_dpp(d);   // (in every lane)
+    const float z = (d + q.zc) + k.bf;
+    const float dzr = bce_dz(z, q.y, scale, B);
+    if ((threadIdx.x & 63) == 0) { logits[r] = z; dz[r] = dzr; }
+#pragma unroll
+    for (int v = 0; v < VE<T>; ++v) {
+      float g = dzr * k.wf[v];
+      float du = (float)(T)(o[v] > 0.f ? g : 0.f);
+      float xh = (q.a[v] - k.mu[v]) * k.is[v];
+      acc[0][v] += du;
+      acc[1][v] += du * xh;
+      acc[2][v] += dzr * o[v];
+      q.b[v] = du;
+    }
+    if (du_out) stv<T>(du_out + r * ld + c, q.b);
+  }
+};
+
 // backward of out = relu(BN2(t2) + x): du = g*[out>0]; g = G or dz (x) wf.
 // REBUILD (last block, g = dz (x) wf): `out` is the block input x and out is
 // rebuilt as the head pass computed it, bf16(relu(t2*sc + sh + x)), so the
@@ -406,6 +457,7 @@ template <typename T> struct Bwd1ApplyOp {
 // (1 / 4 rows in flight measured the same / slower: DESIGN.md section 8)
 template <typename T, bool G, bool R> struct RowUnroll<Bwd2StatsOp<T, G, R>> { static constexpr int v = 2; };
 template <typename T> struct RowUnroll<BnAddReluHeadOp<T>> { static constexpr int v = 2; };
+template <typename T> struct RowUnroll<BnAddReluHeadStatsOp<T>> { static constexpr int v = 2; };
 template <typename T> struct RowUnroll<Bwd1ApplyOp<T>> { static constexpr int v = 2; };
 template <typename T> struct RowUnroll<Bwd2ApplyOp<T>> { static constexpr int v = 2; };
 template <typename T> struct RowUnroll<Bwd2ApplyRank1Op<T>> { static constexpr int v = 2; };
@@ -866,6 +918,24 @@ dcnr_status bn_add_relu_head(int precision, const void* t, const void* x, void* 
   return precision == DCNR_PREC_BF16
              ? bn_add_relu_head_impl<bf16>(t, x, out, B, N, ld, scale, shift, wf, Nr, zc, bf, logits, bits, s)
              : bn_add_relu_head_impl<float>(t, x, out, B, N, ld, scale, shift, wf, Nr, zc, bf, logits, nullptr, s);
+}
+
+dcnr_status bn_add_relu_head_stats(const void* t, const void* x, int64_t B, int N, int ld,
+                                   const float* scale, const float* shift, const float* mean,
+                                   const float* invstd, const float* wf, int Nr, const float* zc,
+                                   const float* bf, const float* labels, float grad_scale,
+                                   float* logits, float* dz, uint8_t* bits, void* du, float* part,
+                                   int* nchunks, hipStream_t s) {
+  if (!bn_add_relu_head_supported(DCNR_PREC_BF16, N)) {
+    set_error("bn_add_relu_head_stats: needs a wave per row (N=%d)", N);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  BnAddReluHeadStatsOp<bf16> op{(const bf16*)t, (const bf16*)x, ld, scale, shift, mean, invstd, wf, Nr,
+                                zc, bf, labels, grad_scale, B, logits, dz, bits, (bf16*)du};
+  return run_rowcol<bf16, 3>(op, B, N, part, nchunks, s);
+}
+int bn2_stats_chunks(int64_t B) {
+  return (int)cdiv(B, std::max<int64_t>(32, cdiv(B, TARGET_CHUNKS)));
 }
 
 template <typename T>

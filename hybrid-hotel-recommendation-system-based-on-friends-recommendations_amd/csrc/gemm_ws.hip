@@ -117,7 +117,11 @@ __device__ __forceinline__ void issue_tile(u32x4 xr, int64_t ldx, int K, uint32_
 // it, and slice 0's workgroups store dt for the weight gradient.  This takes
 // the BatchNorm backward's row pass (read du and t, write dt) and the GEMM's
 // re-read of dt off the backward: one kernel reads du and t once.
-template <int KTP, int EPI, bool XBN = false>
+// R1 (RESID_BN): the residual operand is rank 1 and is not read.  R[m][n] =
+// bf16(r1_dz[m] * wf[n]) where bit n of r1_bits row m is set, else 0 -- the
+// last residual block's du as the head pass forms it (and Bwd2ApplyRank1Op
+// rebuilds it): 8 bytes per row and wave in place of a 16-byte load per lane.
+template <int KTP, int EPI, bool XBN = false, bool R1 = false>
 __global__ __launch_bounds__(WS_NT, 1) void gemm_ws_kernel(NtArgs a) {
   constexpr int WS_TM = ws_tm<KTP, EPI>();
   constexpr int NB = WS_NB;
@@ -125,8 +129,9 @@ __global__ __launch_bounds__(WS_NT, 1) void gemm_ws_kernel(NtArgs a) {
   constexpr int WS_RB = C::RB;
   constexpr bool STATS = (EPI >= NT_EPI_BIAS_STATS && EPI <= NT_EPI_DROP_BN) || EPI == NT_EPI_RESID_SUM;
   constexpr bool HEAD = EPI == NT_EPI_BN_RESID_RELU_HEAD;
-  constexpr bool HAS_R = EPI == NT_EPI_RESID || EPI == NT_EPI_RESID_BN || EPI == NT_EPI_BN_RESID_RELU || HEAD ||
-                         EPI == NT_EPI_RESID_SUM;
+  constexpr bool HAS_R = (EPI == NT_EPI_RESID || EPI == NT_EPI_RESID_BN || EPI == NT_EPI_BN_RESID_RELU || HEAD ||
+                          EPI == NT_EPI_RESID_SUM) && !R1;
+  static_assert(!R1 || EPI == NT_EPI_RESID_BN, "rank-1 residual: the RESID_BN epilogue");
   constexpr bool HAS_HT = EPI == NT_EPI_RESID_BN || EPI == NT_EPI_DROP_BN;
   constexpr bool HAS_SS = EPI >= NT_EPI_BN_RELU && EPI <= NT_EPI_BN_RESID_RELU_HEAD;   // eval BN affine + ReLU
   constexpr bool HAS_BIAS = EPI <= NT_EPI_BIAS_STATS || HAS_SS;
@@ -188,7 +193,7 @@ __global__ __launch_bounds__(WS_NT, 1) void gemm_ws_kernel(NtArgs a) {
   float* bias_s = reinterpret_cast<float*>(lds + NB * C::TILE);
   float* nmi_s = bias_s + WS_TN;
   float* istd_s = bias_s + 2 * WS_TN;
-  float* wf_s = bias_s + 3 * WS_TN;   // HEAD: the slice's deep head weights
+  float* wf_s = bias_s + 3 * WS_TN;   // HEAD, R1: the slice's deep head weights
   for (int c = tid; c < WS_TN; c += WS_NT) {
     const int n = n0 + c;
     bias_s[c] = (HAS_BIAS && a.bias && n < a.N) ? a.bias[n] : 0.f;
@@ -212,7 +217,7 @@ __global__ __launch_bounds__(WS_NT, 1) void gemm_ws_kernel(NtArgs a) {
         istd_s[c] = n < a.N ? a.bn_shift[n] : 0.f;
       }
     }
-    if constexpr (HEAD) wf_s[c] = n < a.Nr ? a.wf[n] : 0.f;
+    if constexpr (HEAD || R1) wf_s[c] = n < a.Nr ? a.wf[n] : 0.f;
   }
   // XBN: the transform's per-column constants [mean, invstd, k0, k1, k2][K]
   float* xc_s = reinterpret_cast<float*>(lds + XOFF + NB * C::TILE);
@@ -239,6 +244,10 @@ __global__ __launch_bounds__(WS_NT, 1) void gemm_ws_kernel(NtArgs a) {
       (void*)a.Hb, (short)0, HAS_HT ? (int)(a.M * a.ldhb * 4) : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t tr = __builtin_amdgcn_make_buffer_rsrc(
       (void*)a.T, (short)0, HAS_HT ? (int)(a.M * a.ldt * 2) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r1z = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)a.r1_dz, (short)0, R1 ? (int)(a.M * 4) : 0, 0x00020000);
+  const __amdgpu_buffer_rsrc_t r1b = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)a.r1_bits, (short)0, R1 ? (int)(a.M * a.ldhb * 4) : 0, 0x00020000);
   const __amdgpu_buffer_rsrc_t hp_r = __builtin_amdgcn_make_buffer_rsrc(
       (void*)a.headp, (short)0, HEAD ? (int)(((a.nslices * WS_WAVES - 1) * a.ldh + a.M) * 4) : 0, 0x00020000);
 
@@ -263,11 +272,17 @@ __global__ __launch_bounds__(WS_NT, 1) void gemm_ws_kernel(NtArgs a) {
   constexpr int NSLOT = WS_OPS_EARLY ? WS_RB : 2;
   u32x4 rv[NSLOT], tv[NSLOT];
   uint32_t hw[NSLOT];   // the mask word of columns nw .. nw+31
+  uint32_t zw[NSLOT], bw[NSLOT];   // R1: the row's dz and its r1_bits word of those columns
   auto load_ops = [&](int64_t m0, int rb, int slot) {
     const int64_t m = m0 + rb * 16 + l15;
     const bool ok = m < a.M && nst < a.N;
     if constexpr (HAS_R)
       rv[slot] = __builtin_amdgcn_raw_buffer_load_b128(rr_, ok ? (int)((m * a.ldr + nst) * 2) : OOR, 0, 0);
+    if constexpr (R1) {
+      zw[slot] = __builtin_amdgcn_raw_buffer_load_b32(r1z, m < a.M ? (int)(m * 4) : OOR, 0, 0);
+      bw[slot] = __builtin_amdgcn_raw_buffer_load_b32(
+          r1b, (m < a.M && nw < a.N) ? (int)((m * a.ldhb + (nw >> 5)) * 4) : OOR, 0, 0);
+    }
     if constexpr (HAS_HT) {
       hw[slot] = __builtin_amdgcn_raw_buffer_load_b32(
           hr, (m < a.M && nw < a.N) ? (int)((m * a.ldhb + (nw >> 5)) * 4) : OOR, 0, 0);
@@ -310,6 +325,19 @@ __global__ __launch_bounds__(WS_NT, 1) void gemm_ws_kernel(NtArgs a) {
         if constexpr (HAS_R) {
 #pragma unroll
           for (int d = 0; d < 2; ++d) v[d] += unpack2(rf[cb][d]);
+        }
+        if constexpr (R1) {
+          const float4 w4 = *reinterpret_cast<const float4*>(wf_s + cl);
+          const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+          const float dzm = __uint_as_float(zw[slot]);
+#pragma unroll
+          for (int d = 0; d < 2; ++d) {
+            // the stored du: the product rounded to bf16, then masked
+            const uint32_t kb = bw[slot] >> (16 * cb + 4 * q + 2 * d);
+            const uint32_t du2 = pack2(dzm * wv[2 * d], dzm * wv[2 * d + 1]) &
+                                 (((kb & 1u) * 0xffffu) | (((kb >> 1) & 1u) * 0xffff0000u));
+            v[d] += unpack2(du2);
+          }
         }
         if constexpr (HAS_SS) {
 #pragma unroll
@@ -531,14 +559,14 @@ __global__ __launch_bounds__(WS_NT, 1) void gemm_ws_kernel(NtArgs a) {
   }
 }
 
-template <int KTP, int EPI, bool XBN = false>
+template <int KTP, int EPI, bool XBN = false, bool R1 = false>
 dcnr_status launch_ws(NtArgs a, hipStream_t s, int* nparts) {
   constexpr int WS_TM = ws_tm<KTP, EPI>();
   using C = WsCfg<KTP, WS_TM>;
   // XBN: + the t tiles and the transform's 5 x K constants
   constexpr size_t LDSB = C::LDS_BYTES + (XBN ? WS_NB * (size_t)C::TILE + 5 * KTP * 32 * 4 : 0);
   static_assert(LDSB <= 160 * 1024, "LDS budget");
-  TRY_ST(set_max_dyn_lds((const void*)gemm_ws_kernel<KTP, EPI, XBN>, LDSB));
+  TRY_ST(set_max_dyn_lds((const void*)gemm_ws_kernel<KTP, EPI, XBN, R1>, LDSB));
   a.nslices = (int)cdiv(a.N, WS_TN);
   // 32-bit buffer offsets: launch in M-chunks of < 2^29 bytes per operand
   const int64_t maxld = std::max<int64_t>({a.ldx, a.ldc * 2, a.R ? a.ldr : 0, a.Hb ? a.ldhb * 2 : 0,
@@ -553,13 +581,14 @@ dcnr_status launch_ws(NtArgs a, hipStream_t s, int* nparts) {
       b.C = (char*)a.C + m0 * a.ldc * (EPI == NT_EPI_F32 ? 4 : 2);
       if (a.R) b.R = (const char*)a.R + m0 * a.ldr * 2;
       if (a.Hb) b.Hb = a.Hb + m0 * a.ldhb;
+      if (a.r1_dz) { b.r1_dz = a.r1_dz + m0; b.r1_bits = a.r1_bits + m0 * a.ldhb; }
       if (a.headp) b.headp = a.headp + m0;   // same row stride ldh
       if (a.T) b.T = a.T + m0 * a.ldt;
       if (a.Tx) b.Tx = a.Tx + m0 * a.ldx;
       if (a.dt) b.dt = a.dt + m0 * a.ldx;
       if (a.part) b.part = a.part + (int64_t)total * 2 * a.N;
       int np = 0;
-      dcnr_status st = launch_ws<KTP, EPI, XBN>(b, s, &np);
+      dcnr_status st = launch_ws<KTP, EPI, XBN, R1>(b, s, &np);
       if (st != DCNR_OK) return st;
       total += np;
     }
@@ -578,7 +607,7 @@ dcnr_status launch_ws(NtArgs a, hipStream_t s, int* nparts) {
   if (need < grid) grid = (int)(cdiv(need, unit) * unit);
   a.groups = grid / a.nslices;
   if (nparts) *nparts = a.groups;
-  hipLaunchKernelGGL((gemm_ws_kernel<KTP, EPI, XBN>), dim3(grid), dim3(WS_NT), LDSB, s, a);
+  hipLaunchKernelGGL((gemm_ws_kernel<KTP, EPI, XBN, R1>), dim3(grid), dim3(WS_NT), LDSB, s, a);
   DCNR_LAUNCH_CHECK();
   return DCNR_OK;
 }
@@ -606,7 +635,8 @@ dcnr_status gemm_ws(int epi, const NtArgs& a, hipStream_t s, int* nparts) {
   const bool ht = epi == NT_EPI_RESID_BN || epi == NT_EPI_DROP_BN;
   if (!gemm_ws_supported(a.K, a.N) || a.ldx % 8 || a.ldw % 8 || a.ldc % 8 ||
       ((epi == NT_EPI_RESID || epi == NT_EPI_RESID_BN || epi == NT_EPI_BN_RESID_RELU || epi == NT_EPI_RESID_SUM) &&
-       (a.ldr % 8 || !a.R)) ||
+       !a.r1_dz && (a.ldr % 8 || !a.R)) ||
+      (a.r1_dz && (epi != NT_EPI_RESID_BN || !a.Tx || !a.r1_bits || !a.wf)) ||
       (epi >= NT_EPI_BN_RELU && epi <= NT_EPI_BN_RESID_RELU_HEAD && !a.bn_rm && (!a.bn_scale || !a.bn_shift)) ||
       (epi >= NT_EPI_BN_RELU && epi <= NT_EPI_BN_RESID_RELU_HEAD && a.bn_rm && (!a.bn_g || !a.bn_b || !a.bn_rv)) ||
       (epi == NT_EPI_BN_RESID_RELU_HEAD &&
@@ -624,6 +654,7 @@ dcnr_status gemm_ws(int epi, const NtArgs& a, hipStream_t s, int* nparts) {
     }
     if (epi == NT_EPI_RESID_SUM) return launch_ws<16, NT_EPI_RESID_SUM, true>(a, s, nparts);
     if (epi == NT_EPI_RESID) return launch_ws<16, NT_EPI_RESID, true>(a, s, nparts);
+    if (a.r1_dz) return launch_ws<16, NT_EPI_RESID_BN, true, true>(a, s, nparts);
     return epi == NT_EPI_RESID_BN ? launch_ws<16, NT_EPI_RESID_BN, true>(a, s, nparts)
                                   : launch_ws<16, NT_EPI_DROP_BN, true>(a, s, nparts);
   }

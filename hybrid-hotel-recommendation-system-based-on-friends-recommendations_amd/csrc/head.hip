@@ -93,7 +93,7 @@ __global__ __launch_bounds__(NT) void bce_kernel(const float* z, const float* y,
     // max(z,0) - z*y + log1p(exp(-|z|))   (torch's binary_cross_entropy_with_logits)
     float l = fmaxf(zz, 0.f) - zz * yy + log1pf(expf(-fabsf(zz)));
     acc += (double)l;
-    if (dz) dz[i] = scale * (1.f / (1.f + expf(-zz)) - yy) / (float)B;
+    if (dz) dz[i] = bce_dz(zz, yy, scale, B);
   }
   red[threadIdx.x] = acc;
   __syncthreads();

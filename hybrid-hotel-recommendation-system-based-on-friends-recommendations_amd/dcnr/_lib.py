@@ -24,6 +24,7 @@ FLAG_CHECK_INDICES = 1
 FLAG_KEEP_INTERMEDIATES = 2
 FLAG_FUSED_TOWER = 4
 FLAG_ROW_MAP = 8
+FLAG_HEAD_STATS = 16
 ABI_VERSION = 4
 # dcnr_ws_tensor (include/dcnr.h)
 WS_KINDS = ["x0", "h", "t1", "t2", "a1", "mask_a1", "mask_h", "bn_mean", "bn_invstd", "bn_scale",
@@ -101,6 +102,9 @@ _SIGS = {
                                              ctypes.c_int, ctypes.c_int, ctypes.POINTER(_I64)]),
     "dcnr_forward": (ctypes.c_int, [ctypes.POINTER(ModelDesc), _P, _P, _P, _P, _P, _I64,
                                     ctypes.c_int, ctypes.c_uint64, _P, _P, ctypes.c_size_t, _P]),
+    "dcnr_forward_bce": (ctypes.c_int, [ctypes.POINTER(ModelDesc), _P, _P, _P, _P, _P, _I64,
+                                        ctypes.c_uint64, _P, ctypes.c_float, _P, _P, _P, _P,
+                                        ctypes.c_size_t, _P, ctypes.c_size_t, _P]),
     "dcnr_gather_cross": (ctypes.c_int, [ctypes.POINTER(ModelDesc), _P, _P, _P, _P, _P, _I64, _P,
                                          _I64, _P, _I64, _P, _P]),
     "dcnr_backward": (ctypes.c_int, [ctypes.POINTER(ModelDesc), _P, _P, _P, _P, _P, _P, _I64, _P,

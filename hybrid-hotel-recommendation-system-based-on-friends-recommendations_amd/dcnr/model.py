@@ -556,10 +556,16 @@ def _hook_error(model):
 
 
 def run_forward(model: DCN_RecSys, train: bool, seed: int, user, item, cat, num,
-                ws: Optional[torch.Tensor] = None, extra_flags: int = 0):
+                ws: Optional[torch.Tensor] = None, extra_flags: int = 0, bce=None):
     """One native forward.  With ``model.check_indices`` the workspace's
     error word (``ws[:4]``) is checked: in this call (``"sync"``) or through
-    the model's deferred watch."""
+    the model's deferred watch.
+
+    ``bce=(labels, grad_scale)`` (train mode): the forward and the
+    BCE-with-logits loss as one call (dcnr_forward_bce); returns
+    ``(logits, ws, loss, dlogits)``.  With ``_lib.FLAG_HEAD_STATS`` in
+    ``extra_flags`` the backward on ``ws`` must get the same flags and that
+    ``dlogits``."""
     lib = _lib.load()
     B = user.shape[0]
     dev = user.device
@@ -578,10 +584,25 @@ def run_forward(model: DCN_RecSys, train: bool, seed: int, user, item, cat, num,
         if slot is not None:
             desc.error_mirror = mirror
     model._active_ws = ws          # the SyncBN hook (dcnr.parallel) maps pointers into it
-    st = lib.dcnr_forward(ctypes.byref(desc), state, user.data_ptr(), item.data_ptr(),
-                          cat.data_ptr() if cat.numel() else None,
-                          num.data_ptr() if num.numel() else None, B, mode, seed,
-                          logits.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
+    call = "dcnr_forward_bce" if bce is not None else "dcnr_forward"
+    if bce is not None:
+        if not train:
+            raise ValueError("run_forward: bce needs train mode")
+        y, grad_scale = bce
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        dz = torch.empty(B, dtype=torch.float32, device=dev)
+        lws = torch.empty(int(lib.dcnr_bce_workspace_size()), dtype=torch.uint8, device=dev)
+        st = lib.dcnr_forward_bce(ctypes.byref(desc), state, user.data_ptr(), item.data_ptr(),
+                                  cat.data_ptr() if cat.numel() else None,
+                                  num.data_ptr() if num.numel() else None, B, seed,
+                                  y.data_ptr(), float(grad_scale), logits.data_ptr(),
+                                  loss.data_ptr(), dz.data_ptr(), lws.data_ptr(), lws.numel(),
+                                  ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
+    else:
+        st = lib.dcnr_forward(ctypes.byref(desc), state, user.data_ptr(), item.data_ptr(),
+                              cat.data_ptr() if cat.numel() else None,
+                              num.data_ptr() if num.numel() else None, B, mode, seed,
+                              logits.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
     model._active_ws = None
     if slot is not None:
         if st == 0:
@@ -589,12 +610,14 @@ def run_forward(model: DCN_RecSys, train: bool, seed: int, user, item, cat, num,
         else:
             model._index_watch.cancel(slot)
     _hook_error(model)
-    _lib.check(st, "dcnr_forward")
+    _lib.check(st, call)
     if model.check_indices == "sync":
         _lib.check(lib.dcnr_check_errors(ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
                    "embedding")
     elif model.check_indices and slot is None and B > 0:
         model._index_watch.push(ws[:4])
+    if bce is not None:
+        return logits, ws, loss, dz
     return logits, ws
 
 

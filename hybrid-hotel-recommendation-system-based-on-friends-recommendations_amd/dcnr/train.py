@@ -2,7 +2,7 @@
 (train.py:219-226: zero_grad -> forward -> BCEWithLogits -> backward ->
 optimizer.step) as native calls over flat parameter/gradient/moment buffers:
 
-    dcnr_forward(train) -> dcnr_bce_with_logits -> dcnr_backward
+    dcnr_forward_bce (train forward + BCEWithLogits) -> dcnr_backward
       -> data-parallel exchange + dcnr_adam_step (dense semantics):
          world == 1: one launch over every parameter
          world > 1: the flat buffers have two segments (model.flatten_): the
@@ -107,7 +107,7 @@ class FusedTrainer:
     def __init__(self, model: DCN_RecSys, lr=1e-3, weight_decay=1e-2, optimizer_name='AdamW',
                  betas=(0.9, 0.999), eps=1e-8, process_group=None, sync_bn=False,
                  shard_optimizer=None, exchange="dense", sparse_ops=None, dense_table_grads=False,
-                 exchange_chunks=4):
+                 exchange_chunks=4, head_stats=True):
         if optimizer_name not in ('AdamW', 'Adam'):
             raise ValueError("optimizer_name must be 'AdamW' or 'Adam' (train.py:201-204)")
         self.model = model
@@ -186,6 +186,13 @@ class FusedTrainer:
         self.row_map = self.world == 1 and not dense_table_grads
         self.dense_table_grads = dense_table_grads
         self._flags = _lib.FLAG_ROW_MAP if self.row_map else 0
+        # the forward's head pass makes dz and the last block's BN2-backward
+        # statistics (DCNR_FLAG_HEAD_STATS: the native plan takes it where it
+        # applies, bit-identical either way); False: forward, loss and
+        # backward as three calls with a statistics pass (tests compare the two)
+        self.head_stats = bool(head_stats)
+        if self.head_stats:
+            self._flags |= _lib.FLAG_HEAD_STATS
         self._rows_cache = None
         # a list: step() appends (backward end, step end) CUDA events to it
         self.step_events = None
@@ -204,15 +211,21 @@ class FusedTrainer:
         model._index_watch.poll()
         sparse_rows = self._sparse_rows()
         flags = self._flags | (_lib.FLAG_ROW_MAP if sparse_rows else 0)
-        logits, self._ws = run_forward(model, True, seed, user, item, cat, num, self._ws,
-                                       extra_flags=flags)
+        # grad_scale 1/world: the SUM all-reduce then yields the global mean gradient
+        if self.head_stats:
+            logits, self._ws, loss, dz = run_forward(model, True, seed, user, item, cat, num,
+                                                     self._ws, extra_flags=flags,
+                                                     bce=(y, 1.0 / self.world))
+        else:
+            logits, self._ws = run_forward(model, True, seed, user, item, cat, num, self._ws,
+                                           extra_flags=flags)
         self._B = user.shape[0]
         if self.exchange == "sparse" and self._sparse is not None:
             # the touched rows come from the forward's id sort: their counts
             # are exchanged now, under the backward
             self._sparse.begin(self.touched_rows())
-        # grad_scale 1/world: the SUM all-reduce then yields the global mean gradient
-        loss, dz = bce_with_logits(logits, y, True, 1.0 / self.world)
+        if not self.head_stats:
+            loss, dz = bce_with_logits(logits, y, True, 1.0 / self.world)
         self._dense_work = None
         if sparse_rows:
             # the categorical tables go through a dense all-reduce: zero them

@@ -15,6 +15,8 @@
  *                         (BASELINE configs[1])
  *   dcnr_backward         loss.backward() through the model   train.py:225
  *   dcnr_bce_with_logits  nn.BCEWithLogitsLoss()(preds, y)    train.py:206,224,233,376
+ *   dcnr_forward_bce      the train forward and that loss as one call: a step's
+ *                         preds = model(...); criterion(preds, y)  train.py:223-224
  *   dcnr_adam_step        torch.optim.AdamW/Adam(...).step()  train.py:201-204,226
  *   dcnr_cosine_topk      NearestNeighbors(metric='cosine', algorithm='brute')
  *                         .kneighbors(vec, n_neighbors=k)      main.py:196-203,268-270,300
@@ -122,6 +124,17 @@ typedef enum { DCNR_EVAL = 0, DCNR_TRAIN = 1 } dcnr_mode;
  * the dense-gradient step.  Only with accumulate = 0 (the flag and accumulate
  * together are DCNR_BAD_ARG).  Same workspace offsets for every other tensor. */
 #define DCNR_FLAG_ROW_MAP 8u
+/* Train step with BCE-with-logits, set on both calls of the pair
+ * dcnr_forward_bce -> dcnr_backward: the forward's head pass goes on from each
+ * row's logit to dlogits and to the last residual block's BatchNorm-backward
+ * column partials, which it leaves in the workspace; dcnr_backward then runs
+ * no statistics pass over that block (it reads those partials, and `dlogits`
+ * must be the buffer that forward wrote, unchanged).  Taken where the bf16
+ * fused head applies (hidden padded to 512) without
+ * DCNR_FLAG_KEEP_INTERMEDIATES and without a bn_allreduce hook; everywhere
+ * else the flag changes nothing.  Same results bit for bit, same workspace
+ * layout.  dcnr_forward ignores it. */
+#define DCNR_FLAG_HEAD_STATS 16u
 
 /* Optional collective hook for SyncBN across data-parallel ranks: called
  * (stream-ordered, from the calling thread) with a device buffer of `count`
@@ -291,6 +304,21 @@ size_t dcnr_bce_workspace_size(void);
 dcnr_status dcnr_bce_with_logits(const float* logits, const float* labels, int64_t B,
                                  float* loss, float* dlogits, float grad_scale, void* ws,
                                  size_t ws_bytes, dcnr_stream_t stream);
+
+/* dcnr_forward in train mode followed by dcnr_bce_with_logits(logits, labels,
+ * B, loss, dlogits, grad_scale, bce_ws, ...) as one call (B >= 2; loss and
+ * dlogits are required): the same logits, loss, dlogits, running statistics
+ * and saved activations, bit for bit.  With DCNR_FLAG_HEAD_STATS in
+ * desc->flags the last residual block's pass also produces dlogits and that
+ * block's BatchNorm-backward partials for the dcnr_backward that follows on
+ * `ws` with the same flags and this `dlogits` (see the flag). */
+dcnr_status dcnr_forward_bce(const dcnr_model_desc* desc, void* const* params,
+                             const int64_t* user_ids, const int64_t* item_ids,
+                             const int64_t* cat_features, const float* num_features, int64_t B,
+                             uint64_t dropout_seed, const float* labels, float grad_scale,
+                             float* logits, float* loss, float* dlogits, void* bce_ws,
+                             size_t bce_ws_bytes, void* ws, size_t ws_bytes,
+                             dcnr_stream_t stream);
 
 /* The reference's validation metrics (train.py:255-265, 366-387) over n
  * logits and labels, all n in one set as the reference's single validation
