@@ -1616,7 +1616,22 @@ dcnr_status dcnr_candidate_union(const int64_t* positives, int64_t Q, const int6
     return DCNR_BAD_ARG;
   }
   if (Q == 0) return DCNR_OK;
-  TRYP(DCNR_K_SERVE, s, candidate_union(positives, Q, knn_idx, k, out_rows, out_count, s));
+  TRYP(DCNR_K_SERVE, s, candidate_union(positives, Q, knn_idx, k, nullptr, 0, 0, out_rows, out_count, s));
+  return DCNR_OK;
+}
+
+dcnr_status dcnr_candidate_union_table(const int64_t* positives, int64_t Q, const int32_t* nbr,
+                                       int32_t kt, int64_t n_items, int32_t k, int64_t* out_rows,
+                                       int32_t* out_count, dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (Q < 0 || k < 1 || kt < k || n_items < 1 ||
+      (Q > 0 && (!positives || !nbr || !out_rows || !out_count))) {
+    set_error("dcnr_candidate_union_table: bad argument (Q=%lld, k=%d, kt=%d, n_items=%lld)",
+              (long long)Q, k, kt, (long long)n_items);
+    return DCNR_BAD_ARG;
+  }
+  if (Q == 0) return DCNR_OK;
+  TRYP(DCNR_K_SERVE, s, candidate_union(positives, Q, nullptr, k, nbr, kt, n_items, out_rows, out_count, s));
   return DCNR_OK;
 }
 
@@ -1690,6 +1705,45 @@ size_t dcnr_requests_workspace_size(int64_t R, int64_t Q_total, int32_t k, int32
   return requests_ws_bytes(R, cap) + 256;
 }
 
+namespace {
+// dcnr_requests_candidates and its table form: neighbours from knn_idx
+// [Q_total][k], or (nbr != null) from the item neighbour table [n_items][kt]
+dcnr_status requests_candidates_api(const char* who, const int64_t* positives,
+                                    const int64_t* pos_offsets, int64_t R, int64_t Q_total,
+                                    const int64_t* knn_idx, const int32_t* nbr, int32_t kt, int32_t k,
+                                    const int64_t* set_rows, int64_t n_set_rows,
+                                    const int64_t* set_offsets, int32_t S, const int32_t* allowed,
+                                    const int32_t* excluded, const int32_t* fallback,
+                                    int32_t min_candidates, int64_t n_items, int32_t cap,
+                                    int64_t* out_rows, int32_t* out_count, int32_t* status,
+                                    int64_t* offsets, int64_t* host_offsets, int32_t* host_status,
+                                    hipStream_t s) {
+  TRY(requests_shape(who, R, cap));
+  if (Q_total < 0 || k < 1 || S < 0 || n_set_rows < 0 || n_items < 1) {
+    set_error("%s: Q_total=%lld, k=%d, S=%d, n_set_rows=%lld, n_items=%lld", who,
+              (long long)Q_total, k, S, (long long)n_set_rows, (long long)n_items);
+    return DCNR_BAD_ARG;
+  }
+  if (R > 0 && (!pos_offsets || !out_rows || !out_count || !status || !offsets ||
+                (Q_total > 0 && (!positives || (!knn_idx && !nbr))) || (S > 0 && !set_offsets) ||
+                (n_set_rows > 0 && !set_rows) ||
+                (S == 0 && (allowed || excluded || fallback)))) {
+    set_error("%s: null argument (or set indices without sets)", who);
+    return DCNR_BAD_ARG;
+  }
+  if (k > 64 || n_set_rows > INT32_MAX) {
+    set_error("%s: k=%d (max 64), n_set_rows=%lld (max 2^31 - 1)", who, k, (long long)n_set_rows);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  if (R == 0) return DCNR_OK;
+  RequestsIn in{positives, pos_offsets, R, Q_total, knn_idx, k, nbr, kt, set_rows, n_set_rows,
+                set_offsets, S, allowed, excluded, fallback};
+  TRYP(DCNR_K_SERVE, s, requests_candidates(in, min_candidates, n_items, cap, out_rows, out_count,
+                                            status, offsets, host_offsets, host_status, s));
+  return DCNR_OK;
+}
+}  // namespace
+
 dcnr_status dcnr_requests_candidates(const int64_t* positives, const int64_t* pos_offsets,
                                      int64_t R, int64_t Q_total, const int64_t* knn_idx, int32_t k,
                                      const int64_t* set_rows, int64_t n_set_rows,
@@ -1699,31 +1753,30 @@ dcnr_status dcnr_requests_candidates(const int64_t* positives, const int64_t* po
                                      int64_t* out_rows, int32_t* out_count, int32_t* status,
                                      int64_t* offsets, int64_t* host_offsets,
                                      int32_t* host_status, dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  TRY(requests_shape("dcnr_requests_candidates", R, cap));
-  if (Q_total < 0 || k < 1 || S < 0 || n_set_rows < 0 || n_items < 1) {
-    set_error("dcnr_requests_candidates: Q_total=%lld, k=%d, S=%d, n_set_rows=%lld, n_items=%lld",
-              (long long)Q_total, k, S, (long long)n_set_rows, (long long)n_items);
+  return requests_candidates_api("dcnr_requests_candidates", positives, pos_offsets, R, Q_total,
+                                 knn_idx, nullptr, 0, k, set_rows, n_set_rows, set_offsets, S, allowed,
+                                 excluded, fallback, min_candidates, n_items, cap, out_rows, out_count,
+                                 status, offsets, host_offsets, host_status, (hipStream_t)stream);
+}
+
+dcnr_status dcnr_requests_candidates_table(const int64_t* positives, const int64_t* pos_offsets,
+                                           int64_t R, int64_t Q_total, const int32_t* nbr, int32_t kt,
+                                           int32_t k, const int64_t* set_rows, int64_t n_set_rows,
+                                           const int64_t* set_offsets, int32_t S,
+                                           const int32_t* allowed, const int32_t* excluded,
+                                           const int32_t* fallback, int32_t min_candidates,
+                                           int64_t n_items, int32_t cap, int64_t* out_rows,
+                                           int32_t* out_count, int32_t* status, int64_t* offsets,
+                                           int64_t* host_offsets, int32_t* host_status,
+                                           dcnr_stream_t stream) {
+  if (kt < k || (R > 0 && Q_total > 0 && !nbr)) {
+    set_error("dcnr_requests_candidates_table: kt=%d below k=%d, or a null table", kt, k);
     return DCNR_BAD_ARG;
   }
-  if (R > 0 && (!pos_offsets || !out_rows || !out_count || !status || !offsets ||
-                (Q_total > 0 && (!positives || !knn_idx)) || (S > 0 && !set_offsets) ||
-                (n_set_rows > 0 && !set_rows) ||
-                (S == 0 && (allowed || excluded || fallback)))) {
-    set_error("dcnr_requests_candidates: null argument (or set indices without sets)");
-    return DCNR_BAD_ARG;
-  }
-  if (k > 64 || n_set_rows > INT32_MAX) {
-    set_error("dcnr_requests_candidates: k=%d (max 64), n_set_rows=%lld (max 2^31 - 1)", k,
-              (long long)n_set_rows);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  if (R == 0) return DCNR_OK;
-  RequestsIn in{positives, pos_offsets, R, Q_total, knn_idx, k, set_rows, n_set_rows,
-                set_offsets, S, allowed, excluded, fallback};
-  TRYP(DCNR_K_SERVE, s, requests_candidates(in, min_candidates, n_items, cap, out_rows, out_count,
-                                            status, offsets, host_offsets, host_status, s));
-  return DCNR_OK;
+  return requests_candidates_api("dcnr_requests_candidates_table", positives, pos_offsets, R, Q_total,
+                                 nullptr, nbr, kt, k, set_rows, n_set_rows, set_offsets, S, allowed,
+                                 excluded, fallback, min_candidates, n_items, cap, out_rows, out_count,
+                                 status, offsets, host_offsets, host_status, (hipStream_t)stream);
 }
 
 dcnr_status dcnr_requests_ranking_batch(const int64_t* cand_rows, int32_t cap,
@@ -2064,6 +2117,37 @@ dcnr_status dcnr_cosine_topk(const float* table, const float* inv_norms, int64_t
                              void* ws, size_t ws_bytes, dcnr_stream_t stream) {
   return dcnr_cosine_topk_packed(table, inv_norms, nullptr, N, d, queries, Q, k, idx, dist, ws, ws_bytes,
                                  stream);
+}
+
+size_t dcnr_cosine_neighbor_table_workspace_size(int64_t N, int32_t k) {
+  if (N < 1 || N > INT32_MAX || k < 1 || k > 64 || k > N) return 256;   // (the build rejects these)
+  return neighbor_table_ws(N, k);   // (exact: one byte less is DCNR_WORKSPACE_TOO_SMALL)
+}
+
+dcnr_status dcnr_cosine_neighbor_table(const float* table, const float* inv_norms, const uint16_t* packed,
+                                       int64_t N, int32_t d, int32_t k, int64_t row_lo, int64_t row_hi,
+                                       int32_t* out_idx, float* out_dist, void* ws, size_t ws_bytes,
+                                       dcnr_stream_t stream) {
+  if (!table || !inv_norms || N < 1 || row_lo < 0 || row_lo > row_hi || row_hi > N || k < 1 || k > N) {
+    set_error("dcnr_cosine_neighbor_table: bad argument (N=%lld, k=%d, rows [%lld, %lld))", (long long)N, k,
+              (long long)row_lo, (long long)row_hi);
+    return DCNR_BAD_ARG;
+  }
+  if (N > INT32_MAX || k > 64) {
+    set_error("dcnr_cosine_neighbor_table: N=%lld (below 2^31), k=%d (max 64)", (long long)N, k);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  if (row_lo == row_hi) return DCNR_OK;
+  if (!out_idx || !ws) {
+    set_error("dcnr_cosine_neighbor_table: null argument");
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // (bytes: one pass over the table and the result; every chunk of queries streams the table again)
+  TRYB(DCNR_K_KNN, s, (double)N * (4.0 * d + 4.0) + (double)(row_hi - row_lo) * k * 8.0,
+       neighbor_table(table, inv_norms, (const bf16*)packed, N, d, k, row_lo, row_hi, out_idx, out_dist, ws,
+                      ws_bytes, s));
+  return DCNR_OK;
 }
 
 dcnr_status dcnr_topk_merge(const float* dist, const int64_t* idx, int32_t lists, int64_t Q,

@@ -777,18 +777,30 @@ size_t topk_ws(int64_t N, int64_t Q, int k);
 dcnr_status topk_merge(const float* dist, const int64_t* idx, int lists, int64_t Q, int k,
                        int64_t* out_idx, float* out_dist, hipStream_t s);
 // tb: the bf16 copy from cosine_pack_rows, or nullptr (scan v4 then rounds
-// the fp32 rows itself)
+// the fp32 rows itself).  allow_v3 = false keeps the fp32-MFMA scan out: every
+// remaining path shares one distance arithmetic, so a query's answer is then
+// the same bits at every batch width
 dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_t N, int d,
                         const float* q, int64_t Q, int k, int64_t* idx, float* dist, void* ws,
-                        size_t ws_bytes, hipStream_t s);
+                        size_t ws_bytes, hipStream_t s, bool allow_v3 = true);
+// rows [row_lo, row_hi) of the item neighbour table: out_idx [rows][k] int32
+// (and out_dist, or null) = cosine_topk of each table row as a single query
+size_t neighbor_table_ws(int64_t N, int k);
+dcnr_status neighbor_table(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
+                           int64_t row_lo, int64_t row_hi, int32_t* out_idx, float* out_dist, void* ws,
+                           size_t ws_bytes, hipStream_t s);
 dcnr_status cosine_pack_rows(const float* t, const float* inv, int64_t N, int d, bf16* out, hipStream_t s);
 
 // serving (serving.hip)
 dcnr_status gather_rows(const int64_t* idx, int64_t n, int64_t n_src, int n_arrays,
                         const void* const* src, void* const* dst, const int64_t* row_bytes,
                         hipStream_t s);
+// neighbours from idx [Q][k], or (nbr != null) from the item neighbour table
+// nbr [n_items][kt], kt >= k: out_count -1 where a positive or a table entry
+// lies outside [0, n_items)
 dcnr_status candidate_union(const int64_t* pos, int64_t Q, const int64_t* idx, int k,
-                            int64_t* out, int32_t* out_count, hipStream_t s);
+                            const int32_t* nbr, int kt, int64_t n_items, int64_t* out,
+                            int32_t* out_count, hipStream_t s);
 dcnr_status ranking_batch(const int64_t* rows, int64_t n, int64_t user_row, const int64_t* item_cat,
                           int K, const float* item_num, int F, int64_t n_items, int64_t* user_out,
                           int64_t* item_out, int64_t* cat_out, float* num_out, hipStream_t s);
@@ -801,6 +813,7 @@ dcnr_status mmr_rerank(const float* table, const float* inv, int d, const int64_
 struct RequestsIn {
   const int64_t* pos; const int64_t* pos_off; int64_t R, Q_total;   // positives [Q_total], [R + 1]
   const int64_t* idx; int k;                                       // their neighbours [Q_total][k]
+  const int32_t* nbr; int kt;   // ... or (idx null) the item neighbour table [n_items][kt], kt >= k
   const int64_t* set_rows; int64_t n_set_rows; const int64_t* set_off; int S;
   const int32_t* allowed; const int32_t* excluded; const int32_t* fallback;   // [R] or null
 };

@@ -24,6 +24,9 @@
 //    k-th-best threshold into a per-query LDS candidate buffer, compacted
 //    by an in-LDS bitonic sort (ties by index: deterministic).
 // v1-v3 end in merge_kernel (the slices' k-lists per query).
+//
+// neighbor_table() builds the item neighbour table from these: every table
+// row's own top-k, chunk by chunk, scan v3 left out (section at the end).
 #include "dcnr_internal.h"
 
 #include <cfloat>
@@ -1832,7 +1835,7 @@ size_t topk_ws(int64_t N, int64_t Q, int k) {
 
 dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_t N, int d,
                         const float* q, int64_t Q, int k, int64_t* idx, float* dist, void* ws,
-                        size_t ws_bytes, hipStream_t s) {
+                        size_t ws_bytes, hipStream_t s, bool allow_v3) {
   if (k < 1 || k > KMAX || d < 4 || d % 4 || d > 256 || N < 1) {
     set_error("cosine_topk: unsupported k=%d d=%d N=%lld (1<=k<=64, d%%4==0, d<=256)", k, d,
               (long long)N);
@@ -1910,7 +1913,7 @@ dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_
                        w.qn, k, w.thr0);
   });
   DCNR_LAUNCH_CHECK();
-  const bool v3 = Q >= MFMA_MIN_Q && d % 16 == 0;
+  const bool v3 = allow_v3 && Q >= MFMA_MIN_Q && d % 16 == 0;
   const int qtiles = (int)cdiv(Q, v3 ? K3_QT : K2_QT);
   const dim3 blocks((unsigned)(rup(w.ns, 8) * qtiles));
   // scan v3 where it applies, else scan v2: the exact VALU scan (the same
@@ -1929,6 +1932,59 @@ dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_
   });
   DCNR_LAUNCH_CHECK();
   return merge_lists(w.cands, Q, w.ns, k, idx, dist, s);
+}
+
+// ---- the item neighbour table: the top-k of every table row, built once
+//
+// Row r of the table is the answer of cosine_topk for the single query t[r].
+// The build walks the rows in chunks of NBR_CHUNK queries through cosine_topk
+// with the query pointer inside the table, and keeps scan v3 out: v1, v2, v4
+// and their fallbacks all end in dot4 / cos_dist, so a row's distances, and
+// with them its order among ties, do not depend on the chunk it was built in
+// or on the width of the batch; v3's MFMA sums in another order.
+constexpr int64_t NBR_CHUNK = 1024;
+
+__global__ void narrow_idx_kernel(const int64_t* __restrict__ in, int64_t n, int32_t* __restrict__ out) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
+    out[e] = (int32_t)in[e];
+}
+
+// One chunk's scratch, carved once: idx [NBR_CHUNK][k] int64 | dist (when the
+// caller wants none) | the search's own workspace, the largest any chunk
+// width up to NBR_CHUNK asks for (the last chunk of a range is narrower, and
+// the search's plan is not monotone in Q)
+struct NbrWs { int64_t* idx; float* dist; void* topk; size_t topk_bytes, total; };
+NbrWs carve_nbr(void* ws, int64_t N, int k) {
+  NbrWs w{};
+  Bump b(ws);
+  w.idx = (int64_t*)b.take((size_t)NBR_CHUNK * k * sizeof(int64_t));
+  w.dist = (float*)b.take((size_t)NBR_CHUNK * k * sizeof(float));
+  for (int64_t Q = 1; Q <= NBR_CHUNK; ++Q) w.topk_bytes = std::max(w.topk_bytes, topk_ws(N, Q, k));
+  w.topk = b.take(w.topk_bytes);
+  w.total = b.off;
+  return w;
+}
+
+size_t neighbor_table_ws(int64_t N, int k) { return carve_nbr(nullptr, N, k).total; }
+
+dcnr_status neighbor_table(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
+                           int64_t row_lo, int64_t row_hi, int32_t* out_idx, float* out_dist, void* ws,
+                           size_t ws_bytes, hipStream_t s) {
+  const NbrWs w = carve_nbr(ws, N, k);
+  if (ws_bytes < w.total) {
+    set_error("neighbor_table: workspace too small");
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  for (int64_t lo = row_lo; lo < row_hi; lo += NBR_CHUNK) {
+    const int64_t Q = std::min(NBR_CHUNK, row_hi - lo);
+    const int64_t o = (lo - row_lo) * k;
+    TRY_ST(cosine_topk(t, inv, tb, N, d, t + lo * d, Q, k, w.idx, out_dist ? out_dist + o : w.dist, w.topk,
+                       w.topk_bytes, s, /*allow_v3=*/false));
+    hipLaunchKernelGGL(narrow_idx_kernel, dim3((unsigned)cdiv(Q * k, 256)), dim3(256), 0, s, w.idx, Q * k,
+                       out_idx + o);
+    DCNR_LAUNCH_CHECK();
+  }
+  return DCNR_OK;
 }
 
 dcnr_status topk_merge(const float* dist, const int64_t* idx, int lists, int64_t Q, int k,

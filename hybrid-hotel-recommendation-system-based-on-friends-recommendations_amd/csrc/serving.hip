@@ -18,7 +18,9 @@
 // exactly as Python's stable sort does.
 //
 // A batch of R requests (req_* kernels) is the same work over CSR segments,
-// request r in workgroup r, side by side on the CUs: candidates with the
+// request r in workgroup r, side by side on the CUs: candidates (their
+// neighbours from the call's top-k lists or from the item neighbour table,
+// one staging loop: KnnLists / NbrTable) with the
 // fallback and the allowed / excluded filters (main.py:204-212) as binary
 // searches in resident row sets, the offsets of the compacted batch, its
 // ranking batch, and rank + MMR per segment.  Both forms call one copy of
@@ -90,11 +92,46 @@ __device__ int block_compact(int n, int* wsum, F flag, W write) {
   return running;
 }
 
-// entry t of a request's staged list: positives[q] at j = 0, else the
-// neighbour idx[q][j] (t = q * k + j); rows < 0 are skipped (INT64_MAX)
-__device__ __forceinline__ int64_t union_entry(const int64_t* pos, const int64_t* idx, int k, int t) {
-  const int64_t q = t / k, j = t % k;
-  const int64_t r = j == 0 ? pos[q] : idx[q * k + j];
+// Where a positive's neighbours come from: the top-k lists of this call's
+// positives (KnnLists: idx [Q][k], row q for positive q), or the item
+// neighbour table built at fit time (NbrTable: nbr [n_items][kt] int32, row p
+// for the hotel p, its first k entries).  at(q, p, j, bad): neighbour j >= 1
+// of positive number q, the hotel p; sets bad where the table cannot answer.
+// positive(p, bad): the positive itself, position 0 of its list.
+struct KnnLists {
+  const int64_t* idx; int k;
+  __device__ KnnLists from(int64_t q0) const { return {idx + q0 * k, k}; }
+  __device__ int64_t positive(int64_t p, bool&) const { return p; }
+  __device__ int64_t at(int64_t q, int64_t, int j, bool&) const { return idx[q * k + j]; }
+};
+struct NbrTable {
+  const int32_t* nbr; int kt; int64_t n_items;
+  __device__ NbrTable from(int64_t) const { return *this; }
+  __device__ int64_t positive(int64_t p, bool& bad) const {
+    if (p >= n_items) bad = true;
+    return p;
+  }
+  // a negative positive is skipped with its neighbours, as the positive
+  // itself is (dcnr_requests_sources pads with -1); one past the table has no
+  // row to read, and an entry outside the table is no hotel (the table holds
+  // no padding): both are bad data
+  __device__ int64_t at(int64_t, int64_t p, int j, bool& bad) const {
+    if (p < 0) return -1;
+    if (p >= n_items) { bad = true; return -1; }
+    const int64_t v = nbr[p * kt + j];
+    if (v < 0 || v >= n_items) bad = true;
+    return v;
+  }
+};
+
+// entry t of a request's staged list: positives[q] at j = 0, else neighbour
+// j of positive q (t = q * k + j); rows < 0 are skipped (INT64_MAX)
+template <class Src>
+__device__ __forceinline__ int64_t union_entry(const int64_t* pos, const Src& src, int k, int t, bool& bad) {
+  const int64_t q = t / k;
+  const int j = t % k;
+  const int64_t p = pos[q];
+  const int64_t r = j == 0 ? src.positive(p, bad) : src.at(q, p, j, bad);
   return r < 0 ? INT64_MAX : r;
 }
 
@@ -111,22 +148,32 @@ __device__ int distinct_rows(const int64_t* key, int n2, int* wsum, W write) {
       write);
 }
 
-// union of positives[Q] and idx[Q][k][1:] (rows < 0 skipped) -> ascending
-// unique rows; out_count[0] = number of rows
-__global__ __launch_bounds__(SV_NT) void union_kernel(const int64_t* pos, int64_t Q,
-                                                      const int64_t* idx, int k, int64_t* out,
-                                                      int32_t* out_count) {
+// union of positives[Q] and their neighbours [1:] (rows < 0 skipped) ->
+// ascending unique rows; out_count[0] = number of rows, or -1 where the
+// neighbour source reported bad data (NbrTable)
+template <class Src>
+__global__ __launch_bounds__(SV_NT) void union_kernel(const int64_t* pos, int64_t Q, Src src, int k,
+                                                      int64_t* out, int32_t* out_count) {
   __shared__ int64_t key[SV_MAX];
   __shared__ int val[SV_MAX];
   __shared__ int wsum[SV_NT / 64];
+  __shared__ int bad;
+  if (threadIdx.x == 0) bad = 0;
+  __syncthreads();
   const int n = (int)(Q * k);   // positives + k-1 neighbours per query
   int n2 = 1;
   while (n2 < n) n2 <<= 1;
   for (int t = threadIdx.x; t < n2; t += SV_NT) {
-    key[t] = t < n ? union_entry(pos, idx, k, t) : INT64_MAX;
+    bool b = false;
+    key[t] = t < n ? union_entry(pos, src, k, t, b) : INT64_MAX;
     val[t] = t;
+    if (b) bad = 1;
   }
   __syncthreads();
+  if (bad) {
+    if (threadIdx.x == 0) *out_count = -1;
+    return;
+  }
   lds_bitonic(key, val, n2);
   const int cnt = distinct_rows(key, n2, wsum, [&](int p, int64_t v) { out[p] = v; });
   if (threadIdx.x == 0) *out_count = cnt;
@@ -177,8 +224,9 @@ __device__ bool req_set(const ReqSets& st, const int32_t* which, int64_t r, cons
 // not fit (count 0), REQ_BAD_DATA when the request's offsets, set indices or
 // rows lie outside the lengths passed by value (count 0).  Every index formed
 // here is checked against one of those lengths first.
+template <class Src>
 __global__ __launch_bounds__(SV_NT) void req_candidates_kernel(
-    const int64_t* pos, const int64_t* pos_off, int64_t R, int64_t Q_total, const int64_t* idx,
+    const int64_t* pos, const int64_t* pos_off, int64_t R, int64_t Q_total, Src src,
     int k, ReqSets st, int min_cand, int64_t n_items, int cap, int64_t* out, int32_t* out_count,
     int32_t* status) {
   __shared__ int64_t key[SV_MAX];
@@ -213,8 +261,9 @@ __global__ __launch_bounds__(SV_NT) void req_candidates_kernel(
   for (int t = threadIdx.x; t < n2; t += SV_NT) {
     int64_t v = INT64_MAX;
     if (t < n) {
-      v = union_entry(pos + q0, idx + q0 * k, k, t);
-      if (v != INT64_MAX && v >= n_items) { bad = 1; v = INT64_MAX; }
+      bool b = false;
+      v = union_entry(pos + q0, src.from(q0), k, t, b);
+      if (b || (v != INT64_MAX && v >= n_items)) { bad = 1; v = INT64_MAX; }
     }
     key[t] = v;
     val[t] = t;
@@ -1019,15 +1068,25 @@ dcnr_status gather_rows(const int64_t* idx, int64_t n, int64_t n_src, int n_arra
   return DCNR_OK;
 }
 
+// the neighbour source of a call: the table where one is given (nbr), else
+// the positives' own top-k lists
+template <class F>
+dcnr_status with_neighbours(const int64_t* idx, int k, const int32_t* nbr, int kt, int64_t n_items, F f) {
+  return nbr ? f(NbrTable{nbr, kt, n_items}) : f(KnnLists{idx, k});
+}
+
 dcnr_status candidate_union(const int64_t* pos, int64_t Q, const int64_t* idx, int k,
-                            int64_t* out, int32_t* out_count, hipStream_t s) {
+                            const int32_t* nbr, int kt, int64_t n_items, int64_t* out,
+                            int32_t* out_count, hipStream_t s) {
   if (Q < 0 || k < 1 || Q * k > SV_MAX) {
     set_error("candidate_union: Q*k=%lld exceeds %d", (long long)(Q * k), SV_MAX);
     return DCNR_UNSUPPORTED_SHAPE;
   }
-  hipLaunchKernelGGL(union_kernel, dim3(1), dim3(SV_NT), 0, s, pos, Q, idx, k, out, out_count);
-  DCNR_LAUNCH_CHECK();
-  return DCNR_OK;
+  return with_neighbours(idx, k, nbr, kt, n_items, [&](auto src) {
+    hipLaunchKernelGGL(union_kernel<decltype(src)>, dim3(1), dim3(SV_NT), 0, s, pos, Q, src, k, out, out_count);
+    DCNR_LAUNCH_CHECK();
+    return DCNR_OK;
+  });
 }
 
 dcnr_status ranking_batch(const int64_t* rows, int64_t n, int64_t user_row, const int64_t* item_cat,
@@ -1097,10 +1156,13 @@ dcnr_status requests_candidates(const RequestsIn& in, int min_candidates, int64_
                                 int64_t* offsets, int64_t* host_offsets, int32_t* host_status,
                                 hipStream_t s) {
   ReqSets st{in.set_rows, in.n_set_rows, in.set_off, in.S, in.allowed, in.excluded, in.fallback};
-  hipLaunchKernelGGL(req_candidates_kernel, dim3((unsigned)in.R), dim3(SV_NT), 0, s, in.pos,
-                     in.pos_off, in.R, in.Q_total, in.idx, in.k, st, min_candidates, n_items, cap,
-                     out_rows, out_count, status);
-  DCNR_LAUNCH_CHECK();
+  TRY_ST(with_neighbours(in.idx, in.k, in.nbr, in.kt, n_items, [&](auto src) {
+    hipLaunchKernelGGL(req_candidates_kernel<decltype(src)>, dim3((unsigned)in.R), dim3(SV_NT), 0, s, in.pos,
+                       in.pos_off, in.R, in.Q_total, src, in.k, st, min_candidates, n_items, cap,
+                       out_rows, out_count, status);
+    DCNR_LAUNCH_CHECK();
+    return DCNR_OK;
+  }));
   hipLaunchKernelGGL(req_offsets_kernel, dim3(1), dim3(SV_NT), 0, s, out_count, status, in.R, cap,
                      offsets, host_offsets, host_status);
   DCNR_LAUNCH_CHECK();

@@ -6,7 +6,8 @@ System-Based-on-Friends-Recommendations):
   DCN_RecSys, CrossLayer, ResBlock   train.py:90-170 / main.py:61-127
   BCEWithLogitsLoss                  train.py:206
   AdamW, Adam                        train.py:201-204
-  NearestNeighbors (cosine, brute)   main.py:268-270
+  NearestNeighbors (cosine, brute)   main.py:268-270; .build_neighbor_table: every
+                                     row's neighbours, computed once
   FusedTrainer                       the train.py:219-226 inner-loop step;
                                      .fit: the epoch loop, train.py:216-253
   PlateauLR                          ReduceLROnPlateau (train.py:208-213, 235)
@@ -16,12 +17,15 @@ System-Based-on-Friends-Recommendations):
   DeviceLoader                       TensorDataset + DataLoader (train.py:195-196)
   serving.rerank_with_mmr            main.py:133-169
   serving.RankingPipeline            the /recommendations + /similar_items core
-                                     (main.py:196-230, 294-332)
+                                     (main.py:196-230, 294-332); neighbor_table=
+                                     serves both from the item neighbour table
   InteractionStore                   main_df's reviews + friendships_df as the
                                      request path reads them (main.py:172-194,
                                      336-351); RankingPipeline.recommend_users
   artifacts.save_artifacts /         final_dcn_model.pth + item_embeddings.npy
   artifacts.load_artifacts           (train.py:391-394, main.py:256-270)
+  artifacts.save_neighbor_table /    item_neighbors.npy (+ fingerprint): the
+  artifacts.load_neighbor_table      neighbour table beside those files
 
 All compute runs in libdcnr.so (C ABI: include/dcnr.h) on the HIP device.
 """

@@ -133,9 +133,14 @@ _SIGS = {
     "dcnr_cosine_pack_rows": (ctypes.c_int, [_P, _P, _I64, ctypes.c_int32, _P, _P]),
     "dcnr_cosine_topk_packed": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.c_int32, _P, _I64,
                                                ctypes.c_int32, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dcnr_cosine_neighbor_table_workspace_size": (ctypes.c_size_t, [_I64, ctypes.c_int32]),
+    "dcnr_cosine_neighbor_table": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.c_int32, ctypes.c_int32,
+                                                  _I64, _I64, _P, _P, _P, ctypes.c_size_t, _P]),
     "dcnr_topk_merge": (ctypes.c_int, [_P, _P, ctypes.c_int32, _I64, ctypes.c_int32, _P, _P, _P]),
     "dcnr_gather_rows": (ctypes.c_int, [_P, _I64, _I64, ctypes.c_int32, _P, _P, _P, _P]),
     "dcnr_candidate_union": (ctypes.c_int, [_P, _I64, _P, ctypes.c_int32, _P, _P, _P]),
+    "dcnr_candidate_union_table": (ctypes.c_int, [_P, _I64, _P, ctypes.c_int32, _I64,
+                                                  ctypes.c_int32, _P, _P, _P]),
     "dcnr_ranking_batch": (ctypes.c_int, [_P, _I64, _I64, _P, ctypes.c_int32, _P, ctypes.c_int32,
                                           _I64, _P, _P, _P, _P, _P]),
     "dcnr_rank_by_score": (ctypes.c_int, [_P, _I64, _P, _P]),
@@ -145,6 +150,10 @@ _SIGS = {
     "dcnr_requests_candidates": (ctypes.c_int, [_P, _P, _I64, _I64, _P, ctypes.c_int32, _P, _I64,
                                                 _P, ctypes.c_int32, _P, _P, _P, ctypes.c_int32,
                                                 _I64, ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    "dcnr_requests_candidates_table": (ctypes.c_int, [_P, _P, _I64, _I64, _P, ctypes.c_int32,
+                                                      ctypes.c_int32, _P, _I64, _P, ctypes.c_int32,
+                                                      _P, _P, _P, ctypes.c_int32, _I64,
+                                                      ctypes.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "dcnr_requests_ranking_batch": (ctypes.c_int, [_P, ctypes.c_int32, _P, _I64, _I64, _P, _P,
                                                    ctypes.c_int32, _P, ctypes.c_int32, _I64, _P,
                                                    _P, _P, _P, _P]),

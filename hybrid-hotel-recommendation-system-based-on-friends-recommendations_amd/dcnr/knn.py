@@ -8,6 +8,10 @@ ascending distance, the query row itself included when it is in the index --
 callers drop position 0 as main.py does).  Ties are ordered by row index
 (sklearn's argsort order among exactly equal distances is unspecified).
 ``kneighbors_device`` takes/returns device tensors for batched callers.
+
+``build_neighbor_table`` precomputes the answer for every row of the fitted
+table (the only queries the reference ever makes: main.py:200, 300), so that a
+server looks neighbours up instead of scanning.
 """
 from __future__ import annotations
 
@@ -37,6 +41,7 @@ class NearestNeighbors:
         self._table = None
         self._inv = None
         self._packed = None
+        self.neighbor_table_ = None
 
     def fit(self, X, y=None):
         t = torch.as_tensor(np.asarray(X, dtype=np.float32) if not torch.is_tensor(X) else X)
@@ -46,6 +51,7 @@ class NearestNeighbors:
         if self.device.type != 'cuda':
             raise RuntimeError("dcnr.NearestNeighbors runs on the HIP device only")
         self._table = t
+        self.neighbor_table_ = None   # (of the table fitted before)
         self._inv = torch.empty(t.shape[0], dtype=torch.float32, device=self.device)
         lib = _lib.load()
         _lib.check(lib.dcnr_row_inv_norms(t.data_ptr(), t.shape[0], t.shape[1], self._inv.data_ptr(),
@@ -84,6 +90,41 @@ class NearestNeighbors:
                                                _lib.stream_ptr(self.device)),
                    "dcnr_cosine_topk")
         return dist, idx
+
+    def build_neighbor_table(self, k=None, rows=None, return_distance=False):
+        """The item neighbour table (dcnr_cosine_neighbor_table): int32
+        [rows, k] on the device, row r exactly ``kneighbors_device(table[r:r+1],
+        k)[1]`` -- the row's k nearest, ascending by (distance, row), the row
+        itself not treated specially.  ``k`` defaults to ``n_neighbors``;
+        ``rows`` = (lo, hi) builds that range only (a build in pieces gives
+        the same rows).  A full build is kept as ``neighbor_table_`` until the
+        next ``fit``.  ``return_distance``: (distances fp32, table)."""
+        if self._table is None:
+            raise RuntimeError("This NearestNeighbors instance is not fitted yet")
+        lib = _lib.load()
+        N, d = self._table.shape
+        k = self.n_neighbors if k is None else int(k)
+        lo, hi = (0, N) if rows is None else (int(rows[0]), int(rows[1]))
+        if not 0 <= lo <= hi <= N:
+            raise ValueError(f"build_neighbor_table: rows ({lo}, {hi}) outside [0, {N}]")
+        if not 1 <= k <= N:
+            raise ValueError(f"Expected n_neighbors <= n_samples_fit, but n_neighbors = {k}, "
+                             f"n_samples_fit = {N}")
+        nbr = torch.empty((hi - lo, k), dtype=torch.int32, device=self.device)
+        dist = torch.empty((hi - lo, k), dtype=torch.float32, device=self.device) \
+            if return_distance else None
+        nb = int(lib.dcnr_cosine_neighbor_table_workspace_size(N, k))
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=self.device)
+        packed = self._packed.data_ptr() if self._packed is not None else None
+        _lib.check(lib.dcnr_cosine_neighbor_table(self._table.data_ptr(), self._inv.data_ptr(), packed,
+                                                  N, d, k, lo, hi, nbr.data_ptr(),
+                                                  dist.data_ptr() if return_distance else None,
+                                                  ws.data_ptr(), ws.numel(),
+                                                  _lib.stream_ptr(self.device)),
+                   "dcnr_cosine_neighbor_table")
+        if (lo, hi) == (0, N):
+            self.neighbor_table_ = nbr
+        return (dist, nbr) if return_distance else nbr
 
     def kneighbors(self, X=None, n_neighbors=None, return_distance=True):
         k = self.n_neighbors if n_neighbors is None else int(n_neighbors)

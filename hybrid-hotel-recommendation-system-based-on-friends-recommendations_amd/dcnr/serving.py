@@ -31,6 +31,13 @@ companion.  ``RankingPipeline.recommend_users`` is the same pass from user
 ids: the positives, the negatives and the ``recommended_by`` lists (main.py:
 172-194, 336-351) come from a ``dcnr.InteractionStore`` on the device
 (dcnr_requests_sources, dcnr_requests_recommended_by).
+
+``RankingPipeline(..., neighbor_table=True)`` builds the item neighbour table
+once (``NearestNeighbors.build_neighbor_table``): every neighbour query of the
+request path is a row of the fitted table, so ``candidates``, ``recommend``,
+``recommend_many``, ``recommend_users``, ``similar_items`` and
+``similar_items_many`` then read their neighbours from it and scan nothing;
+the answers are the same bits.
 """
 from __future__ import annotations
 
@@ -173,9 +180,16 @@ class RankingPipeline:
                train.py:393-394); default: the model's own item table
     item_cat   int64 [n_items, n_cat]: each hotel's encoded categorical codes
     item_num   fp32 [n_items, n_num]: each hotel's scaled numeric features
+    neighbor_table  False: every request scans the index.  True: the item
+               neighbour table is built here with k = n_neighbors; an int:
+               with that k (>= n_neighbors; /similar_items reads it up to
+               n = k - 1); an int32 array or tensor [n_items, kt]: a table built
+               before (``build_neighbor_table``, ``load_artifacts``) is adopted.
+               ValueError for a table of another shape or kt < n_neighbors.
     """
 
-    def __init__(self, model, item_cat, item_num, item_embeddings=None, n_neighbors: int = 11):
+    def __init__(self, model, item_cat, item_num, item_embeddings=None, n_neighbors: int = 11,
+                 neighbor_table=False):
         dev = model.final_linear.weight.device
         if dev.type != 'cuda':
             raise RuntimeError("RankingPipeline runs on the HIP device only")
@@ -199,11 +213,30 @@ class RankingPipeline:
         self._sets = (self._no_rows, np.zeros(1, np.int64))
         self._sets_lock = threading.Lock()
         self._tls = threading.local()
+        self._nbr = self._neighbor_table(neighbor_table)
+
+    def _neighbor_table(self, arg):
+        """The constructor's ``neighbor_table`` as int32 [n_items, kt] on the device, or None."""
+        n, k = self.index._table.shape[0], self.n_neighbors
+        if arg is None or arg is False:
+            return None
+        if arg is True or isinstance(arg, (int, np.integer)):
+            kt = k if arg is True else int(arg)
+            if kt < k:
+                raise ValueError(f"neighbor_table: k = {kt} is below n_neighbors = {k}")
+            return self.index.build_neighbor_table(kt)
+        t = torch.as_tensor(arg)
+        if t.dtype != torch.int32 or t.dim() != 2 or t.shape[0] != n or t.shape[1] < k:
+            raise ValueError(f"neighbor_table: expected int32 [{n}, kt >= {k}], got "
+                             f"{str(t.dtype).replace('torch.', '')} {list(t.shape)}")
+        return t.to(self.device).contiguous()
 
     # ---------------------------------------------------------- /similar_items
     def similar_items(self, item_row: int, n: int = 10) -> torch.Tensor:
         """main.py:294-303: the n nearest hotels, the hotel itself dropped
         (kneighbors(n_neighbors=n+1)[1:])."""
+        if self._nbr is not None and n + 1 <= self._nbr.shape[1]:
+            return self._nbr[int(item_row), 1:n + 1].to(torch.int64)
         q = self.index._table[int(item_row)].reshape(1, -1)
         _, idx = self.index.kneighbors_device(q, n + 1)
         return idx[0, 1:]
@@ -218,18 +251,32 @@ class RankingPipeline:
         if Q == 0:
             return pos
         k = self.n_neighbors
-        _, idx = self.index.kneighbors_device(self.index._table[pos], k)
+        nbr = self._nbr
+        if nbr is None:
+            _, idx = self.index.kneighbors_device(self.index._table[pos], k)
         qc = max(1, SV_MAX // k)     # the union kernel's one-workgroup capacity
         outs = []
         for q0 in range(0, Q, qc):   # > SV_MAX entries: per-chunk unions, then merged
-            p_, i_ = pos[q0:q0 + qc].contiguous(), idx[q0:q0 + qc].contiguous()
+            p_ = pos[q0:q0 + qc].contiguous()
             out = torch.empty(p_.numel() * k, dtype=torch.int64, device=self.device)
             cnt = torch.zeros(1, dtype=torch.int32, device=self.device)
-            _lib.check(lib.dcnr_candidate_union(p_.data_ptr(), p_.numel(), i_.data_ptr(), k,
-                                                out.data_ptr(), cnt.data_ptr(),
-                                                _lib.stream_ptr(self.device)),
-                       "dcnr_candidate_union")
-            outs.append(out[:int(cnt.item())])
+            if nbr is not None:   # the neighbours looked up, nothing scanned
+                _lib.check(lib.dcnr_candidate_union_table(p_.data_ptr(), p_.numel(), nbr.data_ptr(),
+                                                          nbr.shape[1], nbr.shape[0], k,
+                                                          out.data_ptr(), cnt.data_ptr(),
+                                                          _lib.stream_ptr(self.device)),
+                           "dcnr_candidate_union_table")
+            else:
+                i_ = idx[q0:q0 + qc].contiguous()
+                _lib.check(lib.dcnr_candidate_union(p_.data_ptr(), p_.numel(), i_.data_ptr(), k,
+                                                    out.data_ptr(), cnt.data_ptr(),
+                                                    _lib.stream_ptr(self.device)),
+                           "dcnr_candidate_union")
+            c = int(cnt.item())
+            if c < 0:
+                raise ValueError("candidates: a positive row or a neighbour table entry lies "
+                                 "outside the table")
+            outs.append(out[:c])
         if len(outs) == 1:
             return outs[0]
         return torch.unique(torch.cat(outs))   # ascending distinct rows, as one call gives
@@ -317,9 +364,29 @@ class RankingPipeline:
             raise ValueError("similar_items_many: item row outside the index")
         if rows.size == 0:
             return torch.empty((0, n), dtype=torch.int64, device=self.device)
-        q = self.index._table[torch.from_numpy(rows).to(self.device)]
-        _, idx = self.index.kneighbors_device(q, n + 1)
+        d_rows = torch.from_numpy(rows).to(self.device)
+        if self._nbr is not None and n + 1 <= self._nbr.shape[1]:
+            return self._nbr[d_rows][:, 1:n + 1].to(torch.int64)
+        _, idx = self.index.kneighbors_device(self.index._table[d_rows], n + 1)
         return idx[:, 1:]
+
+    def _requests_candidates(self, pos_ptr, d_pos, pos_off_ptr, R, Q, *rest):
+        """dcnr_requests_candidates behind ONE top-k call over all requests'
+        positives d_pos [Q] -- or, with a neighbour table, its table form and no
+        scan.  ``rest``: the arguments from set_rows on."""
+        lib = _lib.load()
+        k = self.n_neighbors
+        if self._nbr is not None:
+            _lib.check(lib.dcnr_requests_candidates_table(
+                pos_ptr, pos_off_ptr, R, Q, self._nbr.data_ptr(), self._nbr.shape[1], k, *rest),
+                "dcnr_requests_candidates_table")
+            return
+        idx = None
+        if Q:
+            _, idx = self.index.kneighbors_device(self.index._table[d_pos], k)
+        _lib.check(lib.dcnr_requests_candidates(
+            pos_ptr, pos_off_ptr, R, Q, idx.data_ptr() if Q else None, k, *rest),
+            "dcnr_requests_candidates")
 
     def register_sets(self, sets) -> List[int]:
         """Upload row sets (a city's hotels, its most reviewed hotels ...) once,
@@ -404,21 +471,17 @@ class RankingPipeline:
             reg_rows = torch.cat([reg_rows, dbuf[o:o + 8 * n_adhoc].view(torch.int64)])
         stream = _lib.stream_ptr(dev)
         Q = pos.size
-        idx = None
-        if Q:   # one top-k call for all requests' positives
-            d_pos = dbuf[at["pos"]:at["pos"] + 8 * Q].view(torch.int64)
-            _, idx = self.index.kneighbors_device(self.index._table[d_pos], k)
+        d_pos = dbuf[at["pos"]:at["pos"] + 8 * Q].view(torch.int64)
         slots = torch.empty((R, cap), dtype=torch.int64, device=dev)
         offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
         words = torch.empty(3 * R, dtype=torch.int32, device=dev)   # count, status, out_count
         count, status, out_count = (words.data_ptr() + 4 * R * j for j in range(3))
-        _lib.check(lib.dcnr_requests_candidates(
-            d_at("pos") if Q else None, d_at("pos_off"), R, Q, idx.data_ptr() if Q else None, k,
+        self._requests_candidates(
+            d_at("pos") if Q else None, d_pos, d_at("pos_off"), R, Q,
             reg_rows.data_ptr() if reg_rows.numel() else None, reg_rows.numel(),
             d_at("set_off"), S, d_at("allowed"), d_at("excluded"), d_at("fallback"),
             int(min_candidates), self.n_rows, cap, slots.data_ptr(), count, status,
-            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream),
-            "dcnr_requests_candidates")
+            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream)
         # (allocated while the device works, not after the wait)
         nb = int(lib.dcnr_requests_workspace_size(R, Q, k, cap))
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -612,19 +675,14 @@ class RankingPipeline:
             d_pos.data_ptr() if Q else None, d_at("set_off") + 8 * S0, n0, n0 + NB,
             set_rows.data_ptr() if NB else None, s_cnt, s_st, pin.data_ptr() + o_cnt,
             pin.data_ptr() + o_sst, stream), "dcnr_requests_sources")
-        idx = None
-        if Q:   # one top-k call for all requests' (padded) positives
-            _, idx = self.index.kneighbors_device(self.index._table[d_pos], k)
         slots = torch.empty((R, cap), dtype=torch.int64, device=dev)
         offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
-        _lib.check(lib.dcnr_requests_candidates(
-            d_pos.data_ptr() if Q else None, d_at("pos_off"), R, Q,
-            idx.data_ptr() if Q else None, k,
+        self._requests_candidates(
+            d_pos.data_ptr() if Q else None, d_pos, d_at("pos_off"), R, Q,
             set_rows.data_ptr() if set_rows.numel() else None, set_rows.numel(),
             d_at("set_off"), S0 + R, d_at("allowed"), d_at("excluded"), d_at("fallback"),
             int(min_candidates), self.n_rows, cap, slots.data_ptr(), count, status,
-            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream),
-            "dcnr_requests_candidates")
+            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream)
         # (allocated while the device works, not after the wait)
         nb = int(lib.dcnr_requests_workspace_size(R, Q, k, cap))
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)

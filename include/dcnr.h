@@ -20,11 +20,16 @@
  *   dcnr_adam_step        torch.optim.AdamW/Adam(...).step()  train.py:201-204,226
  *   dcnr_cosine_topk      NearestNeighbors(metric='cosine', algorithm='brute')
  *                         .kneighbors(vec, n_neighbors=k)      main.py:196-203,268-270,300
+ *   dcnr_cosine_neighbor_table
+ *                         that index's answer for every row of its own fitted
+ *                         data (the only queries main.py:200, 300 make), once
  *   dcnr_row_inv_norms    the row normalisation inside sklearn's cosine metric
  *   dcnr_gather_rows      the batch assembly of TensorDataset + DataLoader
  *                         (train.py:195-196) on a device-resident dataset
  *   dcnr_candidate_union  _generate_candidates' union of positives and their
  *                         neighbours[1:]                      main.py:196-203
+ *                         (dcnr_candidate_union_table, dcnr_requests_candidates_table:
+ *                         the neighbours read from the item neighbour table)
  *   dcnr_ranking_batch    preprocess_for_ranking              main.py:215-230
  *   dcnr_rank_by_score    sorted(zip(scores, ids), reverse=True) main.py:325
  *   dcnr_mmr_rerank       rerank_with_mmr                     main.py:133-169
@@ -409,6 +414,28 @@ dcnr_status dcnr_cosine_topk_packed(const float* table, const float* inv_norms, 
                                     int64_t* idx, float* dist, void* ws, size_t ws_bytes,
                                     dcnr_stream_t stream);
 
+/* The item neighbour table: the k nearest rows of every row of the fitted
+ * table, built once so that /recommendations' candidate step and
+ * /similar_items become row lookups (the reference queries its index with rows
+ * of the fitted data only: main.py:200 with n_neighbors = 11, main.py:300).
+ * For rows [row_lo, row_hi) writes out_idx int32 [row_hi - row_lo][k] and,
+ * unless NULL, out_dist fp32 of the same shape.  Row r holds exactly what
+ * dcnr_cosine_topk_packed returns for the single query table[r]: the k best
+ * ascending by (dist, row), the same bits whatever range or piece of a range
+ * the row was built in.  The row itself is not treated specially (among
+ * duplicate rows it need not be at position 0); callers keep dropping
+ * position 0 as main.py:201 does.  1 <= k <= min(64, N), N < 2^31 (else
+ * DCNR_BAD_ARG / DCNR_UNSUPPORTED_SHAPE); a range outside 0 <= row_lo <=
+ * row_hi <= N is DCNR_BAD_ARG; an empty range returns DCNR_OK without a
+ * launch.  The rows are searched in fixed-size chunks of queries read in place
+ * from the table; stream-ordered, no host synchronisation; `ws` holds one
+ * chunk's scratch (dcnr_cosine_neighbor_table_workspace_size bytes). */
+size_t dcnr_cosine_neighbor_table_workspace_size(int64_t N, int32_t k);
+dcnr_status dcnr_cosine_neighbor_table(const float* table, const float* inv_norms, const uint16_t* packed,
+                                       int64_t N, int32_t d, int32_t k, int64_t row_lo, int64_t row_hi,
+                                       int32_t* out_idx, float* out_dist, void* ws, size_t ws_bytes,
+                                       dcnr_stream_t stream);
+
 /* Merge of row-sharded top-k lists (the cfg5 index split over ranks, SURVEY
  * 8(e)): dist fp32 / idx int64 [lists][Q][k] (global rows; padding entries
  * (FLT_MAX, -1) sort last) -> the k best per query, ascending by (dist, row),
@@ -438,6 +465,16 @@ dcnr_status dcnr_gather_rows(const int64_t* idx, int64_t n, int64_t n_src, int32
 dcnr_status dcnr_candidate_union(const int64_t* positives, int64_t Q, const int64_t* knn_idx,
                                  int32_t k, int64_t* out_rows, int32_t* out_count,
                                  dcnr_stream_t stream);
+
+/* dcnr_candidate_union reading the neighbours from the item neighbour table
+ * (dcnr_cosine_neighbor_table): nbr int32 [n_items][kt], kt >= k; the
+ * neighbours of positive p are nbr[p][1 .. k).  The same rows as
+ * dcnr_candidate_union over knn_idx[q] = nbr[positives[q]][0 .. k).  Negative
+ * positives are skipped, their neighbours with them; a positive >= n_items or a table entry outside
+ * [0, n_items) is never followed and sets out_count[0] = -1. */
+dcnr_status dcnr_candidate_union_table(const int64_t* positives, int64_t Q, const int32_t* nbr,
+                                       int32_t kt, int64_t n_items, int32_t k, int64_t* out_rows,
+                                       int32_t* out_count, dcnr_stream_t stream);
 
 /* Ranking batch of preprocess_for_ranking (main.py:215-230) for one user:
  * user_ids[i] = user_row, item_ids[i] = item_rows[i], and the item's
@@ -523,6 +560,23 @@ dcnr_status dcnr_requests_candidates(const int64_t* positives, const int64_t* po
                                      int64_t* out_rows, int32_t* out_count, int32_t* status,
                                      int64_t* offsets, int64_t* host_offsets,
                                      int32_t* host_status, dcnr_stream_t stream);
+
+/* dcnr_requests_candidates reading the neighbours from the item neighbour
+ * table nbr int32 [n_items][kt], kt >= k (DCNR_BAD_ARG otherwise): the
+ * neighbours of a positive p are nbr[p][1 .. k), and no top-k call precedes
+ * this one.  Everything else as above.  A positive >= n_items or a table entry
+ * outside [0, n_items) (a negative one too) is DCNR_REQ_BAD_DATA for that
+ * request; a negative positive is skipped, its neighbours with it. */
+dcnr_status dcnr_requests_candidates_table(const int64_t* positives, const int64_t* pos_offsets,
+                                           int64_t R, int64_t Q_total, const int32_t* nbr, int32_t kt,
+                                           int32_t k, const int64_t* set_rows, int64_t n_set_rows,
+                                           const int64_t* set_offsets, int32_t S,
+                                           const int32_t* allowed, const int32_t* excluded,
+                                           const int32_t* fallback, int32_t min_candidates,
+                                           int64_t n_items, int32_t cap, int64_t* out_rows,
+                                           int32_t* out_count, int32_t* status, int64_t* offsets,
+                                           int64_t* host_offsets, int32_t* host_status,
+                                           dcnr_stream_t stream);
 
 /* dcnr_ranking_batch over the compacted batch of n = offsets[R] rows: row i
  * belongs to the request r whose segment [offsets[r], offsets[r + 1]) holds

@@ -5,6 +5,7 @@ it: the loop of ``recommend()`` over the same requests, in the same process.
 
     python tools/bench_requests.py [--batches 1 8 64 256] [--iters 20] [--rounds 5]
     python tools/bench_requests.py --one-batch 64      # for a kernel trace of its own
+    python tools/bench_requests.py --neighbor-table    # the pipeline reads the item neighbour table
 
 Workload: bench.py's configs[4] leg (bench_cfg5) -- a 1M x 64 item table, the
 bench model in bf16, 32 random positive hotels per request, lambda 0.7, top 20.
@@ -18,7 +19,9 @@ forward each route ran, observed from the library's launch counts by kernel
 class (the fused tower starts at 16384 rows where it covers the model; this
 model's input is wider than it takes).  The answers of the two routes are
 compared; batch sizes at which they differ are listed under "answers_differ"
-(none is expected while both take the same forward).  Prints one JSON line.
+(none is expected while both take the same forward).  With --neighbor-table the
+pipeline is built with ``neighbor_table=True`` (both routes then look their
+neighbours up; the build's seconds are reported).  Prints one JSON line.
 """
 from __future__ import annotations
 
@@ -40,7 +43,7 @@ import torch  # noqa: E402
 N_ITEMS = 1_000_000
 
 
-def build(dev):
+def build(dev, neighbor_table=False):
     import dcnr
     from bench import CFG
     torch.manual_seed(5)
@@ -49,7 +52,7 @@ def build(dev):
     g = torch.Generator(device=dev).manual_seed(7)
     item_cat = torch.randint(0, 1000, (N_ITEMS, 12), generator=g, device=dev)
     item_num = torch.rand((N_ITEMS, 8), generator=g, device=dev)
-    return dcnr.RankingPipeline(m, item_cat, item_num), g
+    return dcnr.RankingPipeline(m, item_cat, item_num, neighbor_table=neighbor_table), g
 
 
 def forward_seen(fn):
@@ -94,11 +97,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--one-batch", type=int, default=0,
                     help="warm up, then run one batched call of this size and exit")
+    ap.add_argument("--neighbor-table", action="store_true",
+                    help="serve the neighbours from the item neighbour table, built at start")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_requests.py needs the HIP device")
     dev = torch.device("cuda:0")
-    pipe, g = build(dev)
+    t0 = time.perf_counter()
+    pipe, g = build(dev, args.neighbor_table)
+    torch.cuda.synchronize()
+    build_s = time.perf_counter() - t0
 
     if args.one_batch:
         users, pos = requests(args.one_batch, g, dev)
@@ -112,6 +120,7 @@ def main():
 
     out = {"workload": "bench_cfg5: 1M x 64 item table, bench model bf16, 32 positives per "
                        "request, lambda 0.7, top 20", "iters": args.iters, "rounds": args.rounds,
+           "neighbor_table": args.neighbor_table, "pipeline_build_s": round(build_s, 3),
            "batches": {}}
     for R in args.batches:
         users, pos = requests(R, g, dev)

@@ -9,6 +9,7 @@ device) against the route a caller had before it, in the same process:
     python tools/bench_user_requests.py --one-batch 64     # for a kernel trace of its own
     python tools/bench_user_requests.py --kernel-stats run_kernel_stats.csv ...
                                                 # adds that trace's kernel times to the table
+    python tools/bench_user_requests.py --neighbor-table   # neighbours from the item neighbour table
 
 Workload: tools/bench_requests.py's (bench.py's configs[4] leg: a 1M x 64 item
 table, the bench model in bf16, lambda 0.7, top 20) with a synthetic store:
@@ -85,11 +86,13 @@ def main():
                     help="warm up, then run one recommend_users call of this size and exit")
     ap.add_argument("--kernel-stats", default=None,
                     help="a rocprofv3 --kernel-trace --stats CSV of a --one-batch run")
+    ap.add_argument("--neighbor-table", action="store_true",
+                    help="serve the neighbours from the item neighbour table, built at start")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_user_requests.py needs the HIP device")
     dev = torch.device("cuda:0")
-    pipe, g = build(dev)
+    pipe, g = build(dev, args.neighbor_table)
     store = make_store()
     store.on(dev)
     rng = np.random.default_rng(3)
@@ -109,7 +112,8 @@ def main():
     out = {"workload": "bench_cfg5 (1M x 64 item table, bench model bf16, lambda 0.7, top 20); "
                        f"store: {N_REVIEWERS} reviewers x {REVIEWS_EACH} reviews, "
                        f"{FRIENDS_EACH} friends on average, friends mode",
-           "iters": args.iters, "rounds": args.rounds, "batches": {}}
+           "iters": args.iters, "rounds": args.rounds, "neighbor_table": args.neighbor_table,
+           "batches": {}}
     if args.kernel_stats:
         out["kernel_us"] = kernel_times(args.kernel_stats)
     for R in args.batches:
