@@ -2150,6 +2150,84 @@ dcnr_status dcnr_cosine_neighbor_table(const float* table, const float* inv_norm
   return DCNR_OK;
 }
 
+// the shapes both update calls take: dcnr_cosine_neighbor_table's, and a width
+// the search takes (cosine_topk rejects the others only once it runs)
+static dcnr_status nbr_update_shape(const char* what, int64_t N, int32_t d, int32_t k) {
+  if (N < 1 || k < 1 || k > N) {
+    set_error("%s: bad argument (N=%lld, k=%d)", what, (long long)N, k);
+    return DCNR_BAD_ARG;
+  }
+  if (N > INT32_MAX || k > 64 || d < 4 || d % 4 || d > 256) {
+    set_error("%s: N=%lld (below 2^31), k=%d (max 64), d=%d (d %% 4 == 0, 4 <= d <= 256)", what, (long long)N, k,
+              d);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  return DCNR_OK;
+}
+
+size_t dcnr_cosine_neighbor_table_update_workspace_size(int64_t N, int32_t d, int32_t k, int64_t m) {
+  if (nbr_update_shape("dcnr_cosine_neighbor_table_update", N, d, k) != DCNR_OK || m < 0 ||
+      m > neighbor_table_update_max_m())
+    return 256;   // (the calls reject these)
+  return neighbor_table_update_ws(N, d, k, m);   // (exact: one byte less is DCNR_WORKSPACE_TOO_SMALL)
+}
+
+dcnr_status dcnr_cosine_neighbor_table_update(const float* table, const float* inv_norms, const uint16_t* packed,
+                                              int64_t N, int32_t d, int32_t k, const int32_t* changed, int64_t m,
+                                              int32_t* nbr, int32_t* counts, int32_t* host_counts,
+                                              int32_t* research_rows, void* ws, size_t ws_bytes,
+                                              dcnr_stream_t stream) {
+  if (!table || !inv_norms || m < 0) {
+    set_error("dcnr_cosine_neighbor_table_update: bad argument (m=%lld)", (long long)m);
+    return DCNR_BAD_ARG;
+  }
+  TRY_ST(nbr_update_shape("dcnr_cosine_neighbor_table_update", N, d, k));
+  if (m > neighbor_table_update_max_m()) {
+    set_error("dcnr_cosine_neighbor_table_update: m=%lld changed rows (max %d per call)", (long long)m,
+              neighbor_table_update_max_m());
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  if (m == 0) return DCNR_OK;
+  if (!changed || !nbr || !counts || !research_rows || !ws) {
+    set_error("dcnr_cosine_neighbor_table_update: null argument");
+    return DCNR_BAD_ARG;
+  }
+  for (int64_t i = 0; i < m; ++i)
+    if (changed[i] < 0 || changed[i] >= N || (i > 0 && changed[i] <= changed[i - 1])) {
+      set_error("dcnr_cosine_neighbor_table_update: changed[%lld] = %d (ascending, distinct, inside [0, %lld))",
+                (long long)i, changed[i], (long long)N);
+      return DCNR_BAD_ARG;
+    }
+  hipStream_t s = (hipStream_t)stream;
+  // (bytes: the lists, each row's k-th neighbour gathered, one pass over the rows, the changed rows)
+  TRYB(DCNR_K_KNN, s,
+       (double)N * (4.0 * k + 8.0 + 4.0 * d) + (double)N * d * ((d == 32 || d == 64) && packed ? 2.0 : 4.0) +
+           (double)m * (4.0 * d + 8.0),
+       neighbor_table_update(table, inv_norms, (const bf16*)packed, N, d, k, changed, m, nbr, counts, host_counts,
+                             research_rows, ws, ws_bytes, s));
+  return DCNR_OK;
+}
+
+dcnr_status dcnr_cosine_neighbor_table_rows(const float* table, const float* inv_norms, const uint16_t* packed,
+                                            int64_t N, int32_t d, int32_t k, const int32_t* rows, int64_t n,
+                                            int32_t* nbr, void* ws, size_t ws_bytes, dcnr_stream_t stream) {
+  if (!table || !inv_norms || n < 0) {
+    set_error("dcnr_cosine_neighbor_table_rows: bad argument (n=%lld)", (long long)n);
+    return DCNR_BAD_ARG;
+  }
+  TRY_ST(nbr_update_shape("dcnr_cosine_neighbor_table_rows", N, d, k));
+  if (n == 0) return DCNR_OK;
+  if (!rows || !nbr || !ws) {
+    set_error("dcnr_cosine_neighbor_table_rows: null argument");
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // (bytes: as the build's -- every chunk of queries streams the table again)
+  TRYB(DCNR_K_KNN, s, (double)N * (4.0 * d + 4.0) + (double)n * (4.0 * d + 12.0 * k + 4.0),
+       neighbor_table_rows(table, inv_norms, (const bf16*)packed, N, d, k, rows, n, nbr, ws, ws_bytes, s));
+  return DCNR_OK;
+}
+
 dcnr_status dcnr_topk_merge(const float* dist, const int64_t* idx, int32_t lists, int64_t Q,
                             int32_t k, int64_t* out_idx, float* out_dist, dcnr_stream_t stream) {
   if (!dist || !idx || !out_idx || !out_dist || Q < 0) {

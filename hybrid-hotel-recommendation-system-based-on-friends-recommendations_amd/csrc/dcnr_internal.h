@@ -789,6 +789,19 @@ size_t neighbor_table_ws(int64_t N, int k);
 dcnr_status neighbor_table(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
                            int64_t row_lo, int64_t row_hi, int32_t* out_idx, float* out_dist, void* ws,
                            size_t ws_bytes, hipStream_t s);
+// the table updated in place after the m rows `changed` (host, ascending,
+// distinct) got new vectors: the filter and the merge (counts: changed,
+// affected, merged, to re-search; research: those rows), and the build over a
+// device list of rows; one workspace size serves both
+size_t neighbor_table_update_ws(int64_t N, int d, int k, int64_t m);
+int neighbor_table_update_max_m();
+dcnr_status neighbor_table_update(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
+                                  const int32_t* changed, int64_t m, int32_t* nbr, int32_t* counts,
+                                  int32_t* host_counts, int32_t* research, void* ws, size_t ws_bytes,
+                                  hipStream_t s);
+dcnr_status neighbor_table_rows(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
+                                const int32_t* rows, int64_t n, int32_t* nbr, void* ws, size_t ws_bytes,
+                                hipStream_t s);
 dcnr_status cosine_pack_rows(const float* t, const float* inv, int64_t N, int d, bf16* out, hipStream_t s);
 
 // serving (serving.hip)

@@ -1987,6 +1987,473 @@ dcnr_status neighbor_table(const float* t, const float* inv, const bf16* tb, int
   return DCNR_OK;
 }
 
+// ---- the item neighbour table, updated in place after m rows changed
+//
+// C: the changed rows (their vectors, inv and packed rows already new); kt:
+// the table's width; L(r): row r's list as it stands, exact for the table
+// before the change.  Keys are (distance, row) under cless, every distance
+// from the new table.  A row outside C keeps its vector, so its distance to
+// another such row is what it was; the old distance to a changed row is never
+// needed.
+//   * r in C: searched again.
+//   * r not in C, no member of C in L(r), every c in C with a key above the
+//     list's last: untouched (the filter, phase A).
+//   * else (the merge, phase B): K' = the largest key of L(r) \ C.  Every row
+//     outside L(r) and C has its old key, above the old k-th key >= K'.  So
+//     when L(r) \ C and the c in C with key <= K' number at least kt, the kt
+//     smallest of them are the new list; with fewer, a changed row left a
+//     hole that only a scan can fill: searched again.  So is a row with no
+//     entry outside C, and one whose candidates exceed UPD_CAP.
+// The re-search (phase C) is the build over a list of rows.
+//
+// Phase A marks a superset: the exact k-th distance dk of r (its last entry
+// is outside C, or the row is affected anyway), and then, d = 32 / 64, scan
+// v4's coarse bf16 cosine of r against every c -- |coarse - exact| < V4_EPS
+// (DESIGN section 4), so coarse <= dk + V4_EPS + TH_MARGIN holds for every c
+// with exact distance <= dk: one margin, because dk itself is exact (a coarse
+// dk would double it and gather as many rows) -- or, other widths, the exact
+// distance against dk + TH_MARGIN.  A row is appended once, by the block that
+// owns it; the order of the lists decides nothing (each row's result depends
+// on that row alone).
+constexpr int UPD_MAX_M = 16384;   // changed rows per call
+constexpr int UPD_CT = V4_QC;      // changed rows per LDS tile of the MFMA filter
+constexpr int UPD_RPB = 1024;      // table rows per block of the MFMA filter
+constexpr int UPD_XT = 16;         // changed rows per LDS tile of the exact filter
+constexpr int UPD_CAP = CAP;       // merge candidates per row
+constexpr int UPD_DMAX = 256;      // cosine_topk's widest row
+constexpr float UPD_NEVER = -1.f;  // k-th distance of a row the filter skips
+
+namespace {
+
+__device__ __forceinline__ bool upd_bit(const unsigned* __restrict__ bits, int r) {
+  return (bits[r >> 5] >> (r & 31)) & 1u;
+}
+
+// exact distance of table row e to the normalised query qv (dv float4 chunks):
+// dot4 per chunk in order, then cos_dist -- exact_dist's sum at a run-time width
+__device__ __forceinline__ float upd_row_dist(const float* __restrict__ tab, const float* __restrict__ inv,
+                                              int64_t e, int dv, const float4* qv) {
+  const float4* rp = reinterpret_cast<const float4*>(tab) + e * dv;
+  float s = 0.f;
+  for (int v = 0; v < dv; ++v) s += dot4(rp[v], qv[v]);
+  return cos_dist(s, inv[e]);
+}
+
+// the changed rows into the bitmap and the head of the re-search list; counts
+__global__ void upd_mark_kernel(const int* __restrict__ chg, int m, unsigned* bits, int* research, int* counts) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) {
+    const int c = chg[i];
+    atomicOr(&bits[c >> 5], 1u << (c & 31));
+    research[i] = c;
+  }
+  if (i == 0) { counts[0] = m; counts[1] = 0; counts[2] = 0; counts[3] = m; }
+}
+
+// Phase A, first pass, one row per thread: a row whose list holds a member
+// of C (or an entry outside the table) is affected; every other row outside C
+// gets its exact k-th distance, query r against its last entry.
+__global__ __launch_bounds__(256) void upd_kth_kernel(const float* __restrict__ tab, const float* __restrict__ inv,
+                                                      int N, int dv, int kt, const int* __restrict__ nbr,
+                                                      const unsigned* __restrict__ bits, float* kth, int* aff,
+                                                      int* counts) {
+  const int64_t r64 = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r64 >= N) return;
+  const int r = (int)r64;
+  if (upd_bit(bits, r)) { kth[r] = UPD_NEVER; return; }
+  const int* L = nbr + (int64_t)r * kt;
+  bool hit = false;
+  int last = 0;
+  for (int j = 0; j < kt; ++j) {
+    last = L[j];
+    hit = hit || (unsigned)last >= (unsigned)N || upd_bit(bits, last);
+  }
+  if (hit) {
+    aff[atomicAdd(&counts[1], 1)] = r;
+    kth[r] = UPD_NEVER;
+    return;
+  }
+  const float4* xr = reinterpret_cast<const float4*>(tab) + (int64_t)r * dv;
+  const float4* xe = reinterpret_cast<const float4*>(tab) + (int64_t)last * dv;
+  const float ir = inv[r];
+  float s = 0.f;
+  for (int v = 0; v < dv; ++v) {
+    const float4 x = xr[v];
+    s += dot4(xe[v], float4{x.x * ir, x.y * ir, x.z * ir, x.w * ir});
+  }
+  kth[r] = cos_dist(s, inv[last]);
+}
+
+// Phase A, d = 32 / 64: scan4's MFMA with the changed rows in the queries'
+// place.  A block owns UPD_RPB table rows; per tile of UPD_CT changed rows it
+// stages their bf16 B fragments in LDS in fragment order (entry (b, ks, lane)
+// is lane's 16 B: conflict-free ds_read_b128, as scan4's bqs), rounded from
+// the fp32 rows as pack_rows_kernel rounds them, then walks its rows in
+// 16-row A tiles (the packed copy, or fp32 rows scaled and rounded here).
+// Lane (c, g) of an accumulator holds rows 4 g + i against changed row
+// 16 b + c; a row passes when any c reaches its bound.  Hits are kept as a
+// bitmap of the block's rows in LDS and appended once at the end.
+template <int KS, bool PK>
+__global__ __launch_bounds__(256) void upd_filter4_kernel(const float* __restrict__ tab,
+                                                          const float* __restrict__ inv,
+                                                          const bf16* __restrict__ tb, int N,
+                                                          const int* __restrict__ chg, int m,
+                                                          const float* __restrict__ kth, int* aff, int* counts) {
+  constexpr int D = KS * 32;
+  __shared__ bf16x8 bqs[(UPD_CT / 16) * KS * 64];
+  __shared__ unsigned hit[UPD_RPB / 32];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int r16 = lane & 15, g = lane >> 4;
+  const int64_t r0 = (int64_t)blockIdx.x * UPD_RPB;
+  const int64_t r1 = min<int64_t>(N, r0 + UPD_RPB);
+  for (int i = threadIdx.x; i < UPD_RPB / 32; i += 256) hit[i] = 0;
+  for (int c0 = 0; c0 < m; c0 += UPD_CT) {
+    const int nc = min(UPD_CT, m - c0);
+    const int nb = (nc + 15) / 16;
+    __syncthreads();   // (the tile before is read out; hit[] is zeroed)
+    for (int e = threadIdx.x; e < nb * KS * 64; e += 256) {
+      const int l = e & 63, ks = (e >> 6) % KS, b = (e >> 6) / KS;
+      const int ci = 16 * b + (l & 15);
+      bf16x8 v = bf16x8{};
+      if (ci < nc) {
+        const int64_t c = chg[c0 + ci];
+        const float4* p = reinterpret_cast<const float4*>(tab + c * D + ks * 32 + 8 * (l >> 4));
+        const float4 lo = p[0], hi = p[1];
+        const float sc = inv[c];
+        v = bf16x8{(bf16)(lo.x * sc), (bf16)(lo.y * sc), (bf16)(lo.z * sc), (bf16)(lo.w * sc),
+                   (bf16)(hi.x * sc), (bf16)(hi.y * sc), (bf16)(hi.z * sc), (bf16)(hi.w * sc)};
+      }
+      bqs[e] = v;
+    }
+    __syncthreads();
+    for (int64_t base = r0 + 16 * w; base < r1; base += 64) {
+      const int64_t ra = base + r16 < r1 ? base + r16 : r0;
+      bf16x8 a[KS];
+      if constexpr (PK) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) a[ks] = *reinterpret_cast<const bf16x8*>(tb + ra * D + ks * 32 + 8 * g);
+      } else {
+        float4 x[KS][2];
+        v4_load_rows<KS>(tab, ra, x, g);
+        const float sc = inv[ra];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const float4 p = x[ks][0], v = x[ks][1];
+          a[ks] = bf16x8{(bf16)(p.x * sc), (bf16)(p.y * sc), (bf16)(p.z * sc), (bf16)(p.w * sc),
+                         (bf16)(v.x * sc), (bf16)(v.y * sc), (bf16)(v.z * sc), (bf16)(v.w * sc)};
+        }
+      }
+      // a row passes iff a coarse cosine is >= 1 - its bound (the 1e-6 covers
+      // the rounding of 1 - bound); skipped rows and rows past r1: 3, never
+      float th[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int64_t rr = base + 4 * g + i;
+        const float t = rr < r1 ? kth[rr] : UPD_NEVER;
+        th[i] = t < 0.f ? 3.f : (1.f - (t + V4_EPS + TH_MARGIN)) - 1e-6f;
+      }
+      bool pass[4] = {false, false, false, false};
+      for (int b = 0; b < nb; ++b) {
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks)
+          acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[ks], bqs[(b * KS + ks) * 64 + lane], acc, 0, 0, 0);
+        const bool valid = 16 * b + r16 < nc;   // (a padded column's cosine is 0)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) pass[i] = pass[i] || (valid && acc[i] >= th[i]);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const uint64_t mk = __ballot(pass[i]);
+        if (!mk) continue;
+        const int j = (int)(base + 4 * g + i - r0);   // (< UPD_RPB: a passing row lies under r1)
+        if (r16 == 0 && ((mk >> (16 * g)) & 0xffffull)) atomicOr(&hit[j >> 5], 1u << (j & 31));
+      }
+    }
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < UPD_RPB; j += 256)
+    if ((hit[j >> 5] >> (j & 31)) & 1u) aff[atomicAdd(&counts[1], 1)] = (int)(r0 + j);
+}
+
+// Phase A, every other width: one row per thread against tiles of UPD_XT
+// changed rows broadcast from LDS (uniform addresses), exact distances in
+// the merge's direction (query r, row c)
+__global__ __launch_bounds__(256) void upd_filter_exact_kernel(const float* __restrict__ tab,
+                                                               const float* __restrict__ inv, int N, int dv,
+                                                               const int* __restrict__ chg, int m,
+                                                               const float* __restrict__ kth, int* aff,
+                                                               int* counts) {
+  __shared__ float4 xc[UPD_XT * (UPD_DMAX / 4)];
+  __shared__ float ic[UPD_XT];
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const bool ok = r < N;
+  const float t = ok ? kth[r] : UPD_NEVER;
+  const bool active = t >= 0.f;
+  const float ir = ok ? inv[r] : 1.f;
+  const float4* xr = reinterpret_cast<const float4*>(tab) + (ok ? r : 0) * dv;
+  const float4* tab4 = reinterpret_cast<const float4*>(tab);
+  bool pass = false;
+  for (int c0 = 0; c0 < m; c0 += UPD_XT) {
+    const int nc = min(UPD_XT, m - c0);
+    __syncthreads();
+    for (int e = threadIdx.x; e < nc * dv; e += 256) xc[e] = tab4[(int64_t)chg[c0 + e / dv] * dv + e % dv];
+    if ((int)threadIdx.x < nc) ic[threadIdx.x] = inv[chg[c0 + threadIdx.x]];
+    __syncthreads();
+    if (!active || pass) continue;
+    float s[UPD_XT];
+#pragma unroll
+    for (int j = 0; j < UPD_XT; ++j) s[j] = 0.f;
+    for (int v = 0; v < dv; ++v) {
+      const float4 x = xr[v];
+      const float4 q = float4{x.x * ir, x.y * ir, x.z * ir, x.w * ir};
+#pragma unroll
+      for (int j = 0; j < UPD_XT; ++j)
+        if (j < nc) s[j] += dot4(xc[j * dv + v], q);
+    }
+#pragma unroll
+    for (int j = 0; j < UPD_XT; ++j)
+      if (j < nc) pass = pass || cos_dist(s[j], ic[j]) <= t + TH_MARGIN;
+  }
+  if (pass) aff[atomicAdd(&counts[1], 1)] = (int)r;
+}
+
+// Phase B: a workgroup per UPD_G affected rows (grid-stride over the list,
+// whose length only the device knows).  Per row r: the exact distances of
+// L(r) \ C and their largest key K' (a wave per row), then of every c in C,
+// those with key <= K' kept; with at least kt candidates the kt smallest by
+// (distance, row) are written into row r of the table, else r joins the
+// re-search list.  The changed rows are the expensive part -- m gathered rows
+// per affected row -- so a thread loads each chunk of a changed row once and
+// scores it against the UPD_G queries held in LDS (uniform addresses), each
+// query's sum in upd_row_dist's order.
+constexpr int UPD_G = 8;
+__global__ __launch_bounds__(NT) void upd_merge_kernel(const float* __restrict__ tab, const float* __restrict__ inv,
+                                                       int N, int d, int kt, const int* __restrict__ chg, int m,
+                                                       const unsigned* __restrict__ bits,
+                                                       const int* __restrict__ aff, int* nbr, int* research,
+                                                       int* counts) {
+  __shared__ __attribute__((aligned(16))) float qs[UPD_G][UPD_DMAX];
+  __shared__ float cd[UPD_G][UPD_CAP];
+  __shared__ int ci[UPD_G][UPD_CAP];
+  __shared__ int cnt[UPD_G], bad[UPD_G], ki[UPD_G], rowg[UPD_G];
+  __shared__ float kd[UPD_G];
+  const int na = counts[1];
+  const int dv = d >> 2;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const float4* tab4 = reinterpret_cast<const float4*>(tab);
+  for (int a0 = blockIdx.x * UPD_G; a0 < na; a0 += gridDim.x * UPD_G) {
+    const int ng = min(UPD_G, na - a0);
+    __syncthreads();   // (the rows before are done with the LDS words)
+    if (threadIdx.x < UPD_G) {
+      cnt[threadIdx.x] = 0;
+      bad[threadIdx.x] = 0;
+      rowg[threadIdx.x] = (int)threadIdx.x < ng ? aff[a0 + threadIdx.x] : 0;
+    }
+    __syncthreads();
+    for (int e = threadIdx.x; e < ng * d; e += NT) {
+      const int g = e / d, i = e % d, r = rowg[g];
+      qs[g][i] = tab[(int64_t)r * d + i] * inv[r];
+    }
+    __syncthreads();
+    for (int g = w; g < ng; g += NT / 64) {
+      if (lane < kt) {
+        const int e = nbr[(int64_t)rowg[g] * kt + lane];
+        if ((unsigned)e >= (unsigned)N) {
+          bad[g] = 1;
+        } else if (!upd_bit(bits, e)) {
+          const float dd = upd_row_dist(tab, inv, e, dv, reinterpret_cast<const float4*>(qs[g]));
+          const int pos = atomicAdd(&cnt[g], 1);
+          cd[g][pos] = dd;
+          ci[g][pos] = e;
+        }
+      }
+      // K': the largest key among them (the wave's own LDS writes, fenced as wave_compact's)
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+      const int nl = cnt[g];   // <= kt <= 64
+      float dd = lane < nl ? cd[g][lane] : -1.f;
+      int ii = lane < nl ? ci[g][lane] : 0;
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) {
+        const float od = __shfl_xor(dd, o, 64);
+        const int oi = __shfl_xor(ii, o, 64);
+        if (cless(dd, ii, od, oi)) { dd = od; ii = oi; }
+      }
+      if (lane == 0) {
+        kd[g] = dd;
+        ki[g] = ii;
+        if (nl == 0) bad[g] = 1;   // no entry outside C: searched again
+      }
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < m; j += NT) {
+      const int c = chg[j];
+      const float4* rp = tab4 + (int64_t)c * dv;
+      float s[UPD_G];
+#pragma unroll
+      for (int g = 0; g < UPD_G; ++g) s[g] = 0.f;
+      for (int v = 0; v < dv; ++v) {
+        const float4 x = rp[v];
+#pragma unroll
+        for (int g = 0; g < UPD_G; ++g) s[g] += dot4(x, reinterpret_cast<const float4*>(qs[g])[v]);
+      }
+      const float ic = inv[c];
+#pragma unroll
+      for (int g = 0; g < UPD_G; ++g) {
+        if (g >= ng || bad[g]) continue;   // (slots past ng hold another group's queries)
+        const float dd = cos_dist(s[g], ic);
+        if (!cless(kd[g], ki[g], dd, c)) {
+          const int pos = atomicAdd(&cnt[g], 1);
+          if (pos < UPD_CAP) { cd[g][pos] = dd; ci[g][pos] = c; }
+        }
+      }
+    }
+    __syncthreads();
+    // up to 64 candidates (the usual case): a wave per row sorts them in registers
+    for (int g = w; g < ng; g += NT / 64) {
+      const int T = cnt[g];
+      if (bad[g] || T < kt || T > 64) continue;
+      float dd = lane < T ? cd[g][lane] : FLT_MAX;
+      int ii = lane < T ? ci[g][lane] : INT_MAX;
+      wave_sort64(dd, ii, lane);
+      if (lane < kt) nbr[(int64_t)rowg[g] * kt + lane] = ii;
+      if (lane == 0) atomicAdd(&counts[2], 1);
+    }
+    // more: the block's bitonic sort, row by row; the rest joins the re-search list
+    for (int g = 0; g < ng; ++g) {
+      const int T = cnt[g];   // (block-uniform)
+      const bool redo = bad[g] || T < kt || T > UPD_CAP;
+      if (redo) {
+        if (threadIdx.x == 0) research[atomicAdd(&counts[3], 1)] = rowg[g];
+        continue;
+      }
+      if (T <= 64) continue;
+      int n2 = 128;
+      while (n2 < T) n2 <<= 1;
+      for (int t = T + threadIdx.x; t < n2; t += NT) { cd[g][t] = FLT_MAX; ci[g][t] = INT_MAX; }
+      __syncthreads();
+      bitonic<NT>(cd[g], ci[g], n2);
+      if ((int)threadIdx.x < kt) nbr[(int64_t)rowg[g] * kt + threadIdx.x] = ci[g][threadIdx.x];
+      if (threadIdx.x == 0) atomicAdd(&counts[2], 1);
+    }
+  }
+}
+
+// the four count words to the caller's pinned host words
+__global__ void upd_mirror_kernel(const int* counts, int* host_counts) {
+  if (threadIdx.x < 4)
+    __hip_atomic_store(host_counts + threadIdx.x, counts[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// Phase C: the listed rows as a chunk of queries, and the chunk's answers
+// into the listed table rows (a row id outside the table is read as row 0
+// and written nowhere)
+__global__ void upd_gather_kernel(const float* __restrict__ tab, int N, int d, const int* __restrict__ rows,
+                                  int64_t n, float* __restrict__ q) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n * d; e += (int64_t)gridDim.x * blockDim.x) {
+    const int r = rows[e / d];
+    q[e] = tab[(int64_t)((unsigned)r < (unsigned)N ? r : 0) * d + e % d];
+  }
+}
+__global__ void upd_scatter_kernel(const int64_t* __restrict__ idx, int64_t n, int k, int N,
+                                   const int* __restrict__ rows, int32_t* nbr) {
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n * k; e += (int64_t)gridDim.x * blockDim.x) {
+    const int r = rows[e / k];
+    if ((unsigned)r < (unsigned)N) nbr[(int64_t)r * k + e % k] = (int32_t)idx[e];
+  }
+}
+
+// One workspace for both calls: phases A + B carve chg [m] | the bitmap of C
+// | the rows' k-th distances [N] | the affected rows [N]; phase C a chunk of
+// gathered queries and the build's chunk scratch.
+struct UpdWs { int* chg; unsigned* bits; float* kth; int* aff; size_t ab_total;
+               float* q; NbrWs nbr; size_t c_total; };
+UpdWs carve_upd(void* ws, int64_t N, int d, int k, int64_t m) {
+  UpdWs w{};
+  Bump b(ws);
+  w.chg = (int*)b.take((size_t)std::max<int64_t>(m, 1) * 4);
+  w.bits = (unsigned*)b.take((size_t)cdiv(N, 32) * 4);
+  w.kth = (float*)b.take((size_t)N * 4);
+  w.aff = (int*)b.take((size_t)N * 4);
+  w.ab_total = b.off;
+  Bump c(ws);
+  w.q = (float*)c.take((size_t)NBR_CHUNK * d * 4);
+  const size_t q_end = rup((int64_t)c.off, 256);
+  w.nbr = carve_nbr(ws ? (char*)ws + q_end : nullptr, N, k);
+  w.c_total = q_end + w.nbr.total;
+  return w;
+}
+
+}  // namespace
+
+size_t neighbor_table_update_ws(int64_t N, int d, int k, int64_t m) {
+  const UpdWs w = carve_upd(nullptr, N, d, k, m);
+  return std::max(w.ab_total, w.c_total);
+}
+int neighbor_table_update_max_m() { return UPD_MAX_M; }
+
+dcnr_status neighbor_table_update(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
+                                  const int32_t* changed, int64_t m, int32_t* nbr, int32_t* counts,
+                                  int32_t* host_counts, int32_t* research, void* ws, size_t ws_bytes,
+                                  hipStream_t s) {
+  const UpdWs w = carve_upd(ws, N, d, k, m);
+  if (ws_bytes < std::max(w.ab_total, w.c_total)) {
+    set_error("neighbor_table_update: workspace too small");
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  DCNR_HIP(hipMemcpyAsync(w.chg, changed, (size_t)m * 4, hipMemcpyHostToDevice, s));
+  DCNR_HIP(hipMemsetAsync(w.bits, 0, (size_t)cdiv(N, 32) * 4, s));
+  hipLaunchKernelGGL(upd_mark_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, s, w.chg, (int)m, w.bits, research,
+                     counts);
+  DCNR_LAUNCH_CHECK();
+  const unsigned rb = (unsigned)cdiv(N, 256);
+  hipLaunchKernelGGL(upd_kth_kernel, dim3(rb), dim3(256), 0, s, t, inv, (int)N, d / 4, k, nbr, w.bits, w.kth, w.aff,
+                     counts);
+  DCNR_LAUNCH_CHECK();
+  if (d == 32 || d == 64) {
+    with_v4_rows(d, tb != nullptr, [&](auto ks, auto pk) {
+      hipLaunchKernelGGL((upd_filter4_kernel<decltype(ks)::value, decltype(pk)::value>),
+                         dim3((unsigned)cdiv(N, UPD_RPB)), dim3(256), 0, s, t, inv, tb, (int)N, w.chg, (int)m, w.kth,
+                         w.aff, counts);
+    });
+  } else {
+    hipLaunchKernelGGL(upd_filter_exact_kernel, dim3(rb), dim3(256), 0, s, t, inv, (int)N, d / 4, w.chg, (int)m, w.kth,
+                       w.aff, counts);
+  }
+  DCNR_LAUNCH_CHECK();
+  const unsigned mb = (unsigned)std::min<int64_t>(cdiv(N, UPD_G), 4096);
+  hipLaunchKernelGGL(upd_merge_kernel, dim3(mb), dim3(NT), 0, s, t, inv, (int)N, d, k, w.chg, (int)m, w.bits, w.aff, nbr,
+                     research, counts);
+  DCNR_LAUNCH_CHECK();
+  if (host_counts) {
+    hipLaunchKernelGGL(upd_mirror_kernel, dim3(1), dim3(64), 0, s, counts, host_counts);
+    DCNR_LAUNCH_CHECK();
+  }
+  return DCNR_OK;
+}
+
+dcnr_status neighbor_table_rows(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
+                                const int32_t* rows, int64_t n, int32_t* nbr, void* ws, size_t ws_bytes,
+                                hipStream_t s) {
+  const UpdWs w = carve_upd(ws, N, d, k, 0);
+  if (ws_bytes < w.c_total) {
+    set_error("neighbor_table_rows: workspace too small");
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  for (int64_t lo = 0; lo < n; lo += NBR_CHUNK) {
+    const int64_t Q = std::min(NBR_CHUNK, n - lo);
+    hipLaunchKernelGGL(upd_gather_kernel, dim3((unsigned)cdiv(Q * d, 256)), dim3(256), 0, s, t, (int)N, d, rows + lo, Q,
+                       w.q);
+    DCNR_LAUNCH_CHECK();
+    TRY_ST(cosine_topk(t, inv, tb, N, d, w.q, Q, k, w.nbr.idx, w.nbr.dist, w.nbr.topk, w.nbr.topk_bytes, s,
+                       /*allow_v3=*/false));
+    hipLaunchKernelGGL(upd_scatter_kernel, dim3((unsigned)cdiv(Q * k, 256)), dim3(256), 0, s, w.nbr.idx, Q, k, (int)N,
+                       rows + lo, nbr);
+    DCNR_LAUNCH_CHECK();
+  }
+  return DCNR_OK;
+}
+
 dcnr_status topk_merge(const float* dist, const int64_t* idx, int lists, int64_t Q, int k,
                        int64_t* out_idx, float* out_dist, hipStream_t s) {
   if (k < 1 || lists < 1 || (int64_t)lists * k > TM_CAP) {

@@ -25,6 +25,8 @@ from . import _lib
 # rows get the fit-time bf16 copy
 PACKED_D = (32, 64)
 PACKED_MIN_ROWS = 32768
+# changed rows one dcnr_cosine_neighbor_table_update call takes (knn.hip UPD_MAX_M)
+UPDATE_MAX_ROWS = 16384
 
 
 class NearestNeighbors:
@@ -42,6 +44,7 @@ class NearestNeighbors:
         self._inv = None
         self._packed = None
         self.neighbor_table_ = None
+        self._pin = None   # update_rows' pinned count words
 
     def fit(self, X, y=None):
         t = torch.as_tensor(np.asarray(X, dtype=np.float32) if not torch.is_tensor(X) else X)
@@ -126,6 +129,154 @@ class NearestNeighbors:
             self.neighbor_table_ = nbr
         return (dist, nbr) if return_distance else nbr
 
+    def update_rows(self, rows, vectors=None, table=None, return_stats=False, rebuild=None):
+        """New vectors for some rows of the fitted table, with everything
+        derived from it brought back to exactly what ``fit`` +
+        ``build_neighbor_table`` give on the new table: ``_inv``, ``_packed``
+        and the neighbour table, the work growing with the number of rows.
+
+        rows     distinct row ids inside [0, N) (ValueError otherwise, nothing
+                 changed); none at all is a no-op
+        vectors  [m, d], written into the table; None: those rows of the
+                 fitted table were already modified in place (a pipeline's
+                 index shares the model's item table when that is fp32 on the
+                 device: ``fit`` does not copy it)
+        table    int32 [N, kt] on the device, contiguous, updated in place;
+                 default ``neighbor_table_``; with neither only the norms and
+                 the packed copy are refreshed
+        rebuild  None: the range build takes over from the incremental update
+                 where that is estimated at half a rebuild or more
+                 (``rebuild_is_cheaper``); True / False force either path
+                 (the result is the same)
+
+        Precondition: ``table`` was exact for the embeddings before the
+        change -- built from them, or updated through here ever since.  More
+        rows than one native call takes (UPDATE_MAX_ROWS) are applied as
+        consecutive changes (written in place already, they are rebuilt: the
+        vectors in between are gone).  Ordered on the current stream, with one
+        host wait (for the number of rows to search again); not safe against
+        requests in flight on other streams.  ``return_stats``: a dict of the
+        rows changed / affected / merged / searched again (read back only
+        then; ``rebuilt`` when the range build ran)."""
+        if self._table is None:
+            raise RuntimeError("This NearestNeighbors instance is not fitted yet")
+        N, d = self._table.shape
+        r = np.asarray(rows.cpu() if torch.is_tensor(rows) else rows).reshape(-1)
+        if r.size and not np.issubdtype(r.dtype, np.integer):
+            raise ValueError("update_rows: rows must be integers")
+        r = r.astype(np.int64)
+        if r.size and (r.min() < 0 or r.max() >= N):
+            raise ValueError(f"update_rows: rows outside [0, {N})")
+        order = np.argsort(r, kind="stable")
+        r = r[order]
+        if np.any(r[1:] == r[:-1]):
+            raise ValueError("update_rows: duplicate rows")
+        if vectors is not None:
+            v = torch.as_tensor(np.asarray(vectors, dtype=np.float32)) if not torch.is_tensor(vectors) \
+                else vectors
+            v = v.to(self.device, torch.float32).reshape(-1, d)
+            if v.shape[0] != r.size:
+                raise ValueError(f"update_rows: {r.size} rows, {v.shape[0]} vectors")
+            v = v[torch.from_numpy(order).to(self.device)]
+        table = self.neighbor_table_ if table is None else table
+        if table is not None:
+            if (not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 2
+                    or table.shape[0] != N or not 1 <= table.shape[1] <= N
+                    or table.device != self._table.device or not table.is_contiguous()):
+                raise ValueError(f"update_rows: table must be a contiguous int32 [{N}, kt] tensor on "
+                                 f"{self._table.device}")
+        stats = dict(changed=int(r.size), affected=0, merged=0, researched=0, rebuilt=False)
+        m = int(r.size)
+        if m == 0:
+            return stats if return_stats else None
+        kt = table.shape[1] if table is not None else 0
+        full = table is not None and (bool(rebuild) if rebuild is not None
+                                      else rebuild_is_cheaper(m, kt, N))
+        if table is not None and not full and vectors is None and m > UPDATE_MAX_ROWS:
+            full = True
+        if table is None or full:
+            self._refresh_rows(r, None if vectors is None else v)
+            if full:
+                self._build_into(table)
+                stats.update(rebuilt=True, researched=N)
+        else:
+            for lo in range(0, m, UPDATE_MAX_ROWS):
+                hi = min(m, lo + UPDATE_MAX_ROWS)
+                self._refresh_rows(r[lo:hi], None if vectors is None else v[lo:hi])
+                c = self._update_table(r[lo:hi], table, return_stats)
+                if return_stats:
+                    stats["affected"] += c[1]
+                    stats["merged"] += c[2]
+                    stats["researched"] += c[3]
+        return stats if return_stats else None
+
+    def _refresh_rows(self, r, v):
+        """Writes v (or nothing) into rows r of the table and recomputes their
+        inverse norms and packed rows with the fit's kernels on the gathered
+        rows (each row's bits depend on that row alone)."""
+        lib = _lib.load()
+        d = self._table.shape[1]
+        sel = torch.from_numpy(r).to(self.device)
+        if v is not None:
+            self._table[sel] = v
+        g = self._table[sel].contiguous()
+        inv = torch.empty(r.size, dtype=torch.float32, device=self.device)
+        stream = _lib.stream_ptr(self.device)
+        _lib.check(lib.dcnr_row_inv_norms(g.data_ptr(), r.size, d, inv.data_ptr(), stream),
+                   "dcnr_row_inv_norms")
+        self._inv[sel] = inv
+        if self._packed is not None:
+            pk = torch.empty((r.size, d), dtype=torch.int16, device=self.device)
+            _lib.check(lib.dcnr_cosine_pack_rows(g.data_ptr(), inv.data_ptr(), r.size, d, pk.data_ptr(),
+                                                 stream), "dcnr_cosine_pack_rows")
+            self._packed[sel] = pk
+
+    def _build_into(self, table):
+        """The range build of every row, written over ``table``."""
+        lib = _lib.load()
+        N, d = self._table.shape
+        kt = table.shape[1]
+        nb = int(lib.dcnr_cosine_neighbor_table_workspace_size(N, kt))
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=self.device)
+        packed = self._packed.data_ptr() if self._packed is not None else None
+        _lib.check(lib.dcnr_cosine_neighbor_table(self._table.data_ptr(), self._inv.data_ptr(), packed,
+                                                  N, d, kt, 0, N, table.data_ptr(), None, ws.data_ptr(),
+                                                  ws.numel(), _lib.stream_ptr(self.device)),
+                   "dcnr_cosine_neighbor_table")
+
+    def _update_table(self, r, table, want_counts, events=None):
+        """One native update of the sorted rows r (norms and packed rows
+        already new): filter and merge, the one wait, the re-search.  Returns
+        the four counts (the pinned mirror's) when asked.  ``events``: two
+        torch events, recorded behind the first call and behind the second
+        (tools/bench_neighbor_update.py)."""
+        lib = _lib.load()
+        N, d = self._table.shape
+        kt, m = table.shape[1], int(r.size)
+        changed = np.ascontiguousarray(r, dtype=np.int32)
+        nb = int(lib.dcnr_cosine_neighbor_table_update_workspace_size(N, d, kt, m))
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=self.device)
+        counts = torch.empty(4, dtype=torch.int32, device=self.device)
+        research = torch.empty(N, dtype=torch.int32, device=self.device)
+        if self._pin is None:
+            self._pin = torch.zeros(4, dtype=torch.int32).pin_memory()
+        packed = self._packed.data_ptr() if self._packed is not None else None
+        stream = _lib.stream_ptr(self.device)
+        _lib.check(lib.dcnr_cosine_neighbor_table_update(
+            self._table.data_ptr(), self._inv.data_ptr(), packed, N, d, kt, changed.ctypes.data, m,
+            table.data_ptr(), counts.data_ptr(), self._pin.data_ptr(), research.data_ptr(), ws.data_ptr(),
+            ws.numel(), stream), "dcnr_cosine_neighbor_table_update")
+        if events:
+            events[0].record()
+        torch.cuda.current_stream(self.device).synchronize()   # the update's one wait
+        c = self._pin.tolist()
+        _lib.check(lib.dcnr_cosine_neighbor_table_rows(
+            self._table.data_ptr(), self._inv.data_ptr(), packed, N, d, kt, research.data_ptr(), c[3],
+            table.data_ptr(), ws.data_ptr(), ws.numel(), stream), "dcnr_cosine_neighbor_table_rows")
+        if events:
+            events[1].record()
+        return c if want_counts else None
+
     def kneighbors(self, X=None, n_neighbors=None, return_distance=True):
         k = self.n_neighbors if n_neighbors is None else int(n_neighbors)
         if k <= 0:
@@ -139,6 +290,24 @@ class NearestNeighbors:
         if return_distance:
             return dist.cpu().numpy(), idx_np
         return idx_np
+
+
+def rebuild_is_cheaper(m: int, kt: int, N: int) -> bool:
+    """update_rows' fallback point, in pair distances against the rebuild's
+    N^2.  About m (kt + 1) rows are searched again as the build searches them
+    (the changed rows and the lists a changed row left a hole in: m N (kt + 1)
+    pairs).  Before that the merge takes m distances for each of about
+    2 m (kt + 1) affected rows, at 29 times the scan's cost per pair
+    (measured at 1M x 64, k = 11: 47.5 ms at m = 16384 against the rebuild's
+    254 ms) -- counted above m = 1024, under which the
+    merge stays below a millisecond.  The rebuild runs when the estimate
+    reaches half of it: m >= 19.5 k at 1M rows, k = 11 (measured there: the
+    update is 2.9 times faster than the rebuild at m = 16384, one native
+    call's limit; the model puts the crossover near 30 k)."""
+    pairs = m * N * (kt + 1)
+    if m > 1024:
+        pairs += 58 * (kt + 1) * m * m
+    return 2 * pairs >= N * N
 
 
 def index_shard(n: int, rank: int, world: int):

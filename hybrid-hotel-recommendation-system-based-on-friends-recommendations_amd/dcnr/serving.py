@@ -231,6 +231,30 @@ class RankingPipeline:
                              f"{str(t.dtype).replace('torch.', '')} {list(t.shape)}")
         return t.to(self.device).contiguous()
 
+    def update_item_embeddings(self, rows, vectors, update_model: bool = True, return_stats=False):
+        """New embeddings for some hotels: ``index.update_rows`` on the
+        index's table, norms, packed copy and the neighbour table this
+        pipeline serves from, all as a pipeline built fresh on the new
+        embeddings would hold them.  The index's table IS the model's item
+        table when that was fp32 on the device at construction (``fit`` does
+        not copy it), and the one write serves both; otherwise, with
+        ``update_model``, the same rows of ``model.item_embedding`` are
+        written too (a pipeline built on ``item_embeddings`` of another shape
+        than the model's table leaves the model alone).  Ordered on the
+        current stream; not safe against requests in flight on other
+        streams."""
+        out = self.index.update_rows(rows, vectors, table=self._nbr, return_stats=return_stats)
+        w = self.model.item_embedding.weight
+        t = self.index._table
+        if update_model and w.data_ptr() != t.data_ptr() and w.shape == t.shape:
+            r = torch.as_tensor(np.asarray(rows.cpu() if torch.is_tensor(rows) else rows).reshape(-1),
+                                dtype=torch.int64, device=w.device)
+            v = torch.as_tensor(np.asarray(vectors, dtype=np.float32)) if not torch.is_tensor(vectors) \
+                else vectors
+            with torch.no_grad():
+                w[r] = v.to(w.device, w.dtype).reshape(-1, w.shape[1])
+        return out
+
     # ---------------------------------------------------------- /similar_items
     def similar_items(self, item_row: int, n: int = 10) -> torch.Tensor:
         """main.py:294-303: the n nearest hotels, the hotel itself dropped

@@ -436,6 +436,47 @@ dcnr_status dcnr_cosine_neighbor_table(const float* table, const float* inv_norm
                                        int32_t* out_idx, float* out_dist, void* ws, size_t ws_bytes,
                                        dcnr_stream_t stream);
 
+/* The item neighbour table brought up to date, in place, after m rows of
+ * the fitted table got new vectors -- `table`, `inv_norms` and `packed` (or
+ * NULL) already hold them (dcnr_row_inv_norms / dcnr_cosine_pack_rows over the
+ * changed rows give the refit's bits).  Precondition: nbr int32 [N][k] was
+ * exact for the table before the change.  Afterwards every row of nbr is what
+ * dcnr_cosine_neighbor_table builds from the new table, bit for bit, with work
+ * that grows with m: two calls, stream-ordered, no host synchronisation
+ * inside either, and one wait of the caller's between them.
+ *
+ * _update (phases A + B): `changed` is a HOST array int32 [m], ascending,
+ * distinct, inside [0, N), m <= 16384 per call (DCNR_UNSUPPORTED_SHAPE above;
+ * a larger set is applied as consecutive changes).  One pass over the table
+ * finds the rows a change can reach (a changed row in their list, or a
+ * changed row at or under their k-th distance: a superset); each of those
+ * merges its unchanged entries with the changed rows and either rewrites its
+ * own list or joins the re-search list.  counts (device int32 [4]): changed,
+ * affected, merged, to re-search; host_counts (or NULL): the same four words
+ * stored to pinned host memory when the call's work is done.  research_rows
+ * (device int32 [N]): the first counts[3] entries are the rows to search
+ * again, the changed rows among them.
+ *
+ * _rows (phase C): the lists of rows[n] (device int32; a row outside [0, N)
+ * is skipped) searched as the build searches them and written to those rows
+ * of nbr.  n is the host's copy of counts[3].
+ *
+ * Both take `ws` of dcnr_cosine_neighbor_table_update_workspace_size(N, d, k,
+ * m) bytes (exact; DCNR_WORKSPACE_TOO_SMALL below it; _rows needs the m = 0
+ * size at most).  Shapes as dcnr_cosine_neighbor_table, and d % 4 == 0,
+ * 4 <= d <= 256.  m == 0 / n == 0 return DCNR_OK without a launch.  A null
+ * pointer, m < 0, k outside [1, N], or `changed` not ascending, distinct and
+ * in range: DCNR_BAD_ARG, judged on the host before anything is launched. */
+size_t dcnr_cosine_neighbor_table_update_workspace_size(int64_t N, int32_t d, int32_t k, int64_t m);
+dcnr_status dcnr_cosine_neighbor_table_update(const float* table, const float* inv_norms, const uint16_t* packed,
+                                              int64_t N, int32_t d, int32_t k, const int32_t* changed, int64_t m,
+                                              int32_t* nbr, int32_t* counts, int32_t* host_counts,
+                                              int32_t* research_rows, void* ws, size_t ws_bytes,
+                                              dcnr_stream_t stream);
+dcnr_status dcnr_cosine_neighbor_table_rows(const float* table, const float* inv_norms, const uint16_t* packed,
+                                            int64_t N, int32_t d, int32_t k, const int32_t* rows, int64_t n,
+                                            int32_t* nbr, void* ws, size_t ws_bytes, dcnr_stream_t stream);
+
 /* Merge of row-sharded top-k lists (the cfg5 index split over ranks, SURVEY
  * 8(e)): dist fp32 / idx int64 [lists][Q][k] (global rows; padding entries
  * (FLT_MAX, -1) sort last) -> the k best per query, ascending by (dist, row),
