@@ -2023,6 +2023,46 @@ dcnr_status dcnr_eval_metrics(const float* logits, const float* labels, int64_t 
   return DCNR_OK;
 }
 
+static bool group_metrics_sizes_ok(int64_t n, int64_t n_groups) {
+  return n >= 0 && n < ((int64_t)1 << 31) && n_groups >= 1 && n_groups <= ((int64_t)1 << 31) - 1;
+}
+
+size_t dcnr_eval_group_metrics_workspace_size(int64_t n, int64_t n_groups) {
+  return group_metrics_sizes_ok(n, n_groups) ? group_metrics_ws_bytes(n, n_groups) : 0;
+}
+
+dcnr_status dcnr_eval_group_metrics(const float* logits, const float* labels, const int64_t* groups,
+                                    int64_t n, int64_t n_groups, const int32_t* ks, int32_t n_k,
+                                    const double* discount, const double* ideal,
+                                    dcnr_group_summary* out, dcnr_group_record* per_group, void* ws,
+                                    size_t ws_bytes, dcnr_stream_t stream) {
+  bool ok = group_metrics_sizes_ok(n, n_groups) && out && n_k >= 0 && n_k <= DCNR_GROUP_MAX_K &&
+            (n == 0 || (logits && labels && groups)) && (n_k == 0 || (ks && discount && ideal));
+  for (int j = 0; ok && j < n_k; ++j)
+    ok = ks[j] >= 1 && ks[j] <= (1 << 20) && (j == 0 || ks[j] > ks[j - 1]);
+  if (!ok) {
+    set_error("dcnr_eval_group_metrics: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  const size_t need = group_metrics_ws_bytes(n, n_groups);
+  if (ws_bytes < need) {
+    set_error("dcnr_eval_group_metrics: workspace too small: %zu < %zu", ws_bytes, need);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  if (need && !ws) {
+    set_error("dcnr_eval_group_metrics: null workspace");
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // algorithmic bytes: the inputs once, the keys written and read once per sort pass
+  // and read by the two walks
+  const double passes = (double)group_metrics_passes(n_groups);
+  TRYB(DCNR_K_HEAD, s, 16.0 * (double)n + (passes + 1.0) * 16.0 * (double)n,
+       eval_group_metrics(logits, labels, groups, n, n_groups, ks, n_k, discount, ideal, out,
+                          per_group, ws, s));
+  return DCNR_OK;
+}
+
 dcnr_status dcnr_adam_step(int32_t n_tensors, float* const* params, const float* const* grads,
                            float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
                            float lr, float beta1, float beta2, float eps, float weight_decay,

@@ -763,6 +763,13 @@ dcnr_status bce(const float* z, const float* y, int64_t B, float* loss, float* d
 size_t metrics_ws_bytes(int64_t n);
 dcnr_status eval_metrics(const float* z, const float* y, int64_t n, dcnr_metrics* out, void* ws,
                          hipStream_t s);
+// per-group ranking metrics (metrics.hip): arguments checked by the caller
+int group_metrics_passes(int64_t n_groups);
+size_t group_metrics_ws_bytes(int64_t n, int64_t n_groups);
+dcnr_status eval_group_metrics(const float* z, const float* y, const int64_t* g, int64_t n,
+                               int64_t n_groups, const int32_t* ks_host, int32_t n_k,
+                               const double* discount, const double* ideal, dcnr_group_summary* out,
+                               dcnr_group_record* per_group, void* ws, hipStream_t s);
 
 // optimizer
 dcnr_status adam(int n, float* const* p, const float* const* g, float* const* m, float* const* v,

@@ -461,4 +461,610 @@ dcnr_status eval_metrics(const float* z, const float* y, int64_t n, dcnr_metrics
   return DCNR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Per-group ranking metrics (dcnr_eval_group_metrics): GAUC, NDCG@k, hit
+// rate / recall@k and MRR of every group's list in the order the service
+// shows it (descending logit, ties by input position).
+//
+//   pass 1   one 64-bit key per row, group << 33 | ~orderable(z) << 1 | is_pos
+//            (an id outside [0, n_groups) takes the group 2^31 - 1, which no
+//            valid row has), the three counters, the digit histograms
+//   sort     the same radix sort on bits 1 and up, npass = ceil((32 +
+//            bits(n_groups - 1)) / 11) passes: groups become contiguous, each
+//            in served order (stable: ties keep input order, the label bit
+//            rides along unsorted)
+//   heads    per tile: its positives, its last group head and last tie head
+//            with the positives before them; one block turns these into what
+//            each tile needs of the rows before it
+//   walk     per row, from prefixes at the row, at its tie head T and at its
+//            group head G (PB = positives before):
+//              rank r = i - G + 1
+//              2U part of a positive  = negatives in [T, i)
+//              2U part of a negative  = positives in [G, i) + positives in [G, T)
+//            (a tied pair counts once, at whichever comes later; a pair whose
+//            positive scores higher counts twice, at the negative), the first
+//            positive's rank, hits and discount[r - 1] per cutoff.  A wave sums
+//            these per group with a segmented scan; a group inside one wave's
+//            64 rows is finished by its last lane, a group that crosses waves
+//            by thread 0 from the waves' first and last partial sums, a group
+//            that crosses tiles by the close kernel from the tiles' partials
+//            (one wave per tile, 64 following tiles a step).  No group is
+//            walked by one wave: a group of all n rows is n / 64 wave steps
+//            spread over every tile like any other input.
+//   final    fixed-order sums of the per-tile partial means
+//
+// Every fp64 sum (a group's DCG, the means) is taken in an order fixed by
+// where the group boundaries fall in the sorted array: no floating-point
+// atomics, the same input gives the same bits.
+namespace {
+
+constexpr int GK = 4;                                      // cutoffs
+constexpr int G_MAXPASS = (64 - 1 + RBITS - 1) / RBITS;    // 6: bits 1..63
+constexpr int GW_NT = AUC_NT, GW_WAVES = AUC_WAVES;
+constexpr uint64_t G_SENTINEL = 0x7FFFFFFFull;
+
+struct GKs { int k[GK]; int nk; };
+
+// sums over some rows of one group
+struct GSum {
+  long long c, fpr;              // 2U part, rank of the first positive (one row has it)
+  unsigned long long hA, hB;     // hits[0] | hits[1] << 32, hits[2] | hits[3] << 32 (each <= 2^20)
+  double d[GK];
+};
+__device__ __forceinline__ GSum gsum_zero() { return GSum{0, 0, 0ull, 0ull, {0.0, 0.0, 0.0, 0.0}}; }
+__device__ __forceinline__ void gsum_add(GSum& a, const GSum& b) {   // a's rows come first
+  a.c += b.c; a.fpr += b.fpr; a.hA += b.hA; a.hB += b.hB;
+#pragma unroll
+  for (int j = 0; j < GK; ++j) a.d[j] += b.d[j];
+}
+
+// a tile's open ends: the rows before its first group head (they belong to a
+// group that began in an earlier tile) and the rows from its last head on
+struct GTile {
+  GSum head, tail;
+  long long has_head;
+  long long first_g, first_pb;   // index of the first head, positives before it
+  long long tail_g, tail_pb;     // index of the last head, positives before it
+};
+
+// partial sums of the summary over finished groups
+struct GAcc {
+  long long present, nauc, ranked, rows_auc, hitg[GK];
+  double gauc, macro, mrr, recall[GK], ndcg[GK];
+};
+__device__ __forceinline__ GAcc gacc_zero() {
+  GAcc a;
+  a.present = a.nauc = a.ranked = a.rows_auc = 0;
+  a.gauc = a.macro = a.mrr = 0.0;
+#pragma unroll
+  for (int j = 0; j < GK; ++j) { a.hitg[j] = 0; a.recall[j] = 0.0; a.ndcg[j] = 0.0; }
+  return a;
+}
+__device__ __forceinline__ void gacc_add(GAcc& a, const GAcc& b) {
+  a.present += b.present; a.nauc += b.nauc; a.ranked += b.ranked; a.rows_auc += b.rows_auc;
+  a.gauc += b.gauc; a.macro += b.macro; a.mrr += b.mrr;
+#pragma unroll
+  for (int j = 0; j < GK; ++j) { a.hitg[j] += b.hitg[j]; a.recall[j] += b.recall[j]; a.ndcg[j] += b.ndcg[j]; }
+}
+__device__ __forceinline__ void gacc_wave_sum(GAcc& a) {
+  a.present = wave_sum_i64(a.present); a.nauc = wave_sum_i64(a.nauc);
+  a.ranked = wave_sum_i64(a.ranked); a.rows_auc = wave_sum_i64(a.rows_auc);
+  a.gauc = wave_sum_f64(a.gauc); a.macro = wave_sum_f64(a.macro); a.mrr = wave_sum_f64(a.mrr);
+#pragma unroll
+  for (int j = 0; j < GK; ++j) {
+    a.hitg[j] = wave_sum_i64(a.hitg[j]);
+    a.recall[j] = wave_sum_f64(a.recall[j]);
+    a.ndcg[j] = wave_sum_f64(a.ndcg[j]);
+  }
+}
+
+int group_passes(int64_t n_groups) {
+  int bits = 0;
+  for (uint64_t v = (uint64_t)(n_groups - 1); v; v >>= 1) ++bits;
+  return (32 + bits + RBITS - 1) / RBITS;
+}
+
+struct GWs {
+  uint64_t *ka, *kb;             // [n] key ping-pong
+  uint32_t* tot;                 // [npass][NB] digit totals, then the 3 counters (4 x 8 B)
+  uint32_t* counts;              // [units][NB]
+  long long* tsum;               // [tiles][5] positives, last group head, positives before it in
+                                 //            the tile, last tie head, positives before it (-1: none)
+  long long* tcarry;             // [tiles][5] the same at the tile's first row, absolute
+  GTile* tile;                   // [tiles]
+  GAcc* part;                    // [2][tiles] of the walk, of the close
+  size_t total;
+};
+
+size_t gtot_bytes(int npass) { return (size_t)npass * NB * 4 + 32; }
+
+GWs gcarve(const Plan& p, int npass, int64_t n, void* base) {
+  Bump b(base);
+  GWs w;
+  w.ka = (uint64_t*)b.take((size_t)n * 8);
+  w.kb = (uint64_t*)b.take((size_t)n * 8);
+  w.tot = (uint32_t*)b.take(gtot_bytes(npass));
+  w.counts = (uint32_t*)b.take((size_t)p.units * NB * 4);
+  w.tsum = (long long*)b.take((size_t)p.auc_blocks * 40);
+  w.tcarry = (long long*)b.take((size_t)p.auc_blocks * 40);
+  w.tile = (GTile*)b.take((size_t)p.auc_blocks * sizeof(GTile));
+  w.part = (GAcc*)b.take((size_t)2 * p.auc_blocks * sizeof(GAcc));
+  w.total = b.off;
+  return w;
+}
+
+__global__ __launch_bounds__(P1_NT) void group_pass1_kernel(const float* z, const float* y,
+                                                            const int64_t* g, int64_t n,
+                                                            int64_t n_groups, int npass, uint64_t* keys,
+                                                            uint32_t* tot) {
+  __shared__ uint32_t h[G_MAXPASS * NB];
+  __shared__ unsigned long long cnt[3];
+  const int tid = threadIdx.x;
+  for (int j = tid; j < npass * NB; j += P1_NT) h[j] = 0u;
+  if (tid < 3) cnt[tid] = 0ull;
+  __syncthreads();
+  int nbad = 0, nnan = 0, nbadg = 0;
+  for (int64_t i = (int64_t)blockIdx.x * P1_NT + tid; i < n; i += (int64_t)gridDim.x * P1_NT) {
+    const float zz = z[i], yy = y[i];
+    const int64_t gg = g[i];
+    const bool pos = yy == 1.0f;
+    const bool gok = gg >= 0 && gg < n_groups;
+    nbad += !(pos || yy == 0.0f);
+    nnan += zz != zz;
+    nbadg += !gok;
+    // descending score: the complement of the ascending 32-bit field
+    const uint64_t asc = make_key(zz, false) >> 1;
+    const uint64_t key = ((gok ? (uint64_t)gg : G_SENTINEL) << 33) | ((~asc & 0xFFFFFFFFull) << 1) |
+                         (pos ? 1ull : 0ull);
+    keys[i] = key;
+    for (int ps = 0; ps < npass; ++ps)
+      atomicAdd(&h[ps * NB + (int)((key >> (1 + ps * RBITS)) & (NB - 1))], 1u);
+  }
+  if (nbad) atomicAdd(&cnt[0], (unsigned long long)nbad);
+  if (nnan) atomicAdd(&cnt[1], (unsigned long long)nnan);
+  if (nbadg) atomicAdd(&cnt[2], (unsigned long long)nbadg);
+  __syncthreads();
+  for (int j = tid; j < npass * NB; j += P1_NT) {
+    const uint32_t c = h[j];
+    if (c) atomicAdd(&tot[j], c);   // integer: any order, same sum
+  }
+  unsigned long long* gc = (unsigned long long*)(tot + (size_t)npass * NB);
+  if (tid < 3 && cnt[tid]) atomicAdd(&gc[tid], cnt[tid]);
+}
+
+// tsum[b] of one tile of the sorted keys
+__global__ __launch_bounds__(GW_NT) void group_heads_kernel(const uint64_t* k, int64_t n, int64_t tile,
+                                                            long long* tsum) {
+  __shared__ int lastg, lastt;          // offsets in the tile, -1: none
+  __shared__ int np, npg, npt;
+  const int tid = threadIdx.x;
+  const int64_t lo = (int64_t)blockIdx.x * tile, hi = min(n, lo + tile);
+  if (tid == 0) { lastg = -1; lastt = -1; np = 0; npg = 0; npt = 0; }
+  __syncthreads();
+  int mg = -1, mt = -1;
+  for (int64_t i = lo + tid; i < hi; i += GW_NT) {
+    const uint64_t key = k[i], prev = i > 0 ? k[i - 1] : 0ull;
+    if (i == 0 || (key >> 33) != (prev >> 33)) mg = (int)(i - lo);
+    if (i == 0 || (key >> 1) != (prev >> 1)) mt = (int)(i - lo);
+  }
+  if (mg >= 0) atomicMax(&lastg, mg);
+  if (mt >= 0) atomicMax(&lastt, mt);
+  __syncthreads();
+  const int lg = lastg, lt = lastt;
+  int a = 0, ag = 0, at = 0;
+  for (int64_t i = lo + tid; i < hi; i += GW_NT) {
+    const int pos = (int)(k[i] & 1ull), off = (int)(i - lo);
+    a += pos;
+    ag += pos && off < lg;
+    at += pos && off < lt;
+  }
+  if (a) atomicAdd(&np, a);
+  if (ag) atomicAdd(&npg, ag);
+  if (at) atomicAdd(&npt, at);
+  __syncthreads();
+  if (tid == 0) {
+    long long* o = tsum + 5 * (int64_t)blockIdx.x;
+    o[0] = np;
+    o[1] = lg >= 0 ? lo + lg : -1ll;
+    o[2] = lg >= 0 ? npg : -1ll;
+    o[3] = lt >= 0 ? lo + lt : -1ll;
+    o[4] = lt >= 0 ? npt : -1ll;
+  }
+}
+
+// tcarry[b] = (positives before tile b; the last group head before it and
+// the positives before that head; the same for the last tie head): an
+// exclusive sum and four running maxima (a later head has the larger index
+// and no fewer positives before it).  nb <= AUC_MAXB tiles, one block.
+__global__ __launch_bounds__(AUC_MAXB) void group_carry_kernel(const long long* tsum, int nb,
+                                                               long long* tcarry) {
+  __shared__ long long a[AUC_MAXB], m[AUC_MAXB];
+  const int t = threadIdx.x;
+  const long long own = t < nb ? tsum[5 * t] : 0ll;
+  a[t] = own;
+  __syncthreads();
+  for (int o = 1; o < AUC_MAXB; o <<= 1) {
+    const long long v = t >= o ? a[t - o] : 0ll;
+    __syncthreads();
+    a[t] += v;
+    __syncthreads();
+  }
+  const long long P = a[t] - own;
+  if (t < nb) tcarry[5 * t] = P;
+  for (int f = 1; f < 5; ++f) {
+    const long long v0 = t < nb ? tsum[5 * t + f] : -1ll;
+    // indices (f odd) are absolute already, counts are relative to the tile
+    m[t] = v0 < 0 ? -1ll : ((f & 1) ? v0 : P + v0);
+    __syncthreads();
+    for (int o = 1; o < AUC_MAXB; o <<= 1) {
+      const long long v = t >= o ? m[t - o] : -1ll;
+      __syncthreads();
+      m[t] = max(m[t], v);
+      __syncthreads();
+    }
+    if (t < nb) tcarry[5 * t + f] = t > 0 ? m[t - 1] : -1ll;
+    __syncthreads();
+  }
+}
+
+// The finished group whose rows are [G, E) of the sorted keys, PBG / PBE
+// positives before them: its record and its terms of the summary.
+__device__ __forceinline__ void group_finish(const GSum& s, long long G, long long PBG, long long E,
+                                             long long PBE, const uint64_t* k, int64_t n_groups,
+                                             const GKs& ks, const double* ideal,
+                                             dcnr_group_record* per_group, GAcc& acc) {
+  const uint64_t gid = k[G] >> 33;
+  if (gid >= (uint64_t)n_groups) return;   // rows whose id was out of range
+  const long long nu = E - G, P = PBE - PBG, N = nu - P;
+  const long long hits[GK] = {(long long)(s.hA & 0xFFFFFFFFull), (long long)(s.hA >> 32),
+                              (long long)(s.hB & 0xFFFFFFFFull), (long long)(s.hB >> 32)};
+  if (per_group) {
+    dcnr_group_record r;
+    r.n = nu; r.n_pos = P; r.auc_u2 = s.c; r.first_pos_rank = s.fpr;
+#pragma unroll
+    for (int j = 0; j < GK; ++j) { r.hits[j] = hits[j]; r.dcg[j] = s.d[j]; }
+    per_group[gid] = r;
+  }
+  acc.present += 1;
+  if (P > 0 && N > 0) {
+    const double auc = (double)s.c / (2.0 * (double)P * (double)N);
+    acc.nauc += 1;
+    acc.rows_auc += nu;
+    acc.gauc += (double)nu * auc;
+    acc.macro += auc;
+  }
+  if (P > 0) {
+    acc.ranked += 1;
+    acc.mrr += 1.0 / (double)s.fpr;
+#pragma unroll
+    for (int j = 0; j < GK; ++j)
+      if (j < ks.nk) {
+        acc.hitg[j] += hits[j] > 0;
+        acc.recall[j] += (double)hits[j] / (double)P;
+        acc.ndcg[j] += s.d[j] / ideal[min((long long)ks.k[j], P) - 1];
+      }
+  }
+}
+
+// per wave and 64-row step, by lane 0 (positives counted within the wave)
+struct GWaveMeta {
+  int npos;
+  int first_l, first_pb;   // lane of the first group head (-1: none), positives before it
+  int last_l, last_pb;     // of the last group head
+  int tie_l, tie_pb;       // of the last tie head
+};
+
+__device__ __forceinline__ uint64_t below(int lane) { return (1ull << lane) - 1ull; }   // lane < 64
+
+__global__ __launch_bounds__(GW_NT) void group_walk_kernel(const uint64_t* k, int64_t n, int64_t tile,
+                                                           const long long* tcarry, int64_t n_groups,
+                                                           GKs ks, const double* discount,
+                                                           const double* ideal,
+                                                           dcnr_group_record* per_group, GTile* tiles,
+                                                           GAcc* part) {
+  __shared__ GWaveMeta meta[2][GW_WAVES];
+  __shared__ GSum whead[2][GW_WAVES], wtail[2][GW_WAVES];
+  __shared__ GAcc wacc[GW_WAVES];
+  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
+  const uint64_t lt = below(lane), le = lt | (1ull << lane);
+  const int64_t lo = (int64_t)blockIdx.x * tile, hi = min(n, lo + tile);
+  const long long* cr = tcarry + 5 * (int64_t)blockIdx.x;
+  // at the step's first row: positives before it, the last group head and
+  // tie head before it with the positives before them
+  long long cPB = cr[0], cG = cr[1], cPBG = cr[2], cT = cr[3], cPBT = cr[4];
+  const int kmax = ks.nk > 0 ? ks.k[ks.nk - 1] : 0;
+  GAcc acc = gacc_zero();
+  // thread 0: the group open at the step's first row
+  GSum open = gsum_zero();
+  long long oG = -1, oPBG = 0;
+  bool before_first = true;      // no head of this tile seen yet
+  GTile out;
+  out.head = gsum_zero(); out.tail = gsum_zero();
+  out.has_head = 0; out.first_g = -1; out.first_pb = 0; out.tail_g = -1; out.tail_pb = 0;
+  int par = 0;
+  for (int64_t i0 = lo; i0 < hi; i0 += GW_NT, par ^= 1) {   // block-uniform trip count
+    const int64_t base = i0 + w * WAVE, i = base + lane;
+    const bool valid = i < hi;
+    const uint64_t key = valid ? k[i] : 0ull;
+    const uint64_t prev = (valid && i > 0) ? k[i - 1] : 0ull;
+    const bool pos = valid && (key & 1ull);
+    const bool ghead = valid && (i == 0 || (key >> 33) != (prev >> 33));
+    const bool thead = valid && (i == 0 || (key >> 1) != (prev >> 1));
+    const uint64_t posbal = __ballot(pos), gbal = __ballot(ghead), tbal = __ballot(thead);
+    if (lane == 0) {
+      GWaveMeta mm;
+      mm.npos = __popcll(posbal);
+      mm.first_l = gbal ? __ffsll((unsigned long long)gbal) - 1 : -1;
+      mm.first_pb = gbal ? __popcll(posbal & below(mm.first_l)) : 0;
+      mm.last_l = gbal ? 63 - __clzll((long long)gbal) : -1;
+      mm.last_pb = gbal ? __popcll(posbal & below(mm.last_l)) : 0;
+      mm.tie_l = tbal ? 63 - __clzll((long long)tbal) : -1;
+      mm.tie_pb = tbal ? __popcll(posbal & below(mm.tie_l)) : 0;
+      meta[par][w] = mm;
+    }
+    __syncthreads();
+    // what this wave's first row sees, and the carry of the next step
+    long long wPB = cPB, wG = cG, wPBG = cPBG, wT = cT, wPBT = cPBT;
+    long long nPB = cPB, nG = cG, nPBG = cPBG, nT = cT, nPBT = cPBT;
+#pragma unroll
+    for (int v = 0; v < GW_WAVES; ++v) {
+      if (v == w) { wPB = nPB; wG = nG; wPBG = nPBG; wT = nT; wPBT = nPBT; }
+      const GWaveMeta mm = meta[par][v];
+      if (mm.last_l >= 0) { nG = i0 + v * WAVE + mm.last_l; nPBG = nPB + mm.last_pb; }
+      if (mm.tie_l >= 0) { nT = i0 + v * WAVE + mm.tie_l; nPBT = nPB + mm.tie_pb; }
+      nPB += mm.npos;
+    }
+    // this row's prefixes
+    const long long PB = wPB + __popcll(posbal & lt);
+    long long G = wG, PBG = wPBG, T = wT, PBT = wPBT;
+    const uint64_t gb = gbal & le, tb = tbal & le;
+    int seg0 = 0;                                  // first lane of this row's segment of the wave
+    if (gb) {
+      seg0 = 63 - __clzll((long long)gb);
+      G = base + seg0;
+      PBG = wPB + __popcll(posbal & below(seg0));
+    }
+    if (tb) {
+      const int tl = 63 - __clzll((long long)tb);
+      T = base + tl;
+      PBT = wPB + __popcll(posbal & below(tl));
+    }
+    GSum s = gsum_zero();
+    if (valid) {
+      const long long r = (long long)i - G + 1;
+      if (pos) {
+        s.c = ((long long)i - T) - (PB - PBT);
+        s.fpr = PB == PBG ? r : 0;
+        if (r <= kmax) {
+          const double dv = discount[r - 1];
+#pragma unroll
+          for (int j = 0; j < GK; ++j)
+            if (j < ks.nk && r <= ks.k[j]) {
+              s.d[j] = dv;
+              if (j < 2) s.hA += 1ull << (32 * j);
+              else s.hB += 1ull << (32 * (j - 2));
+            }
+        }
+      } else {
+        s.c = (PB - PBG) + (PBT - PBG);
+      }
+    }
+    // inclusive sums over [seg0, lane]
+#pragma unroll
+    for (int o = 1; o < WAVE; o <<= 1) {
+      GSum u;
+      u.c = __shfl_up(s.c, o, WAVE); u.fpr = __shfl_up(s.fpr, o, WAVE);
+      u.hA = __shfl_up(s.hA, o, WAVE); u.hB = __shfl_up(s.hB, o, WAVE);
+#pragma unroll
+      for (int j = 0; j < GK; ++j) u.d[j] = __shfl_up(s.d[j], o, WAVE);
+      if (lane - o >= seg0) { gsum_add(u, s); s = u; }   // the lower rows first
+    }
+    const bool seg_last = lane == 63 || ((gbal >> (lane + 1)) & 1ull);
+    if (valid && gb && lane < 63 && seg_last)     // a group that begins and ends in these 64 rows
+      group_finish(s, G, PBG, (long long)i + 1, PB + (pos ? 1 : 0), k, n_groups, ks, ideal, per_group,
+                   acc);
+    const int fl = gbal ? __ffsll((unsigned long long)gbal) - 1 : WAVE;
+    if (fl == 0) { if (lane == 0) whead[par][w] = gsum_zero(); }
+    else if (lane == fl - 1) whead[par][w] = s;
+    if (gbal && lane == 63) wtail[par][w] = s;
+    __syncthreads();
+    if (tid == 0) {
+      long long pre = cPB;
+#pragma unroll
+      for (int v = 0; v < GW_WAVES; ++v) {
+        const GWaveMeta mm = meta[par][v];
+        gsum_add(open, whead[par][v]);
+        if (mm.first_l >= 0) {
+          const long long E = i0 + v * WAVE + mm.first_l, PBE = pre + mm.first_pb;
+          if (before_first) {
+            out.head = open; out.has_head = 1; out.first_g = E; out.first_pb = PBE;
+            before_first = false;
+          } else {
+            group_finish(open, oG, oPBG, E, PBE, k, n_groups, ks, ideal, per_group, acc);
+          }
+          open = wtail[par][v];
+          oG = i0 + v * WAVE + mm.last_l;
+          oPBG = pre + mm.last_pb;
+        }
+        pre += mm.npos;
+      }
+    }
+    cPB = nPB; cG = nG; cPBG = nPBG; cT = nT; cPBT = nPBT;
+  }
+  if (tid == 0) {
+    if (before_first) out.head = open;
+    else { out.tail = open; out.tail_g = oG; out.tail_pb = oPBG; }
+    tiles[blockIdx.x] = out;
+  }
+  gacc_wave_sum(acc);
+  if (lane == 0) wacc[w] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    GAcc a = wacc[0];
+    for (int v = 1; v < GW_WAVES; ++v) gacc_add(a, wacc[v]);
+    part[blockIdx.x] = a;
+  }
+}
+
+// The last group of tile b (one wave per tile): its rows in tile b, then the
+// head rows of the tiles after it up to the first one that has a head of its
+// own, 64 tiles a step.
+__global__ __launch_bounds__(WAVE) void group_close_kernel(const uint64_t* k, int64_t n, int nb,
+                                                           const long long* tsum,
+                                                           const long long* tcarry, const GTile* tiles,
+                                                           int64_t n_groups, GKs ks, const double* ideal,
+                                                           dcnr_group_record* per_group, GAcc* part2) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  GAcc acc = gacc_zero();
+  if (tiles[b].has_head) {                        // wave-uniform
+    GSum R = tiles[b].tail;
+    long long E = n, PBE = tcarry[5 * (nb - 1)] + tsum[5 * (nb - 1)];
+    for (int u0 = b + 1; u0 < nb; u0 += WAVE) {
+      const int u = u0 + lane;
+      const bool in = u < nb;
+      const bool hh = in && tiles[u].has_head;
+      const uint64_t bal = __ballot(hh);
+      const int stop = bal ? __ffsll((unsigned long long)bal) - 1 : WAVE;   // the last lane to take
+      GSum s = (in && lane <= stop) ? tiles[u].head : gsum_zero();
+      // inclusive sums in tile order; lane 63 holds the step's total
+#pragma unroll
+      for (int o = 1; o < WAVE; o <<= 1) {
+        GSum v;
+        v.c = __shfl_up(s.c, o, WAVE); v.fpr = __shfl_up(s.fpr, o, WAVE);
+        v.hA = __shfl_up(s.hA, o, WAVE); v.hB = __shfl_up(s.hB, o, WAVE);
+#pragma unroll
+        for (int j = 0; j < GK; ++j) v.d[j] = __shfl_up(s.d[j], o, WAVE);
+        if (lane >= o) { gsum_add(v, s); s = v; }
+      }
+      GSum tot;
+      tot.c = __shfl(s.c, 63, WAVE); tot.fpr = __shfl(s.fpr, 63, WAVE);
+      tot.hA = __shfl(s.hA, 63, WAVE); tot.hB = __shfl(s.hB, 63, WAVE);
+#pragma unroll
+      for (int j = 0; j < GK; ++j) tot.d[j] = __shfl(s.d[j], 63, WAVE);
+      gsum_add(R, tot);
+      if (bal) {
+        E = tiles[u0 + stop].first_g;
+        PBE = tiles[u0 + stop].first_pb;
+        break;
+      }
+    }
+    if (lane == 0)
+      group_finish(R, tiles[b].tail_g, tiles[b].tail_pb, E, PBE, k, n_groups, ks, ideal, per_group, acc);
+  }
+  if (lane == 0) part2[b] = acc;
+}
+
+__global__ __launch_bounds__(FIN_NT) void group_final_kernel(const GAcc* part, int np, int64_t n,
+                                                             const uint32_t* tot, int npass, GKs ks,
+                                                             dcnr_group_summary* out) {
+  __shared__ GAcc wacc[FIN_NT / WAVE];
+  const int t = threadIdx.x;
+  GAcc a = gacc_zero();
+  for (int i = t; i < np; i += FIN_NT) gacc_add(a, part[i]);
+  gacc_wave_sum(a);
+  if ((t & 63) == 0) wacc[t >> 6] = a;
+  __syncthreads();
+  if (t == 0) {
+    a = wacc[0];
+    for (int v = 1; v < FIN_NT / WAVE; ++v) gacc_add(a, wacc[v]);
+    const unsigned long long* gc = (const unsigned long long*)(tot + (size_t)npass * NB);
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    dcnr_group_summary m;
+    m.n = n;
+    m.n_groups_present = a.present;
+    m.n_groups_auc = a.nauc;
+    m.n_groups_ranked = a.ranked;
+    m.n_rows_auc = a.rows_auc;
+    m.n_bad_label = (int64_t)gc[0];
+    m.n_nan = (int64_t)gc[1];
+    m.n_bad_group = (int64_t)gc[2];
+    m.gauc = a.nauc ? a.gauc / (double)a.rows_auc : qnan;
+    m.auc_macro = a.nauc ? a.macro / (double)a.nauc : qnan;
+    m.mrr = a.ranked ? a.mrr / (double)a.ranked : qnan;
+    for (int j = 0; j < GK; ++j) {
+      const bool on = j < ks.nk && a.ranked;
+      m.hit_groups[j] = j < ks.nk ? a.hitg[j] : 0;
+      m.hit_rate[j] = on ? (double)a.hitg[j] / (double)a.ranked : qnan;
+      m.recall[j] = on ? a.recall[j] / (double)a.ranked : qnan;
+      m.ndcg[j] = on ? a.ndcg[j] / (double)a.ranked : qnan;
+    }
+    *out = m;
+  }
+}
+
+__global__ void group_empty_kernel(dcnr_group_summary* out) {
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  dcnr_group_summary m;
+  m.n = m.n_groups_present = m.n_groups_auc = m.n_groups_ranked = m.n_rows_auc = 0;
+  m.n_bad_label = m.n_nan = m.n_bad_group = 0;
+  m.gauc = m.auc_macro = m.mrr = qnan;
+  for (int j = 0; j < GK; ++j) {
+    m.hit_groups[j] = 0;
+    m.hit_rate[j] = m.recall[j] = m.ndcg[j] = qnan;
+  }
+  *out = m;
+}
+
+}  // namespace
+
+int group_metrics_passes(int64_t n_groups) { return group_passes(n_groups); }
+
+size_t group_metrics_ws_bytes(int64_t n, int64_t n_groups) {
+  if (n <= 0 || n_groups < 1) return 0;
+  return gcarve(make_plan(n), group_passes(n_groups), n, nullptr).total;
+}
+
+dcnr_status eval_group_metrics(const float* z, const float* y, const int64_t* g, int64_t n,
+                               int64_t n_groups, const int32_t* ks_host, int32_t n_k,
+                               const double* discount, const double* ideal, dcnr_group_summary* out,
+                               dcnr_group_record* per_group, void* ws, hipStream_t s) {
+  if (per_group) TRY_ST(fill_zero(per_group, (size_t)n_groups * sizeof(dcnr_group_record), s));
+  if (n == 0) {
+    hipLaunchKernelGGL(group_empty_kernel, dim3(1), dim3(1), 0, s, out);
+    DCNR_LAUNCH_CHECK();
+    return DCNR_OK;
+  }
+  GKs ks;
+  ks.nk = n_k;
+  for (int j = 0; j < GK; ++j) ks.k[j] = j < n_k ? ks_host[j] : 0;
+  const Plan p = make_plan(n);
+  const int npass = group_passes(n_groups);
+  const GWs w = gcarve(p, npass, n, ws);
+  const int nb = p.auc_blocks;
+  TRY_ST(fill_zero(w.tot, gtot_bytes(npass), s));
+  hipLaunchKernelGGL(group_pass1_kernel, dim3(p.p1_blocks), dim3(P1_NT), 0, s, z, y, g, n, n_groups,
+                     npass, w.ka, w.tot);
+  DCNR_LAUNCH_CHECK();
+  uint64_t *src = w.ka, *dst = w.kb;
+  const int sort_blocks = (int)cdiv(p.units, SORT_WAVES);
+  for (int ps = 0; ps < npass; ++ps) {
+    const int shift = 1 + ps * RBITS;
+    hipLaunchKernelGGL(sort_hist_kernel, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, n, p.units,
+                       p.chunk, shift, w.counts);
+    DCNR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sort_scan_kernel, dim3(NB / WAVE), dim3(SCAN_NT), 0, s, w.tot + ps * NB,
+                       w.counts, p.units);
+    DCNR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(sort_scatter_kernel, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, dst, n,
+                       p.units, p.chunk, shift, w.counts);
+    DCNR_LAUNCH_CHECK();
+    std::swap(src, dst);
+  }
+  hipLaunchKernelGGL(group_heads_kernel, dim3(nb), dim3(GW_NT), 0, s, src, n, p.auc_tile, w.tsum);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(group_carry_kernel, dim3(1), dim3(AUC_MAXB), 0, s, w.tsum, nb, w.tcarry);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(group_walk_kernel, dim3(nb), dim3(GW_NT), 0, s, src, n, p.auc_tile, w.tcarry,
+                     n_groups, ks, discount, ideal, per_group, w.tile, w.part);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(group_close_kernel, dim3(nb), dim3(WAVE), 0, s, src, n, nb, w.tsum, w.tcarry,
+                     w.tile, n_groups, ks, ideal, per_group, w.part + nb);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(group_final_kernel, dim3(1), dim3(FIN_NT), 0, s, w.part, 2 * nb, n, w.tot, npass,
+                     ks, out);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
 }  // namespace dcnr
+

@@ -14,6 +14,9 @@ System-Based-on-Friends-Recommendations):
   eval_metrics, roc_auc_score,       BCEWithLogitsLoss / roc_auc_score / RMSE of
   evaluate                           the validation pass (train.py:228-233,
                                      255-265, 366-387)
+  group_metrics, evaluate_ranking    per-user (or per-item) GAUC, NDCG@k, hit
+                                     rate@k, recall@k and MRR of the order
+                                     /recommendations serves (main.py:325)
   DeviceLoader                       TensorDataset + DataLoader (train.py:195-196)
   serving.rerank_with_mmr            main.py:133-169
   serving.RankingPipeline            the /recommendations + /similar_items core
@@ -33,7 +36,8 @@ from .model import CrossLayer, DCN_RecSys, ResBlock  # noqa: F401
 from .ops import Adam, AdamW, BCEWithLogitsLoss, bce_with_logits  # noqa: F401
 from .knn import NearestNeighbors, ShardedNearestNeighbors  # noqa: F401
 from .train import FusedTrainer, PlateauLR  # noqa: F401
-from .metrics import Metrics, eval_metrics, evaluate, roc_auc_score  # noqa: F401
+from .metrics import (GroupMetrics, Metrics, eval_metrics, evaluate, evaluate_ranking,  # noqa: F401
+                      group_metrics, roc_auc_score)
 from . import serving  # noqa: F401
 from .data import DeviceLoader  # noqa: F401
 from .serving import RankingPipeline, rerank_with_mmr  # noqa: F401

@@ -75,6 +75,42 @@ class MetricsStruct(ctypes.Structure):
     ]
 
 
+GROUP_MAX_K = 4   # DCNR_GROUP_MAX_K
+
+
+class GroupRecordStruct(ctypes.Structure):
+    """dcnr_group_record (one per group, device memory)."""
+    _fields_ = [
+        ("n", ctypes.c_int64),
+        ("n_pos", ctypes.c_int64),
+        ("auc_u2", ctypes.c_int64),
+        ("first_pos_rank", ctypes.c_int64),
+        ("hits", ctypes.c_int64 * GROUP_MAX_K),
+        ("dcg", ctypes.c_double * GROUP_MAX_K),
+    ]
+
+
+class GroupSummaryStruct(ctypes.Structure):
+    """dcnr_group_summary (written to device memory by dcnr_eval_group_metrics)."""
+    _fields_ = [
+        ("n", ctypes.c_int64),
+        ("n_groups_present", ctypes.c_int64),
+        ("n_groups_auc", ctypes.c_int64),
+        ("n_groups_ranked", ctypes.c_int64),
+        ("n_rows_auc", ctypes.c_int64),
+        ("n_bad_label", ctypes.c_int64),
+        ("n_nan", ctypes.c_int64),
+        ("n_bad_group", ctypes.c_int64),
+        ("hit_groups", ctypes.c_int64 * GROUP_MAX_K),
+        ("gauc", ctypes.c_double),
+        ("auc_macro", ctypes.c_double),
+        ("mrr", ctypes.c_double),
+        ("hit_rate", ctypes.c_double * GROUP_MAX_K),
+        ("recall", ctypes.c_double * GROUP_MAX_K),
+        ("ndcg", ctypes.c_double * GROUP_MAX_K),
+    ]
+
+
 class Interactions(ctypes.Structure):
     """dcnr_interactions: the device CSRs of a dcnr.InteractionStore."""
     _fields_ = [
@@ -120,6 +156,9 @@ _SIGS = {
                                             ctypes.c_size_t, _P]),
     "dcnr_eval_metrics_workspace_size": (ctypes.c_size_t, [_I64]),
     "dcnr_eval_metrics": (ctypes.c_int, [_P, _P, _I64, _P, _P, ctypes.c_size_t, _P]),
+    "dcnr_eval_group_metrics_workspace_size": (ctypes.c_size_t, [_I64, _I64]),
+    "dcnr_eval_group_metrics": (ctypes.c_int, [_P, _P, _P, _I64, _I64, ctypes.POINTER(ctypes.c_int32),
+                                               ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "dcnr_adam_step": (ctypes.c_int, [ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_float,
                                       ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                       ctypes.c_float, _I64, ctypes.c_int, _P]),

@@ -268,7 +268,7 @@ class FusedTrainer:
         return (loss, logits) if return_logits else loss
 
     def fit(self, train_loader, val, n_epochs=50, patience=5, lr_scheduler_patience=10,
-            lr_scheduler_factor=0.1, checkpoint_path=None, on_epoch=None):
+            lr_scheduler_factor=0.1, checkpoint_path=None, on_epoch=None, ranking=None):
         """The reference's epoch loop (train.py:216-253, without Optuna).
 
         Each epoch: ``step()`` over ``train_loader`` (an iterable of
@@ -284,13 +284,17 @@ class FusedTrainer:
 
         Returns ``{"epochs": [{"epoch", "metrics", "lr"}, ...], "best_epoch",
         "best_val_loss", "stopped_early"}``; ``lr`` is the rate the schedule set
-        after that epoch's validation.  World 1 only."""
+        after that epoch's validation.  With ``ranking=dict(group_by=..., ks=...)``
+        (the arguments of ``dcnr.evaluate_ranking``) the validation also gives the
+        per-group ranking metrics of the same logits, and each epoch's entry
+        gains a ``"ranking"`` key holding the ``GroupMetrics``; ``on_epoch`` and
+        the schedule see the same ``Metrics`` either way.  World 1 only."""
         if self.world > 1:
             raise NotImplementedError(
                 "FusedTrainer.fit runs at world 1 only: a data-parallel epoch loop (sharded "
                 "validation, one checkpoint writer) is not implemented; drive step() and "
                 "dcnr.evaluate per rank instead")
-        from .metrics import evaluate
+        from .metrics import evaluate, evaluate_ranking
         sched = PlateauLR(self.lr, patience=lr_scheduler_patience, factor=lr_scheduler_factor)
         history = {"epochs": [], "best_epoch": None, "best_val_loss": math.inf,
                    "stopped_early": False}
@@ -299,9 +303,14 @@ class FusedTrainer:
             for batch in train_loader:   # (a host DataLoader's batches are moved, train.py:220-221)
                 collab, cat, num, y = (t.to(self.flat.device) for t in batch)
                 self.step(collab[:, 0], collab[:, 1], cat, num, y)
-            m = evaluate(self.model, *val)
+            if ranking is None:
+                m, rk = evaluate(self.model, *val), None
+            else:
+                m, rk = evaluate_ranking(self.model, *val, **ranking)
             self.lr = sched.step(m.logloss)
             history["epochs"].append({"epoch": epoch, "metrics": m, "lr": self.lr})
+            if rk is not None:
+                history["epochs"][-1]["ranking"] = rk
             if m.logloss < history["best_val_loss"]:
                 history["best_val_loss"], history["best_epoch"] = m.logloss, epoch
                 no_improve = 0

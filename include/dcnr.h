@@ -40,6 +40,8 @@
  *                         lists of those requests    main.py:172-194, 336-351
  *   dcnr_eval_metrics     roc_auc_score / BCEWithLogitsLoss / sqrt(mean_squared_error)
  *                         over the validation logits          train.py:255-265, 366-387
+ *   dcnr_eval_group_metrics  GAUC, NDCG@k, hit rate@k, recall@k and MRR of every
+ *                         user's (or item's) list in the order main.py:325 serves it
  *
  * Conventions
  *  - All tensor pointers are DEVICE pointers owned by the caller; the
@@ -359,6 +361,78 @@ size_t dcnr_eval_metrics_workspace_size(int64_t n);
  * NaN metrics and reads neither input nor workspace. */
 dcnr_status dcnr_eval_metrics(const float* logits, const float* labels, int64_t n,
                               dcnr_metrics* out, void* ws, size_t ws_bytes, dcnr_stream_t stream);
+
+/* Per-group ranking metrics over n (logit, label, group) rows: what
+ * /recommendations does is order one user's hotels by a stable descending
+ * sort of the logits (main.py:325), and these judge that order per group
+ * (user, item, ...): AUC per group (GAUC), NDCG@k, hit rate@k, recall@k and
+ * MRR, for up to DCNR_GROUP_MAX_K cutoffs.  Both structs are written to
+ * DEVICE memory, stream-ordered.
+ *
+ * Inside a group the rows are ranked 1, 2, ... by descending logit under IEEE
+ * equality (-0.0 == +0.0), ties in ascending input position: the served
+ * order, not an average over ties. */
+#define DCNR_GROUP_MAX_K 4
+
+typedef struct {          /* one group u; 96 bytes; all zero for a group with no row */
+  int64_t n, n_pos;       /* rows, labels == 1.0f */
+  int64_t auc_u2;         /* 2U of dcnr_metrics.auc_u2 restricted to the group */
+  int64_t first_pos_rank; /* 1-based rank of the first positive, 0 if n_pos == 0 */
+  int64_t hits[DCNR_GROUP_MAX_K]; /* positives at rank <= ks[j] */
+  double dcg[DCNR_GROUP_MAX_K];   /* sum of discount[r - 1] over positives at rank r <= ks[j] */
+} dcnr_group_record;
+
+typedef struct {          /* 216 bytes */
+  int64_t n;
+  int64_t n_groups_present; /* groups with n_u > 0 */
+  int64_t n_groups_auc;     /* groups with P_u N_u > 0 (the AUC groups) */
+  int64_t n_groups_ranked;  /* groups with P_u >= 1 (the ranked groups) */
+  int64_t n_rows_auc;       /* sum of n_u over the AUC groups */
+  int64_t n_bad_label;      /* labels that are neither 0.0f nor 1.0f */
+  int64_t n_nan;            /* NaN logits */
+  int64_t n_bad_group;      /* group ids outside [0, n_groups) */
+  int64_t hit_groups[DCNR_GROUP_MAX_K]; /* ranked groups with hits[j] > 0 */
+  double gauc;              /* sum of n_u AUC_u over the AUC groups / n_rows_auc,
+                               AUC_u = (double)auc_u2 / (2.0 * P_u * N_u) */
+  double auc_macro;         /* mean of AUC_u over the AUC groups */
+  double mrr;               /* mean of 1.0 / first_pos_rank over the ranked groups */
+  double hit_rate[DCNR_GROUP_MAX_K]; /* hit_groups[j] / n_groups_ranked */
+  double recall[DCNR_GROUP_MAX_K];   /* mean of hits[j] / P_u over the ranked groups */
+  double ndcg[DCNR_GROUP_MAX_K];     /* mean of dcg[j] / ideal[min(ks[j], P_u) - 1], likewise */
+} dcnr_group_summary;     /* a mean over zero groups, and entries j >= n_k, are NaN (counts 0) */
+
+/* Workspace bytes of dcnr_eval_group_metrics (0 for n <= 0): it depends on n
+ * and on the number of sort passes p = ceil((32 + bits(n_groups - 1)) / 11)
+ * (3 for one group, 6 at n_groups = 2^31 - 1; bits(v) = the length of v in
+ * binary), not on the value of n_groups:
+ *   16 n + 4 * 2048 * (p + U) + 32 + 552 * A   (+ < 2 KiB of alignment),
+ * U and A as for dcnr_eval_metrics_workspace_size. */
+size_t dcnr_eval_group_metrics_workspace_size(int64_t n, int64_t n_groups);
+
+/* groups[i] in [0, n_groups) is row i's group.  ks: n_k (0..DCNR_GROUP_MAX_K)
+ * cutoffs on the HOST, each in [1, 2^20], strictly ascending.  discount and
+ * ideal: device arrays of ks[n_k - 1] doubles, discount[i] = 1 / log2(i + 2)
+ * and ideal[i] = discount[0] + ... + discount[i] (not read when n_k = 0):
+ * the caller's doubles, so the device takes no logarithm.  per_group: NULL,
+ * or n_groups records, every one written.  0 <= n < 2^31,
+ * 1 <= n_groups <= 2^31 - 1; anything else is DCNR_BAD_ARG before any launch.
+ * n = 0 writes a zeroed summary with NaN means (and zeroed records) and
+ * reads neither input nor workspace.
+ *
+ * One radix sort of the keys (group, descending logit) with the label riding
+ * along puts every group's list in served order; a segmented walk over it
+ * gives the records.  Every integer is exact.  Every fp64 sum (a group's DCG,
+ * the means) is taken in an order that depends only on where the groups fall
+ * in the sorted rows, with no floating-point atomics: the same input gives
+ * the same bits.  NaN logits, labels other than 0 / 1 and group ids out of
+ * range are counted; the metrics of such an input are unspecified (the
+ * Python layer raises), but no such row indexes per_group or anything else
+ * out of bounds: a row with a bad id belongs to no group. */
+dcnr_status dcnr_eval_group_metrics(const float* logits, const float* labels, const int64_t* groups,
+                                    int64_t n, int64_t n_groups, const int32_t* ks, int32_t n_k,
+                                    const double* discount, const double* ideal,
+                                    dcnr_group_summary* out, dcnr_group_record* per_group, void* ws,
+                                    size_t ws_bytes, dcnr_stream_t stream);
 
 /* One torch.optim.AdamW (decoupled = 1) or Adam (decoupled = 0) step over
  * n_tensors tensors (host arrays of device pointers + element counts).
