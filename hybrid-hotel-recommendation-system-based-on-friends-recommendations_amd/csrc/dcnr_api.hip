@@ -2063,6 +2063,57 @@ dcnr_status dcnr_eval_group_metrics(const float* logits, const float* labels, co
   return DCNR_OK;
 }
 
+static bool list_metrics_shape_ok(int64_t R, int64_t n_items) {
+  return R <= ((int64_t)1 << 22) && n_items < ((int64_t)1 << 31);
+}
+
+size_t dcnr_eval_list_metrics_workspace_size(int64_t R, int64_t n_items) {
+  return list_metrics_shape_ok(R, n_items) ? list_metrics_ws_bytes(R, n_items) : 0;
+}
+
+dcnr_status dcnr_eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* offsets,
+                                   const int32_t* counts, int64_t R, int32_t at,
+                                   const float* table, const float* inv_norms, int32_t d,
+                                   int64_t n_items, const float* scores, const double* info,
+                                   const int64_t* rel_rows, int64_t n_rel_rows,
+                                   const int64_t* rel_offsets, const int32_t* ks, int32_t n_k,
+                                   const double* discount, const double* ideal,
+                                   dcnr_list_summary* out, dcnr_list_record* per_list, void* ws,
+                                   size_t ws_bytes, dcnr_stream_t stream) {
+  bool ok = R >= 0 && n >= 0 && n_rel_rows >= 0 && n_items >= 1 && at >= 1 && at <= 128 && d >= 1 &&
+            d <= 256 && out && n_k >= 0 && n_k <= DCNR_GROUP_MAX_K &&
+            (R == 0 || (offsets && table && inv_norms)) && (R == 0 || n == 0 || rows) &&
+            (!rel_offsets || n_rel_rows == 0 || rel_rows) && (n_k == 0 || ks) &&
+            (n_k == 0 || !rel_offsets || (discount && ideal));
+  for (int j = 0; ok && j < n_k; ++j) ok = ks[j] >= 1 && ks[j] <= at && (j == 0 || ks[j] > ks[j - 1]);
+  if (!ok) {
+    set_error("dcnr_eval_list_metrics: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  if (!list_metrics_shape_ok(R, n_items) || n > ((int64_t)1 << 30)) {
+    set_error("dcnr_eval_list_metrics: R %lld > 2^22, n %lld > 2^30 or n_items %lld >= 2^31",
+              (long long)R, (long long)n, (long long)n_items);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  const size_t need = list_metrics_ws_bytes(R, n_items);
+  if (ws_bytes < need) {
+    set_error("dcnr_eval_list_metrics: workspace too small: %zu < %zu", ws_bytes, need);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  if (need && !ws) {
+    set_error("dcnr_eval_list_metrics: null workspace");
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // algorithmic bytes: the measured rows of the table at most once each, the
+  // row ids, the counts cleared, written and read
+  TRYB(DCNR_K_HEAD, s, (double)std::min<int64_t>(n, R * at) * (4.0 * d + 12.0) + 12.0 * (double)n_items,
+       eval_list_metrics(rows, n, offsets, counts, R, at, table, inv_norms, d, n_items, scores, info,
+                         rel_rows, n_rel_rows, rel_offsets, ks, n_k, discount, ideal, out, per_list,
+                         ws, s));
+  return DCNR_OK;
+}
+
 dcnr_status dcnr_adam_step(int32_t n_tensors, float* const* params, const float* const* grads,
                            float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
                            float lr, float beta1, float beta2, float eps, float weight_decay,

@@ -770,6 +770,14 @@ dcnr_status eval_group_metrics(const float* z, const float* y, const int64_t* g,
                                int64_t n_groups, const int32_t* ks_host, int32_t n_k,
                                const double* discount, const double* ideal, dcnr_group_summary* out,
                                dcnr_group_record* per_group, void* ws, hipStream_t s);
+size_t list_metrics_ws_bytes(int64_t R, int64_t n_items);
+dcnr_status eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* offsets,
+                              const int32_t* counts, int64_t R, int32_t at, const float* table,
+                              const float* inv_norms, int32_t d, int64_t n_items, const float* scores,
+                              const double* info, const int64_t* rel_rows, int64_t n_rel_rows,
+                              const int64_t* rel_offsets, const int32_t* ks_host, int32_t n_k,
+                              const double* discount, const double* ideal, dcnr_list_summary* out,
+                              dcnr_list_record* per_list, void* ws, hipStream_t s);
 
 // optimizer
 dcnr_status adam(int n, float* const* p, const float* const* g, float* const* m, float* const* v,

@@ -1066,5 +1066,512 @@ dcnr_status eval_group_metrics(const float* z, const float* y, const int64_t* g,
   return DCNR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// List metrics (dcnr_eval_list_metrics): what the served lists look like.
+// List r is rows[offsets[r] .. offsets[r] + counts[r]), measured on its first
+// m = min(count, at) positions.
+//
+//   lists    a team of TEAM threads per list (a wave for at <= 32, four lists
+//            a workgroup; the whole workgroup above): thread t < m owns
+//            position t (its row, score, weight, membership in the held-out
+//            set by binary search, one int32 atomic on the exposure count
+//            c[row]); the m rows, each times its inverse norm, are staged in
+//            LDS (16-byte loads and row stride d + 4 where d % 4 == 0 and
+//            the table is 16-byte aligned, else stride d | 1); pair q of the m (m - 1) / 2 goes to
+//            thread q mod TEAM as (i, (i + s) mod m), s = 1 .. m / 2, an fp32
+//            dot of d fmas, summed per thread in fp64, then lanes (butterfly),
+//            then waves in order.  A workgroup walks lists blockIdx, blockIdx
+//            + gridDim, ... and keeps its sums of the summary in that order.
+//   counts   h[v] = items with c == v for v <= R (int32 atomics; the zeros
+//            counted per wave first); an item may exceed R only when a list
+//            repeats a row, and fewer than `at` items can: those counts go to
+//            a list of at most 128, sorted by the final kernel
+//   final    one workgroup: the workgroups' partial sums in a fixed order, the
+//            ascending scan of h up to the largest count seen,
+//            gini_num = sum_v v h_v (2 before_v + h_v - n_items), the struct
+//
+// Every integer comes from integer atomics or fixed-order sums, every fp64 sum
+// has an order fixed by (R, at): the same input gives the same bits.
+namespace {
+
+constexpr int LM_NT = 256;
+constexpr int LM_MAXB = 2048;          // workgroups of the list kernel (partials of the summary)
+constexpr int LM_OVER = 128;           // counts above R kept aside (fewer than `at` exist)
+constexpr int LC_BINS = 1024, LC_MAXB = 512;   // the counts kernel: LDS bins, workgroups
+constexpr int LF_NT = 256;             // the final kernel's workgroup
+
+struct LAcc {
+  long long scored, pairs, marked, bad, entries, rel_lists, hitl[GK];
+  double ild, score, info, mrr, recall[GK], ndcg[GK];
+};
+__device__ __forceinline__ LAcc lacc_zero() {
+  LAcc a;
+  a.scored = a.pairs = a.marked = a.bad = a.entries = a.rel_lists = 0;
+  a.ild = a.score = a.info = a.mrr = 0.0;
+#pragma unroll
+  for (int j = 0; j < GK; ++j) { a.hitl[j] = 0; a.recall[j] = 0.0; a.ndcg[j] = 0.0; }
+  return a;
+}
+__device__ __forceinline__ void lacc_add(LAcc& a, const LAcc& b) {
+  a.scored += b.scored; a.pairs += b.pairs; a.marked += b.marked; a.bad += b.bad;
+  a.entries += b.entries; a.rel_lists += b.rel_lists;
+  a.ild += b.ild; a.score += b.score; a.info += b.info; a.mrr += b.mrr;
+#pragma unroll
+  for (int j = 0; j < GK; ++j) { a.hitl[j] += b.hitl[j]; a.recall[j] += b.recall[j]; a.ndcg[j] += b.ndcg[j]; }
+}
+__device__ __forceinline__ void lacc_wave_sum(LAcc& a) {
+  a.scored = wave_sum_i64(a.scored); a.pairs = wave_sum_i64(a.pairs);
+  a.marked = wave_sum_i64(a.marked); a.bad = wave_sum_i64(a.bad);
+  a.entries = wave_sum_i64(a.entries); a.rel_lists = wave_sum_i64(a.rel_lists);
+  a.ild = wave_sum_f64(a.ild); a.score = wave_sum_f64(a.score);
+  a.info = wave_sum_f64(a.info); a.mrr = wave_sum_f64(a.mrr);
+#pragma unroll
+  for (int j = 0; j < GK; ++j) {
+    a.hitl[j] = wave_sum_i64(a.hitl[j]);
+    a.recall[j] = wave_sum_f64(a.recall[j]);
+    a.ndcg[j] = wave_sum_f64(a.ndcg[j]);
+  }
+}
+
+// one list's sums over its positions and pairs
+struct LRed {
+  double pc, sc, inf, dcg[GK];
+  int hits[GK], fhr;                   // fhr: the first hit's rank, INT_MAX for none
+};
+__device__ __forceinline__ void lred_add(LRed& a, const LRed& b) {
+  a.pc += b.pc; a.sc += b.sc; a.inf += b.inf;
+#pragma unroll
+  for (int j = 0; j < GK; ++j) { a.dcg[j] += b.dcg[j]; a.hits[j] += b.hits[j]; }
+  a.fhr = min(a.fhr, b.fhr);
+}
+__device__ __forceinline__ void lred_wave_sum(LRed& a) {
+  a.pc = wave_sum_f64(a.pc); a.sc = wave_sum_f64(a.sc); a.inf = wave_sum_f64(a.inf);
+#pragma unroll
+  for (int j = 0; j < GK; ++j) a.dcg[j] = wave_sum_f64(a.dcg[j]);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+#pragma unroll
+    for (int j = 0; j < GK; ++j) a.hits[j] += __shfl_xor(a.hits[j], o, 64);
+    a.fhr = min(a.fhr, __shfl_xor(a.fhr, o, 64));
+  }
+}
+
+struct LWs {
+  uint32_t* c;        // [n_items] exposure counts
+  uint32_t* h;        // [R + 1] items per count
+  uint32_t* misc;     // [2 + LM_OVER] the largest count <= R seen, entries of over, over
+  LAcc* part;         // [LM_MAXB]
+  size_t clear, total;   // the first `clear` bytes are zeroed by the call
+};
+
+LWs lcarve(int64_t R, int64_t n_items, void* base) {
+  Bump b(base);
+  LWs w;
+  w.c = (uint32_t*)b.take((size_t)n_items * 4);
+  w.h = (uint32_t*)b.take((size_t)(R + 1) * 4);
+  w.misc = (uint32_t*)b.take((size_t)(2 + LM_OVER) * 4);
+  w.clear = b.off;
+  w.part = (LAcc*)b.take((size_t)LM_MAXB * sizeof(LAcc));
+  w.total = b.off;
+  return w;
+}
+
+struct LArgs {
+  const int64_t* rows; int64_t n;
+  const int64_t* offsets; const int32_t* counts; int64_t R; int at;
+  const float* table; const float* inv; int d; int64_t n_items;
+  const float* scores; const double* info;
+  const int64_t* rel_rows; int64_t n_rel_rows; const int64_t* rel_offsets;
+  GKs ks; const double* discount; const double* ideal;
+  dcnr_list_record* per_list;
+};
+
+// Floats between two staged rows: with 16-byte accesses (VEC = 4, d % 4 == 0)
+// d + 4, so that rows stay 16-byte aligned and consecutive rows start 4 banks
+// apart; otherwise d | 1, odd, so that lanes reading different rows at one
+// column hit different banks.
+__host__ __device__ inline int list_row_stride(int d, int vec) { return vec == 4 ? d + 4 : (d | 1); }
+
+// TEAM threads per list, LM_NT / TEAM lists per workgroup step.  Every
+// __syncthreads below is reached by every thread: the loop bounds and the
+// branches around them do not depend on the list.
+template <int TEAM, int VEC>
+__global__ __launch_bounds__(LM_NT) void list_metrics_kernel(LArgs a, uint32_t* c, LAcc* part) {
+  constexpr int SU = 8;                             // loads in flight per thread while staging
+  constexpr int LPB = LM_NT / TEAM;                 // lists per step
+  constexpr int KT = TEAM == WAVE ? 32 : 128;       // positions a team holds
+  constexpr int TW = TEAM / WAVE;                   // waves per team
+  extern __shared__ __attribute__((aligned(16))) float lm_emb[];   // [LPB][at][dp]
+  __shared__ int s_row[LPB * KT];
+  __shared__ float s_inv[LPB * KT];
+  __shared__ int s_flag[LPB];                       // 1: a row outside the table, 2: the list is marked
+  __shared__ LRed s_red[LM_NT / WAVE];
+  __shared__ LAcc s_acc[LPB];
+  const int tid = threadIdx.x, team = tid / TEAM, t = tid % TEAM, lane = tid & 63;
+  const int dp = list_row_stride(a.d, VEC);
+  float* emb = lm_emb + (size_t)team * a.at * dp;
+  int* row = s_row + team * KT;
+  float* rinv = s_inv + team * KT;
+  LAcc acc = lacc_zero();                           // kept by the team's thread 0
+  for (int64_t base = (int64_t)blockIdx.x * LPB; base < a.R; base += (int64_t)gridDim.x * LPB) {
+    const int64_t r = base + team;
+    const bool live = r < a.R;
+    // ---- the segment, checked against lengths passed by value
+    int m = 0;
+    int64_t o = 0, ro = 0, nrel = 0;
+    bool bad = false, seg_rows = false;             // seg_rows: the segment holds a row
+    if (live) {
+      o = a.offsets[r];
+      const int64_t o1 = a.offsets[r + 1];
+      bad = o < 0 || o1 < o || o1 > a.n;
+      seg_rows = !bad && o1 > o;
+      int64_t cnt = bad ? 0 : o1 - o;
+      if (!bad && a.counts) {
+        cnt = (int64_t)a.counts[r];
+        bad = cnt < 0 || cnt > o1 - o;
+      }
+      if (!bad && a.rel_offsets) {
+        ro = a.rel_offsets[r];
+        const int64_t ro1 = a.rel_offsets[r + 1];
+        bad = ro < 0 || ro1 < ro || ro1 > a.n_rel_rows;
+        nrel = bad ? 0 : ro1 - ro;
+      }
+      m = bad ? 0 : (int)min(cnt, (int64_t)a.at);
+    }
+    if (t == 0) s_flag[team] = 0;
+    __syncthreads();
+    // (a marked answer has out_count 0: the mark is read from the segment's
+    // first row whatever the count says)
+    int64_t myrow = -1;
+    if (t < m || (t == 0 && seg_rows)) {
+      myrow = a.rows[o + t];
+      if (t == 0 && myrow == -1) atomicOr(&s_flag[team], 2);
+      else if (t < m && (myrow < 0 || myrow >= a.n_items)) atomicOr(&s_flag[team], 1);
+      else if (t < m) rinv[t] = a.inv[myrow];
+      if (t < m) row[t] = (int)myrow;
+    }
+    __syncthreads();
+    const int flag = s_flag[team];
+    const bool marked = (flag & 2) != 0;
+    bad = bad || (!marked && (flag & 1));
+    if (bad || marked) m = 0;
+    // ---- position t: score, weight, exposure, membership
+    LRed red;
+    red.pc = red.sc = red.inf = 0.0;
+#pragma unroll
+    for (int j = 0; j < GK; ++j) { red.dcg[j] = 0.0; red.hits[j] = 0; }
+    red.fhr = 0x7fffffff;
+    if (t < m) {
+      atomicAdd(&c[myrow], 1u);
+      if (a.scores) red.sc = (double)a.scores[o + t];
+      if (a.info) red.inf = a.info[myrow];
+      if (nrel > 0) {
+        int64_t lo = ro, hi = ro + nrel;            // first entry >= myrow
+        while (lo < hi) {
+          const int64_t mid = lo + ((hi - lo) >> 1);
+          if (a.rel_rows[mid] < myrow) lo = mid + 1; else hi = mid;
+        }
+        if (lo < ro + nrel && a.rel_rows[lo] == myrow) {
+          red.fhr = t + 1;
+#pragma unroll
+          for (int j = 0; j < GK; ++j)
+            if (j < a.ks.nk && t < a.ks.k[j]) { red.hits[j] = 1; red.dcg[j] = a.discount[t]; }
+        }
+      }
+    }
+    // ---- the m rows, normalised, into LDS
+    // (units of VEC floats, unit e = (row e / dv, column VEC (e % dv)); SU
+    // loads are issued before the first is used: the rows are random 4 d
+    // byte reads and their latency is the cost of this kernel)
+    {
+      typedef float VT __attribute__((ext_vector_type(VEC)));
+      const int dv = a.d / VEC, total = m * dv;
+      for (int e0 = t; e0 < total; e0 += TEAM * SU) {
+        VT v[SU];
+#pragma unroll
+        for (int u = 0; u < SU; ++u) {
+          const int e = min(e0 + u * TEAM, total - 1);      // (a clamped unit is loaded, not stored)
+          const int i = e / dv, cv = e - i * dv;
+          v[u] = *(const VT*)(a.table + (size_t)row[i] * a.d + cv * VEC);
+        }
+#pragma unroll
+        for (int u = 0; u < SU; ++u) {
+          const int e = e0 + u * TEAM;
+          if (e < total) {
+            const int i = e / dv, cv = e - i * dv;
+            const float w = rinv[i];
+            *(VT*)(emb + i * dp + cv * VEC) = v[u] * w;
+          }
+        }
+      }
+    }
+    __syncthreads();
+    // ---- pair q = (i, (i + s) mod m), i = q mod m, s = q / m + 1.  Odd m: (m - 1) / 2
+    // rounds of m pairs.  Even m: m / 2 - 1 rounds of m and a last one, s = m / 2, of the
+    // m / 2 pairs i < m / 2: m (m / 2 - 1) + m / 2 = m (m - 1) / 2.  So q < m (m - 1) / 2
+    // names every unordered pair exactly once.
+    if (m >= 2) {
+      const int npairs = m * (m - 1) / 2;
+      for (int q = t; q < npairs; q += TEAM) {
+        const int s1 = q / m, i = q - s1 * m;
+        int j = i + s1 + 1;
+        if (j >= m) j -= m;
+        const float* x = emb + i * dp;
+        const float* y = emb + j * dp;
+        float dot = 0.0f;                           // (the same order of fmas for either VEC)
+        if (VEC == 4) {
+#pragma unroll 4
+          for (int e = 0; e < a.d; e += 4) {
+            const f32x4 xv = *(const f32x4*)(x + e), yv = *(const f32x4*)(y + e);
+            dot = fmaf(xv.x, yv.x, dot); dot = fmaf(xv.y, yv.y, dot);
+            dot = fmaf(xv.z, yv.z, dot); dot = fmaf(xv.w, yv.w, dot);
+          }
+        } else {
+#pragma unroll 8
+          for (int e = 0; e < a.d; ++e) dot = fmaf(x[e], y[e], dot);
+        }
+        red.pc += (double)dot;
+      }
+    }
+    // ---- the team's sums: lanes, then waves in order
+    lred_wave_sum(red);
+    if (TW > 1) {
+      if (lane == 0) s_red[tid >> 6] = red;
+      __syncthreads();
+      if (t == 0)
+        for (int v = 1; v < TW; ++v) lred_add(red, s_red[team * TW + v]);
+    }
+    if (t == 0 && live) {
+      dcnr_list_record rec;
+      rec.m = m; rec.n_rel = (bad || marked) ? 0 : nrel;
+      rec.first_hit_rank = red.fhr == 0x7fffffff ? 0 : red.fhr;
+#pragma unroll
+      for (int j = 0; j < GK; ++j) { rec.hits[j] = red.hits[j]; rec.dcg[j] = red.dcg[j]; }
+      rec.pair_cos_sum = red.pc; rec.score_sum = red.sc; rec.info_sum = red.inf;
+      if (a.per_list) a.per_list[r] = rec;
+      if (bad) acc.bad += 1;
+      else if (marked) acc.marked += 1;
+      else {
+        acc.scored += m >= 1;
+        acc.entries += m;
+        acc.score += red.sc;
+        acc.info += red.inf;
+        if (m >= 2) {
+          acc.pairs += 1;
+          acc.ild += 1.0 - red.pc / (double)(m * (m - 1) / 2);
+        }
+        if (nrel > 0) {
+          acc.rel_lists += 1;
+          if (rec.first_hit_rank) acc.mrr += 1.0 / (double)rec.first_hit_rank;
+#pragma unroll
+          for (int j = 0; j < GK; ++j)
+            if (j < a.ks.nk) {
+              acc.hitl[j] += red.hits[j] > 0;
+              acc.recall[j] += (double)red.hits[j] / (double)nrel;
+              acc.ndcg[j] += red.dcg[j] / a.ideal[min((int64_t)a.ks.k[j], nrel) - 1];
+            }
+        }
+      }
+    }
+    __syncthreads();                                // LDS is rewritten by the next step
+  }
+  if (t == 0) s_acc[team] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    for (int v = 1; v < LPB; ++v) lacc_add(acc, s_acc[v]);
+    part[blockIdx.x] = acc;
+  }
+}
+
+__global__ __launch_bounds__(LM_NT) void list_counts_kernel(const uint32_t* c, int64_t n_items, int64_t R,
+                                                           uint32_t* h, uint32_t* misc) {
+  // Most items share a handful of counts (all of them 1 at small R): the
+  // counts below LC_BINS are tallied in LDS and reach h once per workgroup,
+  // or every item would queue on the same few words of h.
+  __shared__ uint32_t bins[LC_BINS];
+  for (int j = threadIdx.x; j < LC_BINS; j += LM_NT) bins[j] = 0u;
+  __syncthreads();
+  long long zeros = 0;
+  uint32_t vmax = 0;
+  for (int64_t i = (int64_t)blockIdx.x * LM_NT + threadIdx.x; i < n_items;
+       i += (int64_t)gridDim.x * LM_NT) {
+    const uint32_t v = c[i];
+    if (v == 0) ++zeros;
+    else if ((int64_t)v <= R) {
+      if (v < (uint32_t)LC_BINS) atomicAdd(&bins[v], 1u); else atomicAdd(&h[v], 1u);
+      vmax = max(vmax, v);
+    } else {
+      const uint32_t at = atomicAdd(&misc[1], 1u);
+      if (at < (uint32_t)LM_OVER) misc[2 + at] = v;
+    }
+  }
+  zeros = wave_sum_i64(zeros);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) vmax = max(vmax, (uint32_t)__shfl_xor((int)vmax, o, 64));
+  if ((threadIdx.x & 63) == 0) {
+    if (zeros) atomicAdd(&h[0], (uint32_t)zeros);
+    if (vmax) atomicMax(&misc[0], vmax);
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < LC_BINS; j += LM_NT)       // (j <= R: only such counts were tallied)
+    if (bins[j]) atomicAdd(&h[j], bins[j]);
+}
+
+__global__ __launch_bounds__(LF_NT) void list_final_kernel(const LAcc* part, int np, int64_t R,
+                                                          int64_t n_items, const uint32_t* h,
+                                                          const uint32_t* misc, GKs ks, int has_scores,
+                                                          int has_info, dcnr_list_summary* out) {
+  __shared__ LAcc wacc[LF_NT / WAVE];
+  __shared__ long long s_cnt[LF_NT];
+  __shared__ long long s_term[LF_NT / WAVE];
+  const int t = threadIdx.x;
+  LAcc a = lacc_zero();
+  for (int i = t; i < np; i += LF_NT) lacc_add(a, part[i]);
+  lacc_wave_sum(a);
+  if ((t & 63) == 0) wacc[t >> 6] = a;
+  // ---- counts ascending: thread t owns v in [t * chunk, (t + 1) * chunk) of [0, vmax]
+  const int64_t nv = (int64_t)misc[0] + 1;
+  const int64_t chunk = (nv + LF_NT - 1) / LF_NT;
+  const int64_t v0 = min(nv, (int64_t)t * chunk), v1 = min(nv, v0 + chunk);
+  long long mine = 0;
+  for (int64_t v = v0; v < v1; ++v) mine += h[v];
+  s_cnt[t] = mine;
+  __syncthreads();
+  for (int o = 1; o < LF_NT; o <<= 1) {               // inclusive scan of the threads' item counts
+    const long long add = t >= o ? s_cnt[t - o] : 0;
+    __syncthreads();
+    s_cnt[t] += add;
+    __syncthreads();
+  }
+  long long before = s_cnt[t] - mine, term = 0;
+  for (int64_t v = v0; v < v1; ++v) {
+    const long long hv = h[v];
+    term += (long long)v * hv * (2 * before + hv - (long long)n_items);
+    before += hv;
+  }
+  term = wave_sum_i64(term);
+  if ((t & 63) == 0) s_term[t >> 6] = term;
+  __syncthreads();
+  if (t == 0) {
+    a = wacc[0];
+    for (int v = 1; v < LF_NT / WAVE; ++v) lacc_add(a, wacc[v]);
+    long long gnum = 0;
+    for (int v = 0; v < LF_NT / WAVE; ++v) gnum += s_term[v];
+    // the few counts above R, ascending, one item each
+    long long before_o = s_cnt[LF_NT - 1];
+    const int no = (int)min(misc[1], (uint32_t)LM_OVER);
+    uint32_t prev = 0;
+    for (int k = 0; k < no; ++k) {                    // selection in ascending order (no <= 128)
+      uint32_t best = 0xffffffffu;
+      int nbest = 0;
+      for (int e = 0; e < no; ++e) {
+        const uint32_t v = misc[2 + e];
+        if (v > prev && v < best) { best = v; nbest = 1; }
+        else if (v == best) ++nbest;
+      }
+      if (!nbest) break;
+      gnum += (long long)best * nbest * (2 * before_o + nbest - (long long)n_items);
+      before_o += nbest;
+      prev = best;
+    }
+    const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+    dcnr_list_summary m;
+    m.n_lists = R;
+    m.n_lists_scored = a.scored;
+    m.n_lists_pairs = a.pairs;
+    m.n_marked = a.marked;
+    m.n_bad_list = a.bad;
+    m.n_entries = a.entries;
+    m.n_distinct_items = n_items - (long long)h[0];
+    m.gini_num = gnum;
+    m.n_rel_lists = a.rel_lists;
+    m.ild = a.pairs ? a.ild / (double)a.pairs : qnan;
+    m.mean_score = has_scores && a.entries ? a.score / (double)a.entries : qnan;
+    m.mean_info = has_info && a.entries ? a.info / (double)a.entries : qnan;
+    m.mrr = a.rel_lists ? a.mrr / (double)a.rel_lists : qnan;
+    m.coverage = (double)m.n_distinct_items / (double)n_items;
+    m.gini = a.entries ? (double)gnum / ((double)n_items * (double)a.entries) : qnan;
+#pragma unroll
+    for (int j = 0; j < GK; ++j) {
+      const bool on = j < ks.nk && a.rel_lists;
+      m.hit_lists[j] = j < ks.nk ? a.hitl[j] : 0;
+      m.hit_rate[j] = on ? (double)a.hitl[j] / (double)a.rel_lists : qnan;
+      m.recall[j] = on ? a.recall[j] / (double)a.rel_lists : qnan;
+      m.ndcg[j] = on ? a.ndcg[j] / (double)a.rel_lists : qnan;
+    }
+    *out = m;
+  }
+}
+
+__global__ void list_empty_kernel(dcnr_list_summary* out) {
+  const double qnan = __longlong_as_double(0x7ff8000000000000ll);
+  dcnr_list_summary m;
+  m.n_lists = m.n_lists_scored = m.n_lists_pairs = m.n_marked = m.n_bad_list = 0;
+  m.n_entries = m.n_distinct_items = m.gini_num = m.n_rel_lists = 0;
+  m.ild = m.mean_score = m.mean_info = m.mrr = m.gini = qnan;
+  m.coverage = 0.0;
+  for (int j = 0; j < GK; ++j) {
+    m.hit_lists[j] = 0;
+    m.hit_rate[j] = m.recall[j] = m.ndcg[j] = qnan;
+  }
+  *out = m;
+}
+
+}  // namespace
+
+size_t list_metrics_ws_bytes(int64_t R, int64_t n_items) {
+  if (R <= 0 || n_items < 1) return 0;
+  return lcarve(R, n_items, nullptr).total;
+}
+
+dcnr_status eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* offsets,
+                              const int32_t* counts, int64_t R, int32_t at, const float* table,
+                              const float* inv_norms, int32_t d, int64_t n_items, const float* scores,
+                              const double* info, const int64_t* rel_rows, int64_t n_rel_rows,
+                              const int64_t* rel_offsets, const int32_t* ks_host, int32_t n_k,
+                              const double* discount, const double* ideal, dcnr_list_summary* out,
+                              dcnr_list_record* per_list, void* ws, hipStream_t s) {
+  if (R == 0) {
+    hipLaunchKernelGGL(list_empty_kernel, dim3(1), dim3(1), 0, s, out);
+    DCNR_LAUNCH_CHECK();
+    return DCNR_OK;
+  }
+  LArgs a;
+  a.rows = rows; a.n = n; a.offsets = offsets; a.counts = counts; a.R = R; a.at = at;
+  a.table = table; a.inv = inv_norms; a.d = d; a.n_items = n_items;
+  a.scores = scores; a.info = info;
+  a.rel_rows = rel_rows; a.n_rel_rows = n_rel_rows; a.rel_offsets = rel_offsets;
+  a.ks.nk = rel_offsets ? n_k : 0;
+  for (int j = 0; j < GK; ++j) a.ks.k[j] = j < a.ks.nk ? ks_host[j] : 0;
+  a.discount = discount; a.ideal = ideal; a.per_list = per_list;
+  const LWs w = lcarve(R, n_items, ws);
+  TRY_ST(fill_zero(ws, w.clear, s));
+  const bool wave = at <= 32;
+  const int lpb = wave ? LM_NT / WAVE : 1;
+  const int nb = (int)std::min<int64_t>(LM_MAXB, cdiv(R, lpb));
+  // 16-byte loads where every row of the table starts on 16 bytes
+  const bool vec = d % 4 == 0 && (uintptr_t)table % 16 == 0;
+  const size_t lds = (size_t)lpb * at * list_row_stride(d, vec ? 4 : 1) * sizeof(float);
+#define DCNR_LIST_LAUNCH(TEAM, VEC)                                                              \
+  do {                                                                                           \
+    TRY_ST(set_max_dyn_lds((const void*)list_metrics_kernel<TEAM, VEC>, lds));                   \
+    hipLaunchKernelGGL((list_metrics_kernel<TEAM, VEC>), dim3(nb), dim3(LM_NT), lds, s, a, w.c,  \
+                       w.part);                                                                  \
+  } while (0)
+  if (wave && vec) DCNR_LIST_LAUNCH(WAVE, 4);
+  else if (wave) DCNR_LIST_LAUNCH(WAVE, 1);
+  else if (vec) DCNR_LIST_LAUNCH(LM_NT, 4);
+  else DCNR_LIST_LAUNCH(LM_NT, 1);
+#undef DCNR_LIST_LAUNCH
+  DCNR_LAUNCH_CHECK();
+  const int cb = (int)std::min<int64_t>(LC_MAXB, cdiv(n_items, LM_NT));
+  hipLaunchKernelGGL(list_counts_kernel, dim3(cb), dim3(LM_NT), 0, s, w.c, n_items, R, w.h, w.misc);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(list_final_kernel, dim3(1), dim3(LF_NT), 0, s, w.part, nb, R, n_items, w.h, w.misc,
+                     a.ks, scores != nullptr, info != nullptr, out);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
 }  // namespace dcnr
 

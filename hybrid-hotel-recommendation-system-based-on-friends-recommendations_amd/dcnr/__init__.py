@@ -17,6 +17,11 @@ System-Based-on-Friends-Recommendations):
   group_metrics, evaluate_ranking    per-user (or per-item) GAUC, NDCG@k, hit
                                      rate@k, recall@k and MRR of the order
                                      /recommendations serves (main.py:325)
+  list_metrics,                      what the served lists look like under
+  popularity_information             lambda_param (main.py:133-169): intra-list
+                                     diversity, coverage, Gini, novelty, held-out
+                                     hits; RankingPipeline.list_metrics /
+                                     .lambda_sweep
   DeviceLoader                       TensorDataset + DataLoader (train.py:195-196)
   serving.rerank_with_mmr            main.py:133-169
   serving.RankingPipeline            the /recommendations + /similar_items core
@@ -36,8 +41,9 @@ from .model import CrossLayer, DCN_RecSys, ResBlock  # noqa: F401
 from .ops import Adam, AdamW, BCEWithLogitsLoss, bce_with_logits  # noqa: F401
 from .knn import NearestNeighbors, ShardedNearestNeighbors  # noqa: F401
 from .train import FusedTrainer, PlateauLR  # noqa: F401
-from .metrics import (GroupMetrics, Metrics, eval_metrics, evaluate, evaluate_ranking,  # noqa: F401
-                      group_metrics, roc_auc_score)
+from .metrics import (GroupMetrics, ListMetrics, Metrics, eval_metrics, evaluate,  # noqa: F401
+                      evaluate_ranking, group_metrics, list_metrics, list_metrics_raw,
+                      popularity_information, roc_auc_score)
 from . import serving  # noqa: F401
 from .data import DeviceLoader  # noqa: F401
 from .serving import RankingPipeline, rerank_with_mmr  # noqa: F401

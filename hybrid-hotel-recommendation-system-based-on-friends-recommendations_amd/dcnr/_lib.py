@@ -111,6 +111,45 @@ class GroupSummaryStruct(ctypes.Structure):
     ]
 
 
+class ListRecordStruct(ctypes.Structure):
+    """dcnr_list_record (one per list, device memory)."""
+    _fields_ = [
+        ("m", ctypes.c_int64),
+        ("n_rel", ctypes.c_int64),
+        ("first_hit_rank", ctypes.c_int64),
+        ("hits", ctypes.c_int64 * GROUP_MAX_K),
+        ("pair_cos_sum", ctypes.c_double),
+        ("score_sum", ctypes.c_double),
+        ("info_sum", ctypes.c_double),
+        ("dcg", ctypes.c_double * GROUP_MAX_K),
+    ]
+
+
+class ListSummaryStruct(ctypes.Structure):
+    """dcnr_list_summary (written to device memory by dcnr_eval_list_metrics)."""
+    _fields_ = [
+        ("n_lists", ctypes.c_int64),
+        ("n_lists_scored", ctypes.c_int64),
+        ("n_lists_pairs", ctypes.c_int64),
+        ("n_marked", ctypes.c_int64),
+        ("n_bad_list", ctypes.c_int64),
+        ("n_entries", ctypes.c_int64),
+        ("n_distinct_items", ctypes.c_int64),
+        ("gini_num", ctypes.c_int64),
+        ("n_rel_lists", ctypes.c_int64),
+        ("hit_lists", ctypes.c_int64 * GROUP_MAX_K),
+        ("ild", ctypes.c_double),
+        ("mean_score", ctypes.c_double),
+        ("mean_info", ctypes.c_double),
+        ("mrr", ctypes.c_double),
+        ("coverage", ctypes.c_double),
+        ("gini", ctypes.c_double),
+        ("hit_rate", ctypes.c_double * GROUP_MAX_K),
+        ("recall", ctypes.c_double * GROUP_MAX_K),
+        ("ndcg", ctypes.c_double * GROUP_MAX_K),
+    ]
+
+
 class Interactions(ctypes.Structure):
     """dcnr_interactions: the device CSRs of a dcnr.InteractionStore."""
     _fields_ = [
@@ -159,6 +198,11 @@ _SIGS = {
     "dcnr_eval_group_metrics_workspace_size": (ctypes.c_size_t, [_I64, _I64]),
     "dcnr_eval_group_metrics": (ctypes.c_int, [_P, _P, _P, _I64, _I64, ctypes.POINTER(ctypes.c_int32),
                                                ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
+    "dcnr_eval_list_metrics_workspace_size": (ctypes.c_size_t, [_I64, _I64]),
+    "dcnr_eval_list_metrics": (ctypes.c_int, [_P, _I64, _P, _P, _I64, ctypes.c_int32, _P, _P,
+                                              ctypes.c_int32, _I64, _P, _P, _P, _I64, _P,
+                                              ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, _P, _P,
+                                              _P, _P, _P, ctypes.c_size_t, _P]),
     "dcnr_adam_step": (ctypes.c_int, [ctypes.c_int32, _P, _P, _P, _P, _P, ctypes.c_float,
                                       ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                       ctypes.c_float, _I64, ctypes.c_int, _P]),

@@ -17,6 +17,15 @@
                                  (dcnr_eval_group_metrics), one 216-byte copy
   evaluate_ranking(model, collab, cat, num, y, group_by='user', ks=...)
                                  evaluate and group_metrics from one forward
+  list_metrics(rows, offsets, counts, table=..., at=20, ...)
+                                 what served lists look like (intra-list
+                                 diversity, coverage, Gini of the exposure,
+                                 mean logit / item weight, held-out hits): one
+                                 native call (dcnr_eval_list_metrics) on the
+                                 lists where the batched serving calls left
+                                 them, one 248-byte copy
+  popularity_information(counts) -log2 of each item's smoothed share: the
+                                 ``info`` weight whose mean is novelty
 
 AUC is exact (the midrank Mann-Whitney statistic over a full device sort of the
 scores, ties included): ``auc_u2`` is the integer 2U and ``auc`` is
@@ -224,6 +233,244 @@ def group_metrics(logits, labels, groups, ks=(5, 10, 20), n_groups=None, per_gro
     if m.n_bad_group:
         raise ValueError(f"{m.n_bad_group} group ids are outside [0, {n_groups})")
     return m
+
+
+LIST_MAX_AT = 128   # dcnr_eval_list_metrics: 1 <= at <= 128
+
+
+class ListMetrics(NamedTuple):
+    """dcnr_list_summary; per-cutoff fields are tuples aligned with ``ks``.
+    ``records``: None, or a dict of [R] device tensors (m, n_rel,
+    first_hit_rank int64; hits [R, len(ks)] int64; pair_cos_sum, score_sum,
+    info_sum float64; dcg [R, len(ks)] float64)."""
+    ild: float
+    coverage: float
+    gini: float
+    mean_score: float
+    mean_info: float
+    mrr: float
+    ks: tuple
+    hit_rate: tuple
+    recall: tuple
+    ndcg: tuple
+    n_lists: int
+    n_lists_scored: int
+    n_lists_pairs: int
+    n_marked: int
+    n_bad_list: int
+    n_entries: int
+    n_distinct_items: int
+    gini_num: int
+    n_rel_lists: int
+    hit_lists: tuple
+    records: dict | None = None
+
+
+def popularity_information(counts) -> np.ndarray:
+    """Self-information of each item under add-one smoothing, float64
+    [n_items]: ``-log2((c_i + 1) / (sum(c) + n_items))`` -- finite for an item
+    never seen, never negative; the ``info`` of ``list_metrics`` (its mean is
+    the lists' novelty)."""
+    c = np.asarray(counts.cpu() if torch.is_tensor(counts) else counts, dtype=np.float64).reshape(-1)
+    if c.size and c.min() < 0:
+        raise ValueError("popularity_information: negative count")
+    return -np.log2((c + 1.0) / (c.sum() + c.size))
+
+
+def list_workspace_bytes(R: int, n_items: int) -> int:
+    return int(_lib.load().dcnr_eval_list_metrics_workspace_size(int(R), int(n_items)))
+
+
+def relevant_csr(relevant, R: int, n_items: int):
+    """The held-out sets as the CSR dcnr_eval_list_metrics reads, on the host:
+    (rows int64, offsets int64 [R + 1]), each set ascending and distinct.
+    ``relevant``: a list of R iterables of item rows (None = empty), or a
+    TUPLE ``(rows, offsets)`` of arrays whose sets need be neither."""
+    if isinstance(relevant, tuple):
+        if len(relevant) != 2:
+            raise ValueError("relevant: a list of R iterables or a (rows, offsets) tuple")
+        as_np = lambda a: np.asarray(a.cpu() if torch.is_tensor(a) else a, dtype=np.int64).reshape(-1)
+        rows, off = as_np(relevant[0]), as_np(relevant[1])
+        if off.size != R + 1:
+            raise ValueError(f"relevant: {off.size} offsets for {R} lists")
+        if off[0] < 0 or off[-1] > rows.size or (np.diff(off) < 0).any():
+            raise ValueError("relevant: offsets not monotone or outside the rows")
+        lens = np.diff(off)
+        rows = rows[off[0]:off[-1]]
+    else:
+        if len(relevant) != R:
+            raise ValueError(f"relevant: {len(relevant)} sets for {R} lists")
+        sets = [np.asarray(list(s) if s is not None else [], dtype=np.int64).reshape(-1) for s in relevant]
+        lens = np.array([s.size for s in sets], np.int64)
+        rows = np.concatenate(sets) if sets else np.zeros(0, np.int64)
+    if rows.size and (rows.min() < 0 or rows.max() >= n_items):
+        raise ValueError(f"relevant: item row outside [0, {n_items})")
+    seg = np.repeat(np.arange(R, dtype=np.int64), lens)
+    key = np.unique(seg * int(n_items) + rows)            # sorted by (list, row), duplicates gone
+    seg, rows = key // int(n_items), key % int(n_items)
+    off = np.zeros(R + 1, np.int64)
+    np.cumsum(np.bincount(seg, minlength=R), out=off[1:])
+    return np.ascontiguousarray(rows), off
+
+
+def _list_check(n, n_off, n_counts, table_shape, n_inv, at, n_scores, n_info, ks):
+    """The ValueErrors of list_metrics that need no device."""
+    ks = tuple(int(k) for k in ks)
+    at = int(at)
+    if not 1 <= at <= LIST_MAX_AT:
+        raise ValueError(f"list_metrics: at = {at} outside [1, {LIST_MAX_AT}]")
+    if len(ks) > _lib.GROUP_MAX_K:
+        raise ValueError(f"at most {_lib.GROUP_MAX_K} cutoffs")
+    if any(k < 1 for k in ks) or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"list_metrics: ks = {ks} must be positive and strictly ascending")
+    if ks and ks[-1] > at:
+        raise ValueError(f"list_metrics: cutoff {ks[-1]} above at = {at}")
+    if n_off < 1:
+        raise ValueError("list_metrics: offsets needs R + 1 entries")
+    R = n_off - 1
+    if n_counts is not None and n_counts != R:
+        raise ValueError(f"list_metrics: {n_counts} counts for {R} lists")
+    if len(table_shape) != 2 or table_shape[0] < 1:
+        raise ValueError("list_metrics: table must be [n_items, d] with n_items >= 1")
+    if n_inv is not None and n_inv != table_shape[0]:
+        raise ValueError(f"list_metrics: {n_inv} inverse norms for {table_shape[0]} table rows")
+    if n_scores is not None and n_scores != n:
+        raise ValueError(f"list_metrics: {n_scores} scores beside {n} rows")
+    if n_info is not None and n_info != table_shape[0]:
+        raise ValueError(f"list_metrics: {n_info} info weights for {table_shape[0]} items")
+    return R, at, ks
+
+
+def _list_launch(rows, offsets, counts, table, inv, at, scores, info, rel, ks, per_list, ws, out=None):
+    """Enqueue dcnr_eval_list_metrics on the current stream; every argument a
+    device tensor of the right dtype (or None), ``rel`` a (rows, offsets) pair
+    or None.  Returns (summary bytes on the device, records or None): nothing
+    is read back here."""
+    lib = _lib.load()
+    dev = rows.device
+    R, n, nk = offsets.numel() - 1, rows.numel(), len(ks)
+    n_items, d = table.shape
+    ks_arr = (ctypes.c_int32 * max(1, nk))(*ks)
+    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+    with torch.cuda.device(dev):
+        disc, ideal = _device_tables(ks[-1], dev) if nk else (None, None)
+        if ws is None:
+            ws = torch.empty(list_workspace_bytes(R, n_items), dtype=torch.uint8, device=dev)
+        if out is None:
+            out = torch.empty(ctypes.sizeof(_lib.ListSummaryStruct), dtype=torch.uint8, device=dev)
+        rec = None
+        if per_list:
+            rec = torch.empty((R, ctypes.sizeof(_lib.ListRecordStruct) // 8), dtype=torch.int64, device=dev)
+        _lib.check(lib.dcnr_eval_list_metrics(
+            ptr(rows), n, offsets.data_ptr(), counts.data_ptr() if counts is not None else None, R, at,
+            table.data_ptr(), inv.data_ptr(), d, n_items, ptr(scores) if scores is not None else None,
+            info.data_ptr() if info is not None else None,
+            ptr(rel[0]) if rel is not None else None, rel[0].numel() if rel is not None else 0,
+            rel[1].data_ptr() if rel is not None else None, ks_arr, nk,
+            ptr(disc), ptr(ideal), out.data_ptr(), ptr(rec), ptr(ws), ws.numel(),
+            _lib.stream_ptr(dev)), "dcnr_eval_list_metrics")
+    return out, rec
+
+
+def _list_result(raw: bytes, ks, rec) -> ListMetrics:
+    m = _lib.ListSummaryStruct.from_buffer_copy(raw)
+    nk = len(ks)
+    records = None
+    if rec is not None:
+        f64 = lambda a: a.view(torch.float64)
+        records = {"m": rec[:, 0], "n_rel": rec[:, 1], "first_hit_rank": rec[:, 2],
+                   "hits": rec[:, 3:3 + nk], "pair_cos_sum": f64(rec[:, 7]), "score_sum": f64(rec[:, 8]),
+                   "info_sum": f64(rec[:, 9]), "dcg": f64(rec[:, 10:10 + nk])}
+    return ListMetrics(float(m.ild), float(m.coverage), float(m.gini), float(m.mean_score),
+                       float(m.mean_info), float(m.mrr), tuple(ks),
+                       tuple(float(m.hit_rate[j]) for j in range(nk)),
+                       tuple(float(m.recall[j]) for j in range(nk)),
+                       tuple(float(m.ndcg[j]) for j in range(nk)),
+                       int(m.n_lists), int(m.n_lists_scored), int(m.n_lists_pairs), int(m.n_marked),
+                       int(m.n_bad_list), int(m.n_entries), int(m.n_distinct_items), int(m.gini_num),
+                       int(m.n_rel_lists), tuple(int(m.hit_lists[j]) for j in range(nk)), records)
+
+
+def empty_list_metrics(R: int, ks) -> ListMetrics:
+    """What dcnr_eval_list_metrics gives for R lists that are all empty and
+    have no held-out sets: the counts 0, coverage 0, every mean NaN."""
+    nan, nk = float("nan"), len(ks)
+    return ListMetrics(nan, 0.0, nan, nan, nan, nan, tuple(ks), (nan,) * nk, (nan,) * nk, (nan,) * nk,
+                       int(R), 0, 0, 0, 0, 0, 0, 0, 0, (0,) * nk, None)
+
+
+def list_metrics_raw(rows, offsets, counts=None, *, table, inv_norms, at=20, scores=None, info=None,
+                     relevant=None, ks=(5, 10, 20), per_list=False, ws=None) -> ListMetrics:
+    """dcnr_eval_list_metrics on device tensors as they come: ``relevant`` is a
+    device ``(rows, offsets)`` pair whose sets are already ascending and
+    distinct, ``info`` a float64 device tensor, ``ws`` a uint8 device workspace
+    of at least ``list_workspace_bytes(R, n_items)`` bytes (allocated when
+    None).  One wait: the 248-byte copy of the summary."""
+    R, at, ks = _list_check(rows.numel(), offsets.numel(), None if counts is None else counts.numel(),
+                            tuple(table.shape), inv_norms.numel(), at,
+                            None if scores is None else scores.numel(),
+                            None if info is None else info.numel(), ks)
+    if relevant is not None and relevant[1].numel() != R + 1:
+        raise ValueError(f"relevant: {relevant[1].numel()} offsets for {R} lists")
+    if rows.device.type != 'cuda':
+        raise RuntimeError("dcnr.list_metrics runs on the HIP device only")
+    out, rec = _list_launch(rows, offsets, counts, table, inv_norms, at, scores, info, relevant, ks,
+                            per_list, ws)
+    return _list_result(out.cpu().numpy().tobytes(), ks, rec)   # the one D2H copy
+
+
+def list_metrics(rows, offsets, counts=None, *, table, inv_norms=None, at=20, scores=None, info=None,
+                 relevant=None, ks=(5, 10, 20), per_list=False) -> ListMetrics:
+    """What R served lists look like, measured on the device where the batched
+    serving calls left them.  List r is ``rows[offsets[r] : offsets[r] +
+    counts[r]]`` (``counts=None``: whole segments), measured on its first
+    ``min(count, at)`` positions.
+
+    table, inv_norms  the item embeddings [n_items, d] and their inverse norms
+                   (None: ``dcnr.serving.row_inv_norms(table)``)
+    scores         the logits beside ``rows`` (mean_score), or None
+    info           a float64 weight per item, e.g. ``popularity_information``
+                   (mean_info), or None
+    relevant       held-out items per list: a list of R iterables, or a TUPLE
+                   (rows, offsets); sorted and de-duplicated here, on the host
+    ks             up to 4 ascending cutoffs <= at for hit rate / recall / NDCG
+
+    ``ild`` is the mean over lists of 1 - the mean pairwise cosine;
+    ``coverage`` the share of items in some list; ``gini`` the Gini coefficient
+    of the items' exposure counts (0: every item shown equally often).  A list
+    whose first row is -1 (an answer the device marked) and a list with a bad
+    offset, count or row is skipped and counted in ``n_marked`` /
+    ``n_bad_list``.  Waits once, to read the summary."""
+    as_t = lambda a, dt: a.detach() if torch.is_tensor(a) else torch.as_tensor(np.asarray(a), dtype=dt)
+    rows, offsets = as_t(rows, torch.int64).reshape(-1), as_t(offsets, torch.int64).reshape(-1)
+    table = as_t(table, torch.float32)
+    if counts is not None:
+        counts = as_t(counts, torch.int32).reshape(-1)
+    if scores is not None:
+        scores = as_t(scores, torch.float32).reshape(-1)
+    if info is not None:
+        info = as_t(info, torch.float64).reshape(-1)
+    if inv_norms is not None:
+        inv_norms = as_t(inv_norms, torch.float32).reshape(-1)
+    R, at, ks = _list_check(rows.numel(), offsets.numel(), None if counts is None else counts.numel(),
+                            tuple(table.shape), None if inv_norms is None else inv_norms.numel(), at,
+                            None if scores is None else scores.numel(),
+                            None if info is None else info.numel(), ks)
+    rel = relevant_csr(relevant, R, table.shape[0]) if relevant is not None else None
+    dev = next((t.device for t in (rows, table, offsets) if t.device.type == 'cuda'), None)
+    if dev is None:
+        raise RuntimeError("dcnr.list_metrics runs on the HIP device only")
+    on = lambda t, dt: None if t is None else t.to(device=dev, dtype=dt).contiguous()
+    table = on(table, torch.float32)
+    if inv_norms is None:
+        from .serving import row_inv_norms
+        inv_norms = row_inv_norms(table)
+    if rel is not None:
+        rel = tuple(torch.from_numpy(a).to(dev) for a in rel)
+    return list_metrics_raw(on(rows, torch.int64), on(offsets, torch.int64), on(counts, torch.int32),
+                            table=table, inv_norms=on(inv_norms, torch.float32), at=at,
+                            scores=on(scores, torch.float32), info=on(info, torch.float64),
+                            relevant=rel, ks=ks, per_list=per_list)
 
 
 def _eval_logits(model, collab, cat, num, batch_size):

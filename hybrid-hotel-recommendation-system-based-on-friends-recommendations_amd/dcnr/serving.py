@@ -32,6 +32,12 @@ ids: the positives, the negatives and the ``recommended_by`` lists (main.py:
 172-194, 336-351) come from a ``dcnr.InteractionStore`` on the device
 (dcnr_requests_sources, dcnr_requests_recommended_by).
 
+``RankingPipeline.list_metrics`` measures answers already served
+(``dcnr.list_metrics`` against the pipeline's own table), and
+``RankingPipeline.lambda_sweep`` answers one batch for several values of
+``lambda_param`` from ONE candidates pass and ONE forward, each lambda's
+answers measured on the device where rank + MMR left them.
+
 ``RankingPipeline(..., neighbor_table=True)`` builds the item neighbour table
 once (``NearestNeighbors.build_neighbor_table``): every neighbour query of the
 request path is a row of the fitted table, so ``candidates``, ``recommend``,
@@ -41,6 +47,7 @@ the answers are the same bits.
 """
 from __future__ import annotations
 
+import ctypes
 import threading
 from typing import Any, Dict, Iterable, List, Optional, Tuple
 
@@ -170,6 +177,14 @@ class UserAnswers(list):
         who = pack[3 * c:]
         by = [who[e - m:e].tolist() for e, m in zip(ends, pack[2 * c:3 * c])]
         return (pack[:c].tolist(), pack[c:2 * c].astype(np.int32).view(np.float32).tolist(), by)
+
+
+class SweepResult(list):
+    """What ``RankingPipeline.lambda_sweep`` returns: a list of (answers,
+    ListMetrics) pairs, one per lambda of ``lambdas``; ``skipped``: the
+    request indices left out of every lambda's lists and metrics."""
+    lambdas = ()
+    skipped = ()
 
 
 class RankingPipeline:
@@ -460,8 +475,6 @@ class RankingPipeline:
         or -inf (they have no rank; ``recommend()`` is undefined there too) is
         not reported: the device marks its whole answer, rows -1 and logits
         NaN."""
-        lib = _lib.load()
-        dev = self.device
         if self.index._table.shape[0] != self.n_items:
             raise ValueError(f"recommend_many: the index holds {self.index._table.shape[0]} rows, "
                              f"item_cat / item_num {self.n_items}")
@@ -471,8 +484,50 @@ class RankingPipeline:
             raise ValueError("recommend_many: one positive list per user row")
         if R == 0:
             return []
+        f = self._many_front(users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
+                             min_candidates)
+        info, seg, st, d_at = f["info"], f["seg"], f["st"], f["d_at"]
+        pos, lam, topk = info["pos"], info["lam"], info["topk"]
+        out_rows, out_logits = self._score_and_rank(R, f["cap"], f["n"], f["slots"], f["offsets"],
+                                                    d_at("users"), d_at("lam"), d_at("topk"),
+                                                    f["out_count"], f["status"], f["ws"], f["nb"],
+                                                    f["stream"])
+        # recommend() decides "lambda < 1" on the Python double and computes with its
+        # float32: a lambda that rounds to 1.0f from below goes its way
+        lam64 = info["lam64"]
+        odd = (lam64 < 1.0) != (lam < 1.0)
+        res = []
+        for r in range(R):
+            # above the batched kernels' capacity (or such a lambda): the one-request path
+            if st[r] & REQ_OVERFLOW or odd[r]:
+                pick = lambda v: None if v is None else v[r]
+                p_r = pos[info["pos_off"][r]:info["pos_off"][r + 1]]
+                res.append(self.recommend(int(users[r]), p_r, float(lam64[r]), int(topk[r]),
+                                          allowed=self._set_arg(pick(allowed)),
+                                          excluded=self._set_arg(pick(excluded)),
+                                          fallback=self._set_arg(pick(fallback)),
+                                          min_candidates=min_candidates))
+                continue
+            n_r = int(seg[r + 1] - seg[r])
+            # every candidate is a table row, so the MMR finds min(top_k, n_r) items
+            c_r = min(int(topk[r]), n_r) if lam[r] < 1.0 else n_r
+            o = int(seg[r])
+            res.append((out_rows[o:o + c_r], out_logits[o:o + c_r]))
+        return res
+
+    def _many_front(self, users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
+                    min_candidates, extra=(), pinned_tail=0):
+        """``recommend_many`` up to its one wait: the packed upload (``extra``:
+        further (name, array) pairs to carry along), the top-k or table lookup,
+        the candidates pass, the wait.  Returns what the calls behind the wait
+        need; ``tail``: ``pinned_tail`` bytes of the pinned buffer behind
+        everything this front uses."""
+        lib = _lib.load()
+        dev = self.device
+        R = users.size
         ins, info = self._pack_requests(users, positive_rows, lambda_param, top_k, allowed,
                                         excluded, fallback)
+        ins = ins + list(extra)
         pos, lam, topk, cap, S, n_adhoc = (info[k_] for k_ in ("pos", "lam", "topk", "cap", "S",
                                                                "n_adhoc"))
         k = self.n_neighbors
@@ -484,7 +539,8 @@ class RankingPipeline:
             total += (a.nbytes + 7) & ~7
         o_off = total
         o_st = o_off + 8 * (R + 1)
-        pin, host = self._pinned(o_st + ((4 * R + 7) & ~7))
+        o_tail = o_st + ((4 * R + 7) & ~7)
+        pin, host = self._pinned(o_tail + pinned_tail)
         for name, a in ins:
             host[at[name]:at[name] + a.nbytes] = a.view(np.uint8)
         dbuf = pin[:total].to(dev, non_blocking=True)
@@ -515,41 +571,26 @@ class RankingPipeline:
         st = host[o_st:o_st + 4 * R].view(np.int32)
         if (st & REQ_BAD_DATA).any():
             raise RuntimeError("recommend_many: the device rejected validated input")
-        out_rows, out_logits = self._score_and_rank(R, cap, n, slots, offsets, d_at("users"),
-                                                    d_at("lam"), d_at("topk"), out_count, status,
-                                                    ws, nb, stream)
-        # recommend() decides "lambda < 1" on the Python double and computes with its
-        # float32: a lambda that rounds to 1.0f from below goes its way
-        lam64 = info["lam64"]
-        odd = (lam64 < 1.0) != (lam < 1.0)
-        res = []
-        for r in range(R):
-            # above the batched kernels' capacity (or such a lambda): the one-request path
-            if st[r] & REQ_OVERFLOW or odd[r]:
-                pick = lambda v: None if v is None else v[r]
-                p_r = pos[info["pos_off"][r]:info["pos_off"][r + 1]]
-                res.append(self.recommend(int(users[r]), p_r, float(lam64[r]), int(topk[r]),
-                                          allowed=self._set_arg(pick(allowed)),
-                                          excluded=self._set_arg(pick(excluded)),
-                                          fallback=self._set_arg(pick(fallback)),
-                                          min_candidates=min_candidates))
-                continue
-            n_r = int(seg[r + 1] - seg[r])
-            # every candidate is a table row, so the MMR finds min(top_k, n_r) items
-            c_r = min(int(topk[r]), n_r) if lam[r] < 1.0 else n_r
-            o = int(seg[r])
-            res.append((out_rows[o:o + c_r], out_logits[o:o + c_r]))
-        return res
+        return dict(info=info, seg=seg, st=st, d_at=d_at, cap=cap, n=n, slots=slots, offsets=offsets,
+                    out_count=out_count, status=status, words=words, dbuf=dbuf, ws=ws, nb=nb,
+                    stream=stream, pin=pin, host=host, tail=o_tail)
 
     def _score_and_rank(self, R, cap, n, slots, offsets, d_users, d_lam, d_topk, out_count, status,
                         ws, nb, stream):
         """The batched calls' half behind the wait: the ranking batch of the n
         candidates, one forward, rank + MMR per segment -> (rows, logits) [n]."""
-        lib = _lib.load()
         dev = self.device
         if not n:
             return (torch.empty(0, dtype=torch.int64, device=dev),
                     torch.empty(0, dtype=torch.float32, device=dev))
+        logits = self._score_requests(R, cap, n, slots, offsets, d_users, stream)
+        return self._rank_mmr_requests(logits, R, cap, n, slots, offsets, d_lam, d_topk, out_count,
+                                       status, ws, nb, stream)
+
+    def _score_requests(self, R, cap, n, slots, offsets, d_users, stream):
+        """The ranking batch of the n > 0 candidates and one forward: logits [n]."""
+        lib = _lib.load()
+        dev = self.device
         K, F = self.item_cat.shape[1], self.item_num.shape[1]
         u = torch.empty(n, dtype=torch.int64, device=dev)
         i = torch.empty(n, dtype=torch.int64, device=dev)
@@ -561,7 +602,13 @@ class RankingPipeline:
             self.item_num.data_ptr() if F else None, F, self.n_items, u.data_ptr(),
             i.data_ptr(), c.data_ptr() if K else None, x.data_ptr() if F else None, stream),
             "dcnr_requests_ranking_batch")
-        logits = self.model(u, i, c, x).reshape(-1).to(torch.float32).contiguous()
+        return self.model(u, i, c, x).reshape(-1).to(torch.float32).contiguous()
+
+    def _rank_mmr_requests(self, logits, R, cap, n, slots, offsets, d_lam, d_topk, out_count, status,
+                           ws, nb, stream):
+        """Rank + MMR of every segment of ``logits`` (read only) -> (rows, logits) [n]."""
+        lib = _lib.load()
+        dev = self.device
         out_rows = torch.empty(n, dtype=torch.int64, device=dev)
         out_logits = torch.empty(n, dtype=torch.float32, device=dev)
         table, inv = self.index._table, self.index._inv
@@ -572,6 +619,163 @@ class RankingPipeline:
             out_count, status, ws.data_ptr(), nb, stream),
             "dcnr_requests_rank_mmr")
         return out_rows, out_logits
+
+    # ------------------------------------------------ what the answers look like
+    def _blank_relevant(self, relevant, R, skipped):
+        """``relevant`` as the host CSR of ``dcnr.metrics.relevant_csr``, the
+        sets of the ``skipped`` requests emptied."""
+        from . import metrics as mt
+        rows, off = mt.relevant_csr(relevant, R, self.index._table.shape[0])
+        if len(skipped):
+            keep = np.ones(R, bool)
+            keep[np.asarray(skipped, np.int64)] = False
+            lens = np.diff(off)
+            rows = rows[np.repeat(keep, lens)]
+            off = np.zeros(R + 1, np.int64)
+            np.cumsum(lens * keep, out=off[1:])
+        return rows, off
+
+    def list_metrics(self, answers, *, at: int = 20, info=None, relevant=None, ks=(5, 10, 20),
+                     per_list: bool = False):
+        """``dcnr.list_metrics`` of what ``recommend_many`` / ``recommend_users``
+        returned: a list of (rows, logits) pairs, concatenated on the device
+        (their lengths are known on the host; an answer that came from the
+        one-request path is concatenated like any other), measured against
+        this pipeline's index table, the logits as ``scores``.  An entry that
+        is None (a request ``lambda_sweep`` skipped) is an empty list whose
+        ``relevant`` set is ignored.  ``info`` / ``relevant`` / ``ks`` /
+        ``per_list`` as in ``dcnr.list_metrics``."""
+        from . import metrics as mt
+        dev = self.device
+        R = len(answers)
+        table, inv = self.index._table, self.index._inv
+        lens = np.array([0 if a is None else int(a[0].numel()) for a in answers], np.int64)
+        off = np.zeros(R + 1, np.int64)
+        np.cumsum(lens, out=off[1:])
+        n = int(off[R])
+        _, at, ks = mt._list_check(n, R + 1, None, tuple(table.shape), inv.numel(), at, None,
+                                   None if info is None else len(info), ks)
+        rel = None
+        if relevant is not None:
+            skipped = [r for r, a in enumerate(answers) if a is None]
+            rel = tuple(torch.from_numpy(a).to(dev) for a in self._blank_relevant(relevant, R, skipped))
+        if info is not None:
+            info = torch.as_tensor(info, dtype=torch.float64).reshape(-1).to(dev)
+        some = [a for a in answers if a is not None and a[0].numel()]
+        if some:
+            rows = torch.cat([a[0].to(dev, torch.int64) for a in some])
+            scores = torch.cat([a[1].to(dev, torch.float32) for a in some])
+        else:
+            rows = torch.empty(0, dtype=torch.int64, device=dev)
+            scores = torch.empty(0, dtype=torch.float32, device=dev)
+        return mt.list_metrics_raw(rows, torch.from_numpy(off).to(dev), None, table=table, inv_norms=inv,
+                                   at=at, scores=scores, info=info, relevant=rel, ks=ks,
+                                   per_list=per_list)
+
+    @torch.no_grad()
+    def lambda_sweep(self, user_rows, positive_rows, lambdas, top_k: int = 20, allowed=None,
+                     excluded=None, fallback=None, min_candidates: int = 20, relevant=None,
+                     info=None, ks=(5, 10, 20)):
+        """``recommend_many`` for several values of ``lambda_param`` with the
+        list metrics of each, the candidates scored ONCE: the front of
+        ``recommend_many`` (one upload, one top-k or table lookup, one
+        candidates pass, the one wait) and one forward; then per lambda one
+        rank + MMR launch and one ``dcnr_eval_list_metrics`` launch that reads
+        the answers and their counts where the first left them.  The
+        summaries are read together after the last launch.
+
+        lambdas     the values to compare (each one value for all requests)
+        top_k       one value, at most 128: the MMR's length and the metrics' ``at``
+        relevant, info, ks   as in ``dcnr.list_metrics`` (one entry per request)
+
+        Returns ``SweepResult``: a list of ``(answers, ListMetrics)``, one per
+        lambda, ``answers`` as ``recommend_many`` returns them; ``.lambdas``;
+        ``.skipped``: the indices of requests the batched kernels hand back
+        (candidates above SV_MAX -- or every request, when some lambda rounds
+        to 1.0f from below: decided on the host, nothing is launched then).  Their entry in every ``answers`` is None, never
+        a truncated list, and they take part in no metric but ``n_lists``:
+        serve them with ``recommend()``."""
+        from . import metrics as mt
+        dev = self.device
+        if self.index._table.shape[0] != self.n_items:
+            raise ValueError(f"lambda_sweep: the index holds {self.index._table.shape[0]} rows, "
+                             f"item_cat / item_num {self.n_items}")
+        users = np.asarray(user_rows, dtype=np.int64).reshape(-1)
+        R = users.size
+        if len(positive_rows) != R:
+            raise ValueError("lambda_sweep: one positive list per user row")
+        lam64 = np.asarray(list(lambdas), np.float64).reshape(-1)
+        L = lam64.size
+        if L == 0 or R == 0:
+            raise ValueError("lambda_sweep: no lambda, or no request")
+        if not np.isscalar(top_k):
+            raise ValueError("lambda_sweep: one top_k for all requests")
+        table, inv = self.index._table, self.index._inv
+        _, at, ks = mt._list_check(0, R + 1, R, tuple(table.shape), inv.numel(), top_k, None,
+                                   None if info is None else len(info), ks)
+        out = SweepResult()
+        out.lambdas = tuple(float(v) for v in lam64)
+        rel_host = None
+        if relevant is not None:   # validated before anything is launched
+            rel_host = mt.relevant_csr(relevant, R, table.shape[0])
+        if info is not None:
+            info = torch.as_tensor(info, dtype=torch.float64).reshape(-1).to(dev)
+        lam32 = lam64.astype(np.float32)
+        if ((lam64 < 1.0) != (lam32 < 1.0)).any():
+            # a lambda that rounds to 1.0f from below: recommend() would take its MMR branch, the
+            # kernels would not, so the batched kernels serve no request of this sweep.  Known
+            # here: the rows are validated as usual and nothing is launched.
+            self._pack_requests(users, positive_rows, float(lam64[0]), int(top_k), allowed, excluded,
+                                fallback)
+            out.skipped = list(range(R))
+            for _ in range(L):
+                out.append(([None] * R, mt.empty_list_metrics(R, ks)))
+            return out
+        lams = np.repeat(lam32, R)                     # [L][R]: one lambda array per launch
+        tail = 8 * (rel_host[0].size + R + 1) if rel_host is not None else 0
+        f = self._many_front(users, positive_rows, float(lam64[0]), int(top_k), allowed, excluded,
+                             fallback, min_candidates, extra=[("lams", lams)], pinned_tail=tail)
+        seg, st, d_at, n, cap = f["seg"], f["st"], f["d_at"], f["n"], f["cap"]
+        stream = f["stream"]
+        skip = (st & REQ_OVERFLOW).astype(bool)
+        out.skipped = np.flatnonzero(skip).tolist()
+        # ---- the held-out sets without the skipped requests': pinned, no wait
+        rel = None
+        if rel_host is not None:
+            rr, ro = self._blank_relevant(rel_host, R, out.skipped)
+            o = f["tail"]
+            f["host"][o:o + 8 * (R + 1)] = ro.view(np.uint8)
+            f["host"][o + 8 * (R + 1):o + 8 * (R + 1) + 8 * rr.size] = rr.view(np.uint8)
+            d_rel = f["pin"][o:o + 8 * (R + 1 + rr.size)].to(dev, non_blocking=True).view(torch.int64)
+            rel = (d_rel[R + 1:], d_rel[:R + 1])
+        n_seg = np.diff(seg)
+        nsum = ctypes.sizeof(_lib.ListSummaryStruct)
+        sums = torch.empty((L, nsum), dtype=torch.uint8, device=dev)
+        mws = torch.empty(mt.list_workspace_bytes(R, table.shape[0]), dtype=torch.uint8, device=dev)
+        logits = self._score_requests(R, cap, n, f["slots"], f["offsets"], d_at("users"), stream) \
+            if n else torch.empty(0, dtype=torch.float32, device=dev)
+        per = []
+        for j in range(L):
+            counts = torch.empty(R, dtype=torch.int32, device=dev)   # this lambda's out_count
+            if n:
+                rows_j, logits_j = self._rank_mmr_requests(
+                    logits, R, cap, n, f["slots"], f["offsets"], d_at("lams") + 4 * R * j,
+                    d_at("topk"), counts.data_ptr(), f["status"], f["ws"], f["nb"], stream)
+            else:
+                rows_j = torch.empty(0, dtype=torch.int64, device=dev)
+                logits_j = torch.empty(0, dtype=torch.float32, device=dev)
+                counts.zero_()
+            mt._list_launch(rows_j, f["offsets"], counts, table, inv, at,
+                            logits_j, info, rel, ks, False, mws, out=sums[j])
+            # every candidate is a table row, so the MMR finds min(top_k, n_r) items
+            cnt = np.where(lam32[j] < 1.0, np.minimum(int(top_k), n_seg), n_seg)
+            per.append([None if skip[r] else
+                        (rows_j[int(seg[r]):int(seg[r]) + int(cnt[r])],
+                         logits_j[int(seg[r]):int(seg[r]) + int(cnt[r])]) for r in range(R)])
+        raw = sums.cpu().numpy()                           # every summary, one copy
+        for j in range(L):
+            out.append((per[j], mt._list_result(raw[j].tobytes(), ks, None)))
+        return out
 
     # --------------------------------------------- a batch of requests by user
     @torch.no_grad()

@@ -42,6 +42,9 @@
  *                         over the validation logits          train.py:255-265, 366-387
  *   dcnr_eval_group_metrics  GAUC, NDCG@k, hit rate@k, recall@k and MRR of every
  *                         user's (or item's) list in the order main.py:325 serves it
+ *   dcnr_eval_list_metrics   what the served lists look like under lambda_param
+ *                         (rerank_with_mmr, main.py:133-169): intra-list diversity,
+ *                         coverage, Gini of the exposure, mean weight, held-out hits
  *
  * Conventions
  *  - All tensor pointers are DEVICE pointers owned by the caller; the
@@ -433,6 +436,91 @@ dcnr_status dcnr_eval_group_metrics(const float* logits, const float* labels, co
                                     const double* discount, const double* ideal,
                                     dcnr_group_summary* out, dcnr_group_record* per_group, void* ws,
                                     size_t ws_bytes, dcnr_stream_t stream);
+
+/* List metrics: what R served lists look like, read where the batched serving
+ * calls left them (the out_rows / offsets / out_count of
+ * dcnr_requests_rank_mmr), with no read-back.  List r is
+ * rows[offsets[r] .. offsets[r] + counts[r]); its first m_r = min(counts[r],
+ * at) positions are measured.  Both structs are written to DEVICE memory,
+ * stream-ordered. */
+typedef struct {          /* one list; 112 bytes; all zero for a list that is skipped */
+  int64_t m;              /* measured positions */
+  int64_t n_rel;          /* size of the list's held-out set */
+  int64_t first_hit_rank; /* 1-based position of the first held-out row, 0 for none */
+  int64_t hits[DCNR_GROUP_MAX_K]; /* held-out rows at positions <= ks[j] */
+  double pair_cos_sum;    /* sum over i < j < m of cos(e_i, e_j): each cosine in fp32 from
+                             table and inv_norms as given, the sum in fp64, fixed order */
+  double score_sum;       /* sum of scores over the m positions (0 without scores) */
+  double info_sum;        /* sum of info[row] over the m positions (0 without info) */
+  double dcg[DCNR_GROUP_MAX_K];   /* sum of discount[p] over held-out rows at position p < ks[j] */
+} dcnr_list_record;
+
+typedef struct {          /* 248 bytes */
+  int64_t n_lists;        /* R */
+  int64_t n_lists_scored; /* measured lists with m >= 1 */
+  int64_t n_lists_pairs;  /* measured lists with m >= 2 */
+  int64_t n_marked;       /* lists whose segment begins with row -1 (the "whole answer
+                             marked" of dcnr_requests_rank_mmr, which also sets the count
+                             to 0): skipped */
+  int64_t n_bad_list;     /* an offset or count outside [0, n], beyond its segment or not
+                             monotone, held-out offsets outside their CSR, or one of the m rows
+                             >= n_items or < 0 (a -1 behind the first position too): skipped */
+  int64_t n_entries;      /* sum of m over the measured lists */
+  int64_t n_distinct_items; /* items in at least one measured position */
+  int64_t gini_num;       /* sum over i = 1 .. n_items of (2 i - n_items - 1) c_(i), c_(i) the
+                             items' exposure counts ascending, the zeros included */
+  int64_t n_rel_lists;    /* measured lists with n_rel > 0 */
+  int64_t hit_lists[DCNR_GROUP_MAX_K]; /* of those, lists with hits[j] > 0 */
+  double ild;             /* mean over the lists with m >= 2 of 1 - pair_cos_sum / (m (m - 1) / 2) */
+  double mean_score;      /* sum of score_sum / n_entries (NaN without scores) */
+  double mean_info;       /* sum of info_sum / n_entries (NaN without info) */
+  double mrr;             /* mean over the n_rel_lists of 1 / first_hit_rank (0 for no hit) */
+  double coverage;        /* n_distinct_items / n_items */
+  double gini;            /* gini_num / (n_items * n_entries) */
+  double hit_rate[DCNR_GROUP_MAX_K]; /* hit_lists[j] / n_rel_lists */
+  double recall[DCNR_GROUP_MAX_K];   /* mean of hits[j] / n_rel over the n_rel_lists */
+  double ndcg[DCNR_GROUP_MAX_K];     /* mean of dcg[j] / ideal[min(ks[j], n_rel) - 1], likewise */
+} dcnr_list_summary;      /* a mean over nothing, and entries j >= n_k, are NaN (counts 0) */
+
+/* Workspace bytes of dcnr_eval_list_metrics: the exposure counts (4 n_items),
+ * the count-of-counts histogram (4 (R + 1)), a few words and the workgroups'
+ * partial sums (< 400 KiB); the call clears what it needs on the stream.  0
+ * for R <= 0, n_items < 1 and shapes the call rejects. */
+size_t dcnr_eval_list_metrics_workspace_size(int64_t R, int64_t n_items);
+
+/* rows int64 [n], offsets int64 [R + 1], counts int32 [R] or NULL (whole
+ * segments), all on the device; at in 1..128.  table fp32 [n_items][d] with
+ * inv_norms [n_items] is the pair dcnr_requests_rank_mmr takes, d in 1..256;
+ * a cosine is the fp32 dot of the two rows, each times its inverse norm as
+ * given (a zero-norm row's cosines are whatever its inv_norms entry makes
+ * them).  scores fp32 [n] (the logits beside the rows) or NULL; info fp64
+ * [n_items] (a per-item weight) or NULL.  The held-out sets or NULLs:
+ * rel_rows int64 [n_rel_rows] with rel_offsets [R + 1], each set ascending
+ * and distinct.  ks: n_k (0..DCNR_GROUP_MAX_K) cutoffs on the HOST, strictly
+ * ascending, each in [1, at]; discount and ideal as for
+ * dcnr_eval_group_metrics (ks[n_k - 1] doubles; read only with held-out
+ * sets).  per_list: NULL or R records, every one written.
+ *
+ * DCNR_BAD_ARG (R, n or n_rel_rows < 0, n_items < 1, at or d out of range, bad
+ * ks, a null pointer that is needed), DCNR_UNSUPPORTED_SHAPE (n > 2^30,
+ * n_items >= 2^31, R > 2^22: inside these every partial sum of gini_num is
+ * below n_entries * 2^32 < 2^63) and DCNR_WORKSPACE_TOO_SMALL come before any
+ * launch.  R = 0 writes a summary of zeros with NaN means (coverage 0) and
+ * reads nothing else.  No state outside ws and stream.  The exposure counts
+ * and every other integer are exact and independent of the order of
+ * execution; every fp64 sum is taken in an order fixed by (R, at): the same
+ * input gives the same bytes in the summary and in every record.  Every index
+ * is checked against a length passed by value: a bad list is counted and
+ * skipped, the other lists are unaffected. */
+dcnr_status dcnr_eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* offsets,
+                                   const int32_t* counts, int64_t R, int32_t at,
+                                   const float* table, const float* inv_norms, int32_t d,
+                                   int64_t n_items, const float* scores, const double* info,
+                                   const int64_t* rel_rows, int64_t n_rel_rows,
+                                   const int64_t* rel_offsets, const int32_t* ks, int32_t n_k,
+                                   const double* discount, const double* ideal,
+                                   dcnr_list_summary* out, dcnr_list_record* per_list, void* ws,
+                                   size_t ws_bytes, dcnr_stream_t stream);
 
 /* One torch.optim.AdamW (decoupled = 1) or Adam (decoupled = 0) step over
  * n_tensors tensors (host arrays of device pointers + element counts).
