@@ -2210,6 +2210,50 @@ dcnr_status dcnr_cosine_topk(const float* table, const float* inv_norms, int64_t
                                  stream);
 }
 
+size_t dcnr_cosine_topk_within_workspace_size(int64_t Q, int32_t k, int32_t d, int64_t max_set_rows) {
+  return cosine_topk_within_ws(Q, k, d, max_set_rows);   // (0 for what the call rejects)
+}
+
+dcnr_status dcnr_cosine_topk_within(const float* table, const float* inv_norms, int64_t N, int32_t d,
+                                    const float* queries, int64_t Q, const int64_t* exclude,
+                                    const int64_t* seg_offsets, int64_t G, const int32_t* seg_set,
+                                    const int64_t* set_rows, int64_t n_set_rows, const int64_t* set_offsets,
+                                    int32_t S, int64_t max_set_rows, int32_t k, int64_t ld, int64_t* idx,
+                                    float* dist, int32_t* seg_status, void* ws, size_t ws_bytes,
+                                    dcnr_stream_t stream) {
+  if (Q < 0 || G < 0 || S < 0 || N < 1 || n_set_rows < 0 || max_set_rows < 0 || k < 1 || ld < k) {
+    set_error("dcnr_cosine_topk_within: bad argument (N=%lld, Q=%lld, G=%lld, S=%d, k=%d, ld=%lld, "
+              "n_set_rows=%lld, max_set_rows=%lld)", (long long)N, (long long)Q, (long long)G, S, k,
+              (long long)ld, (long long)n_set_rows, (long long)max_set_rows);
+    return DCNR_BAD_ARG;
+  }
+  // (set_rows may be null when the CSR holds no row)
+  if (Q > 0 && (!table || !inv_norms || !queries || !idx || !dist || !ws ||
+                (G > 0 && (!seg_offsets || !seg_set || !set_offsets || (n_set_rows > 0 && !set_rows))))) {
+    set_error("dcnr_cosine_topk_within: null argument");
+    return DCNR_BAD_ARG;
+  }
+  if (k > 64 || d % 4 || d < 4 || d > 256 || N > INT32_MAX || n_set_rows > INT32_MAX ||
+      max_set_rows > INT32_MAX || Q > INT32_MAX || G > INT32_MAX) {
+    set_error("dcnr_cosine_topk_within: unsupported k=%d d=%d N=%lld n_set_rows=%lld Q=%lld G=%lld "
+              "(k<=64, d%%4==0, 4<=d<=256, the rest below 2^31)", k, d, (long long)N, (long long)n_set_rows,
+              (long long)Q, (long long)G);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  if (Q == 0 || G == 0) return DCNR_OK;   // (no query, or none in a segment: nothing is written)
+  if (ws_bytes < cosine_topk_within_ws(Q, k, d, max_set_rows)) {
+    set_error("dcnr_cosine_topk_within: workspace too small");
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // (bytes: the longest set once per window of 8 queries)
+  TRYB(DCNR_K_KNN, s, (double)((Q + 7) / 8) * (double)max_set_rows * (4.0 * d + 12.0),
+       cosine_topk_within(table, inv_norms, N, d, queries, Q, exclude, seg_offsets, G, seg_set, set_rows,
+                          n_set_rows, set_offsets, S, max_set_rows, k, ld, idx, dist, seg_status, ws, ws_bytes,
+                          s));
+  return DCNR_OK;
+}
+
 size_t dcnr_cosine_neighbor_table_workspace_size(int64_t N, int32_t k) {
   if (N < 1 || N > INT32_MAX || k < 1 || k > 64 || k > N) return 256;   // (the build rejects these)
   return neighbor_table_ws(N, k);   // (exact: one byte less is DCNR_WORKSPACE_TOO_SMALL)

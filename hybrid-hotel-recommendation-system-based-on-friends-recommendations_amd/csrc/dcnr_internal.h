@@ -798,6 +798,14 @@ dcnr_status topk_merge(const float* dist, const int64_t* idx, int lists, int64_t
 dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_t N, int d,
                         const float* q, int64_t Q, int k, int64_t* idx, float* dist, void* ws,
                         size_t ws_bytes, hipStream_t s, bool allow_v3 = true);
+// the set-scoped search (dcnr_cosine_topk_within; arguments already judged):
+// 0 from the size query for a shape the search does not take
+size_t cosine_topk_within_ws(int64_t Q, int k, int d, int64_t max_set_rows);
+dcnr_status cosine_topk_within(const float* t, const float* inv, int64_t N, int d, const float* q, int64_t Q,
+                               const int64_t* excl, const int64_t* seg_off, int64_t G, const int* seg_set,
+                               const int64_t* set_rows, int64_t n_set_rows, const int64_t* set_off, int S,
+                               int64_t max_set_rows, int k, int64_t ld, int64_t* idx, float* dist,
+                               int* seg_status, void* ws, size_t ws_bytes, hipStream_t s);
 // rows [row_lo, row_hi) of the item neighbour table: out_idx [rows][k] int32
 // (and out_dist, or null) = cosine_topk of each table row as a single query
 size_t neighbor_table_ws(int64_t N, int k);

@@ -25,6 +25,10 @@
 //    by an in-LDS bitonic sort (ties by index: deterministic).
 // v1-v3 end in merge_kernel (the slices' k-lists per query).
 //
+// cosine_topk_within() is the same search over a listed subset of the rows (a
+// city's hotels), per segment of queries: scan v2's / v1's loops over a row
+// list, merge_kernel's block at the end (section behind cosine_topk).
+//
 // neighbor_table() builds the item neighbour table from these: every table
 // row's own top-k, chunk by chunk, scan v3 left out (section at the end).
 #include "dcnr_internal.h"
@@ -1538,17 +1542,14 @@ __global__ __launch_bounds__(B4_T) void rescore_kernel(const float* __restrict__
 // running k-th best and compacted in LDS.
 constexpr int MT = 16;
 constexpr int FT = 24;   // fast path: candidates loaded per thread per round
-__global__ __launch_bounds__(NT) void merge_kernel(const Cand* in, int nl, int k, int64_t* idx,
-                                                   float* dist) {
+// (the block's work: one query's lists c [nl][k] -> idx / dist [k]; shared by
+// merge_kernel and the set-scoped search's merge, whose output rows are strided)
+__device__ __forceinline__ void merge_block(const Cand* c, int nl, int k, int64_t* idx, float* dist) {
   __shared__ float cd[CAP];
   __shared__ int ci[CAP];
   __shared__ int cnt;
   __shared__ float thr;
-  const int64_t qq = blockIdx.x;
-  const Cand* c = in + qq * (int64_t)nl * k;
   const int total = nl * k;
-  idx += qq * k;
-  dist += qq * k;
   // fast path 0 (one load round, up to 4 lists per thread): the k-th smallest
   // of the lists' minima bounds the k-th best overall (k lists each hold a
   // candidate at or under it), so only the candidates at or under that bound
@@ -1647,6 +1648,12 @@ __global__ __launch_bounds__(NT) void merge_kernel(const Cand* in, int nl, int k
     idx[t] = ok ? (int64_t)ci[t] : -1;
     dist[t] = ok ? cd[t] : FLT_MAX;
   }
+}
+
+__global__ __launch_bounds__(NT) void merge_kernel(const Cand* in, int nl, int k, int64_t* idx,
+                                                   float* dist) {
+  const int64_t qq = blockIdx.x;
+  merge_block(in + qq * (int64_t)nl * k, nl, k, idx + qq * k, dist + qq * k);
 }
 
 // Per query: the k best of `lists` k-lists [lists][Q][k] (dist, int64 row),
@@ -1932,6 +1939,399 @@ dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_
   });
   DCNR_LAUNCH_CHECK();
   return merge_lists(w.cands, Q, w.ns, k, idx, dist, s);
+}
+
+// ---- the set-scoped search: the k nearest rows within a row set
+//
+// A call carries G segments of queries; segment g searches the rows listed in
+// set seg_set[g] of a CSR of row sets (a city's hotels) instead of the table.
+// Three launches, no device word read by the host:
+//   * within_prep_kernel: one wave per query normalises it, with the
+//     expression of the scan cosine_topk takes at this (d, k) -- the two
+//     round differently (see there); one wave per segment checks the segment's offsets, its set index and the
+//     set's offsets against the lengths passed by value and writes a record
+//     (set start, set length or W_SKIP / W_BAD, segment) for each of its
+//     queries.  Later kernels use a record only after checking that its
+//     segment does hold the query, so a workspace's stale bytes are never
+//     followed: a segment that holds a query has overwritten its record.
+//   * within_scan_kernel (d <= 64, k <= 32: scan v2's wave-register lists) /
+//     within_scan_wide_kernel (the rest: scan v1's LDS buffers and bitonic
+//     compaction): work item (window of W_BQ consecutive queries, chunk of
+//     rpi set positions).  The window's queries are grouped by segment -- one
+//     group when the segments are multiples of W_BQ long, as requests of 8
+//     positives are -- and each group's chunk is read once: a lane loads one
+//     listed row (its id, checked against N; its inverse norm; its d floats as
+//     16-B loads) and scores it against the group's queries.  The k-lists
+//     hold table rows, so the merge needs no second mapping.  A row outside
+//     [0, N) is never dereferenced: it marks the group's records W_BAD.
+//   * within_merge_kernel: merge_kernel's block over the query's chunk lists,
+//     written at the caller's row stride; W_BAD and empty sets are padded,
+//     W_SKIP and queries no segment holds are left as they were.
+// rpi, and with it the chunk count, follows from max_set_rows on the host.
+// Rows reach a wave in set order and are admitted strictly under the k-th
+// best, so ties keep (distance, row) order when the set is ascending.
+constexpr int W_BQ = QT;            // queries per work item
+constexpr int64_t W_RPI = 1024;     // set positions per work item, at least
+constexpr int W_CHUNKS = 256;       // ... and at most this many chunks
+constexpr int W_SKIP = -1, W_BAD = -2;
+struct WithinQ { int64_t lo; int len; int seg; };
+
+namespace {
+
+__global__ __launch_bounds__(256) void within_prep_kernel(
+    const float* __restrict__ q, int64_t Q, int d, int lane_form, float* __restrict__ qn,
+    const int64_t* __restrict__ seg_off,
+    int64_t G, const int* __restrict__ seg_set, const int64_t* __restrict__ set_off, int S, int64_t n_set_rows,
+    int64_t max_set_rows, int64_t qblocks, WithinQ* recs, int* seg_status) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if ((int64_t)blockIdx.x < qblocks) {
+    const int64_t qq = (int64_t)blockIdx.x * 4 + w;
+    if (qq >= Q) return;
+    if (lane_form) {
+      // kth_bound_kernel's / bound5_kernel's wave_sum(v * v), one element per
+      // lane, as the compiler contracts it there: the first butterfly step is
+      // fma(v, v, the partner's rounded square), so the sum, and with it the
+      // scale, may differ between lanes by an ulp -- spelled out, because the
+      // answers are compared with those kernels' bit for bit
+      const float v = lane < d ? q[qq * d + lane] : 0.f;
+      float s = fmaf(v, v, __shfl_xor(v * v, 32, 64));
+#pragma unroll
+      for (int o = 16; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+      const float in = s > 0.f ? 1.f / sqrtf(s) : 1.f;
+      if (lane < d) qn[qq * d + lane] = v * in;
+      return;
+    }
+    // scan v1's (scan_kernel's) form
+    float s = 0.f;
+    for (int i = lane; i < d; i += 64) { float v = q[qq * d + i]; s += v * v; }
+    s = wave_sum(s);
+    float in = s > 0.f ? 1.f / sqrtf(s) : 1.f;
+    for (int i = lane; i < d; i += 64) qn[qq * d + i] = q[qq * d + i] * in;
+    return;
+  }
+  const int64_t g = ((int64_t)blockIdx.x - qblocks) * 4 + w;
+  if (g >= G) return;
+  const int64_t a = seg_off[g], b = seg_off[g + 1];
+  const int s = seg_set[g];
+  WithinQ r{0, 0, (int)g};
+  if (s < 0) {
+    r.len = W_SKIP;
+  } else if (a < 0 || b < a || b > Q || s >= S) {
+    r.len = W_BAD;
+  } else {
+    const int64_t lo = set_off[s], hi = set_off[s + 1];
+    if (lo < 0 || hi < lo || hi > n_set_rows || hi - lo > max_set_rows) r.len = W_BAD;
+    else { r.lo = lo; r.len = (int)(hi - lo); }
+  }
+  if (seg_status && lane == 0) seg_status[g] = r.len == W_BAD ? DCNR_REQ_BAD_DATA : 0;
+  // (every query the segment holds, even when its other offset is out of range)
+  const int64_t q0 = a < 0 ? 0 : a, q1 = b > Q ? Q : b;
+  for (int64_t qq = q0 + lane; qq < q1; qq += 64) recs[qq] = r;
+}
+
+// the record of query qq when its segment does hold it, else a skipped one
+__device__ __forceinline__ WithinQ within_record(const WithinQ* recs, const int64_t* __restrict__ seg_off,
+                                                 int64_t G, int64_t qq) {
+  WithinQ r = recs[qq];
+  const bool held = r.seg >= 0 && r.seg < G && seg_off[r.seg] <= qq && qq < seg_off[r.seg + 1];
+  if (!held) r = WithinQ{0, W_SKIP, -1};
+  return r;
+}
+
+// The window's groups, one at a time: next_group() gives the slots (bit qq =
+// query q0 + qq) of the first pending slot's segment and that set's start and
+// length.  wlen[qq] > p0 marks a slot with rows in this chunk.  (uniform)
+__device__ __forceinline__ unsigned within_next_group(unsigned& pend, const int* wseg) {
+  const int f = __ffs(pend) - 1;
+  unsigned grp = 0;
+#pragma unroll
+  for (int qq = 0; qq < W_BQ; ++qq)
+    if (((pend >> qq) & 1u) && wseg[qq] == wseg[f]) grp |= 1u << qq;
+  grp = __builtin_amdgcn_readfirstlane(grp);
+  pend &= ~grp;
+  return grp;
+}
+
+// a row outside [0, N) was listed: the group's queries are padded, its segment flagged
+__device__ __forceinline__ void within_mark_bad(unsigned grp, int64_t q0, WithinQ* recs, int seg, int* seg_status) {
+  for (int qq = 0; qq < W_BQ; ++qq)
+    if ((grp >> qq) & 1u) recs[q0 + qq].len = W_BAD;
+  if (seg_status) seg_status[seg] = DCNR_REQ_BAD_DATA;
+}
+
+template <int DV>
+__global__ __launch_bounds__(K2_NT) void within_scan_kernel(
+    const float* __restrict__ tab, const float* __restrict__ inv, int64_t N, const float* __restrict__ qn,
+    int64_t Q, const int64_t* __restrict__ excl, const int64_t* __restrict__ seg_off, int64_t G,
+    const int64_t* __restrict__ set_rows, WithinQ* recs, int64_t rpi, int nchunks, int k, Cand* lists,
+    int* seg_status) {
+  __shared__ float cd[K2_WPB][W_BQ][K2_CAP];
+  __shared__ int ci[K2_WPB][W_BQ][K2_CAP];
+  __shared__ int cntl[K2_WPB][W_BQ];
+  __shared__ int64_t wlo[W_BQ];
+  __shared__ int wlen[W_BQ], wseg[W_BQ], wex[W_BQ];
+  const int chunk = (int)(blockIdx.x % (unsigned)nchunks);
+  const int64_t q0 = (int64_t)(blockIdx.x / (unsigned)nchunks) * W_BQ;
+  const int64_t p0 = (int64_t)chunk * rpi;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (threadIdx.x < W_BQ) {
+    const int64_t qq = q0 + threadIdx.x;
+    WithinQ r{0, W_SKIP, -1};
+    int64_t e = -1;
+    if (qq < Q) {
+      r = within_record(recs, seg_off, G, qq);
+      if (excl) e = excl[qq];
+    }
+    wlo[threadIdx.x] = r.lo;
+    wlen[threadIdx.x] = r.len;
+    wseg[threadIdx.x] = r.seg;
+    wex[threadIdx.x] = e >= 0 && e < N ? (int)e : -1;
+  }
+  __syncthreads();
+  unsigned pend = 0;
+#pragma unroll
+  for (int qq = 0; qq < W_BQ; ++qq)
+    if ((int64_t)wlen[qq] > p0) pend |= 1u << qq;
+  pend = __builtin_amdgcn_readfirstlane(pend);
+  const unsigned act = pend;
+  if (!act) return;
+  // slot qq's list count and k-th best of this wave live in lane qq
+  int cntv = 0;
+  float thrv = FLT_MAX;
+  const float4* qv = reinterpret_cast<const float4*>(qn + q0 * DV * 4);
+  while (pend) {
+    const int f = __ffs(pend) - 1;
+    const unsigned grp = within_next_group(pend, wseg);
+    const int64_t lo = wlo[f];
+    const int64_t p1 = min<int64_t>(wlen[f], p0 + rpi);
+    bool bad = false;
+    for (int64_t base = p0 + 64 * w; base < p1; base += 64 * K2_WPB) {
+      const int64_t p = base + lane;
+      bool ok = p < p1;
+      int64_t r = ok ? set_rows[lo + p] : 0;
+      if (r < 0 || r >= N) { bad = true; ok = false; r = 0; }
+      float4 x[DV];
+      load_row<DV>(tab, r, x);
+      const float ir = inv[r];
+#pragma unroll 1
+      for (int qq = 0; qq < W_BQ; ++qq) {
+        if (!((grp >> qq) & 1u)) continue;   // (uniform)
+        const float dist = exact_dist<DV>(x, qv + qq * DV, ir);
+        float th = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(thrv), qq));
+        const bool cand = ok && (int)r != wex[qq];
+        if (!__ballot(cand && dist < th)) continue;
+        int c = __builtin_amdgcn_readlane(cntv, qq);
+        wave_admit(cd[w][qq], ci[w][qq], c, th, k, lane, cand, dist, r);
+        cntv = lane == qq ? c : cntv;
+        thrv = lane == qq ? th : thrv;
+      }
+    }
+    if (__ballot(bad) && lane == 0) within_mark_bad(grp, q0, recs, wseg[f], seg_status);
+  }
+  for (int qq = 0; qq < W_BQ; ++qq) {
+    if (!((act >> qq) & 1u)) continue;
+    float th;
+    const int c = wave_compact(cd[w][qq], ci[w][qq], __builtin_amdgcn_readlane(cntv, qq), k, lane, &th);
+    if (lane == 0) cntl[w][qq] = c;
+  }
+  __syncthreads();
+  for (int qq = w; qq < W_BQ; qq += K2_WPB) {
+    if (!((act >> qq) & 1u)) continue;
+    float d;
+    int i;
+    wave_merge_lists<K2_WPB>(cd[0][qq], ci[0][qq], &cntl[0][qq], W_BQ * K2_CAP, W_BQ, k, lane, d, i);
+    Cand* o = lists + ((q0 + qq) * nchunks + chunk) * (int64_t)k;
+    if (lane < k) o[lane] = Cand{d, i};
+  }
+}
+
+template <int MAXV>
+__global__ __launch_bounds__(NT) void within_scan_wide_kernel(
+    const float* __restrict__ tab, const float* __restrict__ inv, int64_t N, int d, const float* __restrict__ qn,
+    int64_t Q, const int64_t* __restrict__ excl, const int64_t* __restrict__ seg_off, int64_t G,
+    const int64_t* __restrict__ set_rows, WithinQ* recs, int64_t rpi, int nchunks, int k, Cand* lists,
+    int* seg_status) {
+  __shared__ __attribute__((aligned(16))) float qs[W_BQ][MAXV * 4];
+  __shared__ float cd[W_BQ][CAP];
+  __shared__ int ci[W_BQ][CAP];
+  __shared__ int cnt[W_BQ];
+  __shared__ float thr[W_BQ];
+  __shared__ int64_t wlo[W_BQ];
+  __shared__ int wlen[W_BQ], wseg[W_BQ], wex[W_BQ];
+  __shared__ int badf;
+  const int chunk = (int)(blockIdx.x % (unsigned)nchunks);
+  const int64_t q0 = (int64_t)(blockIdx.x / (unsigned)nchunks) * W_BQ;
+  const int64_t p0 = (int64_t)chunk * rpi;
+  const int nq = (int)min<int64_t>(W_BQ, Q - q0);
+  if (threadIdx.x < W_BQ) {
+    const int64_t qq = q0 + threadIdx.x;
+    WithinQ r{0, W_SKIP, -1};
+    int64_t e = -1;
+    if (qq < Q) {
+      r = within_record(recs, seg_off, G, qq);
+      if (excl) e = excl[qq];
+    }
+    wlo[threadIdx.x] = r.lo;
+    wlen[threadIdx.x] = r.len;
+    wseg[threadIdx.x] = r.seg;
+    wex[threadIdx.x] = e >= 0 && e < N ? (int)e : -1;
+    cnt[threadIdx.x] = 0;
+    thr[threadIdx.x] = FLT_MAX;
+  }
+  if (threadIdx.x == 0) badf = 0;
+  for (int i = threadIdx.x; i < nq * d; i += NT) qs[i / d][i % d] = qn[q0 * d + i];
+  __syncthreads();
+  unsigned pend = 0;
+#pragma unroll
+  for (int qq = 0; qq < W_BQ; ++qq)
+    if ((int64_t)wlen[qq] > p0) pend |= 1u << qq;
+  pend = __builtin_amdgcn_readfirstlane(pend);
+  const unsigned act = pend;
+  if (!act) return;
+  const int dv = d >> 2;
+  while (pend) {
+    const int f = __ffs(pend) - 1;
+    const unsigned grp = within_next_group(pend, wseg);
+    const int64_t lo = wlo[f];
+    const int64_t p1 = min<int64_t>(wlen[f], p0 + rpi);
+    for (int64_t base = p0; base < p1; base += NT) {
+      const int64_t p = base + threadIdx.x;
+      if (p < p1) {
+        const int64_t r = set_rows[lo + p];
+        if (r < 0 || r >= N) {
+          badf = 1;
+        } else {
+          float4 x[MAXV];
+          const float4* rp = reinterpret_cast<const float4*>(tab + r * d);
+#pragma unroll
+          for (int v = 0; v < MAXV; ++v) if (v < dv) x[v] = rp[v];
+          const float ir = inv[r];
+          for (int qq = 0; qq < W_BQ; ++qq) {
+            if (!((grp >> qq) & 1u)) continue;
+            const float4* qp = reinterpret_cast<const float4*>(qs[qq]);
+            float s = 0.f;
+#pragma unroll
+            for (int v = 0; v < MAXV; ++v)
+              if (v < dv) {
+                float4 wq = qp[v];
+                s += dot4(x[v], wq);
+              }
+            float dist = cos_dist(s, ir);
+            if (dist <= thr[qq] && (int)r != wex[qq]) {
+              int pos = atomicAdd(&cnt[qq], 1);
+              cd[qq][pos] = dist;
+              ci[qq][pos] = (int)r;
+            }
+          }
+        }
+      }
+      __syncthreads();
+      for (int qq = 0; qq < W_BQ; ++qq) {
+        if (cnt[qq] > CAP - NT) compact(cd[qq], ci[qq], &cnt[qq], &thr[qq], k);
+      }
+      __syncthreads();   // (no append of the next step before every thread has read the counts)
+    }
+    if (badf) {   // (uniform: read after the barrier, reset behind the next one)
+      if (threadIdx.x == 0) within_mark_bad(grp, q0, recs, wseg[f], seg_status);
+      __syncthreads();
+      if (threadIdx.x == 0) badf = 0;
+    }
+  }
+  for (int qq = 0; qq < W_BQ; ++qq) {
+    if (!((act >> qq) & 1u)) continue;
+    compact(cd[qq], ci[qq], &cnt[qq], &thr[qq], k);
+    Cand* o = lists + ((q0 + qq) * nchunks + chunk) * (int64_t)k;
+    for (int t = threadIdx.x; t < k; t += NT) {
+      bool ok = t < cnt[qq];
+      o[t] = Cand{ok ? cd[qq][t] : FLT_MAX, ok ? ci[qq][t] : INT_MAX};
+    }
+  }
+}
+
+__global__ __launch_bounds__(NT) void within_merge_kernel(const Cand* lists, int nchunks, int64_t rpi, int k,
+                                                          int64_t ld, int64_t* idx, float* dist,
+                                                          const int64_t* __restrict__ seg_off, int64_t G,
+                                                          const WithinQ* recs) {
+  const int64_t qq = blockIdx.x;
+  const WithinQ r = within_record(recs, seg_off, G, qq);   // (uniform)
+  if (r.len == W_SKIP) return;
+  idx += qq * ld;
+  dist += qq * ld;
+  if (r.len <= 0) {   // W_BAD, or an empty set
+    for (int t = threadIdx.x; t < k; t += NT) { idx[t] = -1; dist[t] = FLT_MAX; }
+    return;
+  }
+  merge_block(lists + qq * (int64_t)nchunks * k, (int)((r.len + rpi - 1) / rpi), k, idx, dist);
+}
+
+}  // namespace
+
+// The scratch of one set-scoped search (null base: `total` is the size):
+// normalised queries [Q][d] | records [Q] | chunk k-lists [Q][chunks][k]
+struct WithinWs { int nchunks; int64_t rpi; float* qn; WithinQ* recs; Cand* lists; size_t total; };
+WithinWs carve_within(void* ws, int64_t Q, int k, int d, int64_t max_set_rows) {
+  WithinWs w{};
+  Bump b(ws);
+  w.rpi = std::max<int64_t>(W_RPI, rup(cdiv(max_set_rows, W_CHUNKS), 256));
+  w.nchunks = (int)std::max<int64_t>(1, cdiv(max_set_rows, w.rpi));
+  w.qn = (float*)b.take((size_t)Q * d * 4);
+  w.recs = (WithinQ*)b.take((size_t)Q * sizeof(WithinQ));
+  // (room for the most chunks any smaller bound plans, so that the size grows with the bound)
+  const int64_t room = std::max<int64_t>(1, std::min<int64_t>(W_CHUNKS, cdiv(max_set_rows, W_RPI)));
+  w.lists = (Cand*)b.take((size_t)Q * room * k * sizeof(Cand));
+  w.total = b.off;
+  return w;
+}
+
+bool within_shape_ok(int64_t Q, int k, int d, int64_t max_set_rows) {
+  return Q >= 0 && k >= 1 && k <= KMAX && d >= 4 && d % 4 == 0 && d <= 256 && max_set_rows >= 0 &&
+         max_set_rows <= INT32_MAX && Q <= INT32_MAX;
+}
+
+size_t cosine_topk_within_ws(int64_t Q, int k, int d, int64_t max_set_rows) {
+  if (!within_shape_ok(Q, k, d, max_set_rows)) return 0;
+  return carve_within(nullptr, Q, k, d, max_set_rows).total + 256;   // (never 0 for a shape it takes)
+}
+
+dcnr_status cosine_topk_within(const float* t, const float* inv, int64_t N, int d, const float* q, int64_t Q,
+                               const int64_t* excl, const int64_t* seg_off, int64_t G, const int* seg_set,
+                               const int64_t* set_rows, int64_t n_set_rows, const int64_t* set_off, int S,
+                               int64_t max_set_rows, int k, int64_t ld, int64_t* idx, float* dist,
+                               int* seg_status, void* ws, size_t ws_bytes, hipStream_t s) {
+  const WithinWs w = carve_within(ws, Q, k, d, max_set_rows);
+  if (ws_bytes < w.total) {
+    set_error("cosine_topk_within: workspace too small");
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  const int64_t qblocks = cdiv(Q, 4), windows = cdiv(Q, W_BQ);
+  if (qblocks + cdiv(G, 4) > INT32_MAX || windows * w.nchunks > INT32_MAX) {
+    set_error("cosine_topk_within: Q=%lld, G=%lld need more blocks than a launch holds", (long long)Q,
+              (long long)G);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  hipLaunchKernelGGL(within_prep_kernel, dim3((unsigned)(qblocks + cdiv(G, 4))), dim3(256), 0, s, q, Q, d,
+                     use_v2(d, k) ? 1 : 0, w.qn, seg_off, G, seg_set, set_off, S, n_set_rows, max_set_rows, qblocks, w.recs, seg_status);
+  DCNR_LAUNCH_CHECK();
+  if (max_set_rows > 0) {   // (else every set is empty or too long: nothing to scan)
+    const dim3 grid((unsigned)(windows * w.nchunks));
+    if (use_v2(d, k)) {
+      with_dv(d / 4, [&](auto dv) {
+        hipLaunchKernelGGL(within_scan_kernel<decltype(dv)::value>, grid, dim3(K2_NT), 0, s, t, inv, N, w.qn, Q, excl,
+                           seg_off, G, set_rows, w.recs, w.rpi, w.nchunks, k, w.lists, seg_status);
+      });
+    } else if (d <= 64) {
+      hipLaunchKernelGGL(within_scan_wide_kernel<16>, grid, dim3(NT), 0, s, t, inv, N, d, w.qn, Q, excl, seg_off, G,
+                         set_rows, w.recs, w.rpi, w.nchunks, k, w.lists, seg_status);
+    } else {
+      hipLaunchKernelGGL(within_scan_wide_kernel<64>, grid, dim3(NT), 0, s, t, inv, N, d, w.qn, Q, excl, seg_off, G,
+                         set_rows, w.recs, w.rpi, w.nchunks, k, w.lists, seg_status);
+    }
+    DCNR_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(within_merge_kernel, dim3((unsigned)Q), dim3(NT), 0, s, w.lists, w.nchunks, w.rpi, k, ld, idx,
+                     dist, seg_off, G, w.recs);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
 }
 
 // ---- the item neighbour table: the top-k of every table row, built once

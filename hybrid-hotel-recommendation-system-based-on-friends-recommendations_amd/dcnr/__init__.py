@@ -7,7 +7,10 @@ System-Based-on-Friends-Recommendations):
   BCEWithLogitsLoss                  train.py:206
   AdamW, Adam                        train.py:201-204
   NearestNeighbors (cosine, brute)   main.py:268-270; .build_neighbor_table: every
-                                     row's neighbours, computed once
+                                     row's neighbours, computed once;
+                                     .kneighbors(within=rows) /
+                                     .kneighbors_within_device: the k nearest
+                                     rows of a row set (a city's hotels)
   FusedTrainer                       the train.py:219-226 inner-loop step;
                                      .fit: the epoch loop, train.py:216-253
   PlateauLR                          ReduceLROnPlateau (train.py:208-213, 235)
@@ -26,7 +29,10 @@ System-Based-on-Friends-Recommendations):
   serving.rerank_with_mmr            main.py:133-169
   serving.RankingPipeline            the /recommendations + /similar_items core
                                      (main.py:196-230, 294-332); neighbor_table=
-                                     serves both from the item neighbour table
+                                     serves both from the item neighbour table;
+                                     neighbors_within= / within= seek the
+                                     neighbours inside the target city instead
+                                     of intersecting afterwards (main.py:209-210)
   InteractionStore                   main_df's reviews + friendships_df as the
                                      request path reads them (main.py:172-194,
                                      336-351); RankingPipeline.recommend_users

@@ -94,6 +94,86 @@ class NearestNeighbors:
                    "dcnr_cosine_topk")
         return dist, idx
 
+    def kneighbors_within_device(self, q, k, set_rows, set_offsets, seg_offsets, seg_set, max_set_rows,
+                                 exclude=None, out=None, seg_status=None):
+        """The k nearest rows within a row set (dcnr_cosine_topk_within), on
+        device tensors.  Queries [seg_offsets[g], seg_offsets[g+1]) search the
+        rows ``set_rows[set_offsets[s]:set_offsets[s+1]]`` of set ``s =
+        seg_set[g]`` (int64 CSR, ascending rows; ``seg_set`` int32, negative =
+        segment skipped); ``max_set_rows`` is a host bound on the longest set
+        named.  ``exclude`` (int64 [Q], -1 = none) leaves one row out per
+        query.  ``out`` = (idx int64, dist fp32), each [Q, >= k] with unit
+        column stride and one row stride -- column slices of wider buffers
+        will do: columns [0, k) of the rows of segments that are not skipped
+        are overwritten, everything else is kept.  Without it fresh [Q, k]
+        tensors are used (a skipped segment's rows then read (-1, inf)).
+        Returns ``(dist, idx)``; with fewer than k eligible rows the tail is
+        (-1, FLT_MAX).  ``seg_status`` (int32 [G]) receives DCNR_REQ_BAD_DATA
+        for a segment whose device data failed a check."""
+        if self._table is None:
+            raise RuntimeError("This NearestNeighbors instance is not fitted yet")
+        k = int(k)
+        if not 1 <= k <= 64:
+            raise ValueError(f"kneighbors_within_device: n_neighbors = {k} outside [1, 64]")
+        N, d = self._table.shape
+        q = q.to(self.device, torch.float32).reshape(-1, d).contiguous()
+        Q = q.shape[0]
+
+        def same_dev(t):   # ('cuda' names the current device)
+            return t.device.type == self.device.type and self.device.index in (None, t.device.index)
+
+        def dev(t, dtype, what):
+            if not same_dev(t) or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"kneighbors_within_device: {what} must be a contiguous {dtype} tensor "
+                                 f"on {self.device}")
+            return t
+        set_rows = dev(set_rows, torch.int64, "set_rows")
+        set_offsets = dev(set_offsets, torch.int64, "set_offsets")
+        seg_offsets = dev(seg_offsets, torch.int64, "seg_offsets")
+        seg_set = dev(seg_set, torch.int32, "seg_set")
+        G, S = seg_set.numel(), set_offsets.numel() - 1
+        if seg_offsets.numel() != G + 1 or S < 0:
+            raise ValueError("kneighbors_within_device: seg_offsets needs one entry more than seg_set, "
+                             "set_offsets at least one")
+        if exclude is not None and dev(exclude, torch.int64, "exclude").numel() != Q:
+            raise ValueError("kneighbors_within_device: exclude needs one entry per query")
+        if seg_status is not None and dev(seg_status, torch.int32, "seg_status").numel() != G:
+            raise ValueError("kneighbors_within_device: seg_status needs one entry per segment")
+        if out is None:
+            idx = torch.full((Q, k), -1, dtype=torch.int64, device=self.device)
+            dist = torch.full((Q, k), torch.finfo(torch.float32).max, dtype=torch.float32, device=self.device)
+        else:
+            idx, dist = out
+            ok = (idx.dtype == torch.int64 and dist.dtype == torch.float32 and same_dev(idx) and same_dev(dist)
+                  and idx.dim() == 2 and dist.dim() == 2
+                  and idx.shape[0] == Q and dist.shape[0] == Q and idx.shape[1] >= k and dist.shape[1] >= k
+                  and (Q == 0 or (idx.stride(1) == 1 and dist.stride(1) == 1
+                                  and idx.stride(0) == dist.stride(0) >= k)))
+            if not ok:
+                raise ValueError("kneighbors_within_device: out = (idx int64, dist fp32), both [Q, >= k] "
+                                 "with unit column stride and the same row stride")
+        ld = idx.stride(0) if Q > 0 else k
+        lib = _lib.load()
+        nb = int(lib.dcnr_cosine_topk_within_workspace_size(Q, k, d, int(max_set_rows)))
+        ws = torch.empty(max(nb, 16), dtype=torch.uint8, device=self.device)
+        _lib.check(lib.dcnr_cosine_topk_within(
+            self._table.data_ptr(), self._inv.data_ptr(), N, d, q.data_ptr(), Q,
+            exclude.data_ptr() if exclude is not None else None, seg_offsets.data_ptr(), G,
+            seg_set.data_ptr(), set_rows.data_ptr() if set_rows.numel() else None, set_rows.numel(),
+            set_offsets.data_ptr(), S, int(max_set_rows), k, ld, idx.data_ptr(), dist.data_ptr(),
+            seg_status.data_ptr() if seg_status is not None else None, ws.data_ptr(), ws.numel(),
+            _lib.stream_ptr(self.device)), "dcnr_cosine_topk_within")
+        return dist, idx
+
+    def _within_rows(self, rows):
+        """A host row list as kneighbors(within=) takes it: validated, sorted,
+        de-duplicated int64."""
+        r = np.unique(np.asarray(rows, dtype=np.int64).reshape(-1))
+        N = self._table.shape[0]
+        if r.size and (r[0] < 0 or r[-1] >= N):
+            raise ValueError(f"within: row {int(r[0] if r[0] < 0 else r[-1])} outside the index [0, {N})")
+        return r
+
     def build_neighbor_table(self, k=None, rows=None, return_distance=False):
         """The item neighbour table (dcnr_cosine_neighbor_table): int32
         [rows, k] on the device, row r exactly ``kneighbors_device(table[r:r+1],
@@ -277,7 +357,14 @@ class NearestNeighbors:
             events[1].record()
         return c if want_counts else None
 
-    def kneighbors(self, X=None, n_neighbors=None, return_distance=True):
+    def kneighbors(self, X=None, n_neighbors=None, return_distance=True, within=None):
+        """sklearn's ``kneighbors``.  ``within`` (an iterable of rows of the
+        index; not in sklearn) restricts the search to those rows for every
+        query: the answer is what an index fitted on ``table[sorted rows]``
+        returns, as rows of this index.  The rows are validated (one outside
+        the index raises ``ValueError``), sorted and de-duplicated here.
+        Unlike sklearn, ``n_neighbors`` above the set's size is no error: the
+        lists come back padded with row -1 at distance inf."""
         k = self.n_neighbors if n_neighbors is None else int(n_neighbors)
         if k <= 0:
             raise ValueError(f"Expected n_neighbors > 0. Got {k}")
@@ -285,6 +372,18 @@ class NearestNeighbors:
         if q.shape[0] == 0:   # sklearn's check_array
             raise ValueError(f"Found array with 0 sample(s) (shape={tuple(q.shape)}) while a minimum "
                              "of 1 is required by NearestNeighbors.")
+        if within is not None:
+            if self._table is None:
+                raise RuntimeError("This NearestNeighbors instance is not fitted yet")
+            rows = self._within_rows(within)
+            Q = int(q.reshape(-1, self._table.shape[1]).shape[0])
+            i64 = lambda a: torch.tensor(a, dtype=torch.int64, device=self.device)
+            dist, idx = self.kneighbors_within_device(
+                q, k, torch.from_numpy(rows).to(self.device), i64([0, rows.size]), i64([0, Q]),
+                torch.zeros(1, dtype=torch.int32, device=self.device), int(rows.size))
+            dist = dist.cpu().numpy()
+            dist[dist == np.finfo(np.float32).max] = np.inf
+            return (dist, idx.cpu().numpy()) if return_distance else idx.cpu().numpy()
         dist, idx = self.kneighbors_device(q, k)
         idx_np = idx.cpu().numpy()
         if return_distance:

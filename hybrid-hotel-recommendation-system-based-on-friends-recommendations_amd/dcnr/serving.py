@@ -271,9 +271,15 @@ class RankingPipeline:
         return out
 
     # ---------------------------------------------------------- /similar_items
-    def similar_items(self, item_row: int, n: int = 10) -> torch.Tensor:
+    def similar_items(self, item_row: int, n: int = 10, within=None) -> torch.Tensor:
         """main.py:294-303: the n nearest hotels, the hotel itself dropped
-        (kneighbors(n_neighbors=n+1)[1:])."""
+        (kneighbors(n_neighbors=n+1)[1:]).  ``within`` (a ``register_sets``
+        index or an iterable of rows): the n nearest rows of that set other
+        than the hotel itself, whether or not the hotel is in the set -- fewer
+        than n when the set is smaller."""
+        if within is not None:
+            row = self.similar_items_many([int(item_row)], n, within=[within])[0]
+            return row[row >= 0]
         if self._nbr is not None and n + 1 <= self._nbr.shape[1]:
             return self._nbr[int(item_row), 1:n + 1].to(torch.int64)
         q = self.index._table[int(item_row)].reshape(1, -1)
@@ -281,9 +287,13 @@ class RankingPipeline:
         return idx[0, 1:]
 
     # ------------------------------------------------------- /recommendations
-    def candidates(self, positive_rows) -> torch.Tensor:
+    def candidates(self, positive_rows, within=None) -> torch.Tensor:
         """_generate_candidates' union (main.py:196-203): the positive hotels
-        and their n_neighbors-1 nearest neighbours, distinct rows ascending."""
+        and their n_neighbors-1 nearest neighbours, distinct rows ascending.
+        ``within`` (a ``register_sets`` index or an iterable of rows): the
+        neighbours are each positive's n_neighbors-1 nearest rows of that set
+        other than itself (a scan of the set; the neighbour table, which holds
+        global neighbours, is not consulted)."""
         lib = _lib.load()
         pos = torch.as_tensor(positive_rows, dtype=torch.int64).reshape(-1).to(self.device)
         Q = pos.numel()
@@ -291,7 +301,13 @@ class RankingPipeline:
             return pos
         k = self.n_neighbors
         nbr = self._nbr
-        if nbr is None:
+        if within is not None:
+            nbr = None
+            rows, off, w_idx, longest = self._within_csr([within])
+            idx = self._within_overlay(pos, None, rows, off,
+                                       torch.tensor([0, Q], dtype=torch.int64, device=self.device),
+                                       torch.from_numpy(w_idx).to(self.device), longest)
+        elif nbr is None:
             _, idx = self.index.kneighbors_device(self.index._table[pos], k)
         qc = max(1, SV_MAX // k)     # the union kernel's one-workgroup capacity
         outs = []
@@ -365,14 +381,17 @@ class RankingPipeline:
     def recommend(self, user_row: int, positive_rows, lambda_param: float = 1.0,
                   top_k: int = 20, allowed: Optional[Iterable[int]] = None,
                   excluded: Optional[Iterable[int]] = None,
-                  fallback: Optional[Iterable[int]] = None, min_candidates: int = 20):
+                  fallback: Optional[Iterable[int]] = None, min_candidates: int = 20,
+                  neighbors_within=None):
         """The scoring core of /recommendations (main.py:309-332) on hotel rows:
         candidates -> [fallback] -> [filters] -> ranking batch -> logits ->
         sort -> MMR when lambda_param < 1.  ``fallback`` (the city's most
         reviewed hotels) joins the candidates when fewer than
         ``min_candidates`` were found (main.py:204-207).  Returns (ranked
-        rows, their logits) on the device."""
-        cand = self.candidates(positive_rows)
+        rows, their logits) on the device.  ``neighbors_within`` goes to
+        ``candidates``: the positives' neighbours are sought inside that set
+        (the usual call names the city as ``allowed`` and here)."""
+        cand = self.candidates(positive_rows, within=neighbors_within)
         if fallback is not None and cand.numel() < min_candidates:
             extra = torch.as_tensor(list(fallback), dtype=torch.int64).to(self.device)
             cand = torch.unique(torch.cat([cand, extra]))
@@ -395,26 +414,128 @@ class RankingPipeline:
         return ranked, rscores
 
     # ------------------------------------------------- a batch of requests
-    def similar_items_many(self, item_rows, n: int = 10) -> torch.Tensor:
+    def similar_items_many(self, item_rows, n: int = 10, within=None) -> torch.Tensor:
         """R /similar_items queries (main.py:294-303) in one top-k call:
-        int64 [R, n], row r what ``similar_items(item_rows[r], n)`` returns."""
+        int64 [R, n], row r what ``similar_items(item_rows[r], n)`` returns.
+
+        ``within``: None; one set for every query (a ``register_sets`` index,
+        or rows as an array, tensor, set or range); or a list / tuple of R
+        entries, each None, an index or an iterable of rows.  Row r then holds
+        the n nearest rows of its set other than the item itself, padded with
+        -1 when the set is smaller; entries that are None keep the global
+        answer.  One set-scoped kernel call serves all R (queries in a run
+        of equal entries share one pass over the set)."""
         rows = np.asarray(item_rows, dtype=np.int64).reshape(-1)
         if rows.size and (rows.min() < 0 or rows.max() >= self.index._table.shape[0]):
             raise ValueError("similar_items_many: item row outside the index")
         if rows.size == 0:
             return torch.empty((0, n), dtype=torch.int64, device=self.device)
         d_rows = torch.from_numpy(rows).to(self.device)
+        if within is not None:
+            return self._similar_within(d_rows, int(n), within)
         if self._nbr is not None and n + 1 <= self._nbr.shape[1]:
             return self._nbr[d_rows][:, 1:n + 1].to(torch.int64)
         _, idx = self.index.kneighbors_device(self.index._table[d_rows], n + 1)
         return idx[:, 1:]
 
-    def _requests_candidates(self, pos_ptr, d_pos, pos_off_ptr, R, Q, *rest):
+    def _within_csr(self, entries):
+        """Set arguments of the one-request calls (None, a ``register_sets``
+        index, an iterable of rows) as one CSR behind the registered sets:
+        (rows on the device, offsets int64 on the device, set index per entry
+        as int32 with -1 for None, the longest named set)."""
+        reg_rows, reg_off = self._sets
+        n_reg = reg_off.size - 1
+        adhoc, idx = [], np.full(len(entries), -1, np.int32)
+        for r, e in enumerate(entries):
+            if e is None:
+                continue
+            if isinstance(e, (int, np.integer)):
+                if not 0 <= e < n_reg:
+                    raise ValueError(f"within: {e} is not a registered set")
+                idx[r] = e
+            else:
+                adhoc.append(_row_set(e, self.n_rows, "within"))
+                idx[r] = n_reg + len(adhoc) - 1
+        off = np.concatenate([reg_off, reg_off[-1] + np.cumsum([a.size for a in adhoc], dtype=np.int64)])
+        rows = reg_rows
+        if adhoc:
+            rows = torch.cat([reg_rows, torch.from_numpy(np.concatenate(adhoc)).to(self.device)])
+        named = idx[idx >= 0]
+        longest = int(np.diff(off)[named].max()) if named.size else 0
+        return rows, torch.from_numpy(off).to(self.device), idx, longest
+
+    def _within_overlay(self, d_pos, idx, set_rows, set_off, seg_off, seg_set, longest):
+        """knn_idx [Q][k] of the candidate kernels with the set-scoped
+        neighbours laid over it: column 0 is the positive's place (the kernels
+        drop it), columns 1 .. k-1 of every segment that names a set are
+        written by dcnr_cosine_topk_within (exclude = the positive itself).
+        ``idx``: the global answers of the segments that name none, or None
+        when every segment names one."""
+        k = self.n_neighbors
+        Q = d_pos.numel()
+        if idx is None:
+            idx = torch.full((Q, k), -1, dtype=torch.int64, device=self.device)
+        if k > 1 and Q:
+            dist = torch.empty((Q, k), dtype=torch.float32, device=self.device)
+            self.index.kneighbors_within_device(self.index._table[d_pos], k - 1, set_rows, set_off, seg_off,
+                                                seg_set, longest, exclude=d_pos,
+                                                out=(idx[:, 1:], dist[:, 1:]))
+        return idx
+
+    def _similar_within(self, d_rows, n, within):
+        R = d_rows.numel()
+        entries = list(within) if isinstance(within, (list, tuple)) else [within] * R
+        if len(entries) != R:
+            raise ValueError("similar_items_many: within needs one entry per item row (a list or "
+                             "tuple), or one set for all")
+        # equal entries share one CSR slot; runs of them one segment
+        slot, uniq = {}, []
+        for e in entries:
+            key = id(e) if not isinstance(e, (int, np.integer, type(None))) else ("i", e)
+            if key not in slot:
+                slot[key] = len(uniq)
+                uniq.append(e)
+        rows, off, u_idx, longest = self._within_csr(uniq)
+        per = np.array([u_idx[slot[id(e) if not isinstance(e, (int, np.integer, type(None))) else ("i", e)]]
+                        for e in entries], np.int32)
+        starts = np.flatnonzero(np.r_[True, per[1:] != per[:-1]])
+        seg_off = torch.from_numpy(np.r_[starts, R].astype(np.int64)).to(self.device)
+        seg_set = torch.from_numpy(np.ascontiguousarray(per[starts])).to(self.device)
+        out = None
+        if (per < 0).any():   # the global answers first, the sets' laid over them
+            if self._nbr is not None and n + 1 <= self._nbr.shape[1]:
+                idx = self._nbr[d_rows][:, 1:n + 1].to(torch.int64)
+                dist = torch.empty((R, n), dtype=torch.float32, device=self.device)
+            else:
+                dist, idx = self.index.kneighbors_device(self.index._table[d_rows], n + 1)
+                idx, dist = idx[:, 1:], dist[:, 1:]
+            out = (idx, dist)
+        _, idx = self.index.kneighbors_within_device(self.index._table[d_rows], n, rows, off, seg_off, seg_set,
+                                                     longest, exclude=d_rows, out=out)
+        return idx
+
+    def _requests_candidates(self, pos_ptr, d_pos, pos_off_ptr, R, Q, *rest, within=None):
         """dcnr_requests_candidates behind ONE top-k call over all requests'
         positives d_pos [Q] -- or, with a neighbour table, its table form and no
-        scan.  ``rest``: the arguments from set_rows on."""
+        scan.  ``rest``: the arguments from set_rows on.  ``within`` (requests
+        that name a set for their neighbours): (set_rows, set_off, pos_off,
+        set index per request -- device tensors --, the longest named set,
+        whether a request with positives names none).  Those requests' neighbours
+        come from one set-scoped call laid over the global answers (the table's
+        rows, gathered, or the scan's), which only the others keep."""
         lib = _lib.load()
         k = self.n_neighbors
+        if within is not None and Q:
+            set_rows, set_off, seg_off, seg_set, longest, any_global = within
+            idx = None
+            if any_global and self._nbr is not None:
+                idx = self._nbr[d_pos][:, :k].to(torch.int64)
+            elif any_global:
+                _, idx = self.index.kneighbors_device(self.index._table[d_pos], k)
+            idx = self._within_overlay(d_pos, idx, set_rows, set_off, seg_off, seg_set, longest)
+            _lib.check(lib.dcnr_requests_candidates(pos_ptr, pos_off_ptr, R, Q, idx.data_ptr(), k, *rest),
+                       "dcnr_requests_candidates")
+            return
         if self._nbr is not None:
             _lib.check(lib.dcnr_requests_candidates_table(
                 pos_ptr, pos_off_ptr, R, Q, self._nbr.data_ptr(), self._nbr.shape[1], k, *rest),
@@ -447,7 +568,8 @@ class RankingPipeline:
 
     @torch.no_grad()
     def recommend_many(self, user_rows, positive_rows, lambda_param=1.0, top_k=20,
-                       allowed=None, excluded=None, fallback=None, min_candidates: int = 20):
+                       allowed=None, excluded=None, fallback=None, min_candidates: int = 20,
+                       neighbors_within=None):
         """``recommend()`` for R requests in one device pass: returns a list of
         R pairs (ranked rows, their logits), each equal to what ``recommend``
         returns for that request alone, as views into two result tensors.
@@ -458,6 +580,15 @@ class RankingPipeline:
         allowed, excluded, fallback   None, or R entries, each None, an index
                        from ``register_sets`` or an iterable of rows (uploaded
                        for this call)
+        neighbors_within   None, or R entries of the same forms: the set each
+                       request's positives seek their neighbours in
+                       (``recommend``'s ``neighbors_within``; the usual call
+                       names the city here and as ``allowed``).  Requests
+                       whose entry is None keep their global neighbours; the
+                       others' come from ONE set-scoped search over all their
+                       positives (dcnr_cosine_topk_within, the requests as its
+                       segments) laid over them, whether or not the pipeline
+                       has a neighbour table.  Still one wait.
 
         One packed, pinned, non-blocking copy carries every host input; one
         top-k call serves all positives; each request's set work runs in its
@@ -485,7 +616,7 @@ class RankingPipeline:
         if R == 0:
             return []
         f = self._many_front(users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
-                             min_candidates)
+                             min_candidates, neighbors_within=neighbors_within)
         info, seg, st, d_at = f["info"], f["seg"], f["st"], f["d_at"]
         pos, lam, topk = info["pos"], info["lam"], info["topk"]
         out_rows, out_logits = self._score_and_rank(R, f["cap"], f["n"], f["slots"], f["offsets"],
@@ -506,7 +637,8 @@ class RankingPipeline:
                                           allowed=self._set_arg(pick(allowed)),
                                           excluded=self._set_arg(pick(excluded)),
                                           fallback=self._set_arg(pick(fallback)),
-                                          min_candidates=min_candidates))
+                                          min_candidates=min_candidates,
+                                          neighbors_within=self._set_arg(pick(neighbors_within))))
                 continue
             n_r = int(seg[r + 1] - seg[r])
             # every candidate is a table row, so the MMR finds min(top_k, n_r) items
@@ -516,7 +648,7 @@ class RankingPipeline:
         return res
 
     def _many_front(self, users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
-                    min_candidates, extra=(), pinned_tail=0):
+                    min_candidates, extra=(), pinned_tail=0, neighbors_within=None):
         """``recommend_many`` up to its one wait: the packed upload (``extra``:
         further (name, array) pairs to carry along), the top-k or table lookup,
         the candidates pass, the wait.  Returns what the calls behind the wait
@@ -526,7 +658,7 @@ class RankingPipeline:
         dev = self.device
         R = users.size
         ins, info = self._pack_requests(users, positive_rows, lambda_param, top_k, allowed,
-                                        excluded, fallback)
+                                        excluded, fallback, neighbors_within)
         ins = ins + list(extra)
         pos, lam, topk, cap, S, n_adhoc = (info[k_] for k_ in ("pos", "lam", "topk", "cap", "S",
                                                                "n_adhoc"))
@@ -556,12 +688,18 @@ class RankingPipeline:
         offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
         words = torch.empty(3 * R, dtype=torch.int32, device=dev)   # count, status, out_count
         count, status, out_count = (words.data_ptr() + 4 * R * j for j in range(3))
+        within = None
+        if "within" in at:   # some request seeks its neighbours inside a set
+            d_view = lambda name, n_, dt, w_: dbuf[at[name]:at[name] + w_ * n_].view(dt)
+            within = (reg_rows, d_view("set_off", S + 1, torch.int64, 8),
+                      d_view("pos_off", R + 1, torch.int64, 8), d_view("within", R, torch.int32, 4),
+                      info["within_longest"], info["within_any_global"])
         self._requests_candidates(
             d_at("pos") if Q else None, d_pos, d_at("pos_off"), R, Q,
             reg_rows.data_ptr() if reg_rows.numel() else None, reg_rows.numel(),
             d_at("set_off"), S, d_at("allowed"), d_at("excluded"), d_at("fallback"),
             int(min_candidates), self.n_rows, cap, slots.data_ptr(), count, status,
-            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream)
+            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream, within=within)
         # (allocated while the device works, not after the wait)
         nb = int(lib.dcnr_requests_workspace_size(R, Q, k, cap))
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -675,7 +813,7 @@ class RankingPipeline:
     @torch.no_grad()
     def lambda_sweep(self, user_rows, positive_rows, lambdas, top_k: int = 20, allowed=None,
                      excluded=None, fallback=None, min_candidates: int = 20, relevant=None,
-                     info=None, ks=(5, 10, 20)):
+                     info=None, ks=(5, 10, 20), neighbors_within=None):
         """``recommend_many`` for several values of ``lambda_param`` with the
         list metrics of each, the candidates scored ONCE: the front of
         ``recommend_many`` (one upload, one top-k or table lookup, one
@@ -687,6 +825,7 @@ class RankingPipeline:
         lambdas     the values to compare (each one value for all requests)
         top_k       one value, at most 128: the MMR's length and the metrics' ``at``
         relevant, info, ks   as in ``dcnr.list_metrics`` (one entry per request)
+        neighbors_within     as in ``recommend_many``
 
         Returns ``SweepResult``: a list of ``(answers, ListMetrics)``, one per
         lambda, ``answers`` as ``recommend_many`` returns them; ``.lambdas``;
@@ -726,7 +865,7 @@ class RankingPipeline:
             # kernels would not, so the batched kernels serve no request of this sweep.  Known
             # here: the rows are validated as usual and nothing is launched.
             self._pack_requests(users, positive_rows, float(lam64[0]), int(top_k), allowed, excluded,
-                                fallback)
+                                fallback, neighbors_within)
             out.skipped = list(range(R))
             for _ in range(L):
                 out.append(([None] * R, mt.empty_list_metrics(R, ks)))
@@ -734,7 +873,8 @@ class RankingPipeline:
         lams = np.repeat(lam32, R)                     # [L][R]: one lambda array per launch
         tail = 8 * (rel_host[0].size + R + 1) if rel_host is not None else 0
         f = self._many_front(users, positive_rows, float(lam64[0]), int(top_k), allowed, excluded,
-                             fallback, min_candidates, extra=[("lams", lams)], pinned_tail=tail)
+                             fallback, min_candidates, extra=[("lams", lams)], pinned_tail=tail,
+                             neighbors_within=neighbors_within)
         seg, st, d_at, n, cap = f["seg"], f["st"], f["d_at"], f["n"], f["cap"]
         stream = f["stream"]
         skip = (st & REQ_OVERFLOW).astype(bool)
@@ -781,7 +921,7 @@ class RankingPipeline:
     @torch.no_grad()
     def recommend_users(self, store, user_rows, reviewers, modes, lambda_param=1.0, top_k=20,
                         allowed=None, fallback=None, min_candidates: int = 20,
-                        recommended_by: bool = True):
+                        recommended_by: bool = True, neighbors_within=None):
         """``recommend_many`` from user ids: each request's positives, its
         excluded set (the negatives, main.py:193-194, 211) and the
         ``recommended_by`` lists of its answer (main.py:336-351) come from a
@@ -791,7 +931,7 @@ class RankingPipeline:
         user_rows   R model user rows (main.py:217 stays the caller's)
         reviewers   R store indices, -1 for a user the store does not know
         modes       'friends' / 'personal', one value or R
-        lambda_param, top_k, allowed, fallback, min_candidates
+        lambda_param, top_k, allowed, fallback, min_candidates, neighbors_within
                     as in ``recommend_many`` (``excluded`` is the negatives)
 
         Returns a ``UserAnswers``: a list of R (ranked rows, logits) pairs,
@@ -836,7 +976,7 @@ class RankingPipeline:
             raise ValueError("recommend_users: one mode, or one per request")
         # lambda, top_k and the allowed / fallback indices as recommend_many packs them
         ins, info = self._pack_requests(users, [()] * R, lambda_param, top_k, allowed, None,
-                                        fallback)
+                                        fallback, neighbors_within)
         ins = dict(ins)
         lam, lam64, topk = info["lam"], info["lam64"], info["topk"]
         k = self.n_neighbors
@@ -905,12 +1045,19 @@ class RankingPipeline:
             pin.data_ptr() + o_sst, stream), "dcnr_requests_sources")
         slots = torch.empty((R, cap), dtype=torch.int64, device=dev)
         offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
+        within = None
+        if "within" in at:   # the requests as the set-scoped search's segments, as recommend_many
+            d_view = lambda name, n_, dt, w_: dbuf[at[name]:at[name] + w_ * n_].view(dt)
+            w_idx = info["within_idx"]
+            within = (set_rows, d_view("set_off", S0 + R + 1, torch.int64, 8),
+                      d_view("pos_off", R + 1, torch.int64, 8), d_view("within", R, torch.int32, 4),
+                      info["within_longest"], bool(((w_idx < 0) & (zero(pos_b) > 0)).any()))
         self._requests_candidates(
             d_pos.data_ptr() if Q else None, d_pos, d_at("pos_off"), R, Q,
             set_rows.data_ptr() if set_rows.numel() else None, set_rows.numel(),
             d_at("set_off"), S0 + R, d_at("allowed"), d_at("excluded"), d_at("fallback"),
             int(min_candidates), self.n_rows, cap, slots.data_ptr(), count, status,
-            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream)
+            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream, within=within)
         # (allocated while the device works, not after the wait)
         nb = int(lib.dcnr_requests_workspace_size(R, Q, k, cap))
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -956,14 +1103,15 @@ class RankingPipeline:
                 res.append(self.recommend(int(users[r]), p_r, float(lam64[r]), int(topk[r]),
                                           allowed=self._set_arg(pick(allowed)), excluded=n_r,
                                           fallback=self._set_arg(pick(fallback)),
-                                          min_candidates=min_candidates))
+                                          min_candidates=min_candidates,
+                                          neighbors_within=self._set_arg(pick(neighbors_within))))
                 continue
             o = int(seg[r])
             res.append((out_rows[o:o + int(cnt[r])], out_logits[o:o + int(cnt[r])]))
         return res
 
     def _pack_requests(self, users, positive_rows, lambda_param, top_k, allowed, excluded,
-                       fallback):
+                       fallback, neighbors_within=None):
         """The host half of ``recommend_many``: validates the rows and returns
         ([(name, array)] to upload, info).  Without set arguments nothing about
         sets is built or uploaded (the index arrays go as null: no filters)."""
@@ -997,7 +1145,8 @@ class RankingPipeline:
         info = dict(pos=pos_all, pos_off=pos_off, lam=lam, lam64=lam64, topk=topk, S=0, n_adhoc=0,
                     reg_rows=self._no_rows)
         need = np.array(lens, np.int64) * k   # a request's slot: its staged list (+ its fallback set)
-        if allowed is not None or excluded is not None or fallback is not None:
+        if allowed is not None or excluded is not None or fallback is not None or \
+                neighbors_within is not None:
             # registered sets by index, per-call ones appended to the CSR
             reg_rows, reg_off = self._sets
             n_reg = reg_off.size - 1
@@ -1025,10 +1174,12 @@ class RankingPipeline:
             a_idx = set_indices(allowed, "allowed")
             e_idx = set_indices(excluded, "excluded")
             f_idx = set_indices(fallback, "fallback")
+            w_idx = set_indices(neighbors_within, "neighbors_within")
         else:
-            a_idx = e_idx = f_idx = None
+            a_idx = e_idx = f_idx = w_idx = None
         # lists whose entries are all None name no set: nothing about sets is uploaded
-        if a_idx is not None and (a_idx.max() >= 0 or e_idx.max() >= 0 or f_idx.max() >= 0):
+        if a_idx is not None and (a_idx.max() >= 0 or e_idx.max() >= 0 or f_idx.max() >= 0 or
+                                  w_idx.max() >= 0):
             adhoc_rows = np.concatenate(adhoc) if adhoc else np.zeros(0, np.int64)
             set_off = np.concatenate([reg_off, reg_off[-1] + np.cumsum([a.size for a in adhoc],
                                                                          dtype=np.int64)])
@@ -1037,6 +1188,10 @@ class RankingPipeline:
             ins += [("set_off", set_off), ("adhoc_rows", adhoc_rows), ("allowed", a_idx),
                     ("excluded", e_idx), ("fallback", f_idx)]
             info.update(S=set_off.size - 1, n_adhoc=adhoc_rows.size, reg_rows=reg_rows)
+            if w_idx.max() >= 0:   # (else the neighbour step is the parent path, untouched)
+                ins.append(("within", w_idx))
+                info.update(within_idx=w_idx, within_longest=int(set_len[w_idx[w_idx >= 0]].max()),
+                            within_any_global=bool(((w_idx < 0) & (np.array(lens) > 0)).any()))
         info["cap"] = int(min(SV_MAX, max(1, int(need.max()))))
         return ins, info
 

@@ -576,6 +576,62 @@ dcnr_status dcnr_cosine_topk_packed(const float* table, const float* inv_norms, 
                                     int64_t* idx, float* dist, void* ws, size_t ws_bytes,
                                     dcnr_stream_t stream);
 
+/* The k nearest rows within a row set: dcnr_cosine_topk scoped to a listed
+ * subset of the table ("the hotels in this city most like that one"), which
+ * the reference approximates by intersecting global neighbours with the city
+ * afterwards (main.py:196-203, 209-210).  A call carries G segments of
+ * queries: queries [seg_offsets[g], seg_offsets[g+1]) search set seg_set[g]
+ * of the CSR (set_rows int64 [n_set_rows], set_offsets int64 [S+1]; rows
+ * distinct within a set); seg_set[g] < 0 skips the segment.  All of these
+ * live on the device; max_set_rows is a host bound on the longest set a
+ * segment names (it sizes the grid and the workspace).
+ *
+ * Query q of segment g gets the k rows of its set, other than exclude[q]
+ * (int64 [Q] or NULL; -1 or any row outside the set = none), with the
+ * smallest cosine distance, ascending by (dist, table row) for an ascending
+ * set: idx int64 / dist fp32 [Q][ld], columns [0, k) written, ld >= k.  The
+ * queries are raw (normalised inside) and the distance arithmetic is that of
+ * every exact scan of dcnr_cosine_topk, so for an ascending set the answer
+ * equals dcnr_cosine_topk over the compacted table table[set] with positions
+ * mapped back through the set -- the same rows, distances bit for bit (but
+ * for that call's fp32-MFMA leg, Q >= 16 with d % 16 == 0 and d not 32 / 64,
+ * whose sums run in another order).  In a set that is not ascending, a row
+ * tied with the k-th distance that is listed after it may lose to it.
+ * Fewer than k eligible rows: the tail is (-1, FLT_MAX), which
+ * dcnr_candidate_union and dcnr_requests_candidates skip.  A skipped
+ * segment's output rows, a query no segment holds and, with ld > k, the
+ * columns outside [0, k) are left untouched: the call overlays answers onto a
+ * buffer that holds others.
+ *
+ * Device data are checked against the lengths passed by value before they are
+ * used to address anything: a set index >= S; set offsets outside
+ * [0, n_set_rows], decreasing, or longer than max_set_rows; a segment's
+ * offsets decreasing or outside [0, Q]; a set row outside [0, N) (found when
+ * the row is read: a segment without queries reads none).  Such a segment's
+ * queries (those of its range inside [0, Q)) get (-1, FLT_MAX) in all k columns
+ * and seg_status[g] (int32 [G] or NULL) = DCNR_REQ_BAD_DATA, else 0; other
+ * segments are answered as usual.  Segments that overlap -- possible only
+ * beside one with decreasing offsets -- each answer the shared queries, and
+ * one of the answers stays.
+ *
+ * Host-side rejections before any launch: DCNR_BAD_ARG (a null pointer with
+ * Q > 0 -- set_rows may be NULL with n_set_rows = 0 --, Q, G, S, n_set_rows or
+ * max_set_rows < 0, N < 1, k < 1, ld < k), DCNR_UNSUPPORTED_SHAPE (k > 64,
+ * d % 4 != 0, d outside [4, 256], N, n_set_rows, Q or G >= 2^31), then, with
+ * Q > 0 and G > 0, DCNR_WORKSPACE_TOO_SMALL below
+ * dcnr_cosine_topk_within_workspace_size(Q, k, d, max_set_rows) -- which is 0
+ * for a shape the call rejects.  Q = 0 or G = 0 returns DCNR_OK without a
+ * launch.  Stream-ordered: three launches, no host synchronisation, no
+ * allocation. */
+size_t dcnr_cosine_topk_within_workspace_size(int64_t Q, int32_t k, int32_t d, int64_t max_set_rows);
+dcnr_status dcnr_cosine_topk_within(const float* table, const float* inv_norms, int64_t N, int32_t d,
+                                    const float* queries, int64_t Q, const int64_t* exclude,
+                                    const int64_t* seg_offsets, int64_t G, const int32_t* seg_set,
+                                    const int64_t* set_rows, int64_t n_set_rows, const int64_t* set_offsets,
+                                    int32_t S, int64_t max_set_rows, int32_t k, int64_t ld, int64_t* idx,
+                                    float* dist, int32_t* seg_status, void* ws, size_t ws_bytes,
+                                    dcnr_stream_t stream);
+
 /* The item neighbour table: the k nearest rows of every row of the fitted
  * table, built once so that /recommendations' candidate step and
  * /similar_items become row lookups (the reference queries its index with rows
