@@ -1935,6 +1935,10 @@ dcnr_status dcnr_emb_touched_rows(const dcnr_model_desc* desc, const void* ws, s
       set_error("dcnr_emb_touched_rows: table %d out of range", t);
       return DCNR_BAD_ARG;
     }
+    if (elem_off[i] < 0) {   // (off / shard would round a negative offset into owner 0)
+      set_error("dcnr_emb_touched_rows: negative elem_off");
+      return DCNR_BAD_ARG;
+    }
     uint32_t base = 0;
     for (int u = 0; u < t; ++u) base += (uint32_t)d.rows[u];
     a.tab[i] = t;

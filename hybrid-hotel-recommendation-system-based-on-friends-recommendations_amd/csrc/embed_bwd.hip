@@ -1052,8 +1052,8 @@ __global__ __launch_bounds__(256) void sparse_pack_kernel(const float* __restric
 // Accumulate one source's rows (distinct offsets) into the shard [lo, lo +
 // elems): a plain read-add-write, since no two of them share a row; the
 // sources are launched in rank order, so every shard row is summed
-// 0 + g_0 + g_1 + ... whatever the scheduling.  Offsets outside the shard
-// (none, from sparse_pack's owner grouping) are skipped.
+// 0 + g_0 + g_1 + ... whatever the scheduling.  A row not wholly inside the
+// shard (none, from sparse_pack's owner grouping) is skipped whole.
 template <int V>
 __global__ __launch_bounds__(256) void sparse_add_kernel(float* __restrict__ shard, int64_t lo, int64_t elems,
                                                          int width, const int64_t* __restrict__ offs,

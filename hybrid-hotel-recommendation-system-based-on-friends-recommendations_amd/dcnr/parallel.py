@@ -100,16 +100,22 @@ def remove_sync_bn(model):
     model._sync_bn_hook = None
 
 
-def touched_rows(model, ws: torch.Tensor, B: int, tables, elem_off, shard_elems: int, world: int):
+def touched_rows(model, ws: torch.Tensor, B: int, tables, elem_off, shard_elems: int, world: int,
+                 out: Optional[torch.Tensor] = None):
     """Distinct rows of ``tables`` the batch of the last train-mode forward on
     ``ws`` touched, as flat-buffer element offsets (dcnr_emb_touched_rows):
     returns (offsets [len(tables), B] int64, table_counts [len(tables)],
     owner_counts [world]) on the device; offsets[i, :table_counts[i]] are
-    ascending."""
+    ascending.  ``out``: optional preallocated offsets (contiguous int64
+    [len(tables), max(B, 1)]); slots past a table's count are left as they
+    were."""
     lib = _lib.load()
     dev = ws.device
     n = len(tables)
-    offs = torch.empty((n, max(B, 1)), dtype=torch.int64, device=dev)
+    offs = out if out is not None else torch.empty((n, max(B, 1)), dtype=torch.int64, device=dev)
+    if offs.shape != (n, max(B, 1)) or offs.dtype != torch.int64 or not offs.is_contiguous() \
+            or offs.device != dev:
+        raise ValueError("out must be a contiguous int64 [len(tables), max(B, 1)] tensor on ws's device")
     tcnt = torch.empty(n, dtype=torch.int64, device=dev)
     ocnt = torch.empty(world, dtype=torch.int64, device=dev)
     tabs = (ctypes.c_int32 * n)(*[int(t) for t in tables])

@@ -273,7 +273,11 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
  * elem_off[i] + row * width of its distinct rows, ascending, to
  * out_offsets[i*B ..] and their number to table_counts[i]; owner_counts[r]
  * (r < world <= DCNR_TOUCHED_MAX_WORLD) counts the offsets in
- * [r*shard_elems, (r+1)*shard_elems).
+ * [r*shard_elems, (r+1)*shard_elems); an offset at or beyond
+ * world*shard_elems is listed in out_offsets and table_counts but is in no
+ * owner's count.  out_offsets[i*B + table_counts[i] ..] is not written.
+ * B = 0: both counts zeroed.  world outside 1..DCNR_TOUCHED_MAX_WORLD,
+ * shard_elems < 1 or a negative elem_off: DCNR_BAD_ARG, nothing launched.
  * Stream-ordered; outputs are device memory. */
 #define DCNR_TOUCHED_MAX_WORLD 64
 
@@ -294,8 +298,10 @@ dcnr_status dcnr_sparse_pack(const float* grad, const int64_t* offsets, int64_t 
  * rows the n_sources ranks sent, back to back in `offsets` / `rows`
  * (source_counts[r] rows from rank r: a HOST array), sources in rank order --
  * every shard row is summed 0 + g_0 + g_1 + ..., the same bits run to run.
- * Within one source the offsets are distinct.  Offsets outside the shard are
- * skipped. */
+ * Within one source the rows are distinct and do not overlap.  A row is added
+ * only if all of it lies in the shard (shard_lo <= offset and offset + width
+ * <= shard_lo + shard_elems); a row below, beyond or straddling either end
+ * of the shard is skipped whole. */
 dcnr_status dcnr_sparse_accumulate(float* shard, int64_t shard_lo, int64_t shard_elems, int32_t width,
                                    const int64_t* offsets, const float* rows,
                                    const int64_t* source_counts, int32_t n_sources,

@@ -14,6 +14,7 @@ import torch.multiprocessing as mp
 
 import dcnr_oracle as orc
 from dcnr import parallel
+from sparse_exchange_ref import HostSparseOps, accumulate_ref, pack_ref, touched_ref
 
 
 def _free_port():
@@ -258,31 +259,6 @@ def test_sharded_optimizer_exchange_matches_allreduce_adam(world):
     _run(_exchange_worker, world)
 
 
-class HostSparseOps:
-    """Host restatement of libdcnr's sparse-exchange kernels (dcnr_sparse_pack:
-    the tables' touched rows in flat order; dcnr_sparse_accumulate: zero,
-    then every source's rows added in rank order) -- the CPU side of the
-    protocol test; the GPU tests run the kernels."""
-
-    def pack(self, grad, offsets, table_counts, width, n_rows):
-        tc = table_counts.tolist()
-        off = torch.cat([offsets[t, :tc[t]] for t in range(len(tc))])
-        assert off.numel() == n_rows
-        col = torch.arange(width, dtype=torch.int64)
-        rows = grad[off[:, None] + col[None, :]] if n_rows else torch.empty((0, width))
-        return off, rows
-
-    def accumulate(self, shard, lo, width, offsets, rows, counts):
-        shard.zero_()
-        sv = shard.view(-1, width)
-        pos = 0
-        for c in counts:
-            if c:
-                sv.index_add_(0, torch.div(offsets[pos:pos + c] - lo, width, rounding_mode="floor"),
-                              rows[pos:pos + c])
-            pos += c
-
-
 def _sparse_worker(rank, world, port, d):
     """Owner-bucketed sparse exchange of the user and item tables
     (FusedTrainer exchange="sparse"): each rank's table gradients are nonzero
@@ -362,3 +338,55 @@ def test_sparse_exchange_argument_checks():
                                                      n_res_blocks=1, dropout=0.0))
     with pytest.raises(ValueError):
         dcnr.FusedTrainer(m, exchange="sparse", shard_optimizer=False)
+
+
+# ---- the shared references of tests/sparse_exchange_ref.py on hand-written examples
+
+def test_touched_ref_by_hand():
+    ids = [5, 2, 5, 9, 2, 0]                       # distinct rows 0, 2, 5, 9
+    offs, own = touched_ref(ids, 3, 10, 12, 4)
+    assert offs.tolist() == [10, 16, 25, 37] and offs.dtype == np.int64
+    assert own.tolist() == [1, 1, 1, 1]            # 10 | 16 | 25 | 37 in shards of 12
+    offs, own = touched_ref(ids, 3, 10, 12, 2)     # 25 and 37 lie beyond 2 * 12: in no count
+    assert offs.tolist() == [10, 16, 25, 37] and own.tolist() == [1, 1]
+    offs, own = touched_ref(ids, 3, 0, 100, 3)     # shards that receive nothing
+    assert offs.tolist() == [0, 6, 15, 27] and own.tolist() == [4, 0, 0]
+
+
+def test_pack_ref_by_hand():
+    grad = np.arange(40, dtype=np.float32)
+    offsets = np.array([[4, 9, 30], [0, 20, 21]])
+    offs, rows = pack_ref(grad, offsets, [2, 1], 3)
+    assert offs.tolist() == [4, 9, 0]
+    assert rows.tolist() == [[4, 5, 6], [9, 10, 11], [0, 1, 2]]
+    offs, rows = pack_ref(grad, offsets, [0, 3], 2)        # an empty first table
+    assert offs.tolist() == [0, 20, 21] and rows.tolist() == [[0, 1], [20, 21], [21, 22]]
+    offs, rows = pack_ref(grad, offsets, [0, 0], 3)
+    assert offs.shape == (0,) and rows.shape == (0, 3)
+    # the host ops the protocol tests use state the same thing
+    o2, r2 = HostSparseOps().pack(torch.from_numpy(grad), torch.from_numpy(offsets),
+                                  torch.tensor([2, 1]), 3, 3)
+    assert o2.tolist() == [4, 9, 0] and r2.tolist() == [[4, 5, 6], [9, 10, 11], [0, 1, 2]]
+
+
+def test_accumulate_ref_by_hand():
+    lo, elems, w = 10, 8, 4
+    #        kept     kept      below  straddles lo  straddles end  beyond  kept (overlaps)  kept
+    offs = [10,      14,       4,     7,            16,            18,     12,              10]
+    vals = [1.0,     2.0,      64.0,  64.0,         64.0,          64.0,   4.0,             8.0]
+    rows = np.repeat(np.array(vals, np.float32)[:, None], w, 1)
+    got = accumulate_ref(lo, elems, w, offs, rows, [3, 0, 3, 2])
+    assert got.dtype == np.float32
+    assert got.tolist() == [9, 9, 13, 13, 6, 6, 2, 2]
+    assert accumulate_ref(lo, elems, w, [], np.empty((0, w), np.float32), []).tolist() == [0] * 8
+    # source order: ((0 + 1) + 1e8) - 1e8 = 0 in fp32, where (1e8 - 1e8) + 1 would be 1
+    rows = np.array([[1.0], [1e8], [-1e8]], np.float32)
+    assert accumulate_ref(0, 1, 1, [0, 0, 0], rows, [1, 1, 1]).tolist() == [0.0]
+    assert accumulate_ref(0, 1, 1, [0, 0, 0], rows[[1, 2, 0]], [1, 1, 1]).tolist() == [1.0]
+    # row-aligned input: HostSparseOps.accumulate gives the same bits
+    g = np.random.default_rng(0)
+    offs = np.array([8, 0, 4, 8, 12, 0])
+    rows = (g.standard_normal((6, 4)) * 10.0 ** g.integers(-6, 6, (6, 1))).astype(np.float32)
+    sh = torch.full((16,), float("nan"))
+    HostSparseOps().accumulate(sh, 32, 4, torch.from_numpy(offs + 32), torch.from_numpy(rows), [2, 0, 4])
+    assert np.array_equal(sh.numpy(), accumulate_ref(32, 16, 4, offs + 32, rows, [2, 0, 4]))
