@@ -1905,6 +1905,32 @@ dcnr_status dcnr_requests_recommended_by(const dcnr_interactions* store, const i
   return DCNR_OK;
 }
 
+dcnr_status dcnr_csr_insert(const int64_t* old_offsets, int64_t n_old_owners, int64_t n_new_owners,
+                            int64_t n_old_entries, int32_t n_payloads,
+                            const int32_t* const* old_payloads, const int64_t* touched,
+                            const int64_t* insert_prefix, int64_t t, const int64_t* insert_pos,
+                            const int32_t* const* insert_payloads, int64_t m, int64_t* new_offsets,
+                            int32_t* const* new_payloads, dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  bool bad = !old_offsets || !new_offsets || n_old_owners < 0 || n_new_owners < n_old_owners ||
+             n_old_entries < 0 || n_payloads < 1 || n_payloads > 2 || t < 0 || m < 0 || t > m ||
+             (m > 0 && (t == 0 || !touched || !insert_prefix || !insert_pos || !old_payloads ||
+                        !insert_payloads || !new_payloads));
+  for (int w = 0; !bad && m > 0 && w < n_payloads; ++w)
+    bad = !insert_payloads[w] || !new_payloads[w] || (n_old_entries > 0 && !old_payloads[w]);
+  if (bad) {
+    set_error("dcnr_csr_insert: bad argument (owners %lld -> %lld, entries=%lld, payloads=%d, "
+              "t=%lld, m=%lld)", (long long)n_old_owners, (long long)n_new_owners,
+              (long long)n_old_entries, n_payloads, (long long)t, (long long)m);
+    return DCNR_BAD_ARG;
+  }
+  if (m == 0 && n_new_owners == n_old_owners) return DCNR_OK;
+  TRYP(DCNR_K_SERVE, s, csr_insert(old_offsets, n_old_owners, n_new_owners, n_old_entries,
+                                   n_payloads, old_payloads, touched, insert_prefix, t, insert_pos,
+                                   insert_payloads, m, new_offsets, new_payloads, s));
+  return DCNR_OK;
+}
+
 size_t dcnr_bce_workspace_size(void) { return bce_ws_bytes() + 256; }
 
 dcnr_status dcnr_emb_touched_rows(const dcnr_model_desc* desc, const void* ws, size_t ws_bytes,

@@ -886,6 +886,13 @@ dcnr_status requests_recommended_by(const dcnr_interactions& store, const int32_
                                     const int64_t* list_off, int64_t L_total, int32_t* lists,
                                     int32_t* by_count, int64_t* by_off, int32_t* by_reviewers,
                                     int32_t* status, hipStream_t s);
+// dcnr_csr_insert: a new generation of a CSR of 1 or 2 int32 payloads (the
+// payload arrays are neither read nor written when m == 0)
+dcnr_status csr_insert(const int64_t* old_off, int64_t U_old, int64_t U_new, int64_t M_old,
+                       int n_payloads, const int32_t* const* old_val, const int64_t* touched,
+                       const int64_t* prefix, int64_t t, const int64_t* ins_pos,
+                       const int32_t* const* ins_val, int64_t m, int64_t* new_off,
+                       int32_t* const* new_val, hipStream_t s);
 
 dcnr_status fill_zero(void* p, size_t bytes, hipStream_t s);
 // *dst = *src with a system-scope store (dst may be pinned host memory)

@@ -1040,7 +1040,202 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const int64_t* idx, in
   for (int64_t k = lane; k < words; k += 64) d[k] = s[k];
 }
 
+// ---- a new generation of a CSR with m entries inserted (dcnr_csr_insert;
+// InteractionStore.append).  Output-centric: the output positions are cut into
+// chunks of CI_CHUNK, the new offsets into chunks behind them, and a workgroup
+// takes a contiguous range of chunks; every output element is written once, by
+// one lane, from the old generation (read only) or the uploaded batch.  An
+// output position p holds old[p - (the inserts in front of p)]; the inserts in
+// front are constant between two touched segments, so a chunk no touched
+// segment reaches into is a copy shifted by a constant: destination-aligned
+// 16-byte stores, the source read as the two aligned 16-byte words around it
+// (it is misaligned by the shift).  Only chunks a touched segment reaches into
+// search per element.  The touched owners' new segment bounds that a workgroup
+// can meet are staged in LDS when there are at most CI_LDS_RUNS of them and
+// derived from the global arrays otherwise.  All positions are 64-bit.
+constexpr int CI_NT = 256;
+constexpr int CI_CHUNK = DCNR_CSR_INSERT_CHUNK;
+constexpr int CI_LDS_RUNS = 1024;
+constexpr int CI_MAX_BLOCKS = 2048;
+static_assert(CI_CHUNK % (4 * CI_NT) == 0, "a chunk is whole 16-byte stores of the workgroup");
+
+struct CsrInsert {
+  const int64_t* old_off;   // [U_old + 1]
+  const int64_t* touched;   // [t] ascending, distinct
+  const int64_t* prefix;    // [t + 1] inserts in front of touched owner j
+  const int64_t* ins_pos;   // [m] position inside the owner's new segment
+  const int32_t* old_val[2];
+  const int32_t* ins_val[2];
+  int32_t* new_val[2];
+  int64_t* new_off;         // [U_new + 1]
+  int64_t U_old, U_new, M_old, m, t;
+  int64_t n_pay_units, n_units, units_per_block;
+  int n_payloads, vec;
+};
+
+// first j in [lo, hi) where pred holds (pred: false ... false true ... true), else hi
+template <class F>
+__device__ __forceinline__ int64_t ci_first(int64_t lo, int64_t hi, F pred) {
+  while (lo < hi) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (pred(mid)) hi = mid; else lo = mid + 1;
+  }
+  return lo;
+}
+
+// old start of owner o in [0, U_new]: owners at or beyond U_old start from M_old
+__device__ __forceinline__ int64_t ci_old_at(const CsrInsert& a, int64_t o) {
+  return o <= a.U_old ? a.old_off[o] : a.M_old;
+}
+__device__ __forceinline__ int64_t ci_owner(const CsrInsert& a, int64_t j) {
+  const int64_t o = a.touched[j];
+  return o < 0 ? 0 : (o >= a.U_new ? a.U_new - 1 : o);
+}
+// touched owner j's new segment [ns, ne)
+__device__ __forceinline__ int64_t ci_ns(const CsrInsert& a, int64_t j) {
+  return ci_old_at(a, ci_owner(a, j)) + a.prefix[j];
+}
+__device__ __forceinline__ int64_t ci_ne(const CsrInsert& a, int64_t j) {
+  return ci_old_at(a, ci_owner(a, j) + 1) + a.prefix[j + 1];
+}
+
+__device__ __forceinline__ int32_t ci_old(const int32_t* src, int64_t e, int64_t M_old) {
+  if (M_old <= 0) return 0;
+  return src[e < 0 ? 0 : (e >= M_old ? M_old - 1 : e)];
+}
+
+// new[c0, c1) = old[c0 - shift, c1 - shift): c0 is a multiple of CI_CHUNK
+__device__ void ci_copy_shift(const CsrInsert& a, int64_t c0, int64_t c1, int64_t shift) {
+  for (int w = 0; w < a.n_payloads; ++w) {
+    const int32_t* src = a.old_val[w];
+    int32_t* dst = a.new_val[w];
+    for (int64_t p = c0 + (int64_t)threadIdx.x * 4; p < c1; p += 4 * CI_NT) {
+      const int64_t e = p - shift;
+      const int r = (int)(e & 3);
+      const int64_t lo = e - r;
+      if (a.vec && p + 4 <= c1 && e >= 0 && lo + 4 <= a.M_old) {
+        const int4 v0 = *reinterpret_cast<const int4*>(src + lo);
+        int4 v1 = make_int4(0, 0, 0, 0);
+        if (r) {
+          if (lo + 8 <= a.M_old) {
+            v1 = *reinterpret_cast<const int4*>(src + lo + 4);
+          } else {   // the array ends inside the second word
+            v1.x = ci_old(src, lo + 4, a.M_old);
+            v1.y = ci_old(src, lo + 5, a.M_old);
+            v1.z = ci_old(src, lo + 6, a.M_old);
+          }
+        }
+        int4 o;
+        switch (r) {
+          case 0: o = v0; break;
+          case 1: o = make_int4(v0.y, v0.z, v0.w, v1.x); break;
+          case 2: o = make_int4(v0.z, v0.w, v1.x, v1.y); break;
+          default: o = make_int4(v0.w, v1.x, v1.y, v1.z); break;
+        }
+        *reinterpret_cast<int4*>(dst + p) = o;
+      } else {
+        for (int i = 0; i < 4 && p + i < c1; ++i) dst[p + i] = ci_old(src, e + i, a.M_old);
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(CI_NT) void csr_insert_kernel(CsrInsert a) {
+  __shared__ int64_t runs[2 * CI_LDS_RUNS];
+  const int64_t u0 = (int64_t)blockIdx.x * a.units_per_block;
+  const int64_t u1 = u0 + a.units_per_block < a.n_units ? u0 + a.units_per_block : a.n_units;
+  if (u0 >= u1) return;
+  const int64_t M_new = a.M_old + a.m;
+  const int64_t pu1 = u1 < a.n_pay_units ? u1 : a.n_pay_units;
+  if (u0 < pu1) {
+    // the touched segments [j_lo, j_hi) that reach into this workgroup's positions
+    const int64_t p0 = u0 * CI_CHUNK;
+    const int64_t p1 = pu1 * CI_CHUNK < M_new ? pu1 * CI_CHUNK : M_new;
+    const int64_t j_lo = ci_first(0, a.t, [&](int64_t j) { return ci_ne(a, j) > p0; });
+    const int64_t j_hi = ci_first(j_lo, a.t, [&](int64_t j) { return ci_ns(a, j) >= p1; });
+    const bool staged = j_hi - j_lo <= CI_LDS_RUNS;   // (the same in every thread)
+    if (staged) {
+      for (int64_t i = threadIdx.x; i < j_hi - j_lo; i += CI_NT) {
+        runs[2 * i] = ci_ns(a, j_lo + i);
+        runs[2 * i + 1] = ci_ne(a, j_lo + i);
+      }
+      __syncthreads();
+    }
+    auto ns = [&](int64_t j) { return staged ? runs[2 * (j - j_lo)] : ci_ns(a, j); };
+    auto ne = [&](int64_t j) { return staged ? runs[2 * (j - j_lo) + 1] : ci_ne(a, j); };
+    for (int64_t u = u0; u < pu1; ++u) {
+      const int64_t c0 = u * CI_CHUNK;
+      const int64_t c1 = c0 + CI_CHUNK < M_new ? c0 + CI_CHUNK : M_new;
+      const int64_t cj_lo = ci_first(j_lo, j_hi, [&](int64_t j) { return ne(j) > c0; });
+      const int64_t cj_hi = ci_first(cj_lo, j_hi, [&](int64_t j) { return ns(j) >= c1; });
+      if (cj_lo == cj_hi) {
+        ci_copy_shift(a, c0, c1, a.prefix[cj_lo]);
+        continue;
+      }
+      for (int64_t p = c0 + threadIdx.x; p < c1; p += CI_NT) {
+        // k: the inserts in front of p; ins: p is insert k itself
+        const int64_t jj = ci_first(cj_lo, cj_hi, [&](int64_t j) { return ns(j) > p; });
+        int64_t k;
+        bool ins = false;
+        if (jj == cj_lo) {
+          k = a.prefix[cj_lo];
+        } else if (p >= ne(jj - 1)) {
+          k = a.prefix[jj];
+        } else {
+          const int64_t q = p - ns(jj - 1);
+          const int64_t b1 = a.prefix[jj];
+          k = ci_first(a.prefix[jj - 1], b1, [&](int64_t i) { return a.ins_pos[i] >= q; });
+          ins = k < b1 && a.ins_pos[k] == q;
+        }
+        if (ins) k = k < 0 ? 0 : (k >= a.m ? a.m - 1 : k);
+        for (int w = 0; w < a.n_payloads; ++w)
+          a.new_val[w][p] = ins ? a.ins_val[w][k] : ci_old(a.old_val[w], p - k, a.M_old);
+      }
+    }
+  }
+  // new_off[o] = the old start of o + the inserts into owners in front of o
+  for (int64_t u = u0 > a.n_pay_units ? u0 : a.n_pay_units; u < u1; ++u) {
+    const int64_t o0 = (u - a.n_pay_units) * CI_CHUNK;
+    const int64_t o1 = o0 + CI_CHUNK < a.U_new + 1 ? o0 + CI_CHUNK : a.U_new + 1;
+    const int64_t lo = ci_first(0, a.t, [&](int64_t j) { return a.touched[j] >= o0; });
+    const int64_t hi = ci_first(lo, a.t, [&](int64_t j) { return a.touched[j] >= o1; });
+    for (int64_t o = o0 + threadIdx.x; o < o1; o += CI_NT) {
+      const int64_t k = ci_first(lo, hi, [&](int64_t j) { return a.touched[j] >= o; });
+      a.new_off[o] = ci_old_at(a, o) + (a.t ? a.prefix[k] : 0);
+    }
+  }
+}
+
 }  // namespace
+
+dcnr_status csr_insert(const int64_t* old_off, int64_t U_old, int64_t U_new, int64_t M_old,
+                       int n_payloads, const int32_t* const* old_val, const int64_t* touched,
+                       const int64_t* prefix, int64_t t, const int64_t* ins_pos,
+                       const int32_t* const* ins_val, int64_t m, int64_t* new_off,
+                       int32_t* const* new_val, hipStream_t s) {
+  CsrInsert a;
+  a.old_off = old_off; a.touched = touched; a.prefix = prefix; a.ins_pos = ins_pos;
+  a.new_off = new_off;
+  a.U_old = U_old; a.U_new = U_new; a.M_old = M_old; a.m = m; a.t = t;
+  a.n_payloads = n_payloads;
+  a.vec = 1;
+  for (int w = 0; w < 2; ++w) {
+    const bool on = w < n_payloads && m > 0;
+    a.old_val[w] = on ? old_val[w] : nullptr;
+    a.ins_val[w] = on ? ins_val[w] : nullptr;
+    a.new_val[w] = on ? new_val[w] : nullptr;
+    if (((uintptr_t)a.old_val[w] | (uintptr_t)a.new_val[w]) & 15) a.vec = 0;
+  }
+  // without inserts the payloads are the old generation's: the offsets only
+  a.n_pay_units = m > 0 ? cdiv(M_old + m, CI_CHUNK) : 0;
+  a.n_units = a.n_pay_units + cdiv(U_new + 1, CI_CHUNK);
+  int64_t grid = a.n_units < CI_MAX_BLOCKS ? a.n_units : CI_MAX_BLOCKS;
+  a.units_per_block = cdiv(a.n_units, grid);
+  grid = cdiv(a.n_units, a.units_per_block);
+  hipLaunchKernelGGL(csr_insert_kernel, dim3((unsigned)grid), dim3(CI_NT), 0, s, a);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
 
 dcnr_status gather_rows(const int64_t* idx, int64_t n, int64_t n_src, int n_arrays,
                         const void* const* src, void* const* dst, const int64_t* row_bytes,

@@ -35,7 +35,8 @@ ALLREDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, 
 # dcnr_grad_ready_fn(ctx, group, stream); groups below
 GRAD_READY_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p)
 GRADS_DENSE, GRADS_EMBEDDING = 0, 1
-TOUCHED_MAX_WORLD = 64   # DCNR_TOUCHED_MAX_WORLD: ranks dcnr_emb_touched_rows counts owners for
+CSR_INSERT_CHUNK = 4096  # DCNR_CSR_INSERT_CHUNK: output elements per workgroup step of dcnr_csr_insert
+TOUCHED_MAX_WORLD = 64  # DCNR_TOUCHED_MAX_WORLD: ranks dcnr_emb_touched_rows counts owners for
 
 
 class ModelDesc(ctypes.Structure):
@@ -260,6 +261,8 @@ _SIGS = {
     "dcnr_requests_recommended_by": (ctypes.c_int, [ctypes.POINTER(Interactions), _P, _I64, _I64,
                                                     _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P,
                                                     _P, _P]),
+    "dcnr_csr_insert": (ctypes.c_int, [_P, _I64, _I64, _I64, ctypes.c_int32, _P, _P, _P, _I64, _P,
+                                       _P, _I64, _P, _P, _P]),
     "dcnr_check_errors": (ctypes.c_int, [_P, ctypes.c_size_t, _P]),
     "dcnr_linear_bf16": (ctypes.c_int, [_P, _I64, _I64, ctypes.c_int32, _P, _I64, ctypes.c_int32,
                                         _P, _P, _I64, ctypes.c_int, _P]),

@@ -22,7 +22,9 @@ dictionaries stay with the caller, as the joblib pickles do in main.py.
 """
 from __future__ import annotations
 
+import ctypes
 import threading
+import time
 from typing import List, Tuple
 
 import numpy as np
@@ -53,7 +55,8 @@ def _csr(owner: np.ndarray, n: int) -> np.ndarray:
 
 
 class InteractionStore:
-    """Built once from host arrays in row space.
+    """Built from host arrays in row space; ``append`` adds further reviews,
+    friendships and reviewers in place (nothing is ever removed).
 
     review_reviewer [M]  dense reviewer index of each ``main_df`` row, in [0, U)
     review_item [M]      its hotel row, in [0, n_items)
@@ -113,7 +116,8 @@ class InteractionStore:
         self.n_friends = np.diff(self.friend_offsets)
         self.friends_rows, self.friends_pos, self.friends_neg = (
             fsum(self.n_rows), fsum(self.n_pos), fsum(self.n_neg))
-        self._dev = {}
+        self._dev, self._prev = {}, {}   # per device: the newest generation, the one before
+        self.last_append = None          # timings and upload size of the last append that changed something
         self._dev_lock = threading.Lock()
 
     def _distinct(self, srt_rev, items, flag) -> np.ndarray:
@@ -185,9 +189,244 @@ class InteractionStore:
                 pick(self.n_pos, self.friends_pos), pick(self.n_neg, self.friends_neg),
                 nf, np.where(known, self.friends_rows[u], 0), np.where(known, self.friends_pos[u], 0))
 
+    # ---------------------------------------------------------------- append
+    def append(self, review_reviewer=(), review_item=(), review_rating=(), friend_a=(),
+               friend_b=(), n_reviewers: int | None = None) -> None:
+        """Further rows of ``main_df`` and ``friendships_df``, in place.
+
+        The arguments mean what they mean in the constructor: the reviews are
+        the next rows of ``main_df`` (their ``review_row`` values are
+        ``n_reviews .. n_reviews + m - 1``, in argument order), the pairs are
+        further rows of ``friendships_df``.  ``n_reviewers`` may grow U (never
+        shrink it; default: unchanged), and the batch may name the new
+        reviewers.  Afterwards every host array and count, and every device
+        tensor, equals those of a store built from the concatenated inputs
+        with the final ``n_reviewers``: a reviewer's new reviews stand behind
+        the old ones in batch order, a pair adds both directions (one entry
+        for (u, u)) at their ascending places, and entries that exist already,
+        or repeat inside the batch, are dropped.
+
+        The host work is that of the batch and of the touched reviewers' own
+        segments (plus the memory moves of the insertions): no sort of the old
+        reviews, no ``np.unique`` over the old pairs.  On each device the store
+        was uploaded to, dcnr_csr_insert writes the new CSRs from the old ones
+        and the uploaded batch; the host copies are not uploaded again.
+        Everything is validated, and every new array made, before anything
+        changes: a failed append leaves the store as it was, on the host and on
+        the devices.  An empty batch is a no-op.  ``last_append`` keeps the
+        seconds of the host and the device part and the bytes uploaded per
+        device (tools/bench_store_append.py reports them).
+
+        Out of scope: removing or editing a review, unfriending, changing
+        ``n_items``, and stores sharded over several ranks.  For those, build
+        a new store.
+        """
+        rev = np.asarray(review_reviewer, dtype=np.int64).reshape(-1)
+        item = np.asarray(review_item, dtype=np.int64).reshape(-1)
+        rating = np.asarray(review_rating, dtype=np.float64).reshape(-1)
+        fa = np.asarray(friend_a, dtype=np.int64).reshape(-1)
+        fb = np.asarray(friend_b, dtype=np.int64).reshape(-1)
+        if not (rev.size == item.size == rating.size):
+            raise ValueError("InteractionStore.append: review_reviewer, review_item and "
+                             "review_rating must have one entry per review")
+        if fa.size != fb.size:
+            raise ValueError("InteractionStore.append: friend_a and friend_b must have one entry "
+                             "per pair")
+        U0, M0, E0 = self.n_reviewers, self.n_reviews, self.friend_rows.size
+        U = U0 if n_reviewers is None else int(n_reviewers)
+        if U < U0:
+            raise ValueError(f"InteractionStore.append: n_reviewers={U} below the store's {U0}")
+        for a, what in ((rev, "review_reviewer"), (fa, "friend_a"), (fb, "friend_b")):
+            if a.size and (a.min() < 0 or a.max() >= U):
+                raise ValueError(f"InteractionStore.append: {what} outside [0, {U})")
+        if item.size and (item.min() < 0 or item.max() >= self.n_items):
+            raise ValueError(f"InteractionStore.append: review_item outside [0, {self.n_items})")
+        if max(M0 + rev.size, E0 + 2 * fa.size, U) >= 2 ** 31 - 1:
+            raise ValueError("InteractionStore.append: 2^31 - 1 or more reviews, friend rows or "
+                             "reviewers")
+        if rev.size == 0 and fa.size == 0 and U == U0:
+            return
+        t_start = time.perf_counter()
+        grow = lambda a: np.concatenate([a, np.zeros(U - U0, a.dtype)]) if U > U0 else a.copy()
+        ext = lambda off: np.concatenate([off, np.full(U - U0, off[-1], np.int64)])
+
+        # ---- reviews: behind the reviewer's old ones, in batch order
+        r_off = ext(self.review_offsets)
+        order = np.argsort(rev, kind="stable")
+        srt = rev[order]
+        r_own, r_first, r_cnt = np.unique(srt, return_index=True, return_counts=True)
+        r_pre = np.concatenate([[0], np.cumsum(r_cnt)]).astype(np.int64)
+        cls = ((rating >= 8).astype(np.int64) * POS_BIT + (rating <= 4).astype(np.int64) * NEG_BIT)[order]
+        r_at = r_off[srt + 1]                        # old index each one is inserted in front of
+        r_pos = r_off[srt + 1] - r_off[srt] + np.arange(srt.size) - np.repeat(r_first, r_cnt)
+        n_item, n_class = item[order], cls.astype(np.int8)
+        n_row = M0 + order.astype(np.int64)
+        review_item = np.insert(self.review_item, r_at, n_item)
+        review_class = np.insert(self.review_class, r_at, n_class)
+        review_row = np.insert(self.review_row, r_at, n_row)
+        n_rows = grow(self.n_rows)
+        n_rows[r_own] += r_cnt
+        review_offsets = self._shifted(r_off, r_own, r_pre)
+        n_pos, n_neg = grow(self.n_pos), grow(self.n_neg)
+        deltas = [r_cnt]   # of n_rows, n_pos, n_neg at the touched reviewers
+        if r_own.size:   # the distinct positives / negatives of the touched reviewers, anew
+            lo, hi = review_offsets[r_own], review_offsets[r_own + 1]
+            idx = np.repeat(lo - np.concatenate([[0], np.cumsum(hi - lo)[:-1]]), hi - lo) + \
+                np.arange(int((hi - lo).sum()))
+            who = np.repeat(np.arange(r_own.size), hi - lo)
+            for flag, out in ((POS_BIT, n_pos), (NEG_BIT, n_neg)):
+                before = out[r_own].copy()
+                keep = (review_class[idx] & flag) != 0
+                pairs = np.unique(who[keep] * self.n_items + review_item[idx][keep])
+                out[r_own] = np.bincount(pairs // self.n_items, minlength=r_own.size)
+                deltas.append(out[r_own] - before)
+
+        # ---- friends: both directions, distinct, without those that exist already
+        f_off = ext(self.friend_offsets)
+        if fa.size:
+            ent = np.unique(np.stack([np.concatenate([fa, fb]), np.concatenate([fb, fa])], 1), axis=0)
+            at = self._lower_bound(self.friend_rows, f_off[ent[:, 0]], f_off[ent[:, 0] + 1], ent[:, 1])
+            there = at < f_off[ent[:, 0] + 1]
+            there[there] = self.friend_rows[at[there]] == ent[there, 1]
+            ent, f_at = ent[~there], at[~there]
+        else:
+            ent, f_at = np.zeros((0, 2), np.int64), np.zeros(0, np.int64)
+        f_own, f_first, f_cnt = np.unique(ent[:, 0], return_index=True, return_counts=True)
+        f_pre = np.concatenate([[0], np.cumsum(f_cnt)]).astype(np.int64)
+        f_pos = f_at - f_off[ent[:, 0]] + np.arange(ent.shape[0]) - np.repeat(f_first, f_cnt)
+        friend_rows = np.insert(self.friend_rows, f_at, ent[:, 1])
+        friend_offsets = self._shifted(f_off, f_own, f_pre)
+        n_friends = grow(self.n_friends)
+        n_friends[f_own] += f_cnt
+        # the sums over a reviewer's friends: first each touched reviewer's change,
+        # to the friends it had; then a new friend's whole (new) count
+        sums = []
+        if r_own.size:
+            flo, fhi = f_off[r_own], f_off[r_own + 1]
+            fidx = np.repeat(flo - np.concatenate([[0], np.cumsum(fhi - flo)[:-1]]), fhi - flo) + \
+                np.arange(int((fhi - flo).sum()))
+            old_friends, of_who = self.friend_rows[fidx], np.repeat(np.arange(r_own.size), fhi - flo)
+        for j, (new, fsum) in enumerate(((n_rows, self.friends_rows), (n_pos, self.friends_pos),
+                                         (n_neg, self.friends_neg))):
+            fsum = grow(fsum)
+            if r_own.size:
+                np.add.at(fsum, old_friends, deltas[j][of_who])
+            np.add.at(fsum, ent[:, 0], new[ent[:, 1]])
+            sums.append(fsum)
+
+        # ---- the devices, then the host: nothing is published before all of it exists
+        t_host = time.perf_counter()
+        with self._dev_lock:
+            gens = {key: self._device_append(key, hit, U, r_own, r_pre, r_pos,
+                                             [n_item * 4 + n_class, n_row], f_own, f_pre, f_pos,
+                                             [ent[:, 1]])
+                    for key, hit in self._dev.items()}
+            if self._prev:
+                # an older generation is dropped only when no kernel launched against it can still run
+                for key in self._prev:
+                    torch.cuda.synchronize(torch.device(*key))
+            self._prev = dict(self._dev)
+            self._dev.update(gens)
+            self.n_reviewers, self.n_reviews = U, M0 + rev.size
+            self.review_offsets, self.review_item, self.review_class, self.review_row = (
+                review_offsets, review_item, review_class, review_row)
+            self.friend_offsets, self.friend_rows = friend_offsets, friend_rows
+            self.n_rows, self.n_pos, self.n_neg, self.n_friends = n_rows, n_pos, n_neg, n_friends
+            self.friends_rows, self.friends_pos, self.friends_neg = sums
+            self.last_append = dict(host_s=t_host - t_start, device_s=time.perf_counter() - t_host,
+                                    upload_bytes=8 * (r_own.size + r_pre.size + r_pos.size + f_own.size +
+                                                      f_pre.size + f_pos.size + 1) +
+                                    4 * (2 * r_pos.size + f_pos.size + 1), devices=len(gens))
+
+    @staticmethod
+    def _shifted(off, owners, prefix) -> np.ndarray:
+        """off [U + 1] with prefix[j + 1] - prefix[j] entries more in owner owners[j]."""
+        add = np.zeros(off.size, np.int64)
+        add[owners + 1] = np.diff(prefix)
+        return off + np.cumsum(add)
+
+    @staticmethod
+    def _lower_bound(arr, lo, hi, x) -> np.ndarray:
+        """Per entry: the first index in [lo, hi) of the ascending arr[lo:hi] not below x."""
+        lo, hi = lo.copy(), hi.copy()
+        while True:
+            act = lo < hi
+            if not act.any():
+                return lo
+            mid = (lo + hi) >> 1
+            less = act.copy()
+            less[act] = arr[mid[act]] < x[act]
+            lo = np.where(less, mid + 1, lo)
+            hi = np.where(act & ~less, mid, hi)
+
+    def _device_append(self, key, hit, U, r_own, r_pre, r_pos, r_vals, f_own, f_pre, f_pos, f_vals):
+        """The next generation of one device's CSRs: (dcnr_interactions, tensors)."""
+        device = torch.device(*key)
+        _, old = hit
+        lib = _lib.load()
+        # the whole batch in one upload: int64 words, the int32 payloads behind them
+        parts = [r_own, r_pre, r_pos, f_own, f_pre, f_pos]
+        words = np.concatenate([np.asarray(a, np.int64) for a in parts] +
+                               [np.zeros(1, np.int64)])   # (never empty)
+        vals = np.concatenate([np.asarray(a).astype(np.int32) for a in r_vals + f_vals] +
+                              [np.zeros(1, np.int32)])
+        d_words = torch.from_numpy(words).to(device)
+        d_vals = torch.from_numpy(vals).to(device)
+        at, o = [], 0
+        for a in parts:
+            at.append(d_words.data_ptr() + 8 * o)
+            o += a.size
+        new = {}
+        with torch.cuda.device(device):
+            stream = _lib.stream_ptr(device)
+            v = d_vals.data_ptr()
+            for names, off_name, (own, pre, pos), (p_own, p_pre, p_pos), n_vals in (
+                    (["review_items", "review_rows"], "review_offsets", (r_own, r_pre, r_pos), at[:3], 2),
+                    (["friend_rows"], "friend_offsets", (f_own, f_pre, f_pos), at[3:], 1)):
+                m, M_old, U_old = pos.size, old[names[0]].numel(), old[off_name].numel() - 1
+                ins = [v + 4 * m * w for w in range(n_vals)]
+                v += 4 * m * n_vals
+                if m == 0 and U == U_old:   # this CSR is as it was
+                    new.update({k: old[k] for k in names + [off_name]})
+                    continue
+                new[off_name] = torch.empty(U + 1, dtype=torch.int64, device=device)
+                for k in names:
+                    new[k] = torch.empty(M_old + m, dtype=torch.int32, device=device) if m else old[k]
+                ptrs = lambda ps: (ctypes.c_void_p * 2)(*[p or None for p in ps])
+                _lib.check(lib.dcnr_csr_insert(
+                    old[off_name].data_ptr(), U_old, U, M_old, n_vals,
+                    ptrs([old[k].data_ptr() for k in names]), p_own, p_pre, own.size, p_pos,
+                    ptrs(ins), m, new[off_name].data_ptr(),
+                    ptrs([new[k].data_ptr() for k in names]), stream), "dcnr_csr_insert")
+            # published only once written; the uploaded batch may go once read
+            torch.cuda.current_stream(device).synchronize()
+        return self._describe(new, U, new["review_rows"].numel()), new
+
+    @staticmethod
+    def _describe(t, n_reviewers, n_reviews):
+        p = lambda x: x.data_ptr() if x.numel() else None
+        return _lib.Interactions(n_reviewers, p(t["friend_offsets"]), p(t["friend_rows"]),
+                                 t["friend_rows"].numel(), p(t["review_offsets"]),
+                                 p(t["review_items"]), p(t["review_rows"]), n_reviews)
+
     # ---------------------------------------------------------------- device
     def on(self, device):
-        """The device CSRs (uploaded once per device) as (dcnr_interactions, tensors)."""
+        """The device CSRs as (dcnr_interactions, tensors): uploaded on a
+        device's first call, advanced on that device by every ``append`` since.
+
+        Generations.  The tensors of a generation are never written after they
+        are published, and ``append`` publishes the next one only once it is
+        fully written.  A kernel reads the generation its descriptor points
+        into, so whoever launches one keeps the tensors returned here until the
+        kernel has finished (``RankingPipeline.recommend_users`` keeps them with
+        its answers).  For callers that kept the descriptor alone, the store
+        itself holds the generation before the newest, and it synchronizes the
+        device before it lets go of an older one: memory a kernel launched
+        before that ``append`` may read is not released under it.  ``append``
+        and the calls that read the host counts (``bounds``) are not atomic
+        with respect to each other: serialise ``append`` against
+        ``recommend_users`` on the same store.
+        """
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("InteractionStore.on: the device copies live on the HIP device only")
@@ -203,10 +442,5 @@ class InteractionStore:
                          review_rows=up(self.review_row, np.int32))
                 # published only once written: a call on another stream may read it at once
                 torch.cuda.current_stream(device).synchronize()
-                p = lambda x: x.data_ptr() if x.numel() else None
-                desc = _lib.Interactions(self.n_reviewers, p(t["friend_offsets"]),
-                                         p(t["friend_rows"]), t["friend_rows"].numel(),
-                                         p(t["review_offsets"]), p(t["review_items"]),
-                                         p(t["review_rows"]), self.n_reviews)
-                hit = self._dev[key] = (desc, t)
+                hit = self._dev[key] = (self._describe(t, self.n_reviewers, self.n_reviews), t)
         return hit

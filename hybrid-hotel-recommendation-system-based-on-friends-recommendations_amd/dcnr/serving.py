@@ -1031,7 +1031,7 @@ class RankingPipeline:
         if NB:
             sets.append(torch.empty(NB, dtype=torch.int64, device=dev))
         set_rows = torch.cat(sets) if len(sets) > 1 else sets[0]
-        desc, _ = store.on(dev)
+        desc, held = store.on(dev)   # the generation this call's kernels read: kept with the answers
         d_pos = torch.empty(Q, dtype=torch.int64, device=dev)
         # count, status, out_count of the candidate / rank kernels; the source
         # kernel's counts [2 R] + status, the recommended_by kernel's status
@@ -1094,6 +1094,7 @@ class RankingPipeline:
                                                                     by_count, lists)
         res.rows, res.logits = out_rows, out_logits
         res._seg, res._cnt, res._list_off, res._store, res._rv = seg, cnt, list_off, store, rv
+        res._held = held
         res.n_positives, res.positives_bound = s_counts[:, 0], zero(pos_b)
         res.on_host = on_host
         for r in range(R):

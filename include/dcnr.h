@@ -38,6 +38,8 @@
  *   dcnr_requests_sources, dcnr_requests_recommended_by
  *                         the friends, positives / negatives and recommended_by
  *                         lists of those requests    main.py:172-194, 336-351
+ *   dcnr_csr_insert       new main_df / friendships_df rows into those CSRs on the
+ *                         device (the reference reloads both at start-up only)
  *   dcnr_eval_metrics     roc_auc_score / BCEWithLogitsLoss / sqrt(mean_squared_error)
  *                         over the validation logits          train.py:255-265, 366-387
  *   dcnr_eval_group_metrics  GAUC, NDCG@k, hit rate@k, recall@k and MRR of every
@@ -944,6 +946,35 @@ dcnr_status dcnr_requests_recommended_by(const dcnr_interactions* store, const i
                                          int64_t n_list_rows, int32_t* lists, int32_t* by_count,
                                          int64_t* by_offsets, int32_t* by_reviewers,
                                          int32_t* status, dcnr_stream_t stream);
+
+/* A new generation of one of those CSRs with m entries inserted: what
+ * dcnr.InteractionStore.append runs per device when reviews or friendships
+ * arrive, once for the reviews (n_payloads = 2: review_items, review_rows) and
+ * once for the friends (n_payloads = 1).  The old generation, old_offsets
+ * [n_old_owners + 1] and old_payloads[w] [n_old_entries], is read only and
+ * never an output: kernels on other streams may still read it.  The batch, in
+ * device memory, prepared by the host from the batch alone: the t touched
+ * owners, ascending and distinct, in [0, n_new_owners); insert_prefix [t + 1],
+ * the exclusive sums of their insert counts (each >= 1; insert_prefix[t] = m);
+ * and for each inserted entry, grouped by owner in that order, insert_pos: its
+ * position inside the owner's NEW segment, ascending within the owner, and
+ * insert_payloads[w]: its values.  Written: new_offsets [n_new_owners + 1] and
+ * new_payloads[w] [n_old_entries + m]; owners at or beyond n_old_owners start
+ * from n_old_entries.  Every output element is written exactly once by one
+ * lane, without atomics: the same bits on every run.  All positions are 64-bit.
+ * Workgroups take DCNR_CSR_INSERT_CHUNK output elements at a time.
+ * With m = 0 only new_offsets is written (the payloads of the new generation
+ * are the old ones; the payload arguments may be NULL); with m = 0 and
+ * n_new_owners = n_old_owners nothing is launched.  DCNR_BAD_ARG before any
+ * launch: a null or negative argument, n_payloads outside 1..2, n_new_owners <
+ * n_old_owners, t > m, or t = 0 with m > 0. */
+#define DCNR_CSR_INSERT_CHUNK 4096
+dcnr_status dcnr_csr_insert(const int64_t* old_offsets, int64_t n_old_owners, int64_t n_new_owners,
+                            int64_t n_old_entries, int32_t n_payloads,
+                            const int32_t* const* old_payloads, const int64_t* touched,
+                            const int64_t* insert_prefix, int64_t t, const int64_t* insert_pos,
+                            const int32_t* const* insert_payloads, int64_t m, int64_t* new_offsets,
+                            int32_t* const* new_payloads, dcnr_stream_t stream);
 
 /* The deep tower's Linear layer as a standalone bf16 call (nn.Linear forward,
  * train.py:143,105,109): C[M,N] = X[M,K] . W[N,K]^T + bias, X/W bf16
