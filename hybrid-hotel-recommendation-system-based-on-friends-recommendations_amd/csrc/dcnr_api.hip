@@ -1931,6 +1931,27 @@ dcnr_status dcnr_csr_insert(const int64_t* old_offsets, int64_t n_old_owners, in
   return DCNR_OK;
 }
 
+dcnr_status dcnr_csr_remove(const int64_t* old_offsets, int64_t n_owners, int64_t n_old_entries,
+                            int32_t n_payloads, const int32_t* const* old_payloads,
+                            const int64_t* removed, int64_t m, int64_t* new_offsets,
+                            int32_t* const* new_payloads, dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const bool pay = m > 0 && m < n_old_entries;   // some payload words are copied
+  bool bad = !old_offsets || !new_offsets || n_owners < 0 || n_old_entries < 0 || n_payloads < 1 ||
+             n_payloads > 2 || m < 0 || m > n_old_entries || (m > 0 && !removed) ||
+             (pay && (!old_payloads || !new_payloads));
+  for (int w = 0; !bad && pay && w < n_payloads; ++w) bad = !old_payloads[w] || !new_payloads[w];
+  if (bad) {
+    set_error("dcnr_csr_remove: bad argument (owners=%lld, entries=%lld, payloads=%d, m=%lld)",
+              (long long)n_owners, (long long)n_old_entries, n_payloads, (long long)m);
+    return DCNR_BAD_ARG;
+  }
+  if (m == 0) return DCNR_OK;
+  TRYP(DCNR_K_SERVE, s, csr_remove(old_offsets, n_owners, n_old_entries, n_payloads, old_payloads,
+                                   removed, m, new_offsets, new_payloads, s));
+  return DCNR_OK;
+}
+
 size_t dcnr_bce_workspace_size(void) { return bce_ws_bytes() + 256; }
 
 dcnr_status dcnr_emb_touched_rows(const dcnr_model_desc* desc, const void* ws, size_t ws_bytes,

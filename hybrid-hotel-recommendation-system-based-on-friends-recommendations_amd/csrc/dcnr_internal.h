@@ -893,6 +893,11 @@ dcnr_status csr_insert(const int64_t* old_off, int64_t U_old, int64_t U_new, int
                        const int64_t* prefix, int64_t t, const int64_t* ins_pos,
                        const int32_t* const* ins_val, int64_t m, int64_t* new_off,
                        int32_t* const* new_val, hipStream_t s);
+// dcnr_csr_remove: the generation without the m entries at removed[] (m >= 1;
+// the payload arrays are neither read nor written when m == M_old)
+dcnr_status csr_remove(const int64_t* old_off, int64_t U, int64_t M_old, int n_payloads,
+                       const int32_t* const* old_val, const int64_t* removed, int64_t m,
+                       int64_t* new_off, int32_t* const* new_val, hipStream_t s);
 
 dcnr_status fill_zero(void* p, size_t bytes, hipStream_t s);
 // *dst = *src with a system-scope store (dst may be pinned host memory)

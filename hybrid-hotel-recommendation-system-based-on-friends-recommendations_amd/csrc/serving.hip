@@ -941,7 +941,8 @@ __global__ __launch_bounds__(SV_NT) void req_recommended_by_kernel(
     for (int64_t j = lo + lane; j < hi; j += 64) {
       const int32_t wd = st.rv_item[j];
       const int32_t row = st.rv_row[j];
-      if (wd < 0 || (wd >> 2) >= n_items || row < 0 || row >= st.M) { bad = 1; continue; }
+      // (row is a sort key only, and not below M: rows that were removed leave gaps)
+      if (wd < 0 || (wd >> 2) >= n_items || row < 0) { bad = 1; continue; }
       if (!(wd & 1)) continue;
       const int q = lower_bound<int>(mkey, c2, wd >> 2);
       if (q >= c2 || mkey[q] != (wd >> 2)) continue;
@@ -1104,25 +1105,29 @@ __device__ __forceinline__ int32_t ci_old(const int32_t* src, int64_t e, int64_t
   return src[e < 0 ? 0 : (e >= M_old ? M_old - 1 : e)];
 }
 
-// new[c0, c1) = old[c0 - shift, c1 - shift): c0 is a multiple of CI_CHUNK
-__device__ void ci_copy_shift(const CsrInsert& a, int64_t c0, int64_t c1, int64_t shift) {
-  for (int w = 0; w < a.n_payloads; ++w) {
-    const int32_t* src = a.old_val[w];
-    int32_t* dst = a.new_val[w];
+// dst[w][c0, c1) = src[w][c0 - shift, c1 - shift) for each payload: c0 is a
+// multiple of CI_CHUNK, the shift of either sign (inserts in front push the
+// source back, removals pull it forward); vec: every array is 16-byte aligned
+__device__ void ci_copy_shift(const int32_t* const* old_val, int32_t* const* new_val,
+                              int n_payloads, int vec, int64_t M_old, int64_t c0, int64_t c1,
+                              int64_t shift) {
+  for (int w = 0; w < n_payloads; ++w) {
+    const int32_t* src = old_val[w];
+    int32_t* dst = new_val[w];
     for (int64_t p = c0 + (int64_t)threadIdx.x * 4; p < c1; p += 4 * CI_NT) {
       const int64_t e = p - shift;
       const int r = (int)(e & 3);
       const int64_t lo = e - r;
-      if (a.vec && p + 4 <= c1 && e >= 0 && lo + 4 <= a.M_old) {
+      if (vec && p + 4 <= c1 && e >= 0 && lo + 4 <= M_old) {
         const int4 v0 = *reinterpret_cast<const int4*>(src + lo);
         int4 v1 = make_int4(0, 0, 0, 0);
         if (r) {
-          if (lo + 8 <= a.M_old) {
+          if (lo + 8 <= M_old) {
             v1 = *reinterpret_cast<const int4*>(src + lo + 4);
           } else {   // the array ends inside the second word
-            v1.x = ci_old(src, lo + 4, a.M_old);
-            v1.y = ci_old(src, lo + 5, a.M_old);
-            v1.z = ci_old(src, lo + 6, a.M_old);
+            v1.x = ci_old(src, lo + 4, M_old);
+            v1.y = ci_old(src, lo + 5, M_old);
+            v1.z = ci_old(src, lo + 6, M_old);
           }
         }
         int4 o;
@@ -1134,7 +1139,7 @@ __device__ void ci_copy_shift(const CsrInsert& a, int64_t c0, int64_t c1, int64_
         }
         *reinterpret_cast<int4*>(dst + p) = o;
       } else {
-        for (int i = 0; i < 4 && p + i < c1; ++i) dst[p + i] = ci_old(src, e + i, a.M_old);
+        for (int i = 0; i < 4 && p + i < c1; ++i) dst[p + i] = ci_old(src, e + i, M_old);
       }
     }
   }
@@ -1169,7 +1174,8 @@ __global__ __launch_bounds__(CI_NT) void csr_insert_kernel(CsrInsert a) {
       const int64_t cj_lo = ci_first(j_lo, j_hi, [&](int64_t j) { return ne(j) > c0; });
       const int64_t cj_hi = ci_first(cj_lo, j_hi, [&](int64_t j) { return ns(j) >= c1; });
       if (cj_lo == cj_hi) {
-        ci_copy_shift(a, c0, c1, a.prefix[cj_lo]);
+        ci_copy_shift(a.old_val, a.new_val, a.n_payloads, a.vec, a.M_old, c0, c1,
+                      a.prefix[cj_lo]);
         continue;
       }
       for (int64_t p = c0 + threadIdx.x; p < c1; p += CI_NT) {
@@ -1206,7 +1212,96 @@ __global__ __launch_bounds__(CI_NT) void csr_insert_kernel(CsrInsert a) {
   }
 }
 
+// ---- the mirror: a new generation with m entries taken out (dcnr_csr_remove;
+// InteractionStore.remove).  The same cut into chunks of output positions with
+// the offsets behind them.  An output position p holds old[p + c], c the
+// removed positions in front of its source: the first c in [0, m] with c == m
+// or removed[c] - c > p (removed[c] - c, the output position the survivors
+// behind removed[c] start from, does not descend).  c is constant over a chunk
+// no removed position falls into, which is then a shifted copy; the other
+// chunks search per element, between the chunk's first and last c.  The
+// searches index removed[] below m only and p + c <= M_old - 1 whatever its
+// values are (the reads are clamped all the same).
+struct CsrRemove {
+  const int64_t* old_off;   // [U + 1]
+  const int64_t* removed;   // [m] strictly ascending positions of the old payloads
+  const int32_t* old_val[2];
+  int32_t* new_val[2];
+  int64_t* new_off;         // [U + 1]
+  int64_t U, M_old, m;
+  int64_t n_pay_units, n_units, units_per_block;
+  int n_payloads, vec;
+};
+
+// the removed positions in front of the source of output position p, in [lo, hi]
+__device__ __forceinline__ int64_t cr_front(const CsrRemove& a, int64_t lo, int64_t hi, int64_t p) {
+  return ci_first(lo, hi, [&](int64_t c) { return a.removed[c] - c > p; });
+}
+
+__global__ __launch_bounds__(CI_NT) void csr_remove_kernel(CsrRemove a) {
+  const int64_t u0 = (int64_t)blockIdx.x * a.units_per_block;
+  const int64_t u1 = u0 + a.units_per_block < a.n_units ? u0 + a.units_per_block : a.n_units;
+  if (u0 >= u1) return;
+  const int64_t M_new = a.M_old - a.m;
+  const int64_t pu1 = u1 < a.n_pay_units ? u1 : a.n_pay_units;
+  if (u0 < pu1) {
+    // c of this workgroup's first and last position: every chunk's lie between
+    const int64_t p1 = pu1 * CI_CHUNK < M_new ? pu1 * CI_CHUNK : M_new;
+    const int64_t g_lo = cr_front(a, 0, a.m, u0 * CI_CHUNK);
+    const int64_t g_hi = cr_front(a, g_lo, a.m, p1 - 1);
+    for (int64_t u = u0; u < pu1; ++u) {
+      const int64_t c0 = u * CI_CHUNK;
+      const int64_t c1 = c0 + CI_CHUNK < M_new ? c0 + CI_CHUNK : M_new;
+      const int64_t k_lo = cr_front(a, g_lo, g_hi, c0);
+      const int64_t k_hi = cr_front(a, k_lo, g_hi, c1 - 1);
+      if (k_lo == k_hi) {
+        ci_copy_shift(a.old_val, a.new_val, a.n_payloads, a.vec, a.M_old, c0, c1, -k_lo);
+        continue;
+      }
+      for (int64_t p = c0 + threadIdx.x; p < c1; p += CI_NT) {
+        const int64_t c = cr_front(a, k_lo, k_hi, p);
+        for (int w = 0; w < a.n_payloads; ++w)
+          a.new_val[w][p] = ci_old(a.old_val[w], p + c, a.M_old);
+      }
+    }
+  }
+  // new_off[o] = the old start of o - the removed positions in front of it
+  for (int64_t u = u0 > a.n_pay_units ? u0 : a.n_pay_units; u < u1; ++u) {
+    const int64_t o0 = (u - a.n_pay_units) * CI_CHUNK;
+    const int64_t o1 = o0 + CI_CHUNK < a.U + 1 ? o0 + CI_CHUNK : a.U + 1;
+    for (int64_t o = o0 + threadIdx.x; o < o1; o += CI_NT) {
+      const int64_t at = a.old_off[o];
+      a.new_off[o] = at - ci_first(0, a.m, [&](int64_t i) { return a.removed[i] >= at; });
+    }
+  }
+}
+
 }  // namespace
+
+dcnr_status csr_remove(const int64_t* old_off, int64_t U, int64_t M_old, int n_payloads,
+                       const int32_t* const* old_val, const int64_t* removed, int64_t m,
+                       int64_t* new_off, int32_t* const* new_val, hipStream_t s) {
+  CsrRemove a;
+  a.old_off = old_off; a.removed = removed; a.new_off = new_off;
+  a.U = U; a.M_old = M_old; a.m = m;
+  a.n_payloads = n_payloads;
+  a.vec = 1;
+  for (int w = 0; w < 2; ++w) {
+    const bool on = w < n_payloads && m < M_old;
+    a.old_val[w] = on ? old_val[w] : nullptr;
+    a.new_val[w] = on ? new_val[w] : nullptr;
+    if (((uintptr_t)a.old_val[w] | (uintptr_t)a.new_val[w]) & 15) a.vec = 0;
+  }
+  // with every entry removed there are no payloads to write: the offsets only
+  a.n_pay_units = cdiv(M_old - m, CI_CHUNK);
+  a.n_units = a.n_pay_units + cdiv(U + 1, CI_CHUNK);
+  int64_t grid = a.n_units < CI_MAX_BLOCKS ? a.n_units : CI_MAX_BLOCKS;
+  a.units_per_block = cdiv(a.n_units, grid);
+  grid = cdiv(a.n_units, a.units_per_block);
+  hipLaunchKernelGGL(csr_remove_kernel, dim3((unsigned)grid), dim3(CI_NT), 0, s, a);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
 
 dcnr_status csr_insert(const int64_t* old_off, int64_t U_old, int64_t U_new, int64_t M_old,
                        int n_payloads, const int32_t* const* old_val, const int64_t* touched,

@@ -56,7 +56,8 @@ def _csr(owner: np.ndarray, n: int) -> np.ndarray:
 
 class InteractionStore:
     """Built from host arrays in row space; ``append`` adds further reviews,
-    friendships and reviewers in place (nothing is ever removed).
+    friendships and reviewers in place, ``remove`` takes reviews and
+    friendships out, ``set_rating`` edits ratings (the reviewers stay).
 
     review_reviewer [M]  dense reviewer index of each ``main_df`` row, in [0, U)
     review_item [M]      its hotel row, in [0, n_items)
@@ -92,6 +93,7 @@ class InteractionStore:
         if max(rev.size, 2 * fa.size, U) >= 2 ** 31 - 1:
             raise ValueError("InteractionStore: 2^31 - 1 or more reviews, friend rows or reviewers")
         self.n_reviewers, self.n_items, self.n_reviews = U, n_items, rev.size
+        self.next_review_row = rev.size   # main_df rows ever seen: n_reviews until one is removed
         # reviews by reviewer, main_df order kept inside a reviewer
         order = np.argsort(rev, kind="stable")
         cls = (rating >= 8).astype(np.int64) * POS_BIT + (rating <= 4).astype(np.int64) * NEG_BIT
@@ -118,6 +120,7 @@ class InteractionStore:
             fsum(self.n_rows), fsum(self.n_pos), fsum(self.n_neg))
         self._dev, self._prev = {}, {}   # per device: the newest generation, the one before
         self.last_append = None          # timings and upload size of the last append that changed something
+        self.last_remove = None          # ... of the last remove that did
         self._dev_lock = threading.Lock()
 
     def _distinct(self, srt_rev, items, flag) -> np.ndarray:
@@ -196,7 +199,9 @@ class InteractionStore:
 
         The arguments mean what they mean in the constructor: the reviews are
         the next rows of ``main_df`` (their ``review_row`` values are
-        ``n_reviews .. n_reviews + m - 1``, in argument order), the pairs are
+        ``next_review_row .. next_review_row + m - 1``, in argument order;
+        ``next_review_row`` is ``n_reviews`` as long as nothing was removed, and
+        rows that ``remove`` took out are not given again), the pairs are
         further rows of ``friendships_df``.  ``n_reviewers`` may grow U (never
         shrink it; default: unchanged), and the batch may name the new
         reviewers.  Afterwards every host array and count, and every device
@@ -217,9 +222,9 @@ class InteractionStore:
         seconds of the host and the device part and the bytes uploaded per
         device (tools/bench_store_append.py reports them).
 
-        Out of scope: removing or editing a review, unfriending, changing
-        ``n_items``, and stores sharded over several ranks.  For those, build
-        a new store.
+        Removing a review and unfriending: ``remove``; a changed rating:
+        ``set_rating``.  Out of scope: changing ``n_items``, shrinking U, and
+        stores sharded over several ranks.  For those, build a new store.
         """
         rev = np.asarray(review_reviewer, dtype=np.int64).reshape(-1)
         item = np.asarray(review_item, dtype=np.int64).reshape(-1)
@@ -241,7 +246,7 @@ class InteractionStore:
                 raise ValueError(f"InteractionStore.append: {what} outside [0, {U})")
         if item.size and (item.min() < 0 or item.max() >= self.n_items):
             raise ValueError(f"InteractionStore.append: review_item outside [0, {self.n_items})")
-        if max(M0 + rev.size, E0 + 2 * fa.size, U) >= 2 ** 31 - 1:
+        if max(M0 + rev.size, self.next_review_row + rev.size, E0 + 2 * fa.size, U) >= 2 ** 31 - 1:
             raise ValueError("InteractionStore.append: 2^31 - 1 or more reviews, friend rows or "
                              "reviewers")
         if rev.size == 0 and fa.size == 0 and U == U0:
@@ -260,7 +265,7 @@ class InteractionStore:
         r_at = r_off[srt + 1]                        # old index each one is inserted in front of
         r_pos = r_off[srt + 1] - r_off[srt] + np.arange(srt.size) - np.repeat(r_first, r_cnt)
         n_item, n_class = item[order], cls.astype(np.int8)
-        n_row = M0 + order.astype(np.int64)
+        n_row = self.next_review_row + order.astype(np.int64)
         review_item = np.insert(self.review_item, r_at, n_item)
         review_class = np.insert(self.review_class, r_at, n_class)
         review_row = np.insert(self.review_row, r_at, n_row)
@@ -269,17 +274,8 @@ class InteractionStore:
         review_offsets = self._shifted(r_off, r_own, r_pre)
         n_pos, n_neg = grow(self.n_pos), grow(self.n_neg)
         deltas = [r_cnt]   # of n_rows, n_pos, n_neg at the touched reviewers
-        if r_own.size:   # the distinct positives / negatives of the touched reviewers, anew
-            lo, hi = review_offsets[r_own], review_offsets[r_own + 1]
-            idx = np.repeat(lo - np.concatenate([[0], np.cumsum(hi - lo)[:-1]]), hi - lo) + \
-                np.arange(int((hi - lo).sum()))
-            who = np.repeat(np.arange(r_own.size), hi - lo)
-            for flag, out in ((POS_BIT, n_pos), (NEG_BIT, n_neg)):
-                before = out[r_own].copy()
-                keep = (review_class[idx] & flag) != 0
-                pairs = np.unique(who[keep] * self.n_items + review_item[idx][keep])
-                out[r_own] = np.bincount(pairs // self.n_items, minlength=r_own.size)
-                deltas.append(out[r_own] - before)
+        if r_own.size:
+            deltas += self._recount(review_offsets, review_item, review_class, r_own, n_pos, n_neg)
 
         # ---- friends: both directions, distinct, without those that exist already
         f_off = ext(self.friend_offsets)
@@ -302,10 +298,8 @@ class InteractionStore:
         # to the friends it had; then a new friend's whole (new) count
         sums = []
         if r_own.size:
-            flo, fhi = f_off[r_own], f_off[r_own + 1]
-            fidx = np.repeat(flo - np.concatenate([[0], np.cumsum(fhi - flo)[:-1]]), fhi - flo) + \
-                np.arange(int((fhi - flo).sum()))
-            old_friends, of_who = self.friend_rows[fidx], np.repeat(np.arange(r_own.size), fhi - flo)
+            fidx, of_who = self._span(f_off, r_own)
+            old_friends = self.friend_rows[fidx]
         for j, (new, fsum) in enumerate(((n_rows, self.friends_rows), (n_pos, self.friends_pos),
                                          (n_neg, self.friends_neg))):
             fsum = grow(fsum)
@@ -321,13 +315,9 @@ class InteractionStore:
                                              [n_item * 4 + n_class, n_row], f_own, f_pre, f_pos,
                                              [ent[:, 1]])
                     for key, hit in self._dev.items()}
-            if self._prev:
-                # an older generation is dropped only when no kernel launched against it can still run
-                for key in self._prev:
-                    torch.cuda.synchronize(torch.device(*key))
-            self._prev = dict(self._dev)
-            self._dev.update(gens)
+            self._publish(gens)
             self.n_reviewers, self.n_reviews = U, M0 + rev.size
+            self.next_review_row += rev.size
             self.review_offsets, self.review_item, self.review_class, self.review_row = (
                 review_offsets, review_item, review_class, review_row)
             self.friend_offsets, self.friend_rows = friend_offsets, friend_rows
@@ -337,6 +327,257 @@ class InteractionStore:
                                     upload_bytes=8 * (r_own.size + r_pre.size + r_pos.size + f_own.size +
                                                       f_pre.size + f_pos.size + 1) +
                                     4 * (2 * r_pos.size + f_pos.size + 1), devices=len(gens))
+
+    # ---------------------------------------------------- remove, set_rating
+    def remove(self, review_reviewer=(), review_row=(), friend_a=(), friend_b=()) -> None:
+        """Rows of ``main_df`` and friendships taken out, in place.
+
+        A review is named by its reviewer and its ``main_df`` row (its
+        ``review_row`` value): the lookup is a binary search inside the
+        reviewer's segment, where the rows ascend.  A (reviewer, row) the
+        store does not hold raises ``ValueError``; a repeat inside the batch
+        counts once.  The surviving reviews keep their ``review_row`` values
+        and ``next_review_row`` stays, so ``append`` never gives a removed
+        row's number again; ``n_reviews`` is the number of reviews held.  A
+        pair (a, b) ends the friendship in both directions, whatever rows of
+        ``friendships_df`` spelled it ((u, u): the self entry); a pair that is
+        not there is ignored, as ``append`` ignores one that is.  U stays.
+
+        Afterwards every host array and count, and every device tensor, equals
+        those of a store built from the tables without those rows, with
+        ``review_row`` mapped through the surviving rows' original numbers.
+        The host work is that of the batch and of the touched reviewers' own
+        segments and friend lists (plus the memory moves).  On each device the
+        store was uploaded to, the removed positions go up in one upload and
+        dcnr_csr_remove writes the next generation of each CSR that changes;
+        the other keeps its tensors.  The generations are handled as by
+        ``append`` (see ``on``).  Everything is validated, and every new array
+        made, before anything changes: a refused remove leaves the store as it
+        was, on the host and on the devices.  An empty batch is a no-op.
+        ``last_remove`` keeps what ``last_append`` keeps.
+        """
+        rr, row, fa, fb = (np.asarray(a, dtype=np.int64).reshape(-1)
+                           for a in (review_reviewer, review_row, friend_a, friend_b))
+        if rr.size != row.size:
+            raise ValueError("InteractionStore.remove: review_reviewer and review_row must have "
+                             "one entry per review")
+        if fa.size != fb.size:
+            raise ValueError("InteractionStore.remove: friend_a and friend_b must have one entry "
+                             "per pair")
+        U = self.n_reviewers
+        for a, what in ((rr, "review_reviewer"), (fa, "friend_a"), (fb, "friend_b")):
+            if a.size and (a.min() < 0 or a.max() >= U):
+                raise ValueError(f"InteractionStore.remove: {what} outside [0, {U})")
+        if rr.size == 0 and fa.size == 0:
+            return
+        t_start = time.perf_counter()
+        minus = lambda cnt: -np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+
+        # ---- reviews: their positions, ascending
+        r_who, r_at, _ = self._locate("remove", rr, row)
+        r_own, r_cnt = np.unique(r_who, return_counts=True)
+        review_item = np.delete(self.review_item, r_at)
+        review_class = np.delete(self.review_class, r_at)
+        review_row = np.delete(self.review_row, r_at)
+        review_offsets = self._shifted(self.review_offsets, r_own, minus(r_cnt))
+        n_rows, n_pos, n_neg = self.n_rows.copy(), self.n_pos.copy(), self.n_neg.copy()
+        n_rows[r_own] -= r_cnt
+        deltas = [-r_cnt]   # of n_rows, n_pos, n_neg at the touched reviewers
+        if r_own.size:
+            deltas += self._recount(review_offsets, review_item, review_class, r_own, n_pos, n_neg)
+
+        # ---- friends: both directions of the pairs that are there
+        f_off = self.friend_offsets
+        if fa.size:
+            ent = np.unique(np.concatenate([fa * U + fb, fb * U + fa]))   # (owner, friend) as one word
+            ent = np.stack([ent // U, ent % U], 1)
+            at = self._lower_bound(self.friend_rows, f_off[ent[:, 0]], f_off[ent[:, 0] + 1], ent[:, 1])
+            there = at < f_off[ent[:, 0] + 1]
+            there[there] = self.friend_rows[at[there]] == ent[there, 1]
+            ent, f_at = ent[there], at[there]
+        else:
+            ent, f_at = np.zeros((0, 2), np.int64), np.zeros(0, np.int64)
+        if r_at.size == 0 and f_at.size == 0:
+            return
+        f_own, f_cnt = np.unique(ent[:, 0], return_counts=True)
+        friend_rows = np.delete(self.friend_rows, f_at)
+        friend_offsets = self._shifted(f_off, f_own, minus(f_cnt))
+        n_friends = self.n_friends.copy()
+        n_friends[f_own] -= f_cnt
+        # the sums over a reviewer's friends: first a former friend's whole (old)
+        # count, then each touched reviewer's change, to the friends it keeps
+        if r_own.size:
+            fidx, kf_who = self._span(friend_offsets, r_own)
+            kept_friends = friend_rows[fidx]
+        sums = []
+        for j, (old, fsum) in enumerate(((self.n_rows, self.friends_rows), (self.n_pos, self.friends_pos),
+                                         (self.n_neg, self.friends_neg))):
+            fsum = fsum.copy()
+            np.subtract.at(fsum, ent[:, 0], old[ent[:, 1]])
+            if r_own.size:
+                np.add.at(fsum, kept_friends, deltas[j][kf_who])
+            sums.append(fsum)
+
+        # ---- the devices, then the host: nothing is published before all of it exists
+        t_host = time.perf_counter()
+        with self._dev_lock:
+            gens = {key: self._device_remove(key, hit, r_at, f_at) for key, hit in self._dev.items()}
+            self._publish(gens)
+            self.n_reviews -= r_at.size
+            self.review_offsets, self.review_item, self.review_class, self.review_row = (
+                review_offsets, review_item, review_class, review_row)
+            self.friend_offsets, self.friend_rows = friend_offsets, friend_rows
+            self.n_rows, self.n_pos, self.n_neg, self.n_friends = n_rows, n_pos, n_neg, n_friends
+            self.friends_rows, self.friends_pos, self.friends_neg = sums
+            self.last_remove = dict(host_s=t_host - t_start, device_s=time.perf_counter() - t_host,
+                                    upload_bytes=8 * (r_at.size + f_at.size + 1), devices=len(gens))
+
+    def set_rating(self, review_reviewer, review_row, review_rating) -> None:
+        """``rating_overall`` of reviews the store holds, edited in place.
+
+        The reviews are named as for ``remove``; of a (reviewer, row) given
+        several times the last rating counts, and one the store does not hold
+        raises ``ValueError`` and changes nothing.  A review keeps its place
+        and its ``review_row``: only its class bits change, so afterwards the
+        store equals one built from the tables with the rating column edited.
+        The host counts the distinct positives and negatives of the touched
+        reviewers anew and passes the changes on to their friends' sums.  On
+        each device only ``review_items`` gets a new generation, a copy with
+        the changed words scattered in; the other tensors are shared with the
+        generation before.  Ratings that leave every class as it is change
+        nothing.
+        """
+        rr, row = (np.asarray(a, dtype=np.int64).reshape(-1) for a in (review_reviewer, review_row))
+        rating = np.asarray(review_rating, dtype=np.float64).reshape(-1)
+        if not (rr.size == row.size == rating.size):
+            raise ValueError("InteractionStore.set_rating: review_reviewer, review_row and "
+                             "review_rating must have one entry per review")
+        if rr.size and (rr.min() < 0 or rr.max() >= self.n_reviewers):
+            raise ValueError(f"InteractionStore.set_rating: review_reviewer outside "
+                             f"[0, {self.n_reviewers})")
+        if rr.size == 0:
+            return
+        t_start = time.perf_counter()
+        who, at, inverse = self._locate("set_rating", rr, row)
+        last = np.empty(at.size, np.float64)
+        last[inverse] = rating     # (of a repeated index the last value is assigned)
+        cls = ((last >= 8).astype(np.int8) * POS_BIT + (last <= 4).astype(np.int8) * NEG_BIT)
+        changed = cls != self.review_class[at]
+        if not changed.any():
+            return
+        who, at, cls = who[changed], at[changed], cls[changed]
+        review_class = self.review_class.copy()
+        review_class[at] = cls
+        own = np.unique(who)
+        n_pos, n_neg = self.n_pos.copy(), self.n_neg.copy()
+        deltas = self._recount(self.review_offsets, self.review_item, review_class, own, n_pos, n_neg)
+        fidx, f_who = self._span(self.friend_offsets, own)
+        sums = []
+        for d, fsum in zip(deltas, (self.friends_pos, self.friends_neg)):
+            fsum = fsum.copy()
+            np.add.at(fsum, self.friend_rows[fidx], d[f_who])
+            sums.append(fsum)
+        words = (self.review_item[at] * 4 + cls).astype(np.int32)
+        t_host = time.perf_counter()
+        with self._dev_lock:
+            gens = {key: self._device_set_items(key, hit, at, words) for key, hit in self._dev.items()}
+            self._publish(gens)
+            self.review_class, self.n_pos, self.n_neg = review_class, n_pos, n_neg
+            self.friends_pos, self.friends_neg = sums
+
+    def _locate(self, what, rr, row):
+        """The reviews (reviewer, main_df row) of a batch, repeats once: their
+        reviewers, their positions (ascending) and each batch entry's index
+        into the two; ValueError for one the store does not hold."""
+        if rr.size == 0:
+            z = np.zeros(0, np.int64)
+            return z, z, z
+        N = max(self.next_review_row, 1)
+        seen = (row >= 0) & (row < N)
+        if not seen.all():
+            raise ValueError(f"InteractionStore.{what}: reviewer {rr[~seen][0]} has no review at "
+                             f"main_df row {row[~seen][0]}: the store saw rows [0, {N})")
+        # (reviewer, row) as one word: both are below 2^31
+        key, inverse = np.unique(rr * N + row, return_inverse=True)
+        who, key = key // N, key % N
+        lo, hi = self.review_offsets[who], self.review_offsets[who + 1]
+        at = self._lower_bound(self.review_row, lo, hi, key)
+        there = at < hi
+        there[there] = self.review_row[at[there]] == key[there]
+        if not there.all():
+            raise ValueError(f"InteractionStore.{what}: reviewer {who[~there][0]} has no review at "
+                             f"main_df row {key[~there][0]} ({int((~there).sum())} such in the batch)")
+        return who, at, inverse.reshape(-1)
+
+    @staticmethod
+    def _span(off, owners):
+        """Every position of the segments off[o] .. off[o + 1] of ``owners``,
+        in their order, and the index into ``owners`` each belongs to."""
+        lo, n = off[owners], off[owners + 1] - off[owners]
+        idx = np.repeat(lo - np.concatenate([[0], np.cumsum(n)[:-1]]), n) + np.arange(int(n.sum()))
+        return idx, np.repeat(np.arange(owners.size), n)
+
+    def _recount(self, review_offsets, review_item, review_class, owners, n_pos, n_neg):
+        """n_pos / n_neg of the reviewers ``owners``, counted anew from their
+        segments and written in place; returns the two changes."""
+        idx, who = self._span(review_offsets, owners)
+        deltas = []
+        for flag, out in ((POS_BIT, n_pos), (NEG_BIT, n_neg)):
+            before = out[owners].copy()
+            keep = (review_class[idx] & flag) != 0
+            pairs = np.unique(who[keep] * self.n_items + review_item[idx][keep])
+            out[owners] = np.bincount(pairs // self.n_items, minlength=owners.size)
+            deltas.append(out[owners] - before)
+        return deltas
+
+    def _publish(self, gens) -> None:
+        """The next generation of every device (under the lock); an older one
+        is dropped only when no kernel launched against it can still run."""
+        if self._prev:
+            for key in self._prev:
+                torch.cuda.synchronize(torch.device(*key))
+        self._prev = dict(self._dev)
+        self._dev.update(gens)
+
+    def _device_remove(self, key, hit, r_at, f_at):
+        """The next generation of one device's CSRs without the entries at r_at / f_at."""
+        device = torch.device(*key)
+        _, old = hit
+        lib = _lib.load()
+        d_at = torch.from_numpy(np.concatenate([r_at, f_at, np.zeros(1, np.int64)])).to(device)
+        U = old["review_offsets"].numel() - 1
+        new = {}
+        with torch.cuda.device(device):
+            stream = _lib.stream_ptr(device)
+            ptrs = lambda ts: (ctypes.c_void_p * 2)(*[t.data_ptr() or None for t in ts])
+            for names, off_name, m, p_at in (
+                    (["review_items", "review_rows"], "review_offsets", r_at.size, d_at.data_ptr()),
+                    (["friend_rows"], "friend_offsets", f_at.size, d_at.data_ptr() + 8 * r_at.size)):
+                if m == 0:   # this CSR is as it was
+                    new.update({k: old[k] for k in names + [off_name]})
+                    continue
+                M_old = old[names[0]].numel()
+                new[off_name] = torch.empty(U + 1, dtype=torch.int64, device=device)
+                for k in names:
+                    new[k] = torch.empty(M_old - m, dtype=torch.int32, device=device)
+                _lib.check(lib.dcnr_csr_remove(
+                    old[off_name].data_ptr(), U, M_old, len(names), ptrs([old[k] for k in names]),
+                    p_at, m, new[off_name].data_ptr(), ptrs([new[k] for k in names]), stream),
+                    "dcnr_csr_remove")
+            # published only once written; the uploaded positions may go once read
+            torch.cuda.current_stream(device).synchronize()
+        return self._describe(new, U, new["review_rows"].numel()), new
+
+    def _device_set_items(self, key, hit, at, words):
+        """The next generation of one device: review_items with ``words`` at ``at``."""
+        device = torch.device(*key)
+        desc, old = hit
+        new = dict(old)
+        with torch.cuda.device(device):
+            new["review_items"] = old["review_items"].clone()
+            new["review_items"][torch.from_numpy(at).to(device)] = torch.from_numpy(words).to(device)
+            torch.cuda.current_stream(device).synchronize()
+        return self._describe(new, desc.n_reviewers, desc.n_reviews), new
 
     @staticmethod
     def _shifted(off, owners, prefix) -> np.ndarray:
@@ -412,7 +653,9 @@ class InteractionStore:
     # ---------------------------------------------------------------- device
     def on(self, device):
         """The device CSRs as (dcnr_interactions, tensors): uploaded on a
-        device's first call, advanced on that device by every ``append`` since.
+        device's first call, advanced on that device by every ``append``,
+        ``remove`` and ``set_rating`` since (what follows says ``append`` for
+        all three).
 
         Generations.  The tensors of a generation are never written after they
         are published, and ``append`` publishes the next one only once it is

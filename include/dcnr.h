@@ -40,6 +40,8 @@
  *                         lists of those requests    main.py:172-194, 336-351
  *   dcnr_csr_insert       new main_df / friendships_df rows into those CSRs on the
  *                         device (the reference reloads both at start-up only)
+ *   dcnr_csr_remove       the mirror: main_df.drop(rows) and dropped friendships_df
+ *                         rows taken out of those CSRs on the device
  *   dcnr_eval_metrics     roc_auc_score / BCEWithLogitsLoss / sqrt(mean_squared_error)
  *                         over the validation logits          train.py:255-265, 366-387
  *   dcnr_eval_group_metrics  GAUC, NDCG@k, hit rate@k, recall@k and MRR of every
@@ -891,7 +893,8 @@ typedef struct {
   const int64_t* review_offsets; /* [n_reviewers + 1] */
   const int32_t* review_items;   /* [n_reviews] hotel row * 4 + class bits:
                                     1 = rating_overall >= 8, 2 = rating_overall <= 4 */
-  const int32_t* review_rows;    /* [n_reviews] the review's row in main_df */
+  const int32_t* review_rows;    /* [n_reviews] the review's row in main_df: >= 0, ascending
+                                    inside a reviewer; n_reviews or more once rows were removed */
   int64_t n_reviews;
 } dcnr_interactions;
 
@@ -974,6 +977,32 @@ dcnr_status dcnr_csr_insert(const int64_t* old_offsets, int64_t n_old_owners, in
                             const int32_t* const* old_payloads, const int64_t* touched,
                             const int64_t* insert_prefix, int64_t t, const int64_t* insert_pos,
                             const int32_t* const* insert_payloads, int64_t m, int64_t* new_offsets,
+                            int32_t* const* new_payloads, dcnr_stream_t stream);
+
+/* The mirror of dcnr_csr_insert: a new generation of one of those CSRs with m
+ * entries taken out, what dcnr.InteractionStore.remove runs per device when
+ * reviews are withdrawn (n_payloads = 2) or reviewers unfriend (n_payloads =
+ * 1).  The old generation, old_offsets [n_owners + 1] and old_payloads[w]
+ * [n_old_entries], is read only and never an output.  removed [m], in device
+ * memory, prepared by the host from the batch alone: the global positions in
+ * the old payloads that go, strictly ascending, in [0, n_old_entries).
+ * Written: new_payloads[w] [n_old_entries - m], new[p] = old[p + c] with c the
+ * smallest value in [0, m] with c == m or removed[c] - c > p (the removed
+ * positions in front of the source element), and new_offsets [n_owners + 1],
+ * new_offsets[o] = old_offsets[o] - #{i : removed[i] < old_offsets[o]}: the
+ * owners stay.  Every output element is written exactly once by one lane,
+ * without atomics: the same bits on every run.  All positions are 64-bit, and
+ * every index taken from device data is clamped into its array: a malformed
+ * removed list gives unspecified values, never an access outside the buffers.
+ * Workgroups take DCNR_CSR_INSERT_CHUNK output elements at a time; a chunk no
+ * removed position falls into is a shifted copy.  With m = 0 nothing is
+ * launched or written; with m = n_old_entries only new_offsets is written (the
+ * payload arguments may be NULL).  DCNR_BAD_ARG before any launch: a needed
+ * null pointer, a negative count, n_payloads outside 1..2, or m >
+ * n_old_entries.  Stream-ordered; no allocation, no host synchronisation. */
+dcnr_status dcnr_csr_remove(const int64_t* old_offsets, int64_t n_owners, int64_t n_old_entries,
+                            int32_t n_payloads, const int32_t* const* old_payloads,
+                            const int64_t* removed, int64_t m, int64_t* new_offsets,
                             int32_t* const* new_payloads, dcnr_stream_t stream);
 
 /* The deep tower's Linear layer as a standalone bf16 call (nn.Linear forward,
