@@ -1952,6 +1952,50 @@ dcnr_status dcnr_csr_remove(const int64_t* old_offsets, int64_t n_owners, int64_
   return DCNR_OK;
 }
 
+static dcnr_status city_sets_shape(int64_t M, int64_t n_items, int32_t n_cities, int32_t top) {
+  if (M < 0 || n_items < 0 || n_cities < 0 || top < 0) return DCNR_BAD_ARG;
+  if (top < 1 || top > 256 || n_cities < 1 || n_cities > 65536 || n_items > ((int64_t)1 << 29) ||
+      M >= 2147483647ll)
+    return DCNR_UNSUPPORTED_SHAPE;
+  return DCNR_OK;
+}
+
+size_t dcnr_city_sets_workspace_size(int64_t M, int64_t n_items, int32_t n_cities, int32_t top) {
+  if (city_sets_shape(M, n_items, n_cities, top) != DCNR_OK) return 0;
+  return city_sets_ws_bytes(M, n_items, n_cities, top) + 256;
+}
+
+dcnr_status dcnr_city_sets_build(const int32_t* review_item, const int32_t* review_city,
+                                 const double* review_key, const int32_t* review_row, int64_t M,
+                                 int64_t n_items, int32_t n_cities, int32_t top, int64_t* set_offsets,
+                                 int64_t* set_rows, int64_t cap, int32_t* top_rows, int32_t* status,
+                                 int64_t* host_offsets, int32_t* host_status, void* ws, size_t ws_bytes,
+                                 dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const dcnr_status shape = city_sets_shape(M, n_items, n_cities, top);
+  if (shape == DCNR_BAD_ARG || cap < 0 || !set_offsets || !top_rows || !status ||
+      (cap > 0 && !set_rows) || (M > 0 && (!review_item || !review_city || !review_key || !ws))) {
+    set_error("dcnr_city_sets_build: bad argument (M=%lld, n_items=%lld, cities=%d, top=%d, cap=%lld)",
+              (long long)M, (long long)n_items, n_cities, top, (long long)cap);
+    return DCNR_BAD_ARG;
+  }
+  if (shape != DCNR_OK) {
+    set_error("dcnr_city_sets_build: unsupported shape (M=%lld, n_items=%lld, cities=%d, top=%d)",
+              (long long)M, (long long)n_items, n_cities, top);
+    return shape;
+  }
+  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  const size_t need = M > 0 ? city_sets_ws_bytes(M, n_items, n_cities, top) : 0;
+  if (M > 0 && ws_bytes < need + ((char*)base - (char*)ws)) {
+    set_error("dcnr_city_sets_build: workspace too small: %zu < %zu", ws_bytes, need + 256);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  TRYP(DCNR_K_SERVE, s, city_sets_build(review_item, review_city, review_key, review_row, M, n_items,
+                                        n_cities, top, set_offsets, set_rows, cap, top_rows, status,
+                                        host_offsets, host_status, base, s));
+  return DCNR_OK;
+}
+
 size_t dcnr_bce_workspace_size(void) { return bce_ws_bytes() + 256; }
 
 dcnr_status dcnr_emb_touched_rows(const dcnr_model_desc* desc, const void* ws, size_t ws_bytes,

@@ -28,15 +28,10 @@ namespace dcnr {
 namespace {
 
 // (tests/metrics_cases.py places n around UNIT_KEYS and AUC_TILE_MIN)
+// the sort's kernels and constants (RBITS, NB, UNIT_KEYS ...): dcnr_internal.h
+using namespace rsort;
 constexpr int KEY_BITS = 33;
-constexpr int RBITS = 11;                                  // digit width
 constexpr int NPASS = (KEY_BITS + RBITS - 1) / RBITS;      // 3
-constexpr int NB = 1 << RBITS;                             // buckets per pass
-constexpr int UNIT_KEYS = 4096;                            // keys per unit before MAX_UNITS binds
-constexpr int MAX_UNITS = 1024;
-constexpr int SORT_NT = 256, SORT_WAVES = SORT_NT / WAVE;  // 4 units per block
-constexpr int SORT_UNROLL = 4;                             // 64-key steps loaded ahead
-constexpr int SCAN_NT = 1024, SCAN_SEG = SCAN_NT / WAVE;   // 64 buckets x 16 unit segments
 constexpr int P1_NT = 1024, P1_KEYS = 8192, P1_MAXB = 1024;
 constexpr int AUC_NT = 256, AUC_WAVES = AUC_NT / WAVE, AUC_TILE_MIN = 2048, AUC_MAXB = 1024;
 constexpr int FIN_NT = 256;
@@ -156,119 +151,6 @@ __global__ __launch_bounds__(P1_NT) void metrics_pass1_kernel(const float* z, co
   for (int j = tid; j < NPASS * NB; j += P1_NT) {
     const uint32_t c = h[j];
     if (c) atomicAdd(&tot[j], c);   // integer: any order, same sum
-  }
-}
-
-// counts[u][d] = keys of unit u whose digit is d
-__global__ __launch_bounds__(SORT_NT) void sort_hist_kernel(const uint64_t* keys, int64_t n, int units,
-                                                            int64_t chunk, int shift, uint32_t* counts) {
-  __shared__ uint32_t h[SORT_WAVES][NB];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int u = blockIdx.x * SORT_WAVES + w;
-  for (int d = lane; d < NB; d += WAVE) h[w][d] = 0u;
-  __syncthreads();
-  if (u < units) {
-    const int64_t lo = (int64_t)u * chunk, hi = min(n, lo + chunk);
-    for (int64_t i0 = lo + lane; i0 < hi; i0 += SORT_UNROLL * WAVE) {
-      uint64_t k[SORT_UNROLL];
-#pragma unroll
-      for (int q = 0; q < SORT_UNROLL; ++q) k[q] = i0 + q * WAVE < hi ? keys[i0 + q * WAVE] : 0ull;
-#pragma unroll
-      for (int q = 0; q < SORT_UNROLL; ++q)
-        if (i0 + q * WAVE < hi) atomicAdd(&h[w][(int)((k[q] >> shift) & (NB - 1))], 1u);
-    }
-  }
-  __syncthreads();
-  if (u < units)
-    for (int d = lane; d < NB; d += WAVE) counts[(int64_t)u * NB + d] = h[w][d];
-}
-
-// counts[u][d] -> first output position of unit u's keys of digit d: the keys
-// of lower digits (tot), then the lower units' keys of digit d.  One block
-// per 64 digits; thread (j, s) walks digit b0 + j over unit segment s.
-__global__ __launch_bounds__(SCAN_NT) void sort_scan_kernel(const uint32_t* tot, uint32_t* counts,
-                                                            int units) {
-  __shared__ uint32_t red[SCAN_SEG];
-  __shared__ uint32_t tl[WAVE];
-  __shared__ uint32_t seg[SCAN_SEG][WAVE];
-  const int tid = threadIdx.x, j = tid & 63, s = tid >> 6;
-  const int b0 = blockIdx.x * WAVE;
-  uint32_t a = 0u;
-  for (int d = tid; d < b0; d += SCAN_NT) a += tot[d];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) a += (uint32_t)__shfl_xor((int)a, o, 64);
-  if (j == 0) red[s] = a;
-  if (tid < WAVE) tl[tid] = tot[b0 + tid];
-  const int useg = (units + SCAN_SEG - 1) / SCAN_SEG;
-  const int u0 = min(units, s * useg), u1 = min(units, u0 + useg);
-  uint32_t t = 0u;
-  for (int u = u0; u < u1; ++u) t += counts[(int64_t)u * NB + b0 + j];
-  seg[s][j] = t;
-  __syncthreads();
-  uint32_t base = 0u;
-  for (int k = 0; k < SCAN_SEG; ++k) base += red[k];
-  for (int k = 0; k < j; ++k) base += tl[k];
-  for (int k = 0; k < s; ++k) base += seg[k][j];
-  for (int u = u0; u < u1; ++u) {
-    const int64_t idx = (int64_t)u * NB + b0 + j;
-    const uint32_t c = counts[idx];
-    counts[idx] = base;
-    base += c;
-  }
-}
-
-// Stable scatter of one pass.  A wave walks its unit 64 keys at a time; the
-// lanes holding the same digit find each other with RBITS ballots, the lowest
-// of them advances the unit's offset of that digit by their number, and each
-// writes at offset + (equal-digit lanes below it).
-__global__ __launch_bounds__(SORT_NT) void sort_scatter_kernel(const uint64_t* in, uint64_t* out,
-                                                               int64_t n, int units, int64_t chunk,
-                                                               int shift, const uint32_t* counts) {
-  __shared__ uint32_t c[SORT_WAVES][NB];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int u = blockIdx.x * SORT_WAVES + w;
-  if (u < units)
-    for (int d = lane; d < NB; d += WAVE) c[w][d] = counts[(int64_t)u * NB + d];
-  __syncthreads();
-  if (u >= units) return;
-  const uint64_t lt = (1ull << lane) - 1ull;
-  const int64_t lo = (int64_t)u * chunk, hi = min(n, lo + chunk);
-  for (int64_t i0 = lo; i0 < hi; i0 += SORT_UNROLL * WAVE) {   // wave-uniform trip count
-    // the loads of SORT_UNROLL steps up front (the walk is latency-bound: one
-    // dependent chain through the unit's LDS offsets), then the steps in order
-    uint64_t keys[SORT_UNROLL];
-    bool valids[SORT_UNROLL];
-#pragma unroll
-    for (int q = 0; q < SORT_UNROLL; ++q) {
-      const int64_t i = i0 + q * WAVE + lane;
-      valids[q] = i < hi;
-      keys[q] = valids[q] ? in[i] : 0ull;
-    }
-#pragma unroll
-    for (int q = 0; q < SORT_UNROLL; ++q) {
-      const bool valid = valids[q];
-      const uint64_t key = keys[q];
-      const uint32_t d = (uint32_t)((key >> shift) & (NB - 1));
-      uint64_t mask = __ballot(valid);
-#pragma unroll
-      for (int b = 0; b < RBITS; ++b) {
-        const bool bit = (d >> b) & 1u;
-        const uint64_t bal = __ballot(bit);
-        mask &= bit ? bal : ~bal;
-      }
-      const int leader = valid ? __ffsll((unsigned long long)mask) - 1 : lane;
-      uint32_t pre = 0u;
-      if (valid && lane == leader) {
-        pre = c[w][d];
-        c[w][d] = pre + (uint32_t)__popcll(mask);
-      }
-      pre = (uint32_t)__shfl((int)pre, leader, 64);
-      if (valid) {
-        const uint32_t pos = pre + (uint32_t)__popcll(mask & lt);
-        if ((int64_t)pos < n) out[pos] = key;
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
   }
 }
 
@@ -436,13 +318,13 @@ dcnr_status eval_metrics(const float* z, const float* y, int64_t n, dcnr_metrics
   const int sort_blocks = (int)cdiv(p.units, SORT_WAVES);
   for (int ps = 0; ps < NPASS; ++ps) {
     const int shift = ps * RBITS;
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, n, p.units,
+    hipLaunchKernelGGL(sort_hist_kernel<uint64_t>, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, n, p.units,
                        p.chunk, shift, w.counts);
     DCNR_LAUNCH_CHECK();
     hipLaunchKernelGGL(sort_scan_kernel, dim3(NB / WAVE), dim3(SCAN_NT), 0, s, w.tot + ps * NB,
                        w.counts, p.units);
     DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_scatter_kernel, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, dst, n,
+    hipLaunchKernelGGL(sort_scatter_kernel<uint64_t>, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, dst, n,
                        p.units, p.chunk, shift, w.counts);
     DCNR_LAUNCH_CHECK();
     std::swap(src, dst);
@@ -1039,13 +921,13 @@ dcnr_status eval_group_metrics(const float* z, const float* y, const int64_t* g,
   const int sort_blocks = (int)cdiv(p.units, SORT_WAVES);
   for (int ps = 0; ps < npass; ++ps) {
     const int shift = 1 + ps * RBITS;
-    hipLaunchKernelGGL(sort_hist_kernel, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, n, p.units,
+    hipLaunchKernelGGL(sort_hist_kernel<uint64_t>, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, n, p.units,
                        p.chunk, shift, w.counts);
     DCNR_LAUNCH_CHECK();
     hipLaunchKernelGGL(sort_scan_kernel, dim3(NB / WAVE), dim3(SCAN_NT), 0, s, w.tot + ps * NB,
                        w.counts, p.units);
     DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_scatter_kernel, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, dst, n,
+    hipLaunchKernelGGL(sort_scatter_kernel<uint64_t>, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, dst, n,
                        p.units, p.chunk, shift, w.counts);
     DCNR_LAUNCH_CHECK();
     std::swap(src, dst);

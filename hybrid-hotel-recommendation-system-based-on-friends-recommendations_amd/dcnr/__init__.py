@@ -36,6 +36,10 @@ System-Based-on-Friends-Recommendations):
   InteractionStore                   main_df's reviews + friendships_df as the
                                      request path reads them (main.py:172-194,
                                      336-351); RankingPipeline.recommend_users
+  CitySets                           a city's hotels and its most reviewed hotels
+                                     (main.py:204-210) from main_df's rows, on the
+                                     device; recommend_many / recommend_users
+                                     (cities=...) name a request's city by code
   artifacts.save_artifacts /         final_dcn_model.pth + item_embeddings.npy
   artifacts.load_artifacts           (train.py:391-394, main.py:256-270)
   artifacts.save_neighbor_table /    item_neighbors.npy (+ fingerprint): the
@@ -54,6 +58,7 @@ from . import serving  # noqa: F401
 from .data import DeviceLoader  # noqa: F401
 from .serving import RankingPipeline, rerank_with_mmr  # noqa: F401
 from .interactions import InteractionStore  # noqa: F401
+from .cities import CitySets  # noqa: F401
 from . import artifacts  # noqa: F401
 
 __version__ = "0.1.0"

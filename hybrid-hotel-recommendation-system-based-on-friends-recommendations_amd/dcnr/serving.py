@@ -227,6 +227,7 @@ class RankingPipeline:
         self._no_rows = torch.empty(0, dtype=torch.int64, device=dev)
         self._sets = (self._no_rows, np.zeros(1, np.int64))
         self._sets_lock = threading.Lock()
+        self._city_joined = None   # (registered rows, CitySets generation, the two joined)
         self._tls = threading.local()
         self._nbr = self._neighbor_table(neighbor_table)
 
@@ -569,7 +570,8 @@ class RankingPipeline:
     @torch.no_grad()
     def recommend_many(self, user_rows, positive_rows, lambda_param=1.0, top_k=20,
                        allowed=None, excluded=None, fallback=None, min_candidates: int = 20,
-                       neighbors_within=None):
+                       neighbors_within=None, city_sets=None, cities=None,
+                       neighbors_in_city: bool = False):
         """``recommend()`` for R requests in one device pass: returns a list of
         R pairs (ranked rows, their logits), each equal to what ``recommend``
         returns for that request alone, as views into two result tensors.
@@ -589,6 +591,18 @@ class RankingPipeline:
                        positives (dcnr_cosine_topk_within, the requests as its
                        segments) laid over them, whether or not the pipeline
                        has a neighbour table.  Still one wait.
+        city_sets, cities, neighbors_in_city   a ``dcnr.CitySets`` and R city
+                       codes (-1: a city the table does not know): request
+                       r's ``allowed`` is city(cities[r]), its ``fallback``
+                       popular(cities[r]) and, with ``neighbors_in_city``, its
+                       ``neighbors_within`` city(cities[r]); those arguments
+                       must then be None (ValueError), ``excluded`` stays
+                       free.  The sets are the newest generation's on this
+                       device, joined to the call's set CSR behind the
+                       registered sets: nothing but R codes' worth of indices
+                       and the generation's offsets travels.  An unknown city
+                       gets the empty set, so its answer is empty
+                       (main.py:209-212)
 
         One packed, pinned, non-blocking copy carries every host input; one
         top-k call serves all positives; each request's set work runs in its
@@ -615,8 +629,10 @@ class RankingPipeline:
             raise ValueError("recommend_many: one positive list per user row")
         if R == 0:
             return []
+        city = self._city_arg("recommend_many", city_sets, cities, neighbors_in_city, R, allowed,
+                              fallback, neighbors_within)
         f = self._many_front(users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
-                             min_candidates, neighbors_within=neighbors_within)
+                             min_candidates, neighbors_within=neighbors_within, city=city)
         info, seg, st, d_at = f["info"], f["seg"], f["st"], f["d_at"]
         pos, lam, topk = info["pos"], info["lam"], info["topk"]
         out_rows, out_logits = self._score_and_rank(R, f["cap"], f["n"], f["slots"], f["offsets"],
@@ -633,12 +649,12 @@ class RankingPipeline:
             if st[r] & REQ_OVERFLOW or odd[r]:
                 pick = lambda v: None if v is None else v[r]
                 p_r = pos[info["pos_off"][r]:info["pos_off"][r + 1]]
+                sets = self._city_rows(city, r) if city is not None else dict(
+                    allowed=self._set_arg(pick(allowed)), fallback=self._set_arg(pick(fallback)),
+                    neighbors_within=self._set_arg(pick(neighbors_within)))
                 res.append(self.recommend(int(users[r]), p_r, float(lam64[r]), int(topk[r]),
-                                          allowed=self._set_arg(pick(allowed)),
                                           excluded=self._set_arg(pick(excluded)),
-                                          fallback=self._set_arg(pick(fallback)),
-                                          min_candidates=min_candidates,
-                                          neighbors_within=self._set_arg(pick(neighbors_within))))
+                                          min_candidates=min_candidates, **sets))
                 continue
             n_r = int(seg[r + 1] - seg[r])
             # every candidate is a table row, so the MMR finds min(top_k, n_r) items
@@ -648,7 +664,7 @@ class RankingPipeline:
         return res
 
     def _many_front(self, users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
-                    min_candidates, extra=(), pinned_tail=0, neighbors_within=None):
+                    min_candidates, extra=(), pinned_tail=0, neighbors_within=None, city=None):
         """``recommend_many`` up to its one wait: the packed upload (``extra``:
         further (name, array) pairs to carry along), the top-k or table lookup,
         the candidates pass, the wait.  Returns what the calls behind the wait
@@ -658,7 +674,7 @@ class RankingPipeline:
         dev = self.device
         R = users.size
         ins, info = self._pack_requests(users, positive_rows, lambda_param, top_k, allowed,
-                                        excluded, fallback, neighbors_within)
+                                        excluded, fallback, neighbors_within, city)
         ins = ins + list(extra)
         pos, lam, topk, cap, S, n_adhoc = (info[k_] for k_ in ("pos", "lam", "topk", "cap", "S",
                                                                "n_adhoc"))
@@ -921,7 +937,8 @@ class RankingPipeline:
     @torch.no_grad()
     def recommend_users(self, store, user_rows, reviewers, modes, lambda_param=1.0, top_k=20,
                         allowed=None, fallback=None, min_candidates: int = 20,
-                        recommended_by: bool = True, neighbors_within=None):
+                        recommended_by: bool = True, neighbors_within=None, city_sets=None,
+                        cities=None, neighbors_in_city: bool = False):
         """``recommend_many`` from user ids: each request's positives, its
         excluded set (the negatives, main.py:193-194, 211) and the
         ``recommended_by`` lists of its answer (main.py:336-351) come from a
@@ -931,7 +948,8 @@ class RankingPipeline:
         user_rows   R model user rows (main.py:217 stays the caller's)
         reviewers   R store indices, -1 for a user the store does not know
         modes       'friends' / 'personal', one value or R
-        lambda_param, top_k, allowed, fallback, min_candidates, neighbors_within
+        lambda_param, top_k, allowed, fallback, min_candidates, neighbors_within,
+        city_sets, cities, neighbors_in_city
                     as in ``recommend_many`` (``excluded`` is the negatives)
 
         Returns a ``UserAnswers``: a list of R (ranked rows, logits) pairs,
@@ -975,8 +993,10 @@ class RankingPipeline:
         if md.size != R:
             raise ValueError("recommend_users: one mode, or one per request")
         # lambda, top_k and the allowed / fallback indices as recommend_many packs them
+        city = self._city_arg("recommend_users", city_sets, cities, neighbors_in_city, R, allowed,
+                              fallback, neighbors_within)
         ins, info = self._pack_requests(users, [()] * R, lambda_param, top_k, allowed, None,
-                                        fallback, neighbors_within)
+                                        fallback, neighbors_within, city)
         ins = dict(ins)
         lam, lam64, topk = info["lam"], info["lam64"], info["topk"]
         k = self.n_neighbors
@@ -1095,27 +1115,76 @@ class RankingPipeline:
         res.rows, res.logits = out_rows, out_logits
         res._seg, res._cnt, res._list_off, res._store, res._rv = seg, cnt, list_off, store, rv
         res._held = held
+        res._city_held = city[0] if city is not None else None
         res.n_positives, res.positives_bound = s_counts[:, 0], zero(pos_b)
         res.on_host = on_host
         for r in range(R):
             if on_host[r]:   # above the batched kernels' capacity: the one-request path
                 pick = lambda v: None if v is None else v[r]
                 p_r, n_r = store.sources_host(int(rv[r]), int(md[r]))
+                sets = self._city_rows(city, r) if city is not None else dict(
+                    allowed=self._set_arg(pick(allowed)), fallback=self._set_arg(pick(fallback)),
+                    neighbors_within=self._set_arg(pick(neighbors_within)))
                 res.append(self.recommend(int(users[r]), p_r, float(lam64[r]), int(topk[r]),
-                                          allowed=self._set_arg(pick(allowed)), excluded=n_r,
-                                          fallback=self._set_arg(pick(fallback)),
-                                          min_candidates=min_candidates,
-                                          neighbors_within=self._set_arg(pick(neighbors_within))))
+                                          excluded=n_r, min_candidates=min_candidates, **sets))
                 continue
             o = int(seg[r])
             res.append((out_rows[o:o + int(cnt[r])], out_logits[o:o + int(cnt[r])]))
         return res
 
+    def _city_arg(self, what, city_sets, cities, in_city, R, allowed, fallback, neighbors_within):
+        """``city_sets`` / ``cities`` / ``neighbors_in_city`` of a batched call:
+        None, or (the generation on this device, the R codes, the flag)."""
+        if cities is None:
+            if in_city:
+                raise ValueError(f"{what}: neighbors_in_city needs cities")
+            return None
+        if city_sets is None:
+            raise ValueError(f"{what}: cities needs city_sets")
+        if allowed is not None or fallback is not None or (in_city and neighbors_within is not None):
+            raise ValueError(f"{what}: with cities, allowed and fallback (and with neighbors_in_city, "
+                             "neighbors_within) come from the city and must be None")
+        codes = np.asarray(cities, dtype=np.int64).reshape(-1)
+        if codes.size != R:
+            raise ValueError(f"{what}: one city code per request")
+        if codes.min() < -1 or codes.max() >= city_sets.n_cities:
+            raise ValueError(f"{what}: city code outside [-1, {city_sets.n_cities})")
+        if city_sets.n_items > self.n_rows:
+            raise ValueError(f"{what}: the city sets name {city_sets.n_items} hotel rows, the "
+                             f"pipeline holds {self.n_rows}")
+        return city_sets.on(self.device), codes, bool(in_city)
+
+    @staticmethod
+    def _city_rows(city, r):
+        """Request r's set arguments for ``recommend()``, from the host columns
+        of the generation the batched call used."""
+        gen, codes, in_city = city
+        rows = gen.host.city_rows(int(codes[r]))
+        out = dict(allowed=rows, fallback=gen.host.popular_rows(int(codes[r])))
+        if in_city:
+            out["neighbors_within"] = rows
+        return out
+
+    def _city_join(self, reg_rows, gen):
+        """The registered sets' rows with the generation's behind them, on the
+        device; joined once per (registered sets, generation)."""
+        if reg_rows.numel() == 0:
+            return gen.set_rows
+        hit = self._city_joined
+        if hit is None or hit[0] is not reg_rows or hit[1] is not gen:
+            joined = torch.cat([reg_rows, gen.set_rows])
+            # published only once written: a call on another stream may read it at once
+            torch.cuda.current_stream(self.device).synchronize()
+            hit = self._city_joined = (reg_rows, gen, joined)
+        return hit[2]
+
     def _pack_requests(self, users, positive_rows, lambda_param, top_k, allowed, excluded,
-                       fallback, neighbors_within=None):
+                       fallback, neighbors_within=None, city=None):
         """The host half of ``recommend_many``: validates the rows and returns
         ([(name, array)] to upload, info).  Without set arguments nothing about
-        sets is built or uploaded (the index arrays go as null: no filters)."""
+        sets is built or uploaded (the index arrays go as null: no filters).
+        ``city`` (from ``_city_arg``): the generation's 2C + 1 sets stand behind
+        the registered ones, in front of the per-call ones."""
         # (few numpy calls: at R = 1 this host work is latency the device waits for.
         # A row read as unsigned is in range iff it is below the table's length)
         R = users.size
@@ -1147,10 +1216,16 @@ class RankingPipeline:
                     reg_rows=self._no_rows)
         need = np.array(lens, np.int64) * k   # a request's slot: its staged list (+ its fallback set)
         if allowed is not None or excluded is not None or fallback is not None or \
-                neighbors_within is not None:
+                neighbors_within is not None or city is not None:
             # registered sets by index, per-call ones appended to the CSR
             reg_rows, reg_off = self._sets
             n_reg = reg_off.size - 1
+            first_adhoc = n_reg
+            if city is not None:   # the generation's sets between the two
+                gen = city[0]
+                reg_off = np.concatenate([reg_off, reg_off[-1] + gen.host_offsets[1:]])
+                reg_rows = self._city_join(reg_rows, gen)
+                first_adhoc = reg_off.size - 1
             adhoc: List[np.ndarray] = []
 
             def set_indices(entries, what):
@@ -1169,13 +1244,20 @@ class RankingPipeline:
                         out[r] = e
                     else:
                         adhoc.append(_row_set(e, self.n_rows, f"recommend_many: {what}[{r}]"))
-                        out[r] = n_reg + len(adhoc) - 1
+                        out[r] = first_adhoc + len(adhoc) - 1
                 return out
 
             a_idx = set_indices(allowed, "allowed")
             e_idx = set_indices(excluded, "excluded")
             f_idx = set_indices(fallback, "fallback")
             w_idx = set_indices(neighbors_within, "neighbors_within")
+            if city is not None:
+                codes, C = city[1], city[0].n_cities
+                known = codes >= 0
+                a_idx = (n_reg + np.where(known, codes, 2 * C)).astype(np.int32)
+                f_idx = (n_reg + np.where(known, C + codes, 2 * C)).astype(np.int32)
+                if city[2]:
+                    w_idx = a_idx.copy()
         else:
             a_idx = e_idx = f_idx = w_idx = None
         # lists whose entries are all None name no set: nothing about sets is uploaded

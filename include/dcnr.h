@@ -1005,6 +1005,51 @@ dcnr_status dcnr_csr_remove(const int64_t* old_offsets, int64_t n_owners, int64_
                             const int64_t* removed, int64_t m, int64_t* new_offsets,
                             int32_t* const* new_payloads, dcnr_stream_t stream);
 
+/* The row sets a /recommendations request filters by, for every city at once,
+ * from the review rows (main.py:204-210): what dcnr.CitySets runs per device
+ * when it is uploaded and after every append and remove.  One entry per
+ * main_df row, in device memory: review_item [M] the hotel row, in [0,
+ * n_items); review_city [M] the dense city code, in [0, n_cities); review_key
+ * [M] the row's user_reviews_count (NaN, +-inf, +-0.0 allowed); review_row [M]
+ * the row's main_df number, strictly ascending and >= 0 (NULL: the position).
+ * With C = n_cities, for every city c:
+ *   city c       the distinct hotel rows of the rows with review_city == c
+ *   top rows c   the first `top` of those rows by key descending, NaN last,
+ *                equal keys (-0.0 equals +0.0) by ascending main_df row: what
+ *                sort_values(ascending=False, kind='stable').head(top) gives
+ *   popular c    the distinct hotel rows of top rows c
+ * Written: one CSR of 2C + 1 sets, each ascending and distinct, in the form
+ * dcnr_requests_candidates reads: set c is city c, set C + c is popular c, set
+ * 2C is empty (the unknown city); set_offsets [2C + 2], always complete, and
+ * set_rows [cap].  top_rows [C][top]: the main_df numbers of top rows c in
+ * served order, -1 behind a city's last.  status [1] (written): DCNR_REQ_OVERFLOW
+ * if set_offsets[2C + 1] > cap -- nothing is written at or behind set_rows +
+ * cap, and the offsets say what cap must be; DCNR_REQ_BAD_DATA for an item or
+ * city outside its range or rows that do not ascend -- every index taken from
+ * device data is clamped into its array, so the values are then unspecified
+ * but no access leaves the buffers.  set_offsets and status are also stored to
+ * host_offsets [2C + 2] and host_status [1] (pinned, device-visible host
+ * memory, or NULL) with system-scope stores.
+ * The rows are sorted twice with the stable radix sort of the metrics, by
+ * (city, key) as 16-byte records and by (city, hotel) as 64-bit keys; the rest
+ * is one lane per row or one workgroup per city over at most `top` rows, so a
+ * city that holds every row costs what any table of M rows costs.  Every count
+ * is an integer and every output word is written by one lane: the same bits
+ * on every run.  Workspace: dcnr_city_sets_workspace_size bytes, about 32 M +
+ * 4 C (top + 5) (+ 8 MB of sort counts at most); 0 for arguments the call
+ * rejects.  DCNR_BAD_ARG before any launch: a needed null pointer or a
+ * negative argument; DCNR_UNSUPPORTED_SHAPE: top outside 1..256, n_cities
+ * outside 1..65536, n_items > 2^29 or M >= 2^31 - 1; DCNR_WORKSPACE_TOO_SMALL.
+ * With M = 0 the offsets are zeros and top_rows is -1.  Stream-ordered; no
+ * allocation, no host synchronisation. */
+size_t dcnr_city_sets_workspace_size(int64_t M, int64_t n_items, int32_t n_cities, int32_t top);
+dcnr_status dcnr_city_sets_build(const int32_t* review_item, const int32_t* review_city,
+                                 const double* review_key, const int32_t* review_row, int64_t M,
+                                 int64_t n_items, int32_t n_cities, int32_t top, int64_t* set_offsets,
+                                 int64_t* set_rows, int64_t cap, int32_t* top_rows, int32_t* status,
+                                 int64_t* host_offsets, int32_t* host_status, void* ws, size_t ws_bytes,
+                                 dcnr_stream_t stream);
+
 /* The deep tower's Linear layer as a standalone bf16 call (nn.Linear forward,
  * train.py:143,105,109): C[M,N] = X[M,K] . W[N,K]^T + bias, X/W bf16
  * row-major (K, ldx, ldw multiples of 8), C bf16 (out_f32 = 0) or fp32.
