@@ -172,16 +172,24 @@ __device__ __forceinline__ float bn_bwd_dt(float u, float t, float mu, float is,
   return fmaf(-k1, xh, k0 * u) - k2;
 }
 
-// The weight gradient's split-K combine, one 64 k x 16 n tile of
+// The weight gradient's split-K combine, one 32 k x 32 n tile of
 // out[n][k] (+)= sum_z slab[z][k][n] by 256 threads (splitk_reduce_t's
 // kernel, and gemm_dw's tail when it combines the previous call's slab):
 // sum in fixed z order into LDS t, barrier, transposed store of rows of out.
-constexpr int RT_K = 64, RT_N = 16;
+// A tile row is 32 n = one 128-B line of the slab (where ld * 4 is a multiple
+// of 128, the 512-wide layers), read by 8 consecutive lanes x 16 B in ONE
+// wave-level load, so no line is requested twice (the 64 k x 16 n tile asked
+// for each line as two 64-B halves from two wave groups; in gemm_dw's tail
+// the second half often came from HBM again); the transposed store writes
+// 32 k = 128 B per row of out.
+constexpr int RT_K = 32, RT_N = 32;
+constexpr int RT_LPR = RT_N / 4;   // lanes per tile row in the sum, 16 B each
+static_assert(RT_K * RT_LPR == 256 && RT_N * (RT_K / 4) == 256, "combine tile: 256 threads, one float4 each");
 template <bool NT = false>
 __device__ __forceinline__ void splitk_t_sum(const float* slab, int splits, int64_t stride, int ld, int N,
                                              int K, int bx, int by, int idx, float (*t)[RT_N + 1]) {
   const int k0 = bx * RT_K, n0 = by * RT_N;
-  const int kk = idx >> 2, nq = idx & 3;
+  const int kk = idx / RT_LPR, nq = idx % RT_LPR;
   const int k = k0 + kk, n = n0 + 4 * nq;
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
   if (k < K && n < N) {
@@ -213,7 +221,7 @@ __device__ __forceinline__ void splitk_t_sum(const float* slab, int splits, int6
 __device__ __forceinline__ void splitk_t_store(int N, int K, float* out, int accumulate, int vec_out, int bx,
                                                int by, int idx, const float (*t)[RT_N + 1]) {
   const int k0 = bx * RT_K, n0 = by * RT_N;
-  const int nn = idx >> 4, kq = idx & 15;
+  const int nn = idx / (RT_K / 4), kq = idx % (RT_K / 4);
   const int n = n0 + nn, k = k0 + 4 * kq;
   if (n >= N) return;
   float v[4];

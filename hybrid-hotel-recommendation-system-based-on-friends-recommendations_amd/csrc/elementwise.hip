@@ -1045,10 +1045,11 @@ dcnr_status splitk_reduce(const float* slab, int splits, int64_t slab_stride, in
 namespace {
 // out[n][k] (+)= sum_z slab[z][k][n]: the weight-gradient GEMM's transposed
 // slabs (gemm_dw.hip stores 4 consecutive n per lane as one 16-B store).  A
-// block takes 64 k x 16 n: reads along n (4 lanes x 16 B per 64-B row
-// segment, 16 slab loads in flight per lane), sums in fixed z order (the same
-// bits as summing the untransposed slabs), transposes through LDS, writes
-// rows of out along k (16-B stores when out's rows allow).
+// block takes 32 k x 32 n: reads along n (8 lanes x 16 B per 128-B row
+// segment, a whole slab line per wave-level load; 16 slab loads in flight
+// per lane), sums in fixed z order (the same bits as summing the
+// untransposed slabs), transposes through LDS, writes rows of out along k
+// (16-B stores when out's rows allow).
 // (Several thread groups per output tile, each summing a contiguous share of
 // the splits, measured 12-13 us alone either way per 512 x 512 call and
 // 40-54 us under the concurrent dX chain; one group kept -- the summation

@@ -21,7 +21,12 @@
 //  * out-of-range rows/columns are fetched at an out-of-range buffer offset
 //    and read as 0 (branch-free tails);
 //  * fp32 split partials go to a TRANSPOSED slab [S][K][ldc] (16-B stores of
-//    4 consecutive n; summed and transposed back by splitk_reduce_t).
+//    4 consecutive n; summed and transposed back by splitk_reduce_t);
+//  * the PREVIOUS call's slab is combined in this launch's tail (DwArgs::rslab)
+//    by the same splitk_t_sum / splitk_t_store as the stand-alone kernel:
+//    32 k x 32 n tiles, one per 256 threads, each tile row one whole 128-B
+//    slab line fetched by one wave-level load (8 lanes x 16 B), the tiles
+//    dealt singly over all workgroups.
 #include "dcnr_internal.h"
 
 namespace dcnr {
@@ -185,23 +190,30 @@ __global__ __launch_bounds__(DwCfg<T>::NW * 64, 1) void gemm_dw_kernel(DwArgs g)
 
   // the previous call's split-K combine (its slab is complete: that launch
   // ended before this one began on the stream), splitk_reduce_t's tiles
-  // dealt over the workgroups, two at a time (256 threads each): a separate
-  // launch of it on the side stream waited for CUs beside the dX GEMMs
+  // dealt over the workgroups (256 threads per tile): a separate launch of it
+  // on the side stream waited for CUs beside the dX GEMMs
   if (g.rslab) {
     constexpr int NT = C::NW * 64;
     static_assert(NT == 512, "tail: two 256-thread tile groups");
+    static_assert(2 * RT_K * (RT_N + 1) * 4 <= C::LDS, "tail: the transpose tiles alias the ring");
     __syncthreads();   // every wave is past its last read of the LDS ring
-    float(*tt)[RT_N + 1] = reinterpret_cast<float(*)[RT_N + 1]>(lds) + (threadIdx.x / 256) * RT_K;
-    // the two halves take tiles (bx, 2j) and (bx, 2j+1): the two 64-B halves
-    // of each 128-B slab line, read together (dealt singly, each line came
-    // from HBM twice: 134 instead of 67 MB per call by PMC)
+    const int h = threadIdx.x / 256, idx = threadIdx.x % 256;
+    float(*tt)[RT_N + 1] = reinterpret_cast<float(*)[RT_N + 1]>(lds) + h * RT_K;
+    // a tile row is a whole 128-B slab line, so the tiles are independent
+    // and go round the workgroups singly: tile w + j * grid to the first
+    // half of workgroup w for even j, to its second half for odd j (256
+    // tiles at 512 x 512: every workgroup's first half has one; dealt as
+    // pairs of 64-B half lines, 128 workgroups of 256 took part and 107
+    // instead of 67 MB per call came from HBM by PMC)
     const int nbx = (g.rK + RT_K - 1) / RT_K, nby = (g.rN + RT_N - 1) / RT_N;
-    const int npairs = nbx * ((nby + 1) / 2), h = threadIdx.x / 256, idx = threadIdx.x % 256;
-    for (int pr = blockIdx.x; pr < npairs; pr += gridDim.x) {
-      const int bx = pr % nbx, by = 2 * (pr / nbx) + h;
-      if (by < nby) splitk_t_sum<DW_TAIL_NT>(g.rslab, g.rsplits, g.rstride, g.rld, g.rN, g.rK, bx, by, idx, tt);
+    const int ntiles = nbx * nby;
+    for (int t0 = blockIdx.x; t0 < ntiles; t0 += 2 * gridDim.x) {
+      const int tl = t0 + h * gridDim.x;
+      const bool on = tl < ntiles;   // uniform over each half: the barriers below are the workgroup's
+      const int bx = tl % nbx, by = tl / nbx;
+      if (on) splitk_t_sum<DW_TAIL_NT>(g.rslab, g.rsplits, g.rstride, g.rld, g.rN, g.rK, bx, by, idx, tt);
       __syncthreads();
-      if (by < nby) splitk_t_store(g.rN, g.rK, g.rout, g.racc & 1, g.racc >> 1, bx, by, idx, tt);
+      if (on) splitk_t_store(g.rN, g.rK, g.rout, g.racc & 1, g.racc >> 1, bx, by, idx, tt);
       __syncthreads();
     }
   }
