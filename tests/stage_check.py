@@ -1,13 +1,16 @@
-"""Stage-by-stage check of one bf16 training step, on whichever kernel path
-the step's plan takes (csrc/dcnr_api.hip make_plan).
+"""Stage-by-stage check of one training step, bf16 or fp32, on whichever
+kernel path the step's plan takes (csrc/dcnr_api.hip make_plan).
 
 End to end a bf16 step cannot be pinned element-wise to any other
-implementation (tests/test_bf16_train_gpu.py explains the sensitivity), but
-every STAGE can: each tensor the kernels store is recomputed here, in torch
-fp32/fp64 on the device, from the kernels' OWN stored inputs of that stage,
-and compared.  The workspace keeps every block's backward buffers
-(DCNR_FLAG_KEEP_INTERMEDIATES) and tells where each tensor lives
-(dcnr_workspace_offset).  Stages and reference lines:
+implementation (tests/test_bf16_train_gpu.py explains the sensitivity), and
+the fp32 step's end-to-end comparison (a norm-relative 5e-3 on the gradients)
+cannot see a dropped row or a mis-handled padded column, but every STAGE can
+be pinned: each tensor the kernels store is recomputed here, in torch
+fp32/fp64 on the device (bf16) or in fp64 throughout (fp32), from the kernels'
+OWN stored inputs of that stage, and compared.  The workspace keeps every
+block's backward buffers (DCNR_FLAG_KEEP_INTERMEDIATES) and tells where each
+tensor lives (dcnr_workspace_offset).  Stages and reference lines (the bounds
+in the right column are the bf16 step's; the fp32 step's follow below):
 
   forward  (train.py:155-170, ResBlock 112-122)
     x0          gather + concat, bf16 store                       exact
@@ -32,6 +35,35 @@ the magnitude of the summed terms): the kernels and this recomputation
 accumulate in different orders, which moves a value across a bf16 rounding
 boundary now and then (the fraction of such elements is recorded and bounded
 by FLIP_FRAC).
+
+precision="fp32" (the parity path: block_plain, no masks, fp32 storage).  The
+stages, buffers and every "rel" bound above are the same; what changes is the
+rounding model of a stored value:
+
+  storage    activations and gradients are read as fp32, the weights are the
+             fp32 parameters themselves, the stored x0 equals the gathered
+             rows exactly.
+  reference  every reference of a stored tensor is computed in fp64 (an fp32
+             torch matmul is accurate against a bf16 ulp, not against an fp32
+             one).
+  bound      |got - ref| <= one fp32 ulp of ref + ACC_EPS x the summed |terms|
+             (the same ``scale`` the bf16 checks pass).  ACC_EPS = 2^-18 is 64
+             fp32 roundings of the summed magnitude: above the sqrt(K) 2^-24
+             typical error of a K <= 1024 fp32 sum, below its K 2^-24 worst
+             case (the GEMM's v_mfma_f32_16x16x4_f32 makes exact fp32 fma
+             chains).  No flip fraction; max |diff| / bound is recorded per
+             stage instead.
+  dt2, dt1   the summed |terms| include the B terms of each BN-backward
+             coefficient sum (a sum(|dr xh|) / B |xh| + a sum(|dr|) / B), at
+             min(ACC_EPS, B 2^-24): the kernels' fp32 chunk sums are off by a few
+             roundings of these magnitudes, which |k1 xh| + |k2| alone fall
+             below where the signs cancel (bn_back).
+  da         the GEMM stores fp32 dt2 W2 and bwd_bn1_stats overwrites it with
+             that * keep/(1-p) * [fma(t1, scale, shift) > 0]: masked elements
+             exactly 0, the others within inv_keep x the GEMM's bound plus one
+             fp32 ulp of the fp64 dt2 W2 inv_keep (check_da_fp32).
+  plan       no masks are materialised (every mask offset is -1); the fused
+             head pass runs at Hp == 256 (a wave per row at 4 columns a lane).
 
 What follows the plan (Hp = hidden rounded up to 8):
 
@@ -119,6 +151,46 @@ def check_da_plain(name, got, m_ref, mask, inv_keep, stats, scale):
     assert flips <= FLIP_FRAC, (name, flips)
 
 
+def ulp_fp32(x):
+    """One fp32 unit in the last place at |x| (24 significant bits; the
+    subnormals' spacing below 2^-126)."""
+    a = x.double().abs().clamp_min(2.0 ** -126)
+    return torch.exp2(torch.floor(torch.log2(a)) - 23)
+
+
+def _fp32_stat(name, got, d, tol, bad, stats, refs):
+    nb = int(bad.sum())
+    stats.append((name, float((d / tol).max()), float(d.max())))
+    assert nb == 0, (name, nb, float(d.max()), float((d / tol).max()), bad.nonzero()[:5].tolist(),
+                     got[bad][:5].tolist(), refs[bad][:5].tolist())
+
+
+def check_fp32(name, got, ref, stats, scale):
+    """A stored fp32 tensor against its fp64 reference: one fp32 ulp of the
+    reference plus ACC_EPS times ``scale`` (check_bf16's argument).  Records
+    (name, max |diff| / bound, max |diff|)."""
+    got, ref = got.double(), ref.double()
+    assert torch.isfinite(got).all(), name
+    d = (got - ref).abs()
+    tol = ulp_fp32(ref) + ACC_EPS * scale.double()
+    _fp32_stat(name, got, d, tol, d > tol, stats, ref)
+
+
+def check_da_fp32(name, got, m_ref, mask, inv_keep, stats, scale):
+    """The fp32 step's stored da = fp32(c * inv_keep) * mask with c = the dX
+    GEMM's stored fp32 dt2 W2 (overwritten in place).  ``m_ref``: dt2 W2 in
+    fp64.  Masked elements must be exactly 0; the others lie within inv_keep
+    times the GEMM's bound (check_fp32's, at m_ref) plus the product's own
+    rounding, one fp32 ulp of m_ref * inv_keep."""
+    got, m_ref = got.double(), m_ref.double()
+    assert torch.isfinite(got).all(), name
+    assert (got[~mask] == 0).all(), (name, "masked elements not 0")
+    ref = m_ref * inv_keep * mask.double()
+    d = (got - ref).abs()
+    tol = inv_keep * (ulp_fp32(m_ref) + ACC_EPS * scale.double()) + ulp_fp32(m_ref * inv_keep)
+    _fp32_stat(name, got, d, tol, mask & (d > tol), stats, ref)
+
+
 def check_rel(name, got, ref, tol=REL, rels=None):
     got, ref = got.double(), ref.double()
     e = ((got - ref).norm() / ref.norm().clamp_min(1e-300)).item()
@@ -132,9 +204,13 @@ def unpack_bits(b, B, Hp):
     return ((b.view(B, Hp // 8)[:, :, None] >> sh) & 1).reshape(B, Hp).bool()
 
 
-def expected_plan(H):
-    """make_plan's train fields for a bf16 model of hidden width H."""
+def expected_plan(H, precision="bf16"):
+    """make_plan's train fields for a model of hidden width H.  fp32: no masks,
+    no GEMM epilogues; the fused head pass (bn_add_relu_head_supported: a wave
+    per row, 4 fp32 columns a lane) at Hp == 256."""
     Hp = (H + 7) // 8 * 8
+    if precision == "fp32":
+        return dict(masks=False, stats_epi=False, xbn=False, head_fused=Hp == 256, rank1=False)
     masks = Hp % 32 == 0
     stats_epi = masks and Hp <= 512
     head_fused = Hp == 512
@@ -146,8 +222,9 @@ def stage_check(dev, cfg, B, seed, precision="bf16"):
     """One kept-intermediates train step of a model built from ``cfg`` at B
     samples (weights from ``seed``, state perturbed with ``seed + 1``, inputs
     from ``seed - 2``), every stage checked.  Returns a dict: ``logits``,
-    ``loss``, ``grads`` (by parameter name), ``stats`` ((stage, flip fraction,
-    max |diff|) per bf16 stage), ``rels`` ((name, relative error, bound) per fp32
+    ``loss``, ``grads`` (by parameter name), ``stats`` ((stage, flip fraction
+    -- fp32: max |diff| / bound --, max |diff|) per stored stage), ``rels``
+    ((name, relative error, bound) per fp32
     quantity), ``plan`` (expected_plan) and ``plain_step``: a callable that
     runs the same step (same weights, inputs and dropout seed) without
     keep_intermediates and returns (logits, loss, grads)."""
@@ -155,7 +232,10 @@ def stage_check(dev, cfg, B, seed, precision="bf16"):
     from dcnr import _lib
     from dcnr.model import dropout_seed, run_backward, run_forward
     from dcnr.ops import bce_with_logits
-    assert precision == "bf16", "the rounding model here is the bf16 path's"
+    assert precision in ("bf16", "fp32"), precision
+    is_bf = precision == "bf16"
+    st = torch.bfloat16 if is_bf else torch.float32   # the storage type
+    cd = torch.float32 if is_bf else torch.float64    # the references' arithmetic
     torch.manual_seed(seed)
     m = dcnr.DCN_RecSys(cfg["n_users"], cfg["n_items"], cfg["cat_dims"], cfg["n_num"],
                         dict(cfg["params"]), precision=precision)
@@ -176,7 +256,7 @@ def stage_check(dev, cfg, B, seed, precision="bf16"):
     Hp = (H + 7) // 8 * 8
     D = m._dims["input_dim"]
     Dp = (D + 7) // 8 * 8
-    plan = expected_plan(H)
+    plan = expected_plan(H, precision)
     names = [k for k, _ in m.named_parameters()]
 
     seed_d = dropout_seed(dev)
@@ -202,7 +282,7 @@ def stage_check(dev, cfg, B, seed, precision="bf16"):
     def offset(kind, idx=0):
         return m.workspace_offset(B, _lib.TRAIN, kind, idx)
 
-    def T(kind, idx=0, cols=Hp, dtype=torch.bfloat16, rows=B):
+    def T(kind, idx=0, cols=Hp, dtype=st, rows=B):
         off = offset(kind, idx)
         assert off >= 0, (kind, idx)
         nb = rows * cols * torch.tensor([], dtype=dtype).element_size()
@@ -227,7 +307,10 @@ def stage_check(dev, cfg, B, seed, precision="bf16"):
     assert (offset("mask_h", R) >= 0) == plan["rank1"], ("mask_h", R)
 
     f32 = torch.float32
-    Wb = lambda k: bf(sd0[k].float())                # noqa: E731 (bf16-packed weights)
+    # the weights as packed: rounded to bf16, or the fp32 parameters themselves (in fp64)
+    Wb = (lambda k: bf(sd0[k].float())) if is_bf else (lambda k: sd0[k].double())   # noqa: E731
+    rd = lambda t: t.to(cd)                          # noqa: E731 (a stored tensor, for the references)
+    chk = check_bf16 if is_bf else check_fp32
     pad = lambda w, r, cl: torch.nn.functional.pad(w, (0, cl - w.shape[1], 0, r - w.shape[0]))  # noqa: E731
     stats, rels = [], []
     rel = lambda name, got, ref, tol=REL: check_rel(name, got, ref, tol, rels)  # noqa: E731
@@ -236,27 +319,29 @@ def stage_check(dev, cfg, B, seed, precision="bf16"):
     parts = [sd0["user_embedding.weight"][u], sd0["item_embedding.weight"][i]]
     parts += [sd0[f"cat_embeddings.{k}.weight"][c[:, k]] for k in range(K)]
     x0f = torch.cat(parts + [n], 1)
-    x0p = T("x0", cols=Dp).float()
+    x0p = rd(T("x0", cols=Dp))
     x0 = x0p[:, :D]
-    assert torch.equal(x0, bf(x0f)), "x0 gather"
+    assert torch.equal(x0, rd(bf(x0f) if is_bf else x0f)), "x0 gather"
     W0 = Wb("initial_deep_layer.weight")
-    h = T("h", 0).float()
-    check_bf16("h0", h[:, :H], x0 @ W0.T + sd0["initial_deep_layer.bias"], stats,
-               x0.abs() @ W0.abs().T + sd0["initial_deep_layer.bias"].abs())
+    h = rd(T("h", 0))
+    chk("h0", h[:, :H], x0 @ W0.T + sd0["initial_deep_layer.bias"], stats,
+        x0.abs() @ W0.abs().T + sd0["initial_deep_layer.bias"].abs())
     keep = [dropout_mask_torch(seed_d, j, B, H, p, dev) for j in range(R)]
     inv_keep = float(np.float32(1.0 / (1.0 - p)))
     # block_plain's exact second rounding needs the kernels' own fp32 factor
     inv_keep_k = float(np.float32(1) / (np.float32(1) - np.float32(p))) if p > 0 else 1.0
+    if not is_bf:   # one fp32 ulp is the bound here: the kernels' own factor in the forward too
+        inv_keep = inv_keep_k
     hs = [h]
     for j in range(R):
         pre = f"res_blocks.{j}"
         for l, (tk, bi) in enumerate((("t1", 2 * j), ("t2", 2 * j + 1))):
             Xin = hs[j] if l == 0 else a1
-            t = T(tk, j).float()
+            t = rd(T(tk, j))
             W = pad(Wb(f"{pre}.layer{l + 1}.weight"), Hp, Hp)
             b = pad(sd0[f"{pre}.layer{l + 1}.bias"][None], 1, Hp)[0]
-            check_bf16(f"{tk}[{j}]", t[:, :H], (Xin @ W.T + b)[:, :H], stats,
-                       (Xin.abs() @ W.abs().T + b.abs())[:, :H])
+            chk(f"{tk}[{j}]", t[:, :H], (Xin @ W.T + b)[:, :H], stats,
+                (Xin.abs() @ W.abs().T + b.abs())[:, :H])
             t64 = t[:, :H].double()   # all B rows, the last partial tile's included
             mu = t64.mean(0)
             var = (t64 * t64).mean(0) - mu * mu
@@ -266,20 +351,19 @@ def stage_check(dev, cfg, B, seed, precision="bf16"):
             rel(f"scale{bi}", V("bn_scale", bi)[:H], gam * V("bn_invstd", bi)[:H], 1e-6)
             sc, sh = V("bn_scale", bi), V("bn_shift", bi)
             if l == 0:
-                a1 = T("a1", j).float()
+                a1 = rd(T("a1", j))
                 ref = torch.clamp_min(t * sc + sh, 0)[:, :H] * keep[j].float() * inv_keep
-                check_bf16(f"a1[{j}]", a1[:, :H], ref, stats,
-                           ((t * sc).abs() + sh.abs())[:, :H] * inv_keep)
+                chk(f"a1[{j}]", a1[:, :H], ref, stats, ((t * sc).abs() + sh.abs())[:, :H] * inv_keep)
                 if plan["masks"]:
                     assert torch.equal(bits("mask_a1", j)[:, :H], a1[:, :H] != 0), f"mask_a1[{j}]"
             else:
-                hn = T("h", j + 1).float()
-                check_bf16(f"h[{j + 1}]", hn[:, :H], torch.clamp_min(t * sc + sh + hs[j], 0)[:, :H],
-                           stats, ((t * sc).abs() + sh.abs() + hs[j].abs())[:, :H])
+                hn = rd(T("h", j + 1))
+                chk(f"h[{j + 1}]", hn[:, :H], torch.clamp_min(t * sc + sh + hs[j], 0)[:, :H],
+                    stats, ((t * sc).abs() + sh.abs() + hs[j].abs())[:, :H])
                 if plan["masks"] and (j + 1 < R or plan["rank1"]):
                     assert torch.equal(bits("mask_h", j + 1)[:, :H], hn[:, :H] > 0), f"mask_h[{j + 1}]"
                 hs.append(hn)
-    wf = sd0["final_linear.weight"][0].float()
+    wf = sd0["final_linear.weight"][0].to(cd)
     zc = T("zc", cols=1, dtype=f32)[:, 0]
     rel("logits", logits, hs[R][:, :H] @ wf[:H] + zc + sd0["final_linear.bias"][0], 1e-5)
     # cross network in fp64 from the fp32 gathered rows: zc = x_L . w_f[H:]
@@ -308,38 +392,53 @@ def stage_check(dev, cfg, B, seed, precision="bf16"):
         s0 = dr[:, :H].double().sum(0)
         s1 = (dr[:, :H].double() * xh.double()).sum(0)
         a = sd0[gam_key].float() * inv
-        k1 = (a.double() * s1 / B).float()
-        k2 = (a.double() * s0 / B).float()
-        return a * dr[:, :H] - k1 * xh - k2, s0, s1, (a * dr[:, :H]).abs() + (k1 * xh).abs() + k2.abs()
+        k1 = (a.double() * s1 / B).to(cd)
+        k2 = (a.double() * s0 / B).to(cd)
+        scale = (a * dr[:, :H]).abs() + (k1 * xh).abs() + k2.abs()
+        if not is_bf:
+            # k1 and k2 are themselves sums over the B rows, which the kernels make
+            # in fp32 per chunk: an error of a few fp32 roundings of a sum(|dr xh|) / B
+            # and a sum(|dr|) / B, whatever is left of k1 and k2 after the signs
+            # cancel (a column whose s1 nearly vanishes, an element with dr = 0).
+            # Against a bf16 ulp that never shows; against ACC_EPS x (|k1 xh| + |k2|)
+            # it does (measured: 1 - 2.5 roundings of these magnitudes, up to 2.6 x
+            # the bound without them).  So the sums' terms enter the scale as the
+            # terms they are, at ACC_EPS and at most B 2^-24 (the worst case of a
+            # B-term fp32 sum, which is the smaller one for B < 64).
+            A1 = a.double() * (dr[:, :H] * xh).abs().sum(0) / B
+            A0 = a.double() * dr[:, :H].abs().sum(0) / B
+            scale = scale + min(1.0, B * 2.0 ** -24 / ACC_EPS) * (A1 * xh.abs() + A0)
+        return a * dr[:, :H] - k1 * xh - k2, s0, s1, scale
 
-    du = T("du", R - 1).float()
+    du = rd(T("du", R - 1))
     ref = dz[:, None] * wf[:H] * (hs[R][:, :H] > 0).float()
-    check_bf16(f"du[{R - 1}]", du[:, :H], ref, stats, ref.abs())
+    chk(f"du[{R - 1}]", du[:, :H], ref, stats, ref.abs())
     rel("dW_f[:H]", gd["final_linear.weight"][0, :H], hs[R][:, :H].double().T @ dz.double())
     for j in reversed(range(R)):
         pre = f"res_blocks.{j}"
-        du = T("du", j).float()
-        dt2 = T("dt2", j).float()
-        ref, s0, s1, sc_ = bn_back(du, T("t2", j).float(), 2 * j + 1, f"{pre}.bn2.weight")
-        check_bf16(f"dt2[{j}]", dt2[:, :H], ref, stats, sc_)
+        du = rd(T("du", j))
+        dt2 = rd(T("dt2", j))
+        ref, s0, s1, sc_ = bn_back(du, rd(T("t2", j)), 2 * j + 1, f"{pre}.bn2.weight")
+        chk(f"dt2[{j}]", dt2[:, :H], ref, stats, sc_)
         rel(f"dbeta2[{j}]", gd[f"{pre}.bn2.bias"], s0)
         rel(f"dgamma2[{j}]", gd[f"{pre}.bn2.weight"], s1)
-        a1 = T("a1", j).float()
+        a1 = rd(T("a1", j))
         rel(f"dW2[{j}]", gd[f"{pre}.layer2.weight"], dt2[:, :H].double().T @ a1[:, :H].double())
         assert gd[f"{pre}.layer2.bias"].abs().max() == 0
         W2 = pad(Wb(f"{pre}.layer2.weight"), Hp, Hp)
-        da = T("da", j).float()
-        t1 = T("t1", j).float()
+        da = rd(T("da", j))
+        t1 = rd(T("t1", j))
         if plan["stats_epi"]:   # one rounding: the dX GEMM's epilogue masks its accumulator
             check_bf16(f"da[{j}]", da[:, :H], ((dt2 @ W2) * inv_keep * (a1 != 0).float())[:, :H], stats,
                        ((dt2.abs() @ W2.abs()) * inv_keep)[:, :H])
         else:   # two roundings; the ReLU sign from the fp32 fma of t1 (its sign is the exact sum's)
             pos = (t1.double() * V("bn_scale", 2 * j).double() + V("bn_shift", 2 * j).double()) > 0
-            check_da_plain(f"da[{j}]", da[:, :H], (dt2 @ W2)[:, :H], keep[j] & pos[:, :H], inv_keep_k,
-                           stats, (dt2.abs() @ W2.abs())[:, :H])
-        dt1 = T("dt1", j).float()
+            (check_da_plain if is_bf else check_da_fp32)(
+                f"da[{j}]", da[:, :H], (dt2 @ W2)[:, :H], keep[j] & pos[:, :H], inv_keep_k,
+                stats, (dt2.abs() @ W2.abs())[:, :H])
+        dt1 = rd(T("dt1", j))
         ref, s0, s1, sc_ = bn_back(da, t1, 2 * j, f"{pre}.bn1.weight")
-        check_bf16(f"dt1[{j}]", dt1[:, :H], ref, stats, sc_)
+        chk(f"dt1[{j}]", dt1[:, :H], ref, stats, sc_)
         rel(f"dbeta1[{j}]", gd[f"{pre}.bn1.bias"], s0)
         rel(f"dgamma1[{j}]", gd[f"{pre}.bn1.weight"], s1)
         rel(f"dW1[{j}]", gd[f"{pre}.layer1.weight"], dt1[:, :H].double().T @ hs[j][:, :H].double())
@@ -348,11 +447,11 @@ def stage_check(dev, cfg, B, seed, precision="bf16"):
         Gj = dt1 @ W1 + du
         Gs = (dt1.abs() @ W1.abs() + du.abs())[:, :H]
         if j > 0:   # (G is one buffer, overwritten per block on the plain path: checked for block 0)
-            check_bf16(f"du[{j - 1}]", T("du", j - 1).float()[:, :H],
-                       (Gj * (hs[j] > 0).float())[:, :H], stats, Gs)
+            chk(f"du[{j - 1}]", rd(T("du", j - 1))[:, :H],
+                (Gj * (hs[j] > 0).float())[:, :H], stats, Gs)
         else:
-            G = T("G").float()
-            check_bf16("G", G[:, :H], Gj[:, :H], stats, Gs)
+            G = rd(T("G"))
+            chk("G", G[:, :H], Gj[:, :H], stats, Gs)
     rel("db0", gd["initial_deep_layer.bias"], G[:, :H].double().sum(0))
     rel("dW0", gd["initial_deep_layer.weight"], G[:, :H].double().T @ x0.double())
     Dq = (Dp + 31) // 32 * 32
@@ -403,11 +502,13 @@ def stage_check(dev, cfg, B, seed, precision="bf16"):
                 tp = T(kind, j)[:, H:].float()
                 assert not tp.any(), (kind, j, "padded columns", int((tp != 0).sum()))
 
-    print("\n  stage, fraction of elements off by a bf16 rounding flip, max |diff|")
+    what = "fraction of elements off by a bf16 rounding flip" if is_bf else "max |diff| / bound"
+    print(f"\n  stage, {what}, max |diff|")
     for name, fr, mx in stats:
         print(f"    {name:10s} {fr:.2e} {mx:.2e}")
     worst = max((q for q in rels if q[2] == REL), key=lambda q: q[1])
-    print(f"  worst flip {max(s[1] for s in stats):.2e}  worst max|diff| {max(s[2] for s in stats):.2e}"
+    print(f"  worst {'flip' if is_bf else '|diff|/bound'} {max(s[1] for s in stats):.2e}"
+          f"  worst max|diff| {max(s[2] for s in stats):.2e}"
           f"  worst gradient rel {worst[1]:.2e} ({worst[0]})")
     return dict(logits=logits, loss=loss, grads=gd, stats=stats, rels=rels, plan=plan,
                 plain_step=plain_step)

@@ -1,11 +1,17 @@
-"""Stage-by-stage parity of the bf16 training step (the benchmarked path).
+"""Stage-by-stage parity of the training step: bf16 (the benchmarked path) and
+fp32 (the parity path).
 
 The checker is tests/stage_check.py: every tensor a kept-intermediates step
 stores is recomputed in torch fp32/fp64 from the kernels' own stored inputs of
 that stage and compared (stages, reference lines and tolerances are listed
 there).  test_bf16_step_stage_by_stage runs it at the benchmark's shapes,
 test_bf16_step_stage_by_stage_paths at small shapes that take every other
-kernel path, and then runs the same step again in the layout a real step uses.
+kernel path, test_fp32_step_stage_by_stage_paths at the fp32 step's shapes
+(fp64 references, one fp32 ulp + 2^-18 x the summed |terms|), and
+test_step_stage_by_stage_batch_regimes, in both precisions, at narrow models
+whose batch size alone takes the reductions and the fp32 split-K past what
+B <= 8192 reaches.  Every small case then runs the same step again in the
+layout a real step uses.
 """
 import pytest
 import torch
@@ -62,6 +68,29 @@ PATH_CASES = {
 INPUT_DIM = {"h64_r1_D164": 164, "h512_r1_D579": 579}
 
 
+def _run_case(dev, case, precision, hidden, n_res, p, B, tb, seed, flags, input_dim):
+    """The stage check of one case, then the same step in the production
+    layout: logits, loss and every gradient bit-equal to the kept run's."""
+    cfg = dict(n_users=tb["n_users"], n_items=tb["n_items"], cat_dims=tb["cat_dims"], n_num=tb["n_num"],
+               params=dict(emb_dim=tb["emb_dim"], hidden_dim=hidden, n_cross_layers=3,
+                           n_res_blocks=n_res, dropout=p))
+    assert {k for k, v in expected_plan(hidden, precision).items() if v} == set(flags.split()), "the case's path"
+    res = stage_check(dev, cfg, B, seed, precision)
+    assert res["grads"]["initial_deep_layer.weight"].shape[1] == input_dim
+    logits, loss, grads = res["plain_step"]()
+    diff = [k for k, g in res["grads"].items() if not torch.equal(g, grads[k])]
+    if not torch.equal(logits, res["logits"]):
+        diff.append("logits")
+    if not torch.equal(loss, res["loss"]):
+        diff.append("loss")
+    worst = max((q for q in res["rels"] if q[2] == REL), key=lambda q: q[1])
+    print(f"  CASE {case}: {'flip' if precision == 'bf16' else 'diff/bound'} "
+          f"{max(s[1] for s in res['stats']):.2e} diff "
+          f"{max(s[2] for s in res['stats']):.2e} rel {worst[1]:.2e} ({worst[0]}) "
+          f"second run {'bit-equal' if not diff else 'DIFFERS ' + str(diff)}")
+    assert not diff, diff
+
+
 @pytest.mark.parametrize("case", list(PATH_CASES))
 def test_bf16_step_stage_by_stage_paths(dev, case):
     """The stage checks on every kernel path of the bf16 train step, at
@@ -113,21 +142,134 @@ def test_bf16_step_stage_by_stage_paths(dev, case):
     (max |diff| is one bf16 ulp of a value in [4, 8); the gradient errors are fp32
     summation-order differences against fp64 sums of the same stored operands.)
     """
-    hidden, n_res, p, B, tb, seed, flags = PATH_CASES[case]
-    cfg = dict(n_users=tb["n_users"], n_items=tb["n_items"], cat_dims=tb["cat_dims"], n_num=tb["n_num"],
-               params=dict(emb_dim=tb["emb_dim"], hidden_dim=hidden, n_cross_layers=3,
-                           n_res_blocks=n_res, dropout=p))
-    assert {k for k, v in expected_plan(hidden).items() if v} == set(flags.split()), "the case's path"
-    res = stage_check(dev, cfg, B, seed)
-    assert res["grads"]["initial_deep_layer.weight"].shape[1] == INPUT_DIM.get(case, 456)
-    logits, loss, grads = res["plain_step"]()
-    diff = [k for k, g in res["grads"].items() if not torch.equal(g, grads[k])]
-    if not torch.equal(logits, res["logits"]):
-        diff.append("logits")
-    if not torch.equal(loss, res["loss"]):
-        diff.append("loss")
-    worst = max((q for q in res["rels"] if q[2] == REL), key=lambda q: q[1])
-    print(f"  CASE {case}: flip {max(s[1] for s in res['stats']):.2e} diff "
-          f"{max(s[2] for s in res['stats']):.2e} rel {worst[1]:.2e} ({worst[0]}) "
-          f"second run {'bit-equal' if not diff else 'DIFFERS ' + str(diff)}")
-    assert not diff, diff
+    _run_case(dev, case, "bf16", *PATH_CASES[case], INPUT_DIM.get(case, 456))
+
+
+# id: (hidden, blocks, dropout, B, tables, seed, plan fields expected true)
+F32_CASES = {
+    "f32_h40_r1": (40, 1, 0.6, 300, _tables(), 11, ""),
+    "f32_h100_r2": (100, 2, 0.6, 300, _tables(), 11, ""),
+    "f32_h256_r2": (256, 2, 0.6, 300, _tables(), 11, "head_fused"),
+    "f32_h512_r2": (512, 2, 0.6, 300, _tables(), 11, ""),
+    "f32_h1024_r1": (1024, 1, 0.6, 300, _tables(), 11, ""),
+    "f32_h64_r1_D164": (64, 1, 0.6, 300, _tables(8, 16, 4), 11, ""),
+    "f32_h512_r1_D579": (512, 1, 0.6, 300, _tables(16, 32, 3), 11, ""),
+    "f32_h100_r2_B33": (100, 2, 0.6, 33, _tables(), 11, ""),
+    "f32_h64_r2_p0": (64, 2, 0.0, 300, _tables(), 11, ""),
+}
+F32_INPUT_DIM = {"f32_h64_r1_D164": 164, "f32_h512_r1_D579": 579}
+
+
+@pytest.mark.parametrize("case", list(F32_CASES))
+def test_fp32_step_stage_by_stage_paths(dev, case):
+    """The stage checks on the fp32 train step (block_plain, fp32 storage,
+    the generic MFMA GEMM, no masks), with fp64 references and the bound one
+    fp32 ulp + 2^-18 x the summed |terms| (tests/stage_check.py), then the same
+    step in the production layout, bit-equal.
+
+      case              reaches
+      f32_h40_r1        one partial 128-wide GEMM tile, one block
+      f32_h100_r2       Hp = 104: padded columns in every fp32 row pass and in the reduce
+      f32_h256_r2       the fp32 fused head pass (bn_add_relu_head<float>, a wave per row)
+      f32_h512_r2       the benchmark width on the parity path, unfused head
+      f32_h1024_r1      tcols = Hp / 4 = NT = 256: one row per pass, the fp32 row-pass limit; K > 512
+      f32_h64_r1_D164   Dp = 168: initial layer, dW0, dx0
+      f32_h512_r1_D579  Dp = 584: initial layer and dx0 with N > 512
+      f32_h100_r2_B33   one 32-row chunk plus one row
+      f32_h64_r2_p0     inv_keep = 1, no dropout draw
+
+    Measured on an MI355X (worst stage max |diff| / bound, worst max |diff| of
+    a stored stage, worst relative error of a gradient, second run bit-equal):
+
+      case              diff / bound   max |diff|  gradient rel. error               second run
+      f32_h40_r1        7.54e-02       2.04e-06    5.85e-07 (db_f)                   bit-equal
+      f32_h100_r2       1.02e-01       2.22e-06    2.30e-07 (dW1[0])                 bit-equal
+      f32_h256_r2       1.85e-01       3.30e-06    2.85e-07 (dx0)                    bit-equal
+      f32_h512_r2       1.27e-01       3.36e-06    4.06e-07 (dx0)                    bit-equal
+      f32_h1024_r1      1.47e-01       3.35e-06    5.71e-07 (dx0)                    bit-equal
+      f32_h64_r1_D164   9.69e-02       1.10e-06    4.90e-07 (cross_b[2])             bit-equal
+      f32_h512_r1_D579  1.24e-01       3.59e-06    4.06e-07 (dx0)                    bit-equal
+      f32_h100_r2_B33   8.95e-02       1.55e-06    4.38e-07 (cat_embeddings.7.weight) bit-equal
+      f32_h64_r2_p0     3.13e-01       2.20e-06    2.55e-07 (db0)                    bit-equal
+
+    (diff / bound: the worst stored element uses a third of its bound, 2^-18 x the
+    summed |terms| = 64 fp32 roundings of them; max |diff| belongs to h0 / t, values
+    of a few units summed over 456 - 1024 terms.  Before the BN-backward coefficient
+    sums' own terms entered dt2's and dt1's scale (stage_check.bn_back), dt2 / dt1
+    reached 1.01 - 2.6 x the bound in f32_h40_r1, f32_h100_r2 and f32_h100_r2_B33, in
+    columns whose sums nearly cancel; with them the same elements sit at 0.02 - 0.04.)
+    """
+    _run_case(dev, case, "fp32", *F32_CASES[case], F32_INPUT_DIM.get(case, 456))
+
+
+# id: (precision, hidden, blocks, dropout, B, tables, seed, plan fields expected true)
+BATCH_CASES = {
+    "h100_r2_B8225": ("bf16", 100, 2, 0.6, 8225, _tables(), 11, ""),
+    "h250_r2_B8225": ("bf16", 250, 2, 0.6, 8225, _tables(), 11, "masks stats_epi"),
+    "h100_r2_B70001": ("bf16", 100, 2, 0.6, 70001, _tables(), 11, ""),
+    "f32_h96_r2_D68_B8225": ("fp32", 96, 2, 0.6, 8225, _tables(2, 16, 4), 11, ""),
+    "f32_h96_r2_D68_B70001": ("fp32", 96, 2, 0.6, 70001, _tables(2, 16, 4), 11, ""),
+}
+BATCH_INPUT_DIM = {"f32_h96_r2_D68_B8225": 68, "f32_h96_r2_D68_B70001": 68}
+
+
+@pytest.mark.parametrize("case", list(BATCH_CASES))
+def test_step_stage_by_stage_batch_regimes(dev, case):
+    """Narrow models at batch sizes past B = 8192, where the code that depends
+    on B alone changes path, under the same stage checks and the same bit-equal
+    second run.  The counts below follow csrc/elementwise.hip (run_rowcol,
+    reduce_fused) and csrc/dcnr_api.hip (linear_dw, make_layout) by hand.
+
+    Reduction row passes: rows = max(32, cdiv(B, 2048)) per chunk, nc = cdiv(B, rows)
+    chunks; nc > 256 takes the two-stage reduce_fused_kernel, 32 chunk groups of
+    per = cdiv(nc, 32) chunks.
+      B = 8225   rows = 32, nc = 258 (257 x 32 + 1: the last chunk has 1 row), per = 9:
+                 groups 0 - 27 full (252 chunks), group 28 has 6, groups 29 - 31 are empty
+      B = 70001  rows = 35, nc = 2001 (2000 x 35 + 1: the last chunk has 1 row), per = 63:
+                 groups 0 - 30 full (1953 chunks), group 31 has 48
+
+    fp32 weight-gradient split-K (linear_dw's generic path; Hp = 96, Dp = 72: one
+    128 x 128 tile, so S = min(512, cdiv(B, 256)), kps = rup(cdiv(B, S), 64),
+    S = cdiv(B, kps); slab_elems = max(64 * 96 * 96, gemm_dw_splits(96, 96, B) * 96 * 96,
+    gemm_dw_splits(96, 72, B) * 96 * 72)):
+      B = 8225   S = 33, kps = rup(250, 64) = 256, S = cdiv(8225, 256) = 33 (the last
+                 split has 33 rows); 33 * 9216 = 304128 <= slab_elems (>= 64 * 9216): no clamp
+      B = 70001  gemm_dw_splits = 256 (one 256 x 256 tile; cdiv(70001, 256) = 274 >= 64), so
+                 slab_elems = 256 * 96 * 96 = 2359296.  dW1 / dW2 (96 x 96): S = 274,
+                 kps = rup(256, 64) = 256, S = 274; 274 * 9216 = 2525184 > 2359296: the
+                 clamp branch, S = 2359296 / 9216 = 256, kps = rup(cdiv(70001, 256) = 274, 64)
+                 = 320, S = cdiv(70001, 320) = 219 (the last split has 241 rows).
+                 dW0 (96 x 72): S = 274, kps = 256; 274 * 6912 = 1893888 <= 2359296: no
+                 clamp, 274 splits (the last one 113 rows)
+
+      case                   reaches
+      h100_r2_B8225          bf16 block_plain: reduce_fused_kernel<bf16> with ragged and empty
+                             groups and a 1-row last chunk, with a shift (the forward BN
+                             statistics after col_stats: S0 = S0' + nK, S1 = S1' + 2K S0' + nK^2),
+                             NK = 2 (BN1 backward, forward) and NK = 3 (BN2 backward)
+      h250_r2_B8225          bf16 block_epi: the last block's bwd_bn2_stats3 partials through
+                             the two-stage reduce with ragged groups; everything else still
+                             from the GEMM epilogues' partials
+      h100_r2_B70001         bf16: rows_per_chunk = 35 with a ragged tail, nc = 2001, last group 48
+      f32_h96_r2_D68_B8225   the same reduce regime with T = float; generic split-K dW, S = 33
+      f32_h96_r2_D68_B70001  rows_per_chunk = 35; linear_dw's slab clamp (dW1, dW2: S = 219,
+                             kps = 320) and 274 splits on the generic kernel (dW0)
+
+    D = 68: user and item embeddings of 16, two categorical tables of width 16
+    (250 rows), 4 numeric features.
+
+    Measured on an MI355X (worst stage flip fraction -- fp32: max |diff| / bound --,
+    worst max |diff| of a stored stage, worst relative error of a gradient, second
+    run bit-equal):
+
+      case                   flip / bound  max |diff|  gradient rel. error   second run
+      h100_r2_B8225          1.19e-04      5.77e-02    2.24e-07 (dW_f[H:])   bit-equal
+      h250_r2_B8225          1.91e-04      3.12e-02    2.05e-07 (dW1[1])     bit-equal
+      h100_r2_B70001         1.32e-04      6.23e-02    3.69e-07 (dW1[1])     bit-equal
+      f32_h96_r2_D68_B8225   1.94e-01      1.36e-06    2.93e-07 (dW1[0])     bit-equal
+      f32_h96_r2_D68_B70001  4.93e-01      1.32e-06    3.30e-07 (dW1[0])     bit-equal
+
+    (bf16 max |diff|: one bf16 ulp of a value in [8, 16).)
+    """
+    precision, *rest = BATCH_CASES[case]
+    _run_case(dev, case, precision, *rest, BATCH_INPUT_DIM.get(case, 456))
