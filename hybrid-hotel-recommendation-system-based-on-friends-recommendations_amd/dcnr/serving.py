@@ -30,7 +30,10 @@ all candidates, one host wait); ``similar_items_many`` is its /similar_items
 companion.  ``RankingPipeline.recommend_users`` is the same pass from user
 ids: the positives, the negatives and the ``recommended_by`` lists (main.py:
 172-194, 336-351) come from a ``dcnr.InteractionStore`` on the device
-(dcnr_requests_sources, dcnr_requests_recommended_by).
+(dcnr_requests_sources, dcnr_requests_recommended_by).  The pass itself (pack,
+one pinned upload, candidates, the one wait, forward, rank + MMR, the host's
+answers spliced in) is ``dcnr.requests``: ``pack_requests`` and one
+``_RequestBatch`` per call, which the three batched entry points feed and read.
 
 ``RankingPipeline.list_metrics`` measures answers already served
 (``dcnr.list_metrics`` against the pipeline's own table), and
@@ -56,22 +59,10 @@ import torch
 
 from . import _lib
 from .knn import NearestNeighbors
+from .requests import (REQ_OVERFLOW, SV_MAX, _RequestBatch, _row_set, pack_requests, rounds_to_one,
+                       set_entries)
 
 ml_artifacts: Dict[str, Any] = {}
-
-SV_MAX = 4096   # csrc/serving.hip: candidates per union / rank / MMR call
-REQ_OVERFLOW, REQ_BAD_DATA = 1, 2   # DCNR_REQ_* status bits of the batched calls
-
-
-def _row_set(rows, n_rows, what) -> np.ndarray:
-    """A row set as the kernels read it: int64, ascending, distinct, inside the table."""
-    if torch.is_tensor(rows):
-        rows = rows.cpu().numpy()
-    a = np.unique(np.asarray(list(rows) if not isinstance(rows, np.ndarray) else rows,
-                             dtype=np.int64).reshape(-1))
-    if a.size and (a[0] < 0 or a[-1] >= n_rows):
-        raise ValueError(f"{what}: row outside [0, {n_rows})")
-    return a
 
 def _dev_table(emb, device):
     """(table fp32 [n, d] on device, inverse row norms [n]) cached per source array."""
@@ -337,24 +328,29 @@ class RankingPipeline:
             return outs[0]
         return torch.unique(torch.cat(outs))   # ascending distinct rows, as one call gives
 
-    def ranking_batch(self, user_row: int, item_rows: torch.Tensor):
-        """preprocess_for_ranking (main.py:215-230) on the device."""
-        lib = _lib.load()
-        item_rows = item_rows.to(self.device, torch.int64).contiguous()
-        n = item_rows.numel()
+    def _ranking_outputs(self, n):
+        """The model inputs (user ids, item ids, cat, num) of n rows to fill,
+        and the arguments both ranking-batch calls end with, item_cat to num
+        (a pointer is null where the model has no such column)."""
         K, F = self.item_cat.shape[1], self.item_num.shape[1]
         u = torch.empty(n, dtype=torch.int64, device=self.device)
         i = torch.empty(n, dtype=torch.int64, device=self.device)
         c = torch.empty((n, K), dtype=torch.int64, device=self.device)
         x = torch.empty((n, F), dtype=torch.float32, device=self.device)
-        _lib.check(lib.dcnr_ranking_batch(item_rows.data_ptr(), n, int(user_row),
-                                          self.item_cat.data_ptr() if K else None, K,
-                                          self.item_num.data_ptr() if F else None, F,
-                                          self.n_items, u.data_ptr(), i.data_ptr(),
-                                          c.data_ptr() if K else None,
-                                          x.data_ptr() if F else None,
+        return (u, i, c, x), (self.item_cat.data_ptr() if K else None, K,
+                              self.item_num.data_ptr() if F else None, F, self.n_items,
+                              u.data_ptr(), i.data_ptr(), c.data_ptr() if K else None,
+                              x.data_ptr() if F else None)
+
+    def ranking_batch(self, user_row: int, item_rows: torch.Tensor):
+        """preprocess_for_ranking (main.py:215-230) on the device."""
+        lib = _lib.load()
+        item_rows = item_rows.to(self.device, torch.int64).contiguous()
+        n = item_rows.numel()
+        batch, args = self._ranking_outputs(n)
+        _lib.check(lib.dcnr_ranking_batch(item_rows.data_ptr(), n, int(user_row), *args,
                                           _lib.stream_ptr(self.device)), "dcnr_ranking_batch")
-        return u, i, c, x
+        return batch
 
     @torch.no_grad()
     def score(self, user_row: int, item_rows: torch.Tensor) -> torch.Tensor:
@@ -446,17 +442,8 @@ class RankingPipeline:
         as int32 with -1 for None, the longest named set)."""
         reg_rows, reg_off = self._sets
         n_reg = reg_off.size - 1
-        adhoc, idx = [], np.full(len(entries), -1, np.int32)
-        for r, e in enumerate(entries):
-            if e is None:
-                continue
-            if isinstance(e, (int, np.integer)):
-                if not 0 <= e < n_reg:
-                    raise ValueError(f"within: {e} is not a registered set")
-                idx[r] = e
-            else:
-                adhoc.append(_row_set(e, self.n_rows, "within"))
-                idx[r] = n_reg + len(adhoc) - 1
+        adhoc = []
+        idx = set_entries(entries, n_reg, n_reg, self.n_rows, adhoc, "within", ": ")
         off = np.concatenate([reg_off, reg_off[-1] + np.cumsum([a.size for a in adhoc], dtype=np.int64)])
         rows = reg_rows
         if adhoc:
@@ -519,32 +506,24 @@ class RankingPipeline:
         """dcnr_requests_candidates behind ONE top-k call over all requests'
         positives d_pos [Q] -- or, with a neighbour table, its table form and no
         scan.  ``rest``: the arguments from set_rows on.  ``within`` (requests
-        that name a set for their neighbours): (set_rows, set_off, pos_off,
-        set index per request -- device tensors --, the longest named set,
-        whether a request with positives names none).  Those requests' neighbours
-        come from one set-scoped call laid over the global answers (the table's
-        rows, gathered, or the scan's), which only the others keep."""
+        that name a set for their neighbours): (set_rows, set_off, pos_off, set
+        index per request -- device tensors --, the longest named set, whether a
+        request with positives names none).  Those requests' neighbours come
+        from one set-scoped call laid over the global answers (the table's rows,
+        gathered, or the scan's), which only the others keep."""
         lib = _lib.load()
-        k = self.n_neighbors
-        if within is not None and Q:
-            set_rows, set_off, seg_off, seg_set, longest, any_global = within
-            idx = None
-            if any_global and self._nbr is not None:
-                idx = self._nbr[d_pos][:, :k].to(torch.int64)
-            elif any_global:
-                _, idx = self.index.kneighbors_device(self.index._table[d_pos], k)
-            idx = self._within_overlay(d_pos, idx, set_rows, set_off, seg_off, seg_set, longest)
-            _lib.check(lib.dcnr_requests_candidates(pos_ptr, pos_off_ptr, R, Q, idx.data_ptr(), k, *rest),
-                       "dcnr_requests_candidates")
-            return
-        if self._nbr is not None:
+        k, nbr = self.n_neighbors, self._nbr
+        if nbr is not None and (within is None or not Q):
             _lib.check(lib.dcnr_requests_candidates_table(
-                pos_ptr, pos_off_ptr, R, Q, self._nbr.data_ptr(), self._nbr.shape[1], k, *rest),
+                pos_ptr, pos_off_ptr, R, Q, nbr.data_ptr(), nbr.shape[1], k, *rest),
                 "dcnr_requests_candidates_table")
             return
         idx = None
-        if Q:
-            _, idx = self.index.kneighbors_device(self.index._table[d_pos], k)
+        if Q and (within is None or within[5]):   # someone keeps global neighbours
+            idx = nbr[d_pos][:, :k].to(torch.int64) if nbr is not None else \
+                self.index.kneighbors_device(self.index._table[d_pos], k)[1]
+        if Q and within is not None:
+            idx = self._within_overlay(d_pos, idx, *within[:5])
         _lib.check(lib.dcnr_requests_candidates(
             pos_ptr, pos_off_ptr, R, Q, idx.data_ptr() if Q else None, k, *rest),
             "dcnr_requests_candidates")
@@ -620,10 +599,7 @@ class RankingPipeline:
         or -inf (they have no rank; ``recommend()`` is undefined there too) is
         not reported: the device marks its whole answer, rows -1 and logits
         NaN."""
-        if self.index._table.shape[0] != self.n_items:
-            raise ValueError(f"recommend_many: the index holds {self.index._table.shape[0]} rows, "
-                             f"item_cat / item_num {self.n_items}")
-        users = np.asarray(user_rows, dtype=np.int64).reshape(-1)
+        users = self._users_arg("recommend_many", user_rows)
         R = users.size
         if len(positive_rows) != R:
             raise ValueError("recommend_many: one positive list per user row")
@@ -631,148 +607,70 @@ class RankingPipeline:
             return []
         city = self._city_arg("recommend_many", city_sets, cities, neighbors_in_city, R, allowed,
                               fallback, neighbors_within)
-        f = self._many_front(users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
-                             min_candidates, neighbors_within=neighbors_within, city=city)
-        info, seg, st, d_at = f["info"], f["seg"], f["st"], f["d_at"]
-        pos, lam, topk = info["pos"], info["lam"], info["topk"]
-        out_rows, out_logits = self._score_and_rank(R, f["cap"], f["n"], f["slots"], f["offsets"],
-                                                    d_at("users"), d_at("lam"), d_at("topk"),
-                                                    f["out_count"], f["status"], f["ws"], f["nb"],
-                                                    f["stream"])
-        # recommend() decides "lambda < 1" on the Python double and computes with its
-        # float32: a lambda that rounds to 1.0f from below goes its way
-        lam64 = info["lam64"]
-        odd = (lam64 < 1.0) != (lam < 1.0)
-        res = []
-        for r in range(R):
-            # above the batched kernels' capacity (or such a lambda): the one-request path
-            if st[r] & REQ_OVERFLOW or odd[r]:
-                pick = lambda v: None if v is None else v[r]
-                p_r = pos[info["pos_off"][r]:info["pos_off"][r + 1]]
-                sets = self._city_rows(city, r) if city is not None else dict(
-                    allowed=self._set_arg(pick(allowed)), fallback=self._set_arg(pick(fallback)),
-                    neighbors_within=self._set_arg(pick(neighbors_within)))
-                res.append(self.recommend(int(users[r]), p_r, float(lam64[r]), int(topk[r]),
-                                          excluded=self._set_arg(pick(excluded)),
-                                          min_candidates=min_candidates, **sets))
-                continue
-            n_r = int(seg[r + 1] - seg[r])
-            # every candidate is a table row, so the MMR finds min(top_k, n_r) items
-            c_r = min(int(topk[r]), n_r) if lam[r] < 1.0 else n_r
-            o = int(seg[r])
-            res.append((out_rows[o:o + c_r], out_logits[o:o + c_r]))
-        return res
+        p, b = self._many_front(users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
+                                min_candidates, neighbors_within=neighbors_within, city=city)
+        out_rows, out_logits = b.rank_mmr(b.score(), b.ptr("lam"), b.out_count)
+
+        def host(r):   # above the batched kernels' capacity, or a lambda that rounds to 1.0f
+            return self._on_host(r, users, p, p.pos[p.pos_off[r]:p.pos_off[r + 1]],
+                                 self._set_arg(None if excluded is None else excluded[r]),
+                                 min_candidates, (city, allowed, fallback, neighbors_within))
+        return b.answers(out_rows, out_logits, b.answer_lengths(p.lam, p.topk),
+                         (b.st & REQ_OVERFLOW) | p.odd, host)
+
+    def _users_arg(self, what, user_rows):
+        """``user_rows`` of the batched call ``what`` as an array, the tables' row counts checked."""
+        if self.index._table.shape[0] != self.n_items:
+            raise ValueError(f"{what}: the index holds {self.index._table.shape[0]} rows, "
+                             f"item_cat / item_num {self.n_items}")
+        return np.asarray(user_rows, dtype=np.int64).reshape(-1)
+
+    def _pack(self, users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
+              neighbors_within=None, city=None):
+        """``pack_requests`` on this pipeline's tables (``city``: from ``_city_arg``), and the
+        device rows of the sets the packed indices name in front of the per-call ones."""
+        reg_rows, reg_off = self._sets
+        p = pack_requests(users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
+                          neighbors_within, n_users=self.model.user_embedding.weight.shape[0],
+                          n_rows=self.n_rows, k=self.n_neighbors, reg_off=reg_off,
+                          city=None if city is None else (city[0].host_offsets, city[0].n_cities,
+                                                          city[1], city[2]))
+        if not p.S:
+            return p, self._no_rows
+        return p, reg_rows if city is None else self._city_join(reg_rows, city[0])
 
     def _many_front(self, users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
-                    min_candidates, extra=(), pinned_tail=0, neighbors_within=None, city=None):
-        """``recommend_many`` up to its one wait: the packed upload (``extra``:
-        further (name, array) pairs to carry along), the top-k or table lookup,
-        the candidates pass, the wait.  Returns what the calls behind the wait
-        need; ``tail``: ``pinned_tail`` bytes of the pinned buffer behind
-        everything this front uses."""
-        lib = _lib.load()
-        dev = self.device
-        R = users.size
-        ins, info = self._pack_requests(users, positive_rows, lambda_param, top_k, allowed,
-                                        excluded, fallback, neighbors_within, city)
-        ins = ins + list(extra)
-        pos, lam, topk, cap, S, n_adhoc = (info[k_] for k_ in ("pos", "lam", "topk", "cap", "S",
-                                                               "n_adhoc"))
-        k = self.n_neighbors
-        # ---- every host input in one pinned buffer, one non-blocking copy; the
-        # device's mirrors of the offsets and the status words behind them
-        at, total = {}, 0
-        for name, a in ins:
-            at[name] = total
-            total += (a.nbytes + 7) & ~7
-        o_off = total
-        o_st = o_off + 8 * (R + 1)
-        o_tail = o_st + ((4 * R + 7) & ~7)
-        pin, host = self._pinned(o_tail + pinned_tail)
-        for name, a in ins:
-            host[at[name]:at[name] + a.nbytes] = a.view(np.uint8)
-        dbuf = pin[:total].to(dev, non_blocking=True)
-        d_at = lambda name: dbuf.data_ptr() + at[name] if name in at else None
-        reg_rows = info["reg_rows"]
-        if n_adhoc:   # the per-call sets behind the registered ones: one CSR
-            o = at["adhoc_rows"]
-            reg_rows = torch.cat([reg_rows, dbuf[o:o + 8 * n_adhoc].view(torch.int64)])
-        stream = _lib.stream_ptr(dev)
-        Q = pos.size
-        d_pos = dbuf[at["pos"]:at["pos"] + 8 * Q].view(torch.int64)
-        slots = torch.empty((R, cap), dtype=torch.int64, device=dev)
-        offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
-        words = torch.empty(3 * R, dtype=torch.int32, device=dev)   # count, status, out_count
-        count, status, out_count = (words.data_ptr() + 4 * R * j for j in range(3))
-        within = None
-        if "within" in at:   # some request seeks its neighbours inside a set
-            d_view = lambda name, n_, dt, w_: dbuf[at[name]:at[name] + w_ * n_].view(dt)
-            within = (reg_rows, d_view("set_off", S + 1, torch.int64, 8),
-                      d_view("pos_off", R + 1, torch.int64, 8), d_view("within", R, torch.int32, 4),
-                      info["within_longest"], info["within_any_global"])
-        self._requests_candidates(
-            d_at("pos") if Q else None, d_pos, d_at("pos_off"), R, Q,
-            reg_rows.data_ptr() if reg_rows.numel() else None, reg_rows.numel(),
-            d_at("set_off"), S, d_at("allowed"), d_at("excluded"), d_at("fallback"),
-            int(min_candidates), self.n_rows, cap, slots.data_ptr(), count, status,
-            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream, within=within)
-        # (allocated while the device works, not after the wait)
-        nb = int(lib.dcnr_requests_workspace_size(R, Q, k, cap))
-        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
-        torch.cuda.current_stream(dev).synchronize()   # the call's one wait
-        seg = host[o_off:o_st].view(np.int64)
-        n = int(seg[R])
-        st = host[o_st:o_st + 4 * R].view(np.int32)
-        if (st & REQ_BAD_DATA).any():
-            raise RuntimeError("recommend_many: the device rejected validated input")
-        return dict(info=info, seg=seg, st=st, d_at=d_at, cap=cap, n=n, slots=slots, offsets=offsets,
-                    out_count=out_count, status=status, words=words, dbuf=dbuf, ws=ws, nb=nb,
-                    stream=stream, pin=pin, host=host, tail=o_tail)
+                    min_candidates, extra=None, tail=0, neighbors_within=None, city=None):
+        """``recommend_many`` up to its one wait: the packed requests and their
+        ``_RequestBatch``, staged (``extra``: further named arrays to carry along;
+        ``tail``: as ``_RequestBatch``'s), the candidates found and waited for."""
+        p, reg_rows = self._pack(users, positive_rows, lambda_param, top_k, allowed, excluded,
+                                 fallback, neighbors_within, city)
+        b = _RequestBatch(self, "recommend_many", users.size, dict(p.arrays, **(extra or {})),
+                          tail=tail)
+        b.candidates(b.view("pos", p.pos.size, torch.int64), b.set_rows(reg_rows, p.n_adhoc), p.S,
+                     min_candidates, p.cap,
+                     None if p.within_idx is None else (p.within_longest, p.within_any_global))
+        b.wait()
+        return p, b
 
-    def _score_and_rank(self, R, cap, n, slots, offsets, d_users, d_lam, d_topk, out_count, status,
-                        ws, nb, stream):
-        """The batched calls' half behind the wait: the ranking batch of the n
-        candidates, one forward, rank + MMR per segment -> (rows, logits) [n]."""
-        dev = self.device
-        if not n:
-            return (torch.empty(0, dtype=torch.int64, device=dev),
-                    torch.empty(0, dtype=torch.float32, device=dev))
-        logits = self._score_requests(R, cap, n, slots, offsets, d_users, stream)
-        return self._rank_mmr_requests(logits, R, cap, n, slots, offsets, d_lam, d_topk, out_count,
-                                       status, ws, nb, stream)
-
-    def _score_requests(self, R, cap, n, slots, offsets, d_users, stream):
-        """The ranking batch of the n > 0 candidates and one forward: logits [n]."""
-        lib = _lib.load()
-        dev = self.device
-        K, F = self.item_cat.shape[1], self.item_num.shape[1]
-        u = torch.empty(n, dtype=torch.int64, device=dev)
-        i = torch.empty(n, dtype=torch.int64, device=dev)
-        c = torch.empty((n, K), dtype=torch.int64, device=dev)
-        x = torch.empty((n, F), dtype=torch.float32, device=dev)
-        _lib.check(lib.dcnr_requests_ranking_batch(
-            slots.data_ptr(), cap, offsets.data_ptr(), R, n, d_users,
-            self.item_cat.data_ptr() if K else None, K,
-            self.item_num.data_ptr() if F else None, F, self.n_items, u.data_ptr(),
-            i.data_ptr(), c.data_ptr() if K else None, x.data_ptr() if F else None, stream),
-            "dcnr_requests_ranking_batch")
-        return self.model(u, i, c, x).reshape(-1).to(torch.float32).contiguous()
-
-    def _rank_mmr_requests(self, logits, R, cap, n, slots, offsets, d_lam, d_topk, out_count, status,
-                           ws, nb, stream):
-        """Rank + MMR of every segment of ``logits`` (read only) -> (rows, logits) [n]."""
-        lib = _lib.load()
-        dev = self.device
-        out_rows = torch.empty(n, dtype=torch.int64, device=dev)
-        out_logits = torch.empty(n, dtype=torch.float32, device=dev)
-        table, inv = self.index._table, self.index._inv
-        _lib.check(lib.dcnr_requests_rank_mmr(
-            logits.data_ptr(), n, slots.data_ptr(), cap, offsets.data_ptr(), R,
-            table.data_ptr(), inv.data_ptr(), table.shape[1], table.shape[0],
-            d_lam, d_topk, out_rows.data_ptr(), out_logits.data_ptr(),
-            out_count, status, ws.data_ptr(), nb, stream),
-            "dcnr_requests_rank_mmr")
-        return out_rows, out_logits
+    def _on_host(self, r, users, p, positives, excluded, min_candidates, sets):
+        """Request r of a batched call answered by ``recommend()``.  ``sets``: the call's
+        (city, allowed, fallback, neighbors_within), turned into rows here (a city's from
+        the host columns of the generation the batched call used)."""
+        city, allowed, fallback, neighbors_within = sets
+        if city is not None:
+            gen, codes, in_city = city
+            rows = gen.host.city_rows(int(codes[r]))
+            sets = dict(allowed=rows, fallback=gen.host.popular_rows(int(codes[r])))
+            if in_city:
+                sets["neighbors_within"] = rows
+        else:
+            pick = lambda v: None if v is None else self._set_arg(v[r])
+            sets = dict(allowed=pick(allowed), fallback=pick(fallback),
+                        neighbors_within=pick(neighbors_within))
+        return self.recommend(int(users[r]), positives, float(p.lam64[r]), int(p.topk[r]),
+                              excluded=excluded, min_candidates=min_candidates, **sets)
 
     # ------------------------------------------------ what the answers look like
     def _blank_relevant(self, relevant, R, skipped):
@@ -847,15 +745,13 @@ class RankingPipeline:
         lambda, ``answers`` as ``recommend_many`` returns them; ``.lambdas``;
         ``.skipped``: the indices of requests the batched kernels hand back
         (candidates above SV_MAX -- or every request, when some lambda rounds
-        to 1.0f from below: decided on the host, nothing is launched then).  Their entry in every ``answers`` is None, never
-        a truncated list, and they take part in no metric but ``n_lists``:
-        serve them with ``recommend()``."""
+        to 1.0f from below: decided on the host, nothing is launched then).
+        Their entry in every ``answers`` is None, never a truncated list, and
+        they take part in no metric but ``n_lists``: serve them with
+        ``recommend()``."""
         from . import metrics as mt
         dev = self.device
-        if self.index._table.shape[0] != self.n_items:
-            raise ValueError(f"lambda_sweep: the index holds {self.index._table.shape[0]} rows, "
-                             f"item_cat / item_num {self.n_items}")
-        users = np.asarray(user_rows, dtype=np.int64).reshape(-1)
+        users = self._users_arg("lambda_sweep", user_rows)
         R = users.size
         if len(positive_rows) != R:
             raise ValueError("lambda_sweep: one positive list per user row")
@@ -876,58 +772,45 @@ class RankingPipeline:
         if info is not None:
             info = torch.as_tensor(info, dtype=torch.float64).reshape(-1).to(dev)
         lam32 = lam64.astype(np.float32)
-        if ((lam64 < 1.0) != (lam32 < 1.0)).any():
-            # a lambda that rounds to 1.0f from below: recommend() would take its MMR branch, the
-            # kernels would not, so the batched kernels serve no request of this sweep.  Known
-            # here: the rows are validated as usual and nothing is launched.
-            self._pack_requests(users, positive_rows, float(lam64[0]), int(top_k), allowed, excluded,
-                                fallback, neighbors_within)
+        if rounds_to_one(lam64, lam32).any():
+            # such a lambda goes the one-request way, so the batched kernels serve no request of
+            # this sweep.  Known here: the rows are validated as usual and nothing is launched.
+            self._pack(users, positive_rows, float(lam64[0]), int(top_k), allowed, excluded,
+                       fallback, neighbors_within)
             out.skipped = list(range(R))
             for _ in range(L):
                 out.append(([None] * R, mt.empty_list_metrics(R, ks)))
             return out
         lams = np.repeat(lam32, R)                     # [L][R]: one lambda array per launch
         tail = 8 * (rel_host[0].size + R + 1) if rel_host is not None else 0
-        f = self._many_front(users, positive_rows, float(lam64[0]), int(top_k), allowed, excluded,
-                             fallback, min_candidates, extra=[("lams", lams)], pinned_tail=tail,
-                             neighbors_within=neighbors_within)
-        seg, st, d_at, n, cap = f["seg"], f["st"], f["d_at"], f["n"], f["cap"]
-        stream = f["stream"]
-        skip = (st & REQ_OVERFLOW).astype(bool)
+        _, b = self._many_front(users, positive_rows, float(lam64[0]), int(top_k), allowed, excluded,
+                                fallback, min_candidates, extra={"lams": lams}, tail=tail,
+                                neighbors_within=neighbors_within)
+        skip = (b.st & REQ_OVERFLOW).astype(bool)
         out.skipped = np.flatnonzero(skip).tolist()
         # ---- the held-out sets without the skipped requests': pinned, no wait
         rel = None
         if rel_host is not None:
             rr, ro = self._blank_relevant(rel_host, R, out.skipped)
-            o = f["tail"]
-            f["host"][o:o + 8 * (R + 1)] = ro.view(np.uint8)
-            f["host"][o + 8 * (R + 1):o + 8 * (R + 1) + 8 * rr.size] = rr.view(np.uint8)
-            d_rel = f["pin"][o:o + 8 * (R + 1 + rr.size)].to(dev, non_blocking=True).view(torch.int64)
+            o = b.tail
+            b.host[o:o + 8 * (R + 1)] = ro.view(np.uint8)
+            b.host[o + 8 * (R + 1):o + 8 * (R + 1) + 8 * rr.size] = rr.view(np.uint8)
+            d_rel = b.pin[o:o + 8 * (R + 1 + rr.size)].to(dev, non_blocking=True).view(torch.int64)
             rel = (d_rel[R + 1:], d_rel[:R + 1])
-        n_seg = np.diff(seg)
         nsum = ctypes.sizeof(_lib.ListSummaryStruct)
         sums = torch.empty((L, nsum), dtype=torch.uint8, device=dev)
         mws = torch.empty(mt.list_workspace_bytes(R, table.shape[0]), dtype=torch.uint8, device=dev)
-        logits = self._score_requests(R, cap, n, f["slots"], f["offsets"], d_at("users"), stream) \
-            if n else torch.empty(0, dtype=torch.float32, device=dev)
+        logits = b.score()
         per = []
         for j in range(L):
             counts = torch.empty(R, dtype=torch.int32, device=dev)   # this lambda's out_count
-            if n:
-                rows_j, logits_j = self._rank_mmr_requests(
-                    logits, R, cap, n, f["slots"], f["offsets"], d_at("lams") + 4 * R * j,
-                    d_at("topk"), counts.data_ptr(), f["status"], f["ws"], f["nb"], stream)
-            else:
-                rows_j = torch.empty(0, dtype=torch.int64, device=dev)
-                logits_j = torch.empty(0, dtype=torch.float32, device=dev)
+            if not b.n:
                 counts.zero_()
-            mt._list_launch(rows_j, f["offsets"], counts, table, inv, at,
+            rows_j, logits_j = b.rank_mmr(logits, b.ptr("lams") + 4 * R * j, counts.data_ptr())
+            mt._list_launch(rows_j, b.offsets, counts, table, inv, at,
                             logits_j, info, rel, ks, False, mws, out=sums[j])
-            # every candidate is a table row, so the MMR finds min(top_k, n_r) items
-            cnt = np.where(lam32[j] < 1.0, np.minimum(int(top_k), n_seg), n_seg)
-            per.append([None if skip[r] else
-                        (rows_j[int(seg[r]):int(seg[r]) + int(cnt[r])],
-                         logits_j[int(seg[r]):int(seg[r]) + int(cnt[r])]) for r in range(R)])
+            per.append(b.answers(rows_j, logits_j, b.answer_lengths(lam32[j], int(top_k)), skip,
+                                 lambda r: None))
         raw = sums.cpu().numpy()                           # every summary, one copy
         for j in range(L):
             out.append((per[j], mt._list_result(raw[j].tobytes(), ks, None)))
@@ -973,13 +856,10 @@ class RankingPipeline:
         from . import interactions as ia
         lib = _lib.load()
         dev = self.device
-        if self.index._table.shape[0] != self.n_items:
-            raise ValueError(f"recommend_users: the index holds {self.index._table.shape[0]} "
-                             f"rows, item_cat / item_num {self.n_items}")
+        users = self._users_arg("recommend_users", user_rows)
         if store.n_items > self.n_rows:
             raise ValueError(f"recommend_users: the store names {store.n_items} hotel rows, the "
                              f"pipeline holds {self.n_rows}")
-        users = np.asarray(user_rows, dtype=np.int64).reshape(-1)
         R = users.size
         rv = np.asarray(reviewers, dtype=np.int64).reshape(-1)
         if rv.size != R:
@@ -995,15 +875,12 @@ class RankingPipeline:
         # lambda, top_k and the allowed / fallback indices as recommend_many packs them
         city = self._city_arg("recommend_users", city_sets, cities, neighbors_in_city, R, allowed,
                               fallback, neighbors_within)
-        ins, info = self._pack_requests(users, [()] * R, lambda_param, top_k, allowed, None,
-                                        fallback, neighbors_within, city)
-        ins = dict(ins)
-        lam, lam64, topk = info["lam"], info["lam64"], info["topk"]
+        p, reg_rows = self._pack(users, [()] * R, lambda_param, top_k, allowed, None, fallback,
+                                 neighbors_within, city)
         k = self.n_neighbors
         # ---- what the store's host counts say about each request
         n_src, staged, pos_b, neg_b, n_fr, fr_rows, by_b = store.bounds(rv, md)
-        on_host = (n_src > SV_MAX) | (staged > SV_MAX) | (pos_b * k > SV_MAX) | \
-            ((lam64 < 1.0) != (lam < 1.0))
+        on_host = (n_src > SV_MAX) | (staged > SV_MAX) | (pos_b * k > SV_MAX) | p.odd
         if recommended_by:
             on_host |= (n_fr > SV_MAX) | (fr_rows > SV_MAX)
         else:
@@ -1015,100 +892,53 @@ class RankingPipeline:
         np.cumsum(zero(by_b), out=list_off[1:])
         Q, L = int(pos_off[R]), int(list_off[R])
         # the requests' negatives behind the registered and per-call sets, one CSR
-        set_off = ins.get("set_off", np.zeros(1, np.int64))
+        set_off = p.arrays.get("set_off", np.zeros(1, np.int64))
         S0, n0 = set_off.size - 1, int(set_off[-1])
         neg_b = zero(neg_b)
         set_off = np.concatenate([set_off, n0 + np.cumsum(neg_b)])
         NB = int(set_off[-1]) - n0
         e_idx = np.where(neg_b > 0, S0 + np.arange(R), -1).astype(np.int32)
-        if "fallback" in ins and on_host.any():   # (no fallback either: nothing of theirs is scored)
-            ins["fallback"] = np.where(on_host, -1, ins["fallback"]).astype(np.int32)
-        f_len =np.diff(set_off)[ins["fallback"]] * (ins["fallback"] >= 0) if "fallback" in ins else 0
+        # no positives travel (the device finds them); offsets as the store's counts bound them
+        arrays = dict(p.arrays, pos_off=pos_off, set_off=set_off, list_off=list_off, excluded=e_idx,
+                      reviewers=dev_rv, modes=md)
+        del arrays["pos"]
+        f_len = 0
+        if "fallback" in arrays:
+            if on_host.any():   # (no fallback either: nothing of theirs is scored)
+                arrays["fallback"] = np.where(on_host, -1, arrays["fallback"]).astype(np.int32)
+            f_len = np.diff(set_off)[arrays["fallback"]] * (arrays["fallback"] >= 0)
         cap = int(min(SV_MAX, max(1, int((zero(pos_b) * k + f_len).max()))))
-        ins.update(pos_off=pos_off, set_off=set_off, list_off=list_off, excluded=e_idx,
-                   reviewers=dev_rv, modes=md)
-        del ins["pos"]
-        # ---- every host input in one pinned buffer, one non-blocking copy; behind
-        # it the device's mirrors: offsets, candidate status, source counts + status
-        at, total = {}, 0
-        for name, a in ins.items():
-            at[name] = total
-            total += (a.nbytes + 7) & ~7
-        o_off = total
-        o_st = o_off + 8 * (R + 1)
-        o_cnt = o_st + ((4 * R + 7) & ~7)
-        o_sst = o_cnt + 8 * R
-        pin, host = self._pinned(o_sst + ((4 * R + 7) & ~7))
-        for name, a in ins.items():
-            host[at[name]:at[name] + a.nbytes] = a.view(np.uint8)
-        dbuf = pin[:total].to(dev, non_blocking=True)
-        d_at = lambda name: dbuf.data_ptr() + at[name] if name in at else None
-        stream = _lib.stream_ptr(dev)
-        sets = [info["reg_rows"]]
-        if info["n_adhoc"]:
-            o = at["adhoc_rows"]
-            sets.append(dbuf[o:o + 8 * info["n_adhoc"]].view(torch.int64))
-        if NB:
-            sets.append(torch.empty(NB, dtype=torch.int64, device=dev))
-        set_rows = torch.cat(sets) if len(sets) > 1 else sets[0]
+        b = _RequestBatch(self, "recommend_users", R, arrays, sources=True)
+        set_rows = b.set_rows(reg_rows, p.n_adhoc, NB)
         desc, held = store.on(dev)   # the generation this call's kernels read: kept with the answers
         d_pos = torch.empty(Q, dtype=torch.int64, device=dev)
-        # count, status, out_count of the candidate / rank kernels; the source
-        # kernel's counts [2 R] + status, the recommended_by kernel's status
-        words = torch.empty(7 * R, dtype=torch.int32, device=dev)
-        count, status, out_count, s_cnt, s_st, by_st = (words.data_ptr() + 4 * R * j
-                                                        for j in (0, 1, 2, 3, 5, 6))
         _lib.check(lib.dcnr_requests_sources(
-            desc, d_at("reviewers"), d_at("modes"), R, self.n_rows, d_at("pos_off"), Q,
-            d_pos.data_ptr() if Q else None, d_at("set_off") + 8 * S0, n0, n0 + NB,
-            set_rows.data_ptr() if NB else None, s_cnt, s_st, pin.data_ptr() + o_cnt,
-            pin.data_ptr() + o_sst, stream), "dcnr_requests_sources")
-        slots = torch.empty((R, cap), dtype=torch.int64, device=dev)
-        offsets = torch.empty(R + 1, dtype=torch.int64, device=dev)
+            desc, b.ptr("reviewers"), b.ptr("modes"), R, self.n_rows, b.ptr("pos_off"), Q,
+            d_pos.data_ptr() if Q else None, b.ptr("set_off") + 8 * S0, n0, n0 + NB,
+            set_rows.data_ptr() if NB else None, b.src_count, b.src_status, b.pin_src_count,
+            b.pin_src_status, b.stream), "dcnr_requests_sources")
         within = None
-        if "within" in at:   # the requests as the set-scoped search's segments, as recommend_many
-            d_view = lambda name, n_, dt, w_: dbuf[at[name]:at[name] + w_ * n_].view(dt)
-            w_idx = info["within_idx"]
-            within = (set_rows, d_view("set_off", S0 + R + 1, torch.int64, 8),
-                      d_view("pos_off", R + 1, torch.int64, 8), d_view("within", R, torch.int32, 4),
-                      info["within_longest"], bool(((w_idx < 0) & (zero(pos_b) > 0)).any()))
-        self._requests_candidates(
-            d_pos.data_ptr() if Q else None, d_pos, d_at("pos_off"), R, Q,
-            set_rows.data_ptr() if set_rows.numel() else None, set_rows.numel(),
-            d_at("set_off"), S0 + R, d_at("allowed"), d_at("excluded"), d_at("fallback"),
-            int(min_candidates), self.n_rows, cap, slots.data_ptr(), count, status,
-            offsets.data_ptr(), pin.data_ptr() + o_off, pin.data_ptr() + o_st, stream, within=within)
-        # (allocated while the device works, not after the wait)
-        nb = int(lib.dcnr_requests_workspace_size(R, Q, k, cap))
-        ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        if p.within_idx is not None:   # the requests as the set-scoped search's segments
+            within = (p.within_longest, bool(((p.within_idx < 0) & (zero(pos_b) > 0)).any()))
+        b.candidates(d_pos, set_rows, S0 + R, min_candidates, cap, within)
         lists = torch.empty(L, dtype=torch.int32, device=dev)
         by_reviewers = torch.empty(L, dtype=torch.int32, device=dev)
-        torch.cuda.current_stream(dev).synchronize()   # the call's one wait
-        seg = host[o_off:o_st].view(np.int64).copy()
-        n = int(seg[R])
-        st = host[o_st:o_st + 4 * R].view(np.int32).copy()
-        s_counts = host[o_cnt:o_cnt + 8 * R].view(np.int32).reshape(R, 2).copy()
-        sst = host[o_sst:o_sst + 4 * R].view(np.int32)
-        if ((st | sst) & REQ_BAD_DATA).any():
-            raise RuntimeError("recommend_users: the device rejected validated input")
-        on_host = on_host | ((st | sst) & REQ_OVERFLOW).astype(bool)
-        out_rows, out_logits = self._score_and_rank(R, cap, n, slots, offsets, d_at("users"),
-                                                    d_at("lam"), d_at("topk"), out_count, status,
-                                                    ws, nb, stream)
+        b.wait()
+        n, seg = b.n, b.seg.copy()
+        on_host = on_host | (b.st & REQ_OVERFLOW).astype(bool)
+        out_rows, out_logits = b.rank_mmr(b.score(), b.ptr("lam"), b.out_count)
         by_count = torch.empty(n, dtype=torch.int32, device=dev)
         by_offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
         if recommended_by and n:
             _lib.check(lib.dcnr_requests_recommended_by(
-                desc, d_at("reviewers"), R, self.n_rows, out_rows.data_ptr(), n,
-                offsets.data_ptr(), out_count, d_at("list_off"), L,
+                desc, b.ptr("reviewers"), R, self.n_rows, out_rows.data_ptr(), n,
+                b.offsets.data_ptr(), b.out_count, b.ptr("list_off"), L,
                 lists.data_ptr() if L else None, by_count.data_ptr(), by_offsets.data_ptr(),
-                by_reviewers.data_ptr() if L else None, by_st, stream),
+                by_reviewers.data_ptr() if L else None, b.by_status, b.stream),
                 "dcnr_requests_recommended_by")
         elif n:
             by_count.zero_()
-        n_seg = np.diff(seg)
-        # every candidate is a table row, so the MMR finds min(top_k, n_r) items
-        cnt = np.where(lam < 1.0, np.minimum(topk, n_seg), n_seg)
+        cnt = b.answer_lengths(p.lam, p.topk)
         res = UserAnswers()
         res.by_offsets, res.by_reviewers, res.by_count, res.lists = (by_offsets, by_reviewers,
                                                                     by_count, lists)
@@ -1116,20 +946,14 @@ class RankingPipeline:
         res._seg, res._cnt, res._list_off, res._store, res._rv = seg, cnt, list_off, store, rv
         res._held = held
         res._city_held = city[0] if city is not None else None
-        res.n_positives, res.positives_bound = s_counts[:, 0], zero(pos_b)
+        res.n_positives, res.positives_bound = b.src_counts[:, 0].copy(), zero(pos_b)
         res.on_host = on_host
-        for r in range(R):
-            if on_host[r]:   # above the batched kernels' capacity: the one-request path
-                pick = lambda v: None if v is None else v[r]
-                p_r, n_r = store.sources_host(int(rv[r]), int(md[r]))
-                sets = self._city_rows(city, r) if city is not None else dict(
-                    allowed=self._set_arg(pick(allowed)), fallback=self._set_arg(pick(fallback)),
-                    neighbors_within=self._set_arg(pick(neighbors_within)))
-                res.append(self.recommend(int(users[r]), p_r, float(lam64[r]), int(topk[r]),
-                                          excluded=n_r, min_candidates=min_candidates, **sets))
-                continue
-            o = int(seg[r])
-            res.append((out_rows[o:o + int(cnt[r])], out_logits[o:o + int(cnt[r])]))
+
+        def host(r):   # above the batched kernels' capacity: the store's host copies
+            p_r, n_r = store.sources_host(int(rv[r]), int(md[r]))
+            return self._on_host(r, users, p, p_r, n_r, min_candidates,
+                                 (city, allowed, fallback, neighbors_within))
+        res.extend(b.answers(out_rows, out_logits, cnt, on_host, host))
         return res
 
     def _city_arg(self, what, city_sets, cities, in_city, R, allowed, fallback, neighbors_within):
@@ -1154,17 +978,6 @@ class RankingPipeline:
                              f"pipeline holds {self.n_rows}")
         return city_sets.on(self.device), codes, bool(in_city)
 
-    @staticmethod
-    def _city_rows(city, r):
-        """Request r's set arguments for ``recommend()``, from the host columns
-        of the generation the batched call used."""
-        gen, codes, in_city = city
-        rows = gen.host.city_rows(int(codes[r]))
-        out = dict(allowed=rows, fallback=gen.host.popular_rows(int(codes[r])))
-        if in_city:
-            out["neighbors_within"] = rows
-        return out
-
     def _city_join(self, reg_rows, gen):
         """The registered sets' rows with the generation's behind them, on the
         device; joined once per (registered sets, generation)."""
@@ -1177,106 +990,6 @@ class RankingPipeline:
             torch.cuda.current_stream(self.device).synchronize()
             hit = self._city_joined = (reg_rows, gen, joined)
         return hit[2]
-
-    def _pack_requests(self, users, positive_rows, lambda_param, top_k, allowed, excluded,
-                       fallback, neighbors_within=None, city=None):
-        """The host half of ``recommend_many``: validates the rows and returns
-        ([(name, array)] to upload, info).  Without set arguments nothing about
-        sets is built or uploaded (the index arrays go as null: no filters).
-        ``city`` (from ``_city_arg``): the generation's 2C + 1 sets stand behind
-        the registered ones, in front of the per-call ones."""
-        # (few numpy calls: at R = 1 this host work is latency the device waits for.
-        # A row read as unsigned is in range iff it is below the table's length)
-        R = users.size
-        n_users = self.model.user_embedding.weight.shape[0]
-        if users.view(np.uint64).max() >= n_users:
-            raise ValueError(f"recommend_many: user row outside [0, {n_users})")
-        pos = [np.asarray(p.cpu() if torch.is_tensor(p) else p, dtype=np.int64).reshape(-1)
-               for p in positive_rows]
-        lens = [p.size for p in pos]
-        pos_off = np.zeros(R + 1, np.int64)
-        if R == 1:
-            pos_all, pos_off[1] = pos[0], lens[0]
-        else:
-            pos_all = np.concatenate(pos)
-            np.cumsum(lens, out=pos_off[1:])
-        if pos_all.size and pos_all.view(np.uint64).max() >= self.n_rows:
-            raise ValueError(f"recommend_many: positive row outside [0, {self.n_rows})")
-        lam64 = np.full(R, lambda_param, np.float64) if np.isscalar(lambda_param) else \
-            np.array(lambda_param, np.float64).reshape(R)
-        lam = lam64.astype(np.float32)   # what the kernels (and dcnr_mmr_rerank) compute with
-        topk = np.full(R, top_k, np.int32) if np.isscalar(top_k) else \
-            np.array(top_k, np.int32).reshape(R)
-        if (top_k if np.isscalar(top_k) else topk.min()) < 1:
-            raise ValueError("recommend_many: top_k must be at least 1")
-        k = self.n_neighbors
-        ins = [("pos", pos_all), ("pos_off", pos_off), ("users", users), ("lam", lam),
-               ("topk", topk)]
-        info = dict(pos=pos_all, pos_off=pos_off, lam=lam, lam64=lam64, topk=topk, S=0, n_adhoc=0,
-                    reg_rows=self._no_rows)
-        need = np.array(lens, np.int64) * k   # a request's slot: its staged list (+ its fallback set)
-        if allowed is not None or excluded is not None or fallback is not None or \
-                neighbors_within is not None or city is not None:
-            # registered sets by index, per-call ones appended to the CSR
-            reg_rows, reg_off = self._sets
-            n_reg = reg_off.size - 1
-            first_adhoc = n_reg
-            if city is not None:   # the generation's sets between the two
-                gen = city[0]
-                reg_off = np.concatenate([reg_off, reg_off[-1] + gen.host_offsets[1:]])
-                reg_rows = self._city_join(reg_rows, gen)
-                first_adhoc = reg_off.size - 1
-            adhoc: List[np.ndarray] = []
-
-            def set_indices(entries, what):
-                out = np.full(R, -1, np.int32)
-                if entries is None:
-                    return out
-                if len(entries) != R:
-                    raise ValueError(f"recommend_many: {what} needs one entry per request")
-                for r, e in enumerate(entries):
-                    if e is None:
-                        continue
-                    if isinstance(e, (int, np.integer)):
-                        if not 0 <= e < n_reg:
-                            raise ValueError(f"recommend_many: {what}[{r}] = {e} is not a "
-                                             "registered set")
-                        out[r] = e
-                    else:
-                        adhoc.append(_row_set(e, self.n_rows, f"recommend_many: {what}[{r}]"))
-                        out[r] = first_adhoc + len(adhoc) - 1
-                return out
-
-            a_idx = set_indices(allowed, "allowed")
-            e_idx = set_indices(excluded, "excluded")
-            f_idx = set_indices(fallback, "fallback")
-            w_idx = set_indices(neighbors_within, "neighbors_within")
-            if city is not None:
-                codes, C = city[1], city[0].n_cities
-                known = codes >= 0
-                a_idx = (n_reg + np.where(known, codes, 2 * C)).astype(np.int32)
-                f_idx = (n_reg + np.where(known, C + codes, 2 * C)).astype(np.int32)
-                if city[2]:
-                    w_idx = a_idx.copy()
-        else:
-            a_idx = e_idx = f_idx = w_idx = None
-        # lists whose entries are all None name no set: nothing about sets is uploaded
-        if a_idx is not None and (a_idx.max() >= 0 or e_idx.max() >= 0 or f_idx.max() >= 0 or
-                                  w_idx.max() >= 0):
-            adhoc_rows = np.concatenate(adhoc) if adhoc else np.zeros(0, np.int64)
-            set_off = np.concatenate([reg_off, reg_off[-1] + np.cumsum([a.size for a in adhoc],
-                                                                         dtype=np.int64)])
-            set_len = np.append(np.diff(set_off), 0)   # [-1] = 0: no fallback named
-            need = need + set_len[f_idx]
-            ins += [("set_off", set_off), ("adhoc_rows", adhoc_rows), ("allowed", a_idx),
-                    ("excluded", e_idx), ("fallback", f_idx)]
-            info.update(S=set_off.size - 1, n_adhoc=adhoc_rows.size, reg_rows=reg_rows)
-            if w_idx.max() >= 0:   # (else the neighbour step is the parent path, untouched)
-                ins.append(("within", w_idx))
-                info.update(within_idx=w_idx, within_longest=int(set_len[w_idx[w_idx >= 0]].max()),
-                            within_any_global=bool(((w_idx < 0) & (np.array(lens) > 0)).any()))
-        info["cap"] = int(min(SV_MAX, max(1, int(need.max()))))
-        return ins, info
 
     def _pinned(self, nbytes):
         """This thread's pinned staging buffer (tensor, numpy view), grown as
