@@ -920,6 +920,15 @@ dcnr_status city_sets_build(const int32_t* item, const int32_t* city, const doub
                             int32_t* status, int64_t* host_offsets, int32_t* host_status, void* ws,
                             hipStream_t s);
 
+// hotel feature tables from each hotel's first review row (item_features.hip):
+// arguments checked by the caller; counts = {hotels with a row, status}
+size_t item_features_ws_bytes(int64_t n_items);
+dcnr_status item_features_build(const int32_t* item, const int32_t* row, const int32_t* cat,
+                                const double* num, const double* scale, const double* mn, int64_t M,
+                                int64_t n_items, int n_cat, int n_num, int32_t* first_row,
+                                int64_t* item_cat, float* item_num, int32_t* counts,
+                                int32_t* host_counts, void* ws, hipStream_t s);
+
 // ---------------------------------------------------------------------------
 // The stable LSD radix sort of metrics.hip and city_sets.hip: passes of RBITS
 // bits over records T, a 64-bit key or a struct with its own radix_digit (found

@@ -40,6 +40,9 @@ System-Based-on-Friends-Recommendations):
                                      (main.py:204-210) from main_df's rows, on the
                                      device; recommend_many / recommend_users
                                      (cities=...) name a request's city by code
+  ItemFeatures                       each hotel's ranking features from its first
+                                     main_df row (main.py:315, 215-230), on the
+                                     device; RankingPipeline(item_features=...)
   artifacts.save_artifacts /         final_dcn_model.pth + item_embeddings.npy
   artifacts.load_artifacts           (train.py:391-394, main.py:256-270)
   artifacts.save_neighbor_table /    item_neighbors.npy (+ fingerprint): the
@@ -59,6 +62,7 @@ from .data import DeviceLoader  # noqa: F401
 from .serving import RankingPipeline, rerank_with_mmr  # noqa: F401
 from .interactions import InteractionStore  # noqa: F401
 from .cities import CitySets  # noqa: F401
+from .item_features import ItemFeatures  # noqa: F401
 from . import artifacts  # noqa: F401
 
 __version__ = "0.1.0"

@@ -51,6 +51,7 @@ the answers are the same bits.
 from __future__ import annotations
 
 import ctypes
+import functools
 import threading
 from typing import Any, Dict, Iterable, List, Optional, Tuple
 
@@ -132,6 +133,35 @@ def rerank_with_mmr(ranked_items_with_scores: List[Tuple[float, int]], lambda_pa
     return [ids[p] for p in pos]
 
 
+def _one_generation(fn):
+    """A scoring entry point of ``RankingPipeline``: with ``item_features``, the
+    outermost call on a thread takes the newest generation once; everything the
+    call launches, the entry points it calls included, scores from that one.
+    A list it returns keeps the generation (``_features_held``).  A pipeline
+    built from arrays goes straight through."""
+    @functools.wraps(fn)
+    def call(self, *args, **kwargs):
+        if self._features is None or getattr(self._tls, "feat", None) is not None:
+            return fn(self, *args, **kwargs)
+        gen = self._tls.feat = self._features.on(self.device)
+        try:
+            out = fn(self, *args, **kwargs)
+        finally:
+            self._tls.feat = None
+        if type(out) is list:
+            out = Answers(out)
+        if isinstance(out, list):
+            out._features_held = gen
+        return out
+    return call
+
+
+class Answers(list):
+    """What ``recommend_many`` returns from a pipeline with ``item_features``:
+    the list of R (ranked rows, logits) pairs, keeping the feature generation
+    the call scored from."""
+
+
 class UserAnswers(list):
     """What ``RankingPipeline.recommend_users`` returns: a list of R (ranked
     rows, logits) pairs, views into ``rows`` / ``logits`` [n] as
@@ -186,6 +216,18 @@ class RankingPipeline:
                train.py:393-394); default: the model's own item table
     item_cat   int64 [n_items, n_cat]: each hotel's encoded categorical codes
     item_num   fp32 [n_items, n_num]: each hotel's scaled numeric features
+    item_features  a ``dcnr.ItemFeatures`` in place of the two arrays (give the
+               pair or this; anything else is a ValueError, as are widths that
+               do not fit the model): the tables then follow the object's
+               ``append`` / ``remove`` / ``set_values`` / ``set_scaler``.  Every
+               scoring entry point (``ranking_batch``, ``score``, ``recommend``,
+               ``recommend_many``, ``recommend_users``, ``lambda_sweep``) takes
+               ``item_features.on(device)`` once when it is entered and scores
+               every launch of the call from that one generation -- the
+               requests a batched call answers through ``recommend()``
+               included -- and the batched calls' answers keep it alive.
+               ``item_cat`` / ``item_num`` read the newest generation.
+               Serialise the object's changes against requests
     neighbor_table  False: every request scans the index.  True: the item
                neighbour table is built here with k = n_neighbors; an int:
                with that k (>= n_neighbors; /similar_items reads it up to
@@ -194,8 +236,8 @@ class RankingPipeline:
                ValueError for a table of another shape or kt < n_neighbors.
     """
 
-    def __init__(self, model, item_cat, item_num, item_embeddings=None, n_neighbors: int = 11,
-                 neighbor_table=False):
+    def __init__(self, model, item_cat=None, item_num=None, item_embeddings=None,
+                 n_neighbors: int = 11, neighbor_table=False, item_features=None):
         dev = model.final_linear.weight.device
         if dev.type != 'cuda':
             raise RuntimeError("RankingPipeline runs on the HIP device only")
@@ -204,12 +246,28 @@ class RankingPipeline:
         emb = model.item_embedding.weight.detach() if item_embeddings is None else item_embeddings
         self.index = NearestNeighbors(n_neighbors=n_neighbors, metric='cosine',
                                       algorithm='brute', device=dev).fit(emb)
-        self.item_cat = torch.as_tensor(item_cat).to(dev, torch.int64).contiguous()
-        self.item_num = torch.as_tensor(item_num).to(dev, torch.float32).contiguous()
-        self.n_items = self.item_cat.shape[0]
+        self._tls = threading.local()
+        self._features = item_features
+        if item_features is not None:
+            if item_cat is not None or item_num is not None:
+                raise ValueError("RankingPipeline: give item_cat and item_num, or item_features")
+            dims = getattr(model, "_dims", None)
+            want = (len(model.cat_embeddings), item_features.n_num if dims is None else dims["n_num"])
+            if (item_features.n_cat, item_features.n_num) != want:
+                raise ValueError(f"RankingPipeline: item_features holds {item_features.n_cat} "
+                                 f"categorical and {item_features.n_num} numeric columns, the model "
+                                 f"takes {want[0]} and {want[1]}")
+            self._tables = None
+            self.n_items = item_features.n_items
+        else:
+            if item_cat is None or item_num is None:
+                raise ValueError("RankingPipeline: give item_cat and item_num, or item_features")
+            self._tables = (torch.as_tensor(item_cat).to(dev, torch.int64).contiguous(),
+                            torch.as_tensor(item_num).to(dev, torch.float32).contiguous())
+            self.n_items = self._tables[0].shape[0]
+            if self._tables[1].shape[0] != self.n_items:
+                raise ValueError("item_cat and item_num must have one row per item")
         self.n_neighbors = n_neighbors
-        if self.item_num.shape[0] != self.n_items:
-            raise ValueError("item_cat and item_num must have one row per item")
         # hotel rows every table holds (index, item_cat, item_num): what a
         # batched request may name
         self.n_rows = min(self.n_items, self.index._table.shape[0])
@@ -219,8 +277,19 @@ class RankingPipeline:
         self._sets = (self._no_rows, np.zeros(1, np.int64))
         self._sets_lock = threading.Lock()
         self._city_joined = None   # (registered rows, CitySets generation, the two joined)
-        self._tls = threading.local()
         self._nbr = self._neighbor_table(neighbor_table)
+
+    def _feature_tables(self):
+        """(item_cat, item_num) this call scores from: the arrays the pipeline
+        was built from, or the ``ItemFeatures`` generation the entry point
+        took (outside one: the newest)."""
+        if self._tables is not None:
+            return self._tables
+        gen = getattr(self._tls, "feat", None) or self._features.on(self.device)
+        return gen.item_cat, gen.item_num
+
+    item_cat = property(lambda self: self._feature_tables()[0])
+    item_num = property(lambda self: self._feature_tables()[1])
 
     def _neighbor_table(self, arg):
         """The constructor's ``neighbor_table`` as int32 [n_items, kt] on the device, or None."""
@@ -332,16 +401,18 @@ class RankingPipeline:
         """The model inputs (user ids, item ids, cat, num) of n rows to fill,
         and the arguments both ranking-batch calls end with, item_cat to num
         (a pointer is null where the model has no such column)."""
-        K, F = self.item_cat.shape[1], self.item_num.shape[1]
+        item_cat, item_num = self._feature_tables()
+        K, F = item_cat.shape[1], item_num.shape[1]
         u = torch.empty(n, dtype=torch.int64, device=self.device)
         i = torch.empty(n, dtype=torch.int64, device=self.device)
         c = torch.empty((n, K), dtype=torch.int64, device=self.device)
         x = torch.empty((n, F), dtype=torch.float32, device=self.device)
-        return (u, i, c, x), (self.item_cat.data_ptr() if K else None, K,
-                              self.item_num.data_ptr() if F else None, F, self.n_items,
+        return (u, i, c, x), (item_cat.data_ptr() if K else None, K,
+                              item_num.data_ptr() if F else None, F, self.n_items,
                               u.data_ptr(), i.data_ptr(), c.data_ptr() if K else None,
                               x.data_ptr() if F else None)
 
+    @_one_generation
     def ranking_batch(self, user_row: int, item_rows: torch.Tensor):
         """preprocess_for_ranking (main.py:215-230) on the device."""
         lib = _lib.load()
@@ -352,6 +423,7 @@ class RankingPipeline:
                                           _lib.stream_ptr(self.device)), "dcnr_ranking_batch")
         return batch
 
+    @_one_generation
     @torch.no_grad()
     def score(self, user_row: int, item_rows: torch.Tensor) -> torch.Tensor:
         """Eval-mode DCN-R logits of (user, hotel) pairs (main.py:319-322)."""
@@ -374,6 +446,7 @@ class RankingPipeline:
                                               _lib.stream_ptr(self.device)), "dcnr_rank_by_score")
         return order
 
+    @_one_generation
     @torch.no_grad()
     def recommend(self, user_row: int, positive_rows, lambda_param: float = 1.0,
                   top_k: int = 20, allowed: Optional[Iterable[int]] = None,
@@ -546,6 +619,7 @@ class RankingPipeline:
                 self._sets = (rows, np.concatenate([off, off[-1] + np.cumsum(lens)]))
         return list(range(first, first + len(new)))
 
+    @_one_generation
     @torch.no_grad()
     def recommend_many(self, user_rows, positive_rows, lambda_param=1.0, top_k=20,
                        allowed=None, excluded=None, fallback=None, min_candidates: int = 20,
@@ -724,6 +798,7 @@ class RankingPipeline:
                                    at=at, scores=scores, info=info, relevant=rel, ks=ks,
                                    per_list=per_list)
 
+    @_one_generation
     @torch.no_grad()
     def lambda_sweep(self, user_rows, positive_rows, lambdas, top_k: int = 20, allowed=None,
                      excluded=None, fallback=None, min_candidates: int = 20, relevant=None,
@@ -817,6 +892,7 @@ class RankingPipeline:
         return out
 
     # --------------------------------------------- a batch of requests by user
+    @_one_generation
     @torch.no_grad()
     def recommend_users(self, store, user_rows, reviewers, modes, lambda_param=1.0, top_k=20,
                         allowed=None, fallback=None, min_candidates: int = 20,

@@ -1050,6 +1050,56 @@ dcnr_status dcnr_city_sets_build(const int32_t* review_item, const int32_t* revi
                                  int64_t* host_offsets, int32_t* host_status, void* ws, size_t ws_bytes,
                                  dcnr_stream_t stream);
 
+/* Every hotel's ranking features from its first main_df row (main.py:315's
+ * isin + drop_duplicates(subset=['item_id']), then preprocess_for_ranking,
+ * main.py:215-230): what dcnr.ItemFeatures runs per device when it is uploaded
+ * and after every append, remove, set_values and set_scaler.  One entry per
+ * main_df row, in device memory and in ascending main_df row order:
+ * review_item [M] the hotel row, in [0, n_items); review_row [M] the row's
+ * main_df number, strictly ascending and >= 0 (NULL: the position);
+ * review_cat [M][n_cat] the caller's encoded codes; review_num [M][n_num] the
+ * raw column values (anything a double holds).  scaler_scale, scaler_min
+ * [n_num]: MinMaxScaler's scale_ and min_, in device memory.
+ * Written, for every hotel h (all of every table, whatever the input):
+ *   first_row [n_items]        the main_df number of h's first row, -1: none
+ *   item_cat [n_items][n_cat]  that row's codes as int64; zeros without a row
+ *   item_num [n_items][n_num]  float32(x * scale_ + min_) of that row's values:
+ *                              the product and the sum each rounded to float64
+ *                              (never an fma), then to float32 to nearest even,
+ *                              as MinMaxScaler.transform followed by
+ *                              torch.tensor(dtype=float32) gives, bit for bit;
+ *                              NaN, +-inf and -0.0 as numpy passes them; zeros
+ *                              without a row
+ *   counts [2]                 {the hotels with a row, a status word}: the
+ *                              status is 0 or DCNR_REQ_BAD_DATA for a
+ *                              review_item outside [0, n_items) or a review_row
+ *                              that is negative or does not ascend.  Such a row
+ *                              names no hotel and nothing is read or written
+ *                              outside the buffers; the tables are then those
+ *                              of the other rows.  Also stored to host_counts
+ *                              [2] (pinned, device-visible host memory, or
+ *                              NULL) with system-scope stores.
+ * The first row is the smallest position per hotel: an integer atomicMin into
+ * an int32 [n_items] scratch, skipped where a plain load shows the slot already
+ * lower; then one hotel per lane group gathers its row, and the hotels with a
+ * row are counted per workgroup and summed by one.  Every word is an integer
+ * or written by one lane: the same bytes on every run.  Workspace:
+ * dcnr_item_features_workspace_size bytes, 4 n_items + 8 KiB (+ 512 at most); 0
+ * for arguments the call rejects.  DCNR_BAD_ARG before any launch: a needed null pointer (a
+ * column or table of width 0 may be NULL, and with M = 0 every column and the
+ * workspace) or a negative argument; DCNR_UNSUPPORTED_SHAPE: n_cat or n_num
+ * above 64, n_items > 2^29 or M >= 2^31 - 1; DCNR_WORKSPACE_TOO_SMALL.  With
+ * M = 0 every first_row is -1 and the tables are zeros.  Stream-ordered; no
+ * allocation, no host synchronisation. */
+size_t dcnr_item_features_workspace_size(int64_t M, int64_t n_items, int32_t n_cat, int32_t n_num);
+dcnr_status dcnr_item_features_build(const int32_t* review_item, const int32_t* review_row,
+                                     const int32_t* review_cat, const double* review_num,
+                                     const double* scaler_scale, const double* scaler_min, int64_t M,
+                                     int64_t n_items, int32_t n_cat, int32_t n_num, int32_t* first_row,
+                                     int64_t* item_cat, float* item_num, int32_t* counts,
+                                     int32_t* host_counts, void* ws, size_t ws_bytes,
+                                     dcnr_stream_t stream);
+
 /* The deep tower's Linear layer as a standalone bf16 call (nn.Linear forward,
  * train.py:143,105,109): C[M,N] = X[M,K] . W[N,K]^T + bias, X/W bf16
  * row-major (K, ldx, ldw multiples of 8), C bf16 (out_f32 = 0) or fp32.
