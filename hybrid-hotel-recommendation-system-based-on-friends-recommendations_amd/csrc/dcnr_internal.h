@@ -929,6 +929,10 @@ dcnr_status item_features_build(const int32_t* item, const int32_t* row, const i
                                 int64_t* item_cat, float* item_num, int32_t* counts,
                                 int32_t* host_counts, void* ws, hipStream_t s);
 
+// prepare_data on the device (train_table.hip): arguments checked by the caller, M > 0
+size_t train_table_ws_bytes(int64_t M, int n_num);
+dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, hipStream_t s);
+
 // ---------------------------------------------------------------------------
 // The stable LSD radix sort of metrics.hip and city_sets.hip: passes of RBITS
 // bits over records T, a 64-bit key or a struct with its own radix_digit (found

@@ -43,6 +43,11 @@ System-Based-on-Friends-Recommendations):
   ItemFeatures                       each hotel's ranking features from its first
                                      main_df row (main.py:315, 215-230), on the
                                      device; RankingPipeline(item_features=...)
+  prepare_data, PreparedData         the driver's filter and derived columns and
+                                     prepare_data (train.py:280-287, 36-87) on the
+                                     device: raw review columns to the training
+                                     tensors, id maps, encoders and scaler;
+                                     prepare_data_host: the numpy yardstick
   artifacts.save_artifacts /         final_dcn_model.pth + item_embeddings.npy
   artifacts.load_artifacts           (train.py:391-394, main.py:256-270)
   artifacts.save_neighbor_table /    item_neighbors.npy (+ fingerprint): the
@@ -63,6 +68,7 @@ from .serving import RankingPipeline, rerank_with_mmr  # noqa: F401
 from .interactions import InteractionStore  # noqa: F401
 from .cities import CitySets  # noqa: F401
 from .item_features import ItemFeatures  # noqa: F401
+from .prepare import PreparedData, category_keys, prepare_data, prepare_data_host  # noqa: F401
 from . import artifacts  # noqa: F401
 
 __version__ = "0.1.0"

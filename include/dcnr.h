@@ -1100,6 +1100,75 @@ dcnr_status dcnr_item_features_build(const int32_t* review_item, const int32_t* 
                                      int32_t* host_counts, void* ws, size_t ws_bytes,
                                      dcnr_stream_t stream);
 
+/* prepare_data on the device: the driver's noise filter and derived columns
+ * (train.py:280-287) and prepare_data (train.py:36-65) up to the split, from
+ * the raw review columns to the reference's training tensors and preprocessing
+ * artifacts, bit for bit (DESIGN.md section 9 has the contract in full; the
+ * split itself is a host permutation and two dcnr_gather_rows, dcnr/prepare.py).
+ * Inputs, device memory, M rows in main_df order:
+ *   user, item [M]        raw ids, any int64
+ *   target [M]            uint8, 0 or not 0 (y is 0.0f or 1.0f)
+ *   cat_key [M][n_cat]    int64 keys whose numeric order is the categories'
+ *                         sorted order; any negative key: the value is missing
+ *   raw [M][n_raw]        float64, anything a double holds
+ *   filter_col, filter_lo, filter_hi   a row passes when raw[filter_col] >=
+ *                         filter_hi or <= filter_lo (NaN fails); -1: no filter
+ *   derived [n_derived][3]  HOST memory: {op, i, j} over raw columns, appended
+ *                         behind the raw ones in this order.  DCNR_DERIVED_RATIO:
+ *                         raw[i] / raw[j], +-inf and NaN become 0;
+ *                         DCNR_DERIVED_DIFF: raw[i] - raw[j], NaN stays
+ * n_num = n_raw + n_derived.  Over the rows that pass the filter: a numeric
+ * NaN becomes its column's median over the non-NaN values of those rows (even
+ * count: (v[k/2-1] + v[k/2]) / 2, one add, one halving; all NaN: NaN); rows
+ * with a missing category are then dropped.  Over the n surviving rows: user
+ * and item codes by first appearance, category codes by rank among the sorted
+ * present keys, MinMaxScaler().fit (scale_ = 1 / range, 1 where range < 10
+ * DBL_EPSILON; min_ = 0 - data_min_ * scale_) and float32(x * scale_ + min_),
+ * the product and the sum each rounded to float64 (never an fma).
+ * Outputs, device memory, every row-shaped one with room for M rows:
+ *   row [n]               int32: the surviving rows' input positions, ascending
+ *   collab [n][2], cat [n][n_cat] (int64), num [n][n_num], y [n] (float32)
+ *   user_ids, item_ids [M]  the raw id of every code (n_users, n_items used)
+ *   cat_keys [n_cat][M]   per column the sorted present keys
+ *   stats [5][n_num]      float64: median, data_min_, data_max_, scale_, min_;
+ *                         also stored to host_stats (pinned, or NULL)
+ *   counts [DCNR_TRAIN_TABLE_COUNTS + n_cat]  int32: {n, n_users, n_items,
+ *                         rows that passed the filter, status}, then each
+ *                         category column's cardinality; also stored to
+ *                         host_counts (pinned, or NULL) with system-scope
+ *                         stores.  The status is 0, or DCNR_REQ_BAD_DATA when a
+ *                         surviving, filled value is +-inf (where scikit-learn
+ *                         raises); the other outputs are then unspecified, and
+ *                         nothing is read or written outside the buffers.
+ * The sign of a zero median, data_min_ or data_max_ is unspecified.  Every
+ * atomic is an integer one and no atomic decides a position: the same bytes on
+ * every run.  Workspace: dcnr_train_table_workspace_size bytes, about
+ * M (8 n_num + 41) (0 for arguments the call rejects).  DCNR_BAD_ARG before
+ * any launch: a null args, a needed null pointer (a column of width 0 may be
+ * NULL, and with M = 0 everything but counts), a negative size, a derived op
+ * that is neither, a derived or filter column outside [0, n_raw);
+ * DCNR_UNSUPPORTED_SHAPE: M >= 2^31 - 1, n_cat > 64, n_raw + n_derived > 64;
+ * DCNR_WORKSPACE_TOO_SMALL.  With M = 0 no kernel is launched: counts is
+ * zeroed by a stream-ordered memset and host_counts by the calling thread.
+ * Stream-ordered; no allocation, no host synchronisation. */
+#define DCNR_DERIVED_RATIO 0
+#define DCNR_DERIVED_DIFF 1
+#define DCNR_TRAIN_TABLE_COUNTS 5
+typedef struct {
+  const int64_t* user; const int64_t* item; const uint8_t* target;
+  const int64_t* cat_key; const double* raw;
+  int64_t M; int32_t n_cat, n_raw;
+  int32_t filter_col; double filter_lo, filter_hi;
+  int32_t n_derived; const int32_t* derived;
+  int32_t* row; int64_t* collab; int64_t* cat; float* num; float* y;
+  int64_t* user_ids; int64_t* item_ids; int64_t* cat_keys;
+  double* stats; double* host_stats;
+  int32_t* counts; int32_t* host_counts;
+} dcnr_train_table_args;
+size_t dcnr_train_table_workspace_size(int64_t M, int32_t n_cat, int32_t n_raw, int32_t n_derived);
+dcnr_status dcnr_train_table_build(const dcnr_train_table_args* args, void* ws, size_t ws_bytes,
+                                   dcnr_stream_t stream);
+
 /* The deep tower's Linear layer as a standalone bf16 call (nn.Linear forward,
  * train.py:143,105,109): C[M,N] = X[M,K] . W[N,K]^T + bias, X/W bf16
  * row-major (K, ldx, ldw multiples of 8), C bf16 (out_f32 = 0) or fp32.
