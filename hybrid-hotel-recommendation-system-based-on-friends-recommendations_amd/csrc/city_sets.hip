@@ -381,15 +381,15 @@ dcnr_status sort_passes(T*& src, T*& dst, int64_t M, const Plan& p, int npass, c
 
 }  // namespace
 
-size_t city_sets_ws_bytes(int64_t M, int64_t n_items, int n_cities, int top) {
+static size_t city_sets_ws_bytes(int64_t M, int64_t n_items, int n_cities, int top) {
   return carve(make_plan(M, n_items, n_cities), M, n_cities, top, nullptr).total;
 }
 
-dcnr_status city_sets_build(const int32_t* item, const int32_t* city, const double* key,
-                            const int32_t* row, int64_t M, int64_t n_items, int C, int top,
-                            int64_t* set_offsets, int64_t* set_rows, int64_t cap, int32_t* top_rows,
-                            int32_t* status, int64_t* host_offsets, int32_t* host_status, void* ws,
-                            hipStream_t s) {
+static dcnr_status city_sets_build(const int32_t* item, const int32_t* city, const double* key,
+                                   const int32_t* row, int64_t M, int64_t n_items, int C, int top,
+                                   int64_t* set_offsets, int64_t* set_rows, int64_t cap, int32_t* top_rows,
+                                   int32_t* status, int64_t* host_offsets, int32_t* host_status, void* ws,
+                                   hipStream_t s) {
   if (M == 0) {
     const int blocks = (int)std::min<int64_t>(CS_MAXB, cdiv(std::max<int64_t>(2 * (int64_t)C + 2,
                                                                               (int64_t)C * top), CS_NT));
@@ -402,14 +402,14 @@ dcnr_status city_sets_build(const int32_t* item, const int32_t* city, const doub
   const Ws w = carve(p, M, C, top, ws);
   uint32_t *cstart = w.cwords, *cend = w.cwords + C, *cfirst = w.cwords + 2 * (size_t)C,
            *clast = w.cwords + 3 * (size_t)C;
-  TRY_ST(fill_zero(w.cwords, (size_t)C * 16, s));
-  TRY_ST(fill_zero(status, 4, s));
+  TRY(fill_zero(w.cwords, (size_t)C * 16, s));
+  TRY(fill_zero(status, 4, s));
   // ---- top_rows and the popular sets
   hipLaunchKernelGGL(cs_records_kernel, dim3(p.blocks), dim3(CS_NT), 0, s, item, city, key, row, M, n_items,
                      C, w.ra, status);
   DCNR_LAUNCH_CHECK();
   Rec *src = w.ra, *dst = w.rb;
-  TRY_ST(sort_passes(src, dst, M, p, p.pass_a, w, s));
+  TRY(sort_passes(src, dst, M, p, p.pass_a, w, s));
   hipLaunchKernelGGL(cs_bounds_kernel, dim3(p.blocks), dim3(CS_NT), 0, s, (const Rec*)src, M, cstart, cend);
   DCNR_LAUNCH_CHECK();
   hipLaunchKernelGGL(cs_popular_kernel, dim3(C), dim3(CS_TOP_MAX), 0, s, (const Rec*)src,
@@ -421,7 +421,7 @@ dcnr_status city_sets_build(const int32_t* item, const int32_t* city, const doub
   hipLaunchKernelGGL(cs_keys_kernel, dim3(p.blocks), dim3(CS_NT), 0, s, item, city, M, n_items, C, p.ibits,
                      ka);
   DCNR_LAUNCH_CHECK();
-  TRY_ST(sort_passes(ka, kb, M, p, p.pass_b, w, s));
+  TRY(sort_passes(ka, kb, M, p, p.pass_b, w, s));
   hipLaunchKernelGGL(cs_head_count_kernel, dim3((unsigned)p.tiles), dim3(CS_NT), 0, s, (const uint64_t*)ka,
                      M, w.tilebase);
   DCNR_LAUNCH_CHECK();
@@ -441,3 +441,53 @@ dcnr_status city_sets_build(const int32_t* item, const int32_t* city, const doub
 }
 
 }  // namespace dcnr
+
+using namespace dcnr;
+
+extern "C" {
+
+static dcnr_status city_sets_shape(int64_t M, int64_t n_items, int32_t n_cities, int32_t top) {
+  if (M < 0 || n_items < 0 || n_cities < 0 || top < 0) return DCNR_BAD_ARG;
+  if (top < 1 || top > CS_TOP_MAX || n_cities < 1 || n_cities > 65536 || n_items > ((int64_t)1 << 29) ||
+      M >= 2147483647ll)
+    return DCNR_UNSUPPORTED_SHAPE;
+  return DCNR_OK;
+}
+
+size_t dcnr_city_sets_workspace_size(int64_t M, int64_t n_items, int32_t n_cities, int32_t top) {
+  if (city_sets_shape(M, n_items, n_cities, top) != DCNR_OK) return 0;
+  return city_sets_ws_bytes(M, n_items, n_cities, top) + 256;
+}
+
+dcnr_status dcnr_city_sets_build(const int32_t* review_item, const int32_t* review_city,
+                                 const double* review_key, const int32_t* review_row, int64_t M,
+                                 int64_t n_items, int32_t n_cities, int32_t top, int64_t* set_offsets,
+                                 int64_t* set_rows, int64_t cap, int32_t* top_rows, int32_t* status,
+                                 int64_t* host_offsets, int32_t* host_status, void* ws, size_t ws_bytes,
+                                 dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const dcnr_status shape = city_sets_shape(M, n_items, n_cities, top);
+  if (shape == DCNR_BAD_ARG || cap < 0 || !set_offsets || !top_rows || !status ||
+      (cap > 0 && !set_rows) || (M > 0 && (!review_item || !review_city || !review_key || !ws))) {
+    set_error("dcnr_city_sets_build: bad argument (M=%lld, n_items=%lld, cities=%d, top=%d, cap=%lld)",
+              (long long)M, (long long)n_items, n_cities, top, (long long)cap);
+    return DCNR_BAD_ARG;
+  }
+  if (shape != DCNR_OK) {
+    set_error("dcnr_city_sets_build: unsupported shape (M=%lld, n_items=%lld, cities=%d, top=%d)",
+              (long long)M, (long long)n_items, n_cities, top);
+    return shape;
+  }
+  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  const size_t need = M > 0 ? city_sets_ws_bytes(M, n_items, n_cities, top) : 0;
+  if (M > 0 && ws_bytes < need + ((char*)base - (char*)ws)) {
+    set_error("dcnr_city_sets_build: workspace too small: %zu < %zu", ws_bytes, need + 256);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  TRYP(DCNR_K_SERVE, s, city_sets_build(review_item, review_city, review_key, review_row, M, n_items,
+                                        n_cities, top, set_offsets, set_rows, cap, top_rows, status,
+                                        host_offsets, host_status, base, s));
+  return DCNR_OK;
+}
+
+}  // extern "C"

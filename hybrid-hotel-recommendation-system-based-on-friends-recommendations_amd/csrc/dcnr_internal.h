@@ -1,5 +1,8 @@
 // Internal declarations shared by the libdcnr HIP translation units.
 // gfx950 (MI355X / CDNA4) only: 64-lane waves, MFMA, 160 KiB LDS per CU.
+// Only what two files share is declared here: a subsystem's C entry points
+// stand at the end of its own .hip file, beside the kernels they launch, and
+// its launchers are local to that file; step.hip holds the train / eval step.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -27,6 +30,16 @@ void set_error(const char* fmt, ...);
 // device: thread-safe and per device (the serving path runs the eval forward
 // from several host threads; one process may drive several devices).
 dcnr_status set_max_dyn_lds(const void* kernel, size_t bytes);
+// Times what is enqueued on `s` during its lifetime when profiling is on
+// (dcnr_profile_enable; runtime.hip), attributed to kernel class `cat`.
+struct ProfScope {
+  int cat; hipStream_t s; double bytes; hipEvent_t a = nullptr;
+  ProfScope(int c, hipStream_t st, double nbytes = 0.0);
+  ~ProfScope();
+};
+// false while every launch is timed alone on the caller's stream (profile
+// mode 1): the backward then keeps its weight gradients off the side stream
+bool prof_side_stream_ok();
 #define DCNR_HIP(call)                                                              \
   do {                                                                              \
     hipError_t e_ = (call);                                                         \
@@ -35,10 +48,24 @@ dcnr_status set_max_dyn_lds(const void* kernel, size_t bytes);
       return DCNR_HIP_ERROR;                                                        \
     }                                                                               \
   } while (0)
-#define TRY_ST(x)                         \
-  do {                                    \
-    dcnr_status st_ = (x);                \
-    if (st_ != DCNR_OK) return st_;       \
+#define TRY(x)                       \
+  do {                               \
+    dcnr_status st_ = (x);           \
+    if (st_ != DCNR_OK) return st_;  \
+  } while (0)
+// TRY with the launch timed on `stream` and attributed to a kernel class
+#define TRYP(cat, stream, x)            \
+  do {                                  \
+    ::dcnr::ProfScope ps_(cat, stream); \
+    dcnr_status st_ = (x);              \
+    if (st_ != DCNR_OK) return st_;     \
+  } while (0)
+// ... and its algorithmic bytes
+#define TRYB(cat, stream, nbytes, x)                      \
+  do {                                                    \
+    ::dcnr::ProfScope ps_(cat, stream, (double)(nbytes)); \
+    dcnr_status st_ = (x);                                \
+    if (st_ != DCNR_OK) return st_;                       \
   } while (0)
 
 #define DCNR_LAUNCH_CHECK()                                                         \
@@ -653,13 +680,6 @@ struct TouchedArgs {
 };
 dcnr_status emb_touched_rows(const TouchedArgs& a, const EmbSortBufs& sb, int64_t B, int64_t* out,
                              int64_t* table_counts, int64_t* owner_counts, hipStream_t s);
-// the data-parallel sparse exchange's device halves (embed_bwd.hip): pack the
-// touched rows (+ their offsets) into the all_to_all send buffer; add what
-// each source rank sent into the owner's shard, sources in order
-dcnr_status sparse_pack(const float* grad, const int64_t* offs, int64_t ld, const int64_t* tcnt,
-                        int n_tables, int width, int64_t* out_off, float* out_rows, hipStream_t s);
-dcnr_status sparse_accumulate(float* shard, int64_t lo, int64_t elems, int width, const int64_t* offs,
-                              const float* rows, const int64_t* counts, int n_sources, hipStream_t s);
 // grad row r of table t = sum over its samples of dx0_deep[b][off_t:off_t+w_t]
 // + sum_k (sum over its samples of coef[b][k]) V[k][off_t:off_t+w_t]
 dcnr_status emb_segment_sum(const EmbBwdDesc& e, const EmbSortBufs& sb, int64_t B,
@@ -767,171 +787,10 @@ size_t bce_ws_bytes();
 dcnr_status bce(const float* z, const float* y, int64_t B, float* loss, float* dz, float scale,
                 double* part, hipStream_t s);
 
-// validation metrics (metrics.hip): logloss, exact AUC, RMSE over n logits
-size_t metrics_ws_bytes(int64_t n);
-dcnr_status eval_metrics(const float* z, const float* y, int64_t n, dcnr_metrics* out, void* ws,
-                         hipStream_t s);
-// per-group ranking metrics (metrics.hip): arguments checked by the caller
-int group_metrics_passes(int64_t n_groups);
-size_t group_metrics_ws_bytes(int64_t n, int64_t n_groups);
-dcnr_status eval_group_metrics(const float* z, const float* y, const int64_t* g, int64_t n,
-                               int64_t n_groups, const int32_t* ks_host, int32_t n_k,
-                               const double* discount, const double* ideal, dcnr_group_summary* out,
-                               dcnr_group_record* per_group, void* ws, hipStream_t s);
-size_t list_metrics_ws_bytes(int64_t R, int64_t n_items);
-dcnr_status eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* offsets,
-                              const int32_t* counts, int64_t R, int32_t at, const float* table,
-                              const float* inv_norms, int32_t d, int64_t n_items, const float* scores,
-                              const double* info, const int64_t* rel_rows, int64_t n_rel_rows,
-                              const int64_t* rel_offsets, const int32_t* ks_host, int32_t n_k,
-                              const double* discount, const double* ideal, dcnr_list_summary* out,
-                              dcnr_list_record* per_list, void* ws, hipStream_t s);
-
-// optimizer
-dcnr_status adam(int n, float* const* p, const float* const* g, float* const* m, float* const* v,
-                 const int64_t* numel, float lr, float b1, float b2, float eps, float wd,
-                 int64_t step, int decoupled, hipStream_t s,
-                 const uint8_t* const* row_map = nullptr, const int32_t* row_width = nullptr);
-
-// knn
-dcnr_status row_inv_norms(const float* t, int64_t N, int d, float* out, hipStream_t s);
-size_t topk_ws(int64_t N, int64_t Q, int k);
-// k best of lists k-lists [lists][Q][k] by (dist, row as unsigned)
-dcnr_status topk_merge(const float* dist, const int64_t* idx, int lists, int64_t Q, int k,
-                       int64_t* out_idx, float* out_dist, hipStream_t s);
-// tb: the bf16 copy from cosine_pack_rows, or nullptr (scan v4 then rounds
-// the fp32 rows itself).  allow_v3 = false keeps the fp32-MFMA scan out: every
-// remaining path shares one distance arithmetic, so a query's answer is then
-// the same bits at every batch width
-dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_t N, int d,
-                        const float* q, int64_t Q, int k, int64_t* idx, float* dist, void* ws,
-                        size_t ws_bytes, hipStream_t s, bool allow_v3 = true);
-// the set-scoped search (dcnr_cosine_topk_within; arguments already judged):
-// 0 from the size query for a shape the search does not take
-size_t cosine_topk_within_ws(int64_t Q, int k, int d, int64_t max_set_rows);
-dcnr_status cosine_topk_within(const float* t, const float* inv, int64_t N, int d, const float* q, int64_t Q,
-                               const int64_t* excl, const int64_t* seg_off, int64_t G, const int* seg_set,
-                               const int64_t* set_rows, int64_t n_set_rows, const int64_t* set_off, int S,
-                               int64_t max_set_rows, int k, int64_t ld, int64_t* idx, float* dist,
-                               int* seg_status, void* ws, size_t ws_bytes, hipStream_t s);
-// rows [row_lo, row_hi) of the item neighbour table: out_idx [rows][k] int32
-// (and out_dist, or null) = cosine_topk of each table row as a single query
-size_t neighbor_table_ws(int64_t N, int k);
-dcnr_status neighbor_table(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
-                           int64_t row_lo, int64_t row_hi, int32_t* out_idx, float* out_dist, void* ws,
-                           size_t ws_bytes, hipStream_t s);
-// the table updated in place after the m rows `changed` (host, ascending,
-// distinct) got new vectors: the filter and the merge (counts: changed,
-// affected, merged, to re-search; research: those rows), and the build over a
-// device list of rows; one workspace size serves both
-size_t neighbor_table_update_ws(int64_t N, int d, int k, int64_t m);
-int neighbor_table_update_max_m();
-dcnr_status neighbor_table_update(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
-                                  const int32_t* changed, int64_t m, int32_t* nbr, int32_t* counts,
-                                  int32_t* host_counts, int32_t* research, void* ws, size_t ws_bytes,
-                                  hipStream_t s);
-dcnr_status neighbor_table_rows(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
-                                const int32_t* rows, int64_t n, int32_t* nbr, void* ws, size_t ws_bytes,
-                                hipStream_t s);
-dcnr_status cosine_pack_rows(const float* t, const float* inv, int64_t N, int d, bf16* out, hipStream_t s);
-
-// serving (serving.hip)
-dcnr_status gather_rows(const int64_t* idx, int64_t n, int64_t n_src, int n_arrays,
-                        const void* const* src, void* const* dst, const int64_t* row_bytes,
-                        hipStream_t s);
-// neighbours from idx [Q][k], or (nbr != null) from the item neighbour table
-// nbr [n_items][kt], kt >= k: out_count -1 where a positive or a table entry
-// lies outside [0, n_items)
-dcnr_status candidate_union(const int64_t* pos, int64_t Q, const int64_t* idx, int k,
-                            const int32_t* nbr, int kt, int64_t n_items, int64_t* out,
-                            int32_t* out_count, hipStream_t s);
-dcnr_status ranking_batch(const int64_t* rows, int64_t n, int64_t user_row, const int64_t* item_cat,
-                          int K, const float* item_num, int F, int64_t n_items, int64_t* user_out,
-                          int64_t* item_out, int64_t* cat_out, float* num_out, hipStream_t s);
-dcnr_status rank_desc(const float* scores, int64_t n, int64_t* order, hipStream_t s);
-dcnr_status mmr_rerank(const float* table, const float* inv, int d, const int64_t* rows,
-                       const float* scores, int64_t n, float lambda, int top_k, int64_t* out_pos,
-                       int32_t* out_count, hipStream_t s);
-// the same steps for a batch of R requests, one workgroup each, over CSR
-// segments (dcnr_requests_*)
-struct RequestsIn {
-  const int64_t* pos; const int64_t* pos_off; int64_t R, Q_total;   // positives [Q_total], [R + 1]
-  const int64_t* idx; int k;                                       // their neighbours [Q_total][k]
-  const int32_t* nbr; int kt;   // ... or (idx null) the item neighbour table [n_items][kt], kt >= k
-  const int64_t* set_rows; int64_t n_set_rows; const int64_t* set_off; int S;
-  const int32_t* allowed; const int32_t* excluded; const int32_t* fallback;   // [R] or null
-};
-struct RequestsWs { int64_t* rrows; float* rscores; };   // [R][cap] ranked lists for the MMR
-int requests_cap_max();
-RequestsWs requests_ws(Bump& b, int64_t R, int cap);
-size_t requests_ws_bytes(int64_t R, int cap);
-dcnr_status requests_candidates(const RequestsIn& in, int min_candidates, int64_t n_items, int cap,
-                                int64_t* out_rows, int32_t* out_count, int32_t* status,
-                                int64_t* offsets, int64_t* host_offsets, int32_t* host_status,
-                                hipStream_t s);
-dcnr_status requests_batch(const int64_t* slots, int cap, const int64_t* offsets, int64_t R,
-                           int64_t n, const int64_t* user_rows, const int64_t* item_cat, int K,
-                           const float* item_num, int F, int64_t n_items, int64_t* user_out,
-                           int64_t* item_out, int64_t* cat_out, float* num_out, hipStream_t s);
-dcnr_status requests_rank_mmr(const float* logits, int64_t n, const int64_t* slots, int cap,
-                              const int64_t* offsets, int64_t R, const float* table,
-                              const float* inv, int d, int64_t n_items, const float* lambda,
-                              const int32_t* top_k, const RequestsWs& w, int64_t* out_rows,
-                              float* out_logits, int32_t* out_count, int32_t* status,
-                              hipStream_t s);
-// requests by user: the positives / negatives in front of requests_candidates,
-// the recommended_by lists behind requests_rank_mmr (dcnr_requests_sources,
-// dcnr_requests_recommended_by)
-dcnr_status requests_sources(const dcnr_interactions& store, const int32_t* reviewers,
-                             const int32_t* modes, int64_t R, int64_t n_items,
-                             const int64_t* pos_off, int64_t Q_total, int64_t* pos,
-                             const int64_t* neg_off, int64_t neg_lo, int64_t neg_hi, int64_t* neg,
-                             int32_t* counts, int32_t* status, int32_t* host_counts,
-                             int32_t* host_status, hipStream_t s);
-dcnr_status requests_recommended_by(const dcnr_interactions& store, const int32_t* reviewers,
-                                    int64_t R, int64_t n_items, const int64_t* out_rows, int64_t n,
-                                    const int64_t* offsets, const int32_t* out_count,
-                                    const int64_t* list_off, int64_t L_total, int32_t* lists,
-                                    int32_t* by_count, int64_t* by_off, int32_t* by_reviewers,
-                                    int32_t* status, hipStream_t s);
-// dcnr_csr_insert: a new generation of a CSR of 1 or 2 int32 payloads (the
-// payload arrays are neither read nor written when m == 0)
-dcnr_status csr_insert(const int64_t* old_off, int64_t U_old, int64_t U_new, int64_t M_old,
-                       int n_payloads, const int32_t* const* old_val, const int64_t* touched,
-                       const int64_t* prefix, int64_t t, const int64_t* ins_pos,
-                       const int32_t* const* ins_val, int64_t m, int64_t* new_off,
-                       int32_t* const* new_val, hipStream_t s);
-// dcnr_csr_remove: the generation without the m entries at removed[] (m >= 1;
-// the payload arrays are neither read nor written when m == M_old)
-dcnr_status csr_remove(const int64_t* old_off, int64_t U, int64_t M_old, int n_payloads,
-                       const int32_t* const* old_val, const int64_t* removed, int64_t m,
-                       int64_t* new_off, int32_t* const* new_val, hipStream_t s);
-
 dcnr_status fill_zero(void* p, size_t bytes, hipStream_t s);
 // *dst = *src with a system-scope store (dst may be pinned host memory)
 dcnr_status mirror_word(const int* src, int* dst, hipStream_t s);
 dcnr_status fill_zero_multi(int n, void* const* ptrs, const int64_t* bytes, hipStream_t s);
-
-// city and popular-hotel sets (city_sets.hip): arguments checked by the caller
-size_t city_sets_ws_bytes(int64_t M, int64_t n_items, int n_cities, int top);
-dcnr_status city_sets_build(const int32_t* item, const int32_t* city, const double* key,
-                            const int32_t* row, int64_t M, int64_t n_items, int n_cities, int top,
-                            int64_t* set_offsets, int64_t* set_rows, int64_t cap, int32_t* top_rows,
-                            int32_t* status, int64_t* host_offsets, int32_t* host_status, void* ws,
-                            hipStream_t s);
-
-// hotel feature tables from each hotel's first review row (item_features.hip):
-// arguments checked by the caller; counts = {hotels with a row, status}
-size_t item_features_ws_bytes(int64_t n_items);
-dcnr_status item_features_build(const int32_t* item, const int32_t* row, const int32_t* cat,
-                                const double* num, const double* scale, const double* mn, int64_t M,
-                                int64_t n_items, int n_cat, int n_num, int32_t* first_row,
-                                int64_t* item_cat, float* item_num, int32_t* counts,
-                                int32_t* host_counts, void* ws, hipStream_t s);
-
-// prepare_data on the device (train_table.hip): arguments checked by the caller, M > 0
-size_t train_table_ws_bytes(int64_t M, int n_num);
-dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, hipStream_t s);
 
 // ---------------------------------------------------------------------------
 // The stable LSD radix sort of metrics.hip and city_sets.hip: passes of RBITS

@@ -897,8 +897,8 @@ dcnr_status emb_sort(const EmbBwdDesc& e, const int64_t* user, const int64_t* it
   uint32_t* hist = (uint32_t*)sb.tmp;
   // dynamic LDS above the 64 KiB default
   const size_t lds_bk = (size_t)SC_W * p.max_bk * 4, lds_low = (size_t)4 * p.max_low * 4;
-  if (lds_bk > 65536) TRY_ST(set_max_dyn_lds((const void*)emb_scatter_kernel, lds_bk));
-  if (lds_low + ENT * 4 > 65536) TRY_ST(set_max_dyn_lds((const void*)emb_bucket_sort_kernel, lds_low));
+  if (lds_bk > 65536) TRY(set_max_dyn_lds((const void*)emb_scatter_kernel, lds_bk));
+  if (lds_low + ENT * 4 > 65536) TRY(set_max_dyn_lds((const void*)emb_bucket_sort_kernel, lds_low));
   const dim3 gc((unsigned)p.C, (unsigned)e.n_tab);
   hipLaunchKernelGGL(emb_ids_kernel, dim3((unsigned)cdiv(B, ENT)), dim3(ENT),
                      (size_t)std::max(e.n_tab - 2, 1) * ENT * 4, s, p.st, e.n_tab, user, item,
@@ -1084,8 +1084,8 @@ __global__ __launch_bounds__(256) void sparse_add_kernel(float* __restrict__ sha
 
 }  // namespace
 
-dcnr_status sparse_pack(const float* grad, const int64_t* offs, int64_t ld, const int64_t* tcnt, int n_tables,
-                        int width, int64_t* out_off, float* out_rows, hipStream_t s) {
+static dcnr_status sparse_pack(const float* grad, const int64_t* offs, int64_t ld, const int64_t* tcnt, int n_tables,
+                               int width, int64_t* out_off, float* out_rows, hipStream_t s) {
   if (ld <= 0 || n_tables < 1) return DCNR_OK;
   const bool v4 = width % 4 == 0 && (uintptr_t)grad % 16 == 0 && (uintptr_t)out_rows % 16 == 0;
   const int per = v4 ? width / 4 : width;
@@ -1100,8 +1100,8 @@ dcnr_status sparse_pack(const float* grad, const int64_t* offs, int64_t ld, cons
   return DCNR_OK;
 }
 
-dcnr_status sparse_accumulate(float* shard, int64_t lo, int64_t elems, int width, const int64_t* offs,
-                              const float* rows, const int64_t* counts, int n_sources, hipStream_t s) {
+static dcnr_status sparse_accumulate(float* shard, int64_t lo, int64_t elems, int width, const int64_t* offs,
+                                     const float* rows, const int64_t* counts, int n_sources, hipStream_t s) {
   DCNR_HIP(hipMemsetAsync(shard, 0, (size_t)elems * 4, s));
   const bool v4 = width % 4 == 0 && lo % 4 == 0 && (uintptr_t)shard % 16 == 0 && (uintptr_t)rows % 16 == 0;
   int64_t pos = 0;
@@ -1187,3 +1187,46 @@ dcnr_status emb_segment_sum(const EmbBwdDesc& e, const EmbSortBufs& sb, int64_t 
 }
 
 }  // namespace dcnr
+
+using namespace dcnr;
+
+extern "C" {
+
+dcnr_status dcnr_sparse_pack(const float* grad, const int64_t* offsets, int64_t ld,
+                             const int64_t* table_counts, int32_t n_tables, int32_t width,
+                             int64_t* out_offsets, float* out_rows, dcnr_stream_t stream) {
+  if (!grad || !offsets || !table_counts || !out_offsets || !out_rows || ld < 0 || n_tables < 1 ||
+      width < 1) {
+    set_error("dcnr_sparse_pack: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  TRYP(DCNR_K_SERVE, s, sparse_pack(grad, offsets, ld, table_counts, n_tables, width, out_offsets, out_rows, s));
+  return DCNR_OK;
+}
+
+dcnr_status dcnr_sparse_accumulate(float* shard, int64_t shard_lo, int64_t shard_elems, int32_t width,
+                                   const int64_t* offsets, const float* rows,
+                                   const int64_t* source_counts, int32_t n_sources,
+                                   dcnr_stream_t stream) {
+  if (!shard || shard_lo < 0 || shard_elems < 0 || width < 1 || n_sources < 0 ||
+      (n_sources > 0 && !source_counts)) {
+    set_error("dcnr_sparse_accumulate: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  int64_t n = 0;
+  for (int r = 0; r < n_sources; ++r) {
+    if (source_counts[r] < 0) { set_error("dcnr_sparse_accumulate: negative count"); return DCNR_BAD_ARG; }
+    n += source_counts[r];
+  }
+  if (n > 0 && (!offsets || !rows)) {
+    set_error("dcnr_sparse_accumulate: null rows");
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  TRYP(DCNR_K_SERVE, s, sparse_accumulate(shard, shard_lo, shard_elems, width, offsets, rows, source_counts,
+                                       n_sources, s));
+  return DCNR_OK;
+}
+
+}  // extern "C"

@@ -242,7 +242,7 @@ dcnr_status gemm_dw(const DwArgs& a0, hipStream_t s) {
     return DCNR_UNSUPPORTED_SHAPE;
   }
   using C = DwCfg<DW_T>;
-  TRY_ST(set_max_dyn_lds((const void*)gemm_dw_kernel<DW_T>, C::LDS));
+  TRY(set_max_dyn_lds((const void*)gemm_dw_kernel<DW_T>, C::LDS));
   a.tiles_n = (int)cdiv(a.N, DW_T);
   a.tiles_k = (int)cdiv(a.K, DW_T);
   const int grid = a.tiles_n * a.tiles_k * a.splits;

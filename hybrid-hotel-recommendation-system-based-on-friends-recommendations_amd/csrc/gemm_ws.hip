@@ -566,7 +566,7 @@ dcnr_status launch_ws(NtArgs a, hipStream_t s, int* nparts) {
   // XBN: + the t tiles and the transform's 5 x K constants
   constexpr size_t LDSB = C::LDS_BYTES + (XBN ? WS_NB * (size_t)C::TILE + 5 * KTP * 32 * 4 : 0);
   static_assert(LDSB <= 160 * 1024, "LDS budget");
-  TRY_ST(set_max_dyn_lds((const void*)gemm_ws_kernel<KTP, EPI, XBN, R1>, LDSB));
+  TRY(set_max_dyn_lds((const void*)gemm_ws_kernel<KTP, EPI, XBN, R1>, LDSB));
   a.nslices = (int)cdiv(a.N, WS_TN);
   // 32-bit buffer offsets: launch in M-chunks of < 2^29 bytes per operand
   const int64_t maxld = std::max<int64_t>({a.ldx, a.ldc * 2, a.R ? a.ldr : 0, a.Hb ? a.ldhb * 2 : 0,

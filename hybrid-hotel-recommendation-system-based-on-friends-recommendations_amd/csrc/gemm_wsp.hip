@@ -339,7 +339,7 @@ template <bool STATS>
 dcnr_status launch_wsp(NtArgs a, hipStream_t s, int* nparts) {
   const void* kt = a.M % WP_TM ? (const void*)gemm_wsp_kernel<STATS, true>
                                : (const void*)gemm_wsp_kernel<STATS, false>;
-  TRY_ST(set_max_dyn_lds(kt, WP_LDS));
+  TRY(set_max_dyn_lds(kt, WP_LDS));
   a.nslices = (int)cdiv(a.N, WP_TN);
   // 32-bit buffer offsets: launch in M-chunks of < 2^29 bytes per operand
   const int64_t maxld = std::max<int64_t>(a.ldx, a.ldc);
@@ -353,7 +353,7 @@ dcnr_status launch_wsp(NtArgs a, hipStream_t s, int* nparts) {
       b.C = (char*)a.C + m0 * a.ldc * 2;
       if (a.part) b.part = a.part + (int64_t)total * 2 * a.N;
       int np = 0;
-      TRY_ST(launch_wsp<STATS>(b, s, &np));
+      TRY(launch_wsp<STATS>(b, s, &np));
       total += np;
     }
     if (nparts) *nparts = total;

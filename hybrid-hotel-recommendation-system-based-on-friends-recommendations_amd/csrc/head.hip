@@ -263,10 +263,10 @@ dcnr_status bce(const float* z, const float* y, int64_t B, float* loss, float* d
   return DCNR_OK;
 }
 
-dcnr_status adam(int n, float* const* p, const float* const* g, float* const* m, float* const* v,
-                 const int64_t* numel, float lr, float b1, float b2, float eps, float wd,
-                 int64_t step, int decoupled, hipStream_t s, const uint8_t* const* row_map,
-                 const int32_t* row_width) {
+static dcnr_status adam(int n, float* const* p, const float* const* g, float* const* m, float* const* v,
+                        const int64_t* numel, float lr, float b1, float b2, float eps, float wd,
+                        int64_t step, int decoupled, hipStream_t s,
+                        const uint8_t* const* row_map = nullptr, const int32_t* row_width = nullptr) {
   double bc1 = 1.0 - std::pow((double)b1, (double)step);
   double bc2 = 1.0 - std::pow((double)b2, (double)step);
   float step_size = (float)(lr / bc1);
@@ -292,3 +292,55 @@ dcnr_status adam(int n, float* const* p, const float* const* g, float* const* m,
 }
 
 }  // namespace dcnr
+
+using namespace dcnr;
+
+extern "C" {
+
+dcnr_status dcnr_adam_step(int32_t n_tensors, float* const* params, const float* const* grads,
+                           float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
+                           float lr, float beta1, float beta2, float eps, float weight_decay,
+                           int64_t step, int decoupled, dcnr_stream_t stream) {
+  if (n_tensors < 0 || (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel)) ||
+      step < 1) {
+    set_error("dcnr_adam_step: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  double nparam = 0;
+  for (int i = 0; i < n_tensors; ++i) nparam += (double)numel[i];
+  TRYB(DCNR_K_ADAM, s, 28.0 * nparam, adam(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2,
+                         eps, weight_decay, step, decoupled, s));
+  return DCNR_OK;
+}
+
+dcnr_status dcnr_adam_step_rows(int32_t n_tensors, float* const* params, const float* const* grads,
+                                float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
+                                const uint8_t* const* row_map, const int32_t* row_width,
+                                float lr, float beta1, float beta2, float eps, float weight_decay,
+                                int64_t step, int decoupled, dcnr_stream_t stream) {
+  if (n_tensors < 0 || (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel ||
+                                          !row_map || !row_width)) || step < 1) {
+    set_error("dcnr_adam_step_rows: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  double nbytes = 0;
+  for (int i = 0; i < n_tensors; ++i) {
+    if (row_map[i] && (row_width[i] < 1 || numel[i] % row_width[i])) {
+      set_error("dcnr_adam_step_rows: tensor %d: %lld elements in rows of %d", i, (long long)numel[i],
+                row_width[i]);
+      return DCNR_BAD_ARG;
+    }
+    // p, m, v read and written, the map byte per row; the gradient of a
+    // mapped tensor only where marked (a share the library does not know:
+    // not counted, so the figure is a floor)
+    nbytes += (row_map[i] ? 24.0 : 28.0) * (double)numel[i] +
+              (row_map[i] ? (double)numel[i] / row_width[i] : 0.0);
+  }
+  hipStream_t s = (hipStream_t)stream;
+  TRYB(DCNR_K_ADAM, s, nbytes, adam(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2,
+                                 eps, weight_decay, step, decoupled, s, row_map, row_width));
+  return DCNR_OK;
+}
+
+}  // extern "C"

@@ -180,13 +180,13 @@ int blocks_for(int64_t n, int64_t per_block) {
 }  // namespace
 
 // firstpos [n_items], then partial [IF_MAXB]
-size_t item_features_ws_bytes(int64_t n_items) { return (size_t)rup(n_items * 4, 256) + IF_MAXB * 4; }
+static size_t item_features_ws_bytes(int64_t n_items) { return (size_t)rup(n_items * 4, 256) + IF_MAXB * 4; }
 
-dcnr_status item_features_build(const int32_t* item, const int32_t* row, const int32_t* cat,
-                                const double* num, const double* scale, const double* mn, int64_t M,
-                                int64_t n_items, int n_cat, int n_num, int32_t* first_row,
-                                int64_t* item_cat, float* item_num, int32_t* counts,
-                                int32_t* host_counts, void* ws, hipStream_t s) {
+static dcnr_status item_features_build(const int32_t* item, const int32_t* row, const int32_t* cat,
+                                       const double* num, const double* scale, const double* mn, int64_t M,
+                                       int64_t n_items, int n_cat, int n_num, int32_t* first_row,
+                                       int64_t* item_cat, float* item_num, int32_t* counts,
+                                       int32_t* host_counts, void* ws, hipStream_t s) {
   // (without rows there may be no workspace: no hotel has a row, nothing is counted)
   int32_t* firstpos = M > 0 ? (int32_t*)ws : nullptr;
   int32_t* partial = M > 0 ? (int32_t*)((char*)ws + rup(n_items * 4, 256)) : nullptr;
@@ -221,3 +221,56 @@ dcnr_status item_features_build(const int32_t* item, const int32_t* row, const i
 }
 
 }  // namespace dcnr
+
+using namespace dcnr;
+
+extern "C" {
+
+static dcnr_status item_features_shape(int64_t M, int64_t n_items, int32_t n_cat, int32_t n_num) {
+  if (M < 0 || n_items < 0 || n_cat < 0 || n_num < 0) return DCNR_BAD_ARG;
+  if (n_cat > 64 || n_num > 64 || n_items > ((int64_t)1 << 29) || M >= 2147483647ll)
+    return DCNR_UNSUPPORTED_SHAPE;
+  return DCNR_OK;
+}
+
+size_t dcnr_item_features_workspace_size(int64_t M, int64_t n_items, int32_t n_cat, int32_t n_num) {
+  if (item_features_shape(M, n_items, n_cat, n_num) != DCNR_OK) return 0;
+  return item_features_ws_bytes(n_items) + 256;
+}
+
+dcnr_status dcnr_item_features_build(const int32_t* review_item, const int32_t* review_row,
+                                     const int32_t* review_cat, const double* review_num,
+                                     const double* scaler_scale, const double* scaler_min, int64_t M,
+                                     int64_t n_items, int32_t n_cat, int32_t n_num, int32_t* first_row,
+                                     int64_t* item_cat, float* item_num, int32_t* counts,
+                                     int32_t* host_counts, void* ws, size_t ws_bytes,
+                                     dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const dcnr_status shape = item_features_shape(M, n_items, n_cat, n_num);
+  if (shape == DCNR_BAD_ARG || !counts ||
+      (n_items > 0 && (!first_row || (n_cat > 0 && !item_cat) || (n_num > 0 && !item_num))) ||
+      (n_num > 0 && n_items > 0 && (!scaler_scale || !scaler_min)) ||
+      (M > 0 && (!review_item || !ws || (n_cat > 0 && !review_cat) || (n_num > 0 && !review_num)))) {
+    set_error("dcnr_item_features_build: bad argument (M=%lld, n_items=%lld, n_cat=%d, n_num=%d)",
+              (long long)M, (long long)n_items, n_cat, n_num);
+    return DCNR_BAD_ARG;
+  }
+  if (shape != DCNR_OK) {
+    set_error("dcnr_item_features_build: unsupported shape (M=%lld, n_items=%lld, n_cat=%d, n_num=%d)",
+              (long long)M, (long long)n_items, n_cat, n_num);
+    return shape;
+  }
+  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  const size_t need = M > 0 ? item_features_ws_bytes(n_items) : 0;
+  if (M > 0 && ws_bytes < need + ((char*)base - (char*)ws)) {
+    set_error("dcnr_item_features_build: workspace too small: %zu < %zu", ws_bytes, need + 256);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  TRYP(DCNR_K_SERVE, s, item_features_build(review_item, review_row, review_cat, review_num,
+                                            scaler_scale, scaler_min, M, n_items, n_cat, n_num,
+                                            first_row, item_cat, item_num, counts, host_counts, base,
+                                            s));
+  return DCNR_OK;
+}
+
+}  // extern "C"

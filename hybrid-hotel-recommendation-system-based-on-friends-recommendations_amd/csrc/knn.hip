@@ -1724,26 +1724,6 @@ __global__ void pack_rows_kernel(const float* __restrict__ t, const float* __res
 
 }  // namespace
 
-dcnr_status row_inv_norms(const float* t, int64_t N, int d, float* out, hipStream_t s) {
-  if (N <= 0) return DCNR_OK;
-  int64_t blocks = std::min<int64_t>(cdiv(N, 4), 8192);
-  hipLaunchKernelGGL(inv_norm_kernel, dim3((unsigned)blocks), dim3(256), 0, s, t, N, d, out);
-  DCNR_LAUNCH_CHECK();
-  return DCNR_OK;
-}
-
-dcnr_status cosine_pack_rows(const float* t, const float* inv, int64_t N, int d, bf16* out, hipStream_t s) {
-  if (d % 8) {
-    set_error("cosine_pack_rows: d=%d is not a multiple of 8", d);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  if (N <= 0) return DCNR_OK;
-  const int64_t blocks = std::min<int64_t>(cdiv(N * d / 8, 256), 8192);
-  hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, s, t, inv, N, d, out);
-  DCNR_LAUNCH_CHECK();
-  return DCNR_OK;
-}
-
 bool use_v2(int d, int k) { return d % 4 == 0 && d >= 4 && d <= 64 && k <= K2_KMAX; }
 
 // v2 plan: up to 512 row slices (2 blocks per CU per query tile), slices a
@@ -1836,13 +1816,13 @@ void with_v4_nqb(int nqb, F f) {
 
 // enough for every d (the v2 path keeps Q x d <= Q x 64 normalised queries;
 // wider rows take scan v1)
-size_t topk_ws(int64_t N, int64_t Q, int k) {
+static size_t topk_ws(int64_t N, int64_t Q, int k) {
   return std::max(carve_topk(nullptr, N, Q, k, 64).total, carve_topk(nullptr, N, Q, k, 256).total);
 }
 
-dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_t N, int d,
-                        const float* q, int64_t Q, int k, int64_t* idx, float* dist, void* ws,
-                        size_t ws_bytes, hipStream_t s, bool allow_v3) {
+static dcnr_status cosine_topk(const float* t, const float* inv, const bf16* tb, int64_t N, int d,
+                               const float* q, int64_t Q, int k, int64_t* idx, float* dist, void* ws,
+                               size_t ws_bytes, hipStream_t s, bool allow_v3 = true) {
   if (k < 1 || k > KMAX || d < 4 || d % 4 || d > 256 || N < 1) {
     set_error("cosine_topk: unsupported k=%d d=%d N=%lld (1<=k<=64, d%%4==0, d<=256)", k, d,
               (long long)N);
@@ -2288,50 +2268,9 @@ bool within_shape_ok(int64_t Q, int k, int d, int64_t max_set_rows) {
          max_set_rows <= INT32_MAX && Q <= INT32_MAX;
 }
 
-size_t cosine_topk_within_ws(int64_t Q, int k, int d, int64_t max_set_rows) {
+static size_t cosine_topk_within_ws(int64_t Q, int k, int d, int64_t max_set_rows) {
   if (!within_shape_ok(Q, k, d, max_set_rows)) return 0;
   return carve_within(nullptr, Q, k, d, max_set_rows).total + 256;   // (never 0 for a shape it takes)
-}
-
-dcnr_status cosine_topk_within(const float* t, const float* inv, int64_t N, int d, const float* q, int64_t Q,
-                               const int64_t* excl, const int64_t* seg_off, int64_t G, const int* seg_set,
-                               const int64_t* set_rows, int64_t n_set_rows, const int64_t* set_off, int S,
-                               int64_t max_set_rows, int k, int64_t ld, int64_t* idx, float* dist,
-                               int* seg_status, void* ws, size_t ws_bytes, hipStream_t s) {
-  const WithinWs w = carve_within(ws, Q, k, d, max_set_rows);
-  if (ws_bytes < w.total) {
-    set_error("cosine_topk_within: workspace too small");
-    return DCNR_WORKSPACE_TOO_SMALL;
-  }
-  const int64_t qblocks = cdiv(Q, 4), windows = cdiv(Q, W_BQ);
-  if (qblocks + cdiv(G, 4) > INT32_MAX || windows * w.nchunks > INT32_MAX) {
-    set_error("cosine_topk_within: Q=%lld, G=%lld need more blocks than a launch holds", (long long)Q,
-              (long long)G);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  hipLaunchKernelGGL(within_prep_kernel, dim3((unsigned)(qblocks + cdiv(G, 4))), dim3(256), 0, s, q, Q, d,
-                     use_v2(d, k) ? 1 : 0, w.qn, seg_off, G, seg_set, set_off, S, n_set_rows, max_set_rows, qblocks, w.recs, seg_status);
-  DCNR_LAUNCH_CHECK();
-  if (max_set_rows > 0) {   // (else every set is empty or too long: nothing to scan)
-    const dim3 grid((unsigned)(windows * w.nchunks));
-    if (use_v2(d, k)) {
-      with_dv(d / 4, [&](auto dv) {
-        hipLaunchKernelGGL(within_scan_kernel<decltype(dv)::value>, grid, dim3(K2_NT), 0, s, t, inv, N, w.qn, Q, excl,
-                           seg_off, G, set_rows, w.recs, w.rpi, w.nchunks, k, w.lists, seg_status);
-      });
-    } else if (d <= 64) {
-      hipLaunchKernelGGL(within_scan_wide_kernel<16>, grid, dim3(NT), 0, s, t, inv, N, d, w.qn, Q, excl, seg_off, G,
-                         set_rows, w.recs, w.rpi, w.nchunks, k, w.lists, seg_status);
-    } else {
-      hipLaunchKernelGGL(within_scan_wide_kernel<64>, grid, dim3(NT), 0, s, t, inv, N, d, w.qn, Q, excl, seg_off, G,
-                         set_rows, w.recs, w.rpi, w.nchunks, k, w.lists, seg_status);
-    }
-    DCNR_LAUNCH_CHECK();
-  }
-  hipLaunchKernelGGL(within_merge_kernel, dim3((unsigned)Q), dim3(NT), 0, s, w.lists, w.nchunks, w.rpi, k, ld, idx,
-                     dist, seg_off, G, w.recs);
-  DCNR_LAUNCH_CHECK();
-  return DCNR_OK;
 }
 
 // ---- the item neighbour table: the top-k of every table row, built once
@@ -2365,27 +2304,7 @@ NbrWs carve_nbr(void* ws, int64_t N, int k) {
   return w;
 }
 
-size_t neighbor_table_ws(int64_t N, int k) { return carve_nbr(nullptr, N, k).total; }
-
-dcnr_status neighbor_table(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
-                           int64_t row_lo, int64_t row_hi, int32_t* out_idx, float* out_dist, void* ws,
-                           size_t ws_bytes, hipStream_t s) {
-  const NbrWs w = carve_nbr(ws, N, k);
-  if (ws_bytes < w.total) {
-    set_error("neighbor_table: workspace too small");
-    return DCNR_WORKSPACE_TOO_SMALL;
-  }
-  for (int64_t lo = row_lo; lo < row_hi; lo += NBR_CHUNK) {
-    const int64_t Q = std::min(NBR_CHUNK, row_hi - lo);
-    const int64_t o = (lo - row_lo) * k;
-    TRY_ST(cosine_topk(t, inv, tb, N, d, t + lo * d, Q, k, w.idx, out_dist ? out_dist + o : w.dist, w.topk,
-                       w.topk_bytes, s, /*allow_v3=*/false));
-    hipLaunchKernelGGL(narrow_idx_kernel, dim3((unsigned)cdiv(Q * k, 256)), dim3(256), 0, s, w.idx, Q * k,
-                       out_idx + o);
-    DCNR_LAUNCH_CHECK();
-  }
-  return DCNR_OK;
-}
+static size_t neighbor_table_ws(int64_t N, int k) { return carve_nbr(nullptr, N, k).total; }
 
 // ---- the item neighbour table, updated in place after m rows changed
 //
@@ -2786,16 +2705,254 @@ UpdWs carve_upd(void* ws, int64_t N, int d, int k, int64_t m) {
 
 }  // namespace
 
-size_t neighbor_table_update_ws(int64_t N, int d, int k, int64_t m) {
+static size_t neighbor_table_update_ws(int64_t N, int d, int k, int64_t m) {
   const UpdWs w = carve_upd(nullptr, N, d, k, m);
   return std::max(w.ab_total, w.c_total);
 }
-int neighbor_table_update_max_m() { return UPD_MAX_M; }
+}  // namespace dcnr
 
-dcnr_status neighbor_table_update(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
-                                  const int32_t* changed, int64_t m, int32_t* nbr, int32_t* counts,
-                                  int32_t* host_counts, int32_t* research, void* ws, size_t ws_bytes,
-                                  hipStream_t s) {
+using namespace dcnr;
+
+extern "C" {
+
+dcnr_status dcnr_row_inv_norms(const float* table, int64_t N, int32_t d, float* inv_norms,
+                               dcnr_stream_t stream) {
+  if (!table || !inv_norms || d < 1 || N < 0) {
+    set_error("dcnr_row_inv_norms: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  if (N <= 0) return DCNR_OK;
+  int64_t blocks = std::min<int64_t>(cdiv(N, 4), 8192);
+  hipLaunchKernelGGL(inv_norm_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table, N, d,
+                     inv_norms);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
+size_t dcnr_cosine_topk_workspace_size(int64_t N, int64_t Q, int32_t k) {
+  if (N < 1 || Q < 1 || k < 1) return 256;   // nothing to plan (cosine_topk returns or rejects)
+  return topk_ws(N, Q, k) + 256;
+}
+
+dcnr_status dcnr_cosine_pack_rows(const float* table, const float* inv_norms, int64_t N, int32_t d,
+                                  uint16_t* packed, dcnr_stream_t stream) {
+  if (!table || !inv_norms || !packed || d < 1 || N < 0) {
+    set_error("dcnr_cosine_pack_rows: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  if (d % 8) {
+    set_error("cosine_pack_rows: d=%d is not a multiple of 8", d);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  if (N <= 0) return DCNR_OK;
+  const int64_t blocks = std::min<int64_t>(cdiv(N * d / 8, 256), 8192);
+  hipLaunchKernelGGL(pack_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, table,
+                     inv_norms, N, d, (bf16*)packed);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
+dcnr_status dcnr_cosine_topk_packed(const float* table, const float* inv_norms, const uint16_t* packed,
+                                    int64_t N, int32_t d, const float* queries, int64_t Q, int32_t k,
+                                    int64_t* idx, float* dist, void* ws, size_t ws_bytes,
+                                    dcnr_stream_t stream) {
+  // (no queries: the query and output pointers may be null)
+  if (!table || !inv_norms || (Q > 0 && (!queries || !idx || !dist || !ws))) {
+    set_error("dcnr_cosine_topk: null argument");
+    return DCNR_BAD_ARG;
+  }
+  if (k > N) {
+    set_error("Expected n_neighbors <= n_samples_fit, but n_neighbors = %d, n_samples_fit = %lld",
+              k, (long long)N);
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  TRYB(DCNR_K_KNN, s, (double)N * (4.0 * d + 4.0),
+       cosine_topk(table, inv_norms, (const bf16*)packed, N, d, queries, Q, k, idx, dist, ws, ws_bytes, s));
+  return DCNR_OK;
+}
+
+dcnr_status dcnr_cosine_topk(const float* table, const float* inv_norms, int64_t N, int32_t d,
+                             const float* queries, int64_t Q, int32_t k, int64_t* idx, float* dist,
+                             void* ws, size_t ws_bytes, dcnr_stream_t stream) {
+  return dcnr_cosine_topk_packed(table, inv_norms, nullptr, N, d, queries, Q, k, idx, dist, ws, ws_bytes,
+                                 stream);
+}
+
+size_t dcnr_cosine_topk_within_workspace_size(int64_t Q, int32_t k, int32_t d, int64_t max_set_rows) {
+  return cosine_topk_within_ws(Q, k, d, max_set_rows);   // (0 for what the call rejects)
+}
+
+dcnr_status dcnr_cosine_topk_within(const float* table, const float* inv_norms, int64_t N, int32_t d,
+                                    const float* queries, int64_t Q, const int64_t* exclude,
+                                    const int64_t* seg_offsets, int64_t G, const int32_t* seg_set,
+                                    const int64_t* set_rows, int64_t n_set_rows, const int64_t* set_offsets,
+                                    int32_t S, int64_t max_set_rows, int32_t k, int64_t ld, int64_t* idx,
+                                    float* dist, int32_t* seg_status, void* ws, size_t ws_bytes,
+                                    dcnr_stream_t stream) {
+  if (Q < 0 || G < 0 || S < 0 || N < 1 || n_set_rows < 0 || max_set_rows < 0 || k < 1 || ld < k) {
+    set_error("dcnr_cosine_topk_within: bad argument (N=%lld, Q=%lld, G=%lld, S=%d, k=%d, ld=%lld, "
+              "n_set_rows=%lld, max_set_rows=%lld)", (long long)N, (long long)Q, (long long)G, S, k,
+              (long long)ld, (long long)n_set_rows, (long long)max_set_rows);
+    return DCNR_BAD_ARG;
+  }
+  // (set_rows may be null when the CSR holds no row)
+  if (Q > 0 && (!table || !inv_norms || !queries || !idx || !dist || !ws ||
+                (G > 0 && (!seg_offsets || !seg_set || !set_offsets || (n_set_rows > 0 && !set_rows))))) {
+    set_error("dcnr_cosine_topk_within: null argument");
+    return DCNR_BAD_ARG;
+  }
+  if (k > KMAX || d % 4 || d < 4 || d > 256 || N > INT32_MAX || n_set_rows > INT32_MAX ||
+      max_set_rows > INT32_MAX || Q > INT32_MAX || G > INT32_MAX) {
+    set_error("dcnr_cosine_topk_within: unsupported k=%d d=%d N=%lld n_set_rows=%lld Q=%lld G=%lld "
+              "(k<=64, d%%4==0, 4<=d<=256, the rest below 2^31)", k, d, (long long)N, (long long)n_set_rows,
+              (long long)Q, (long long)G);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  if (Q == 0 || G == 0) return DCNR_OK;   // (no query, or none in a segment: nothing is written)
+  if (ws_bytes < cosine_topk_within_ws(Q, k, d, max_set_rows)) {
+    set_error("dcnr_cosine_topk_within: workspace too small");
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // (bytes: the longest set once per window of 8 queries)
+  ProfScope ps(DCNR_K_KNN, s, (double)((Q + 7) / 8) * (double)max_set_rows * (4.0 * d + 12.0));
+  const WithinWs w = carve_within(ws, Q, k, d, max_set_rows);
+  if (ws_bytes < w.total) {
+    set_error("cosine_topk_within: workspace too small");
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  const int64_t qblocks = cdiv(Q, 4), windows = cdiv(Q, W_BQ);
+  if (qblocks + cdiv(G, 4) > INT32_MAX || windows * w.nchunks > INT32_MAX) {
+    set_error("cosine_topk_within: Q=%lld, G=%lld need more blocks than a launch holds", (long long)Q,
+              (long long)G);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  hipLaunchKernelGGL(within_prep_kernel, dim3((unsigned)(qblocks + cdiv(G, 4))), dim3(256), 0, s, queries, Q, d,
+                     use_v2(d, k) ? 1 : 0, w.qn, seg_offsets, G, seg_set, set_offsets, S, n_set_rows,
+                     max_set_rows, qblocks, w.recs, seg_status);
+  DCNR_LAUNCH_CHECK();
+  if (max_set_rows > 0) {   // (else every set is empty or too long: nothing to scan)
+    const dim3 grid((unsigned)(windows * w.nchunks));
+    if (use_v2(d, k)) {
+      with_dv(d / 4, [&](auto dv) {
+        hipLaunchKernelGGL(within_scan_kernel<decltype(dv)::value>, grid, dim3(K2_NT), 0, s, table, inv_norms, N,
+                           w.qn, Q, exclude, seg_offsets, G, set_rows, w.recs, w.rpi, w.nchunks, k, w.lists,
+                           seg_status);
+      });
+    } else if (d <= 64) {
+      hipLaunchKernelGGL(within_scan_wide_kernel<16>, grid, dim3(NT), 0, s, table, inv_norms, N, d, w.qn, Q,
+                         exclude, seg_offsets, G, set_rows, w.recs, w.rpi, w.nchunks, k, w.lists, seg_status);
+    } else {
+      hipLaunchKernelGGL(within_scan_wide_kernel<64>, grid, dim3(NT), 0, s, table, inv_norms, N, d, w.qn, Q,
+                         exclude, seg_offsets, G, set_rows, w.recs, w.rpi, w.nchunks, k, w.lists, seg_status);
+    }
+    DCNR_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(within_merge_kernel, dim3((unsigned)Q), dim3(NT), 0, s, w.lists, w.nchunks, w.rpi, k, ld, idx,
+                     dist, seg_offsets, G, w.recs);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
+size_t dcnr_cosine_neighbor_table_workspace_size(int64_t N, int32_t k) {
+  if (N < 1 || N > INT32_MAX || k < 1 || k > KMAX || k > N) return 256;   // (the build rejects these)
+  return neighbor_table_ws(N, k);   // (exact: one byte less is DCNR_WORKSPACE_TOO_SMALL)
+}
+
+dcnr_status dcnr_cosine_neighbor_table(const float* table, const float* inv_norms, const uint16_t* packed,
+                                       int64_t N, int32_t d, int32_t k, int64_t row_lo, int64_t row_hi,
+                                       int32_t* out_idx, float* out_dist, void* ws, size_t ws_bytes,
+                                       dcnr_stream_t stream) {
+  if (!table || !inv_norms || N < 1 || row_lo < 0 || row_lo > row_hi || row_hi > N || k < 1 || k > N) {
+    set_error("dcnr_cosine_neighbor_table: bad argument (N=%lld, k=%d, rows [%lld, %lld))", (long long)N, k,
+              (long long)row_lo, (long long)row_hi);
+    return DCNR_BAD_ARG;
+  }
+  if (N > INT32_MAX || k > KMAX) {
+    set_error("dcnr_cosine_neighbor_table: N=%lld (below 2^31), k=%d (max 64)", (long long)N, k);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  if (row_lo == row_hi) return DCNR_OK;
+  if (!out_idx || !ws) {
+    set_error("dcnr_cosine_neighbor_table: null argument");
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // (bytes: one pass over the table and the result; every chunk of queries streams the table again)
+  ProfScope ps(DCNR_K_KNN, s, (double)N * (4.0 * d + 4.0) + (double)(row_hi - row_lo) * k * 8.0);
+  const bf16* tb = (const bf16*)packed;
+  const NbrWs w = carve_nbr(ws, N, k);
+  if (ws_bytes < w.total) {
+    set_error("neighbor_table: workspace too small");
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  for (int64_t lo = row_lo; lo < row_hi; lo += NBR_CHUNK) {
+    const int64_t Q = std::min(NBR_CHUNK, row_hi - lo);
+    const int64_t o = (lo - row_lo) * k;
+    TRY(cosine_topk(table, inv_norms, tb, N, d, table + lo * d, Q, k, w.idx, out_dist ? out_dist + o : w.dist,
+                    w.topk, w.topk_bytes, s, /*allow_v3=*/false));
+    hipLaunchKernelGGL(narrow_idx_kernel, dim3((unsigned)cdiv(Q * k, 256)), dim3(256), 0, s, w.idx, Q * k,
+                       out_idx + o);
+    DCNR_LAUNCH_CHECK();
+  }
+  return DCNR_OK;
+}
+
+// the shapes both update calls take: dcnr_cosine_neighbor_table's, and a width
+// the search takes (cosine_topk rejects the others only once it runs)
+static dcnr_status nbr_update_shape(const char* what, int64_t N, int32_t d, int32_t k) {
+  if (N < 1 || k < 1 || k > N) {
+    set_error("%s: bad argument (N=%lld, k=%d)", what, (long long)N, k);
+    return DCNR_BAD_ARG;
+  }
+  if (N > INT32_MAX || k > KMAX || d < 4 || d % 4 || d > UPD_DMAX) {
+    set_error("%s: N=%lld (below 2^31), k=%d (max 64), d=%d (d %% 4 == 0, 4 <= d <= 256)", what, (long long)N, k,
+              d);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  return DCNR_OK;
+}
+
+size_t dcnr_cosine_neighbor_table_update_workspace_size(int64_t N, int32_t d, int32_t k, int64_t m) {
+  if (nbr_update_shape("dcnr_cosine_neighbor_table_update", N, d, k) != DCNR_OK || m < 0 ||
+      m > UPD_MAX_M)
+    return 256;   // (the calls reject these)
+  return neighbor_table_update_ws(N, d, k, m);   // (exact: one byte less is DCNR_WORKSPACE_TOO_SMALL)
+}
+
+dcnr_status dcnr_cosine_neighbor_table_update(const float* table, const float* inv_norms, const uint16_t* packed,
+                                              int64_t N, int32_t d, int32_t k, const int32_t* changed, int64_t m,
+                                              int32_t* nbr, int32_t* counts, int32_t* host_counts,
+                                              int32_t* research_rows, void* ws, size_t ws_bytes,
+                                              dcnr_stream_t stream) {
+  if (!table || !inv_norms || m < 0) {
+    set_error("dcnr_cosine_neighbor_table_update: bad argument (m=%lld)", (long long)m);
+    return DCNR_BAD_ARG;
+  }
+  TRY(nbr_update_shape("dcnr_cosine_neighbor_table_update", N, d, k));
+  if (m > UPD_MAX_M) {
+    set_error("dcnr_cosine_neighbor_table_update: m=%lld changed rows (max %d per call)", (long long)m,
+              UPD_MAX_M);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  if (m == 0) return DCNR_OK;
+  if (!changed || !nbr || !counts || !research_rows || !ws) {
+    set_error("dcnr_cosine_neighbor_table_update: null argument");
+    return DCNR_BAD_ARG;
+  }
+  for (int64_t i = 0; i < m; ++i)
+    if (changed[i] < 0 || changed[i] >= N || (i > 0 && changed[i] <= changed[i - 1])) {
+      set_error("dcnr_cosine_neighbor_table_update: changed[%lld] = %d (ascending, distinct, inside [0, %lld))",
+                (long long)i, changed[i], (long long)N);
+      return DCNR_BAD_ARG;
+    }
+  hipStream_t s = (hipStream_t)stream;
+  // (bytes: the lists, each row's k-th neighbour gathered, one pass over the rows, the changed rows)
+  ProfScope ps(DCNR_K_KNN, s,
+               (double)N * (4.0 * k + 8.0 + 4.0 * d) +
+                   (double)N * d * ((d == 32 || d == 64) && packed ? 2.0 : 4.0) + (double)m * (4.0 * d + 8.0));
+  const bf16* tb = (const bf16*)packed;
   const UpdWs w = carve_upd(ws, N, d, k, m);
   if (ws_bytes < std::max(w.ab_total, w.c_total)) {
     set_error("neighbor_table_update: workspace too small");
@@ -2803,27 +2960,27 @@ dcnr_status neighbor_table_update(const float* t, const float* inv, const bf16* 
   }
   DCNR_HIP(hipMemcpyAsync(w.chg, changed, (size_t)m * 4, hipMemcpyHostToDevice, s));
   DCNR_HIP(hipMemsetAsync(w.bits, 0, (size_t)cdiv(N, 32) * 4, s));
-  hipLaunchKernelGGL(upd_mark_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, s, w.chg, (int)m, w.bits, research,
-                     counts);
+  hipLaunchKernelGGL(upd_mark_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, s, w.chg, (int)m, w.bits,
+                     research_rows, counts);
   DCNR_LAUNCH_CHECK();
   const unsigned rb = (unsigned)cdiv(N, 256);
-  hipLaunchKernelGGL(upd_kth_kernel, dim3(rb), dim3(256), 0, s, t, inv, (int)N, d / 4, k, nbr, w.bits, w.kth, w.aff,
-                     counts);
+  hipLaunchKernelGGL(upd_kth_kernel, dim3(rb), dim3(256), 0, s, table, inv_norms, (int)N, d / 4, k, nbr, w.bits,
+                     w.kth, w.aff, counts);
   DCNR_LAUNCH_CHECK();
   if (d == 32 || d == 64) {
     with_v4_rows(d, tb != nullptr, [&](auto ks, auto pk) {
       hipLaunchKernelGGL((upd_filter4_kernel<decltype(ks)::value, decltype(pk)::value>),
-                         dim3((unsigned)cdiv(N, UPD_RPB)), dim3(256), 0, s, t, inv, tb, (int)N, w.chg, (int)m, w.kth,
-                         w.aff, counts);
+                         dim3((unsigned)cdiv(N, UPD_RPB)), dim3(256), 0, s, table, inv_norms, tb, (int)N, w.chg,
+                         (int)m, w.kth, w.aff, counts);
     });
   } else {
-    hipLaunchKernelGGL(upd_filter_exact_kernel, dim3(rb), dim3(256), 0, s, t, inv, (int)N, d / 4, w.chg, (int)m, w.kth,
-                       w.aff, counts);
+    hipLaunchKernelGGL(upd_filter_exact_kernel, dim3(rb), dim3(256), 0, s, table, inv_norms, (int)N, d / 4, w.chg,
+                       (int)m, w.kth, w.aff, counts);
   }
   DCNR_LAUNCH_CHECK();
   const unsigned mb = (unsigned)std::min<int64_t>(cdiv(N, UPD_G), 4096);
-  hipLaunchKernelGGL(upd_merge_kernel, dim3(mb), dim3(NT), 0, s, t, inv, (int)N, d, k, w.chg, (int)m, w.bits, w.aff, nbr,
-                     research, counts);
+  hipLaunchKernelGGL(upd_merge_kernel, dim3(mb), dim3(NT), 0, s, table, inv_norms, (int)N, d, k, w.chg, (int)m,
+                     w.bits, w.aff, nbr, research_rows, counts);
   DCNR_LAUNCH_CHECK();
   if (host_counts) {
     hipLaunchKernelGGL(upd_mirror_kernel, dim3(1), dim3(64), 0, s, counts, host_counts);
@@ -2832,9 +2989,23 @@ dcnr_status neighbor_table_update(const float* t, const float* inv, const bf16* 
   return DCNR_OK;
 }
 
-dcnr_status neighbor_table_rows(const float* t, const float* inv, const bf16* tb, int64_t N, int d, int k,
-                                const int32_t* rows, int64_t n, int32_t* nbr, void* ws, size_t ws_bytes,
-                                hipStream_t s) {
+dcnr_status dcnr_cosine_neighbor_table_rows(const float* table, const float* inv_norms, const uint16_t* packed,
+                                            int64_t N, int32_t d, int32_t k, const int32_t* rows, int64_t n,
+                                            int32_t* nbr, void* ws, size_t ws_bytes, dcnr_stream_t stream) {
+  if (!table || !inv_norms || n < 0) {
+    set_error("dcnr_cosine_neighbor_table_rows: bad argument (n=%lld)", (long long)n);
+    return DCNR_BAD_ARG;
+  }
+  TRY(nbr_update_shape("dcnr_cosine_neighbor_table_rows", N, d, k));
+  if (n == 0) return DCNR_OK;
+  if (!rows || !nbr || !ws) {
+    set_error("dcnr_cosine_neighbor_table_rows: null argument");
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  // (bytes: as the build's -- every chunk of queries streams the table again)
+  ProfScope ps(DCNR_K_KNN, s, (double)N * (4.0 * d + 4.0) + (double)n * (4.0 * d + 12.0 * k + 4.0));
+  const bf16* tb = (const bf16*)packed;
   const UpdWs w = carve_upd(ws, N, d, k, 0);
   if (ws_bytes < w.c_total) {
     set_error("neighbor_table_rows: workspace too small");
@@ -2842,11 +3013,11 @@ dcnr_status neighbor_table_rows(const float* t, const float* inv, const bf16* tb
   }
   for (int64_t lo = 0; lo < n; lo += NBR_CHUNK) {
     const int64_t Q = std::min(NBR_CHUNK, n - lo);
-    hipLaunchKernelGGL(upd_gather_kernel, dim3((unsigned)cdiv(Q * d, 256)), dim3(256), 0, s, t, (int)N, d, rows + lo, Q,
-                       w.q);
+    hipLaunchKernelGGL(upd_gather_kernel, dim3((unsigned)cdiv(Q * d, 256)), dim3(256), 0, s, table, (int)N, d,
+                       rows + lo, Q, w.q);
     DCNR_LAUNCH_CHECK();
-    TRY_ST(cosine_topk(t, inv, tb, N, d, w.q, Q, k, w.nbr.idx, w.nbr.dist, w.nbr.topk, w.nbr.topk_bytes, s,
-                       /*allow_v3=*/false));
+    TRY(cosine_topk(table, inv_norms, tb, N, d, w.q, Q, k, w.nbr.idx, w.nbr.dist, w.nbr.topk, w.nbr.topk_bytes, s,
+                    /*allow_v3=*/false));
     hipLaunchKernelGGL(upd_scatter_kernel, dim3((unsigned)cdiv(Q * k, 256)), dim3(256), 0, s, w.nbr.idx, Q, k, (int)N,
                        rows + lo, nbr);
     DCNR_LAUNCH_CHECK();
@@ -2854,8 +3025,14 @@ dcnr_status neighbor_table_rows(const float* t, const float* inv, const bf16* tb
   return DCNR_OK;
 }
 
-dcnr_status topk_merge(const float* dist, const int64_t* idx, int lists, int64_t Q, int k,
-                       int64_t* out_idx, float* out_dist, hipStream_t s) {
+dcnr_status dcnr_topk_merge(const float* dist, const int64_t* idx, int32_t lists, int64_t Q,
+                            int32_t k, int64_t* out_idx, float* out_dist, dcnr_stream_t stream) {
+  if (!dist || !idx || !out_idx || !out_dist || Q < 0) {
+    set_error("dcnr_topk_merge: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  ProfScope ps(DCNR_K_KNN, s, (double)lists * Q * k * 12.0 + Q * k * 12.0);
   if (k < 1 || lists < 1 || (int64_t)lists * k > TM_CAP) {
     set_error("topk_merge: %d lists of k=%d unsupported (lists * k <= %d)", lists, k, TM_CAP);
     return DCNR_UNSUPPORTED_SHAPE;
@@ -2867,4 +3044,4 @@ dcnr_status topk_merge(const float* dist, const int64_t* idx, int lists, int64_t
   return DCNR_OK;
 }
 
-}  // namespace dcnr
+}  // extern "C"

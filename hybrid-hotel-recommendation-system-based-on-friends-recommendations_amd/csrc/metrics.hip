@@ -296,13 +296,13 @@ __global__ void metrics_empty_kernel(dcnr_metrics* out) {
 
 }  // namespace
 
-size_t metrics_ws_bytes(int64_t n) {
+static size_t metrics_ws_bytes(int64_t n) {
   if (n <= 0) return 0;
   return carve(make_plan(n), n, nullptr).total;
 }
 
-dcnr_status eval_metrics(const float* z, const float* y, int64_t n, dcnr_metrics* out, void* ws,
-                         hipStream_t s) {
+static dcnr_status eval_metrics(const float* z, const float* y, int64_t n, dcnr_metrics* out, void* ws,
+                                hipStream_t s) {
   if (n == 0) {
     hipLaunchKernelGGL(metrics_empty_kernel, dim3(1), dim3(1), 0, s, out);
     DCNR_LAUNCH_CHECK();
@@ -310,7 +310,7 @@ dcnr_status eval_metrics(const float* z, const float* y, int64_t n, dcnr_metrics
   }
   const Plan p = make_plan(n);
   const Ws w = carve(p, n, ws);
-  TRY_ST(fill_zero(w.tot, (size_t)NPASS * NB * 4, s));
+  TRY(fill_zero(w.tot, (size_t)NPASS * NB * 4, s));
   hipLaunchKernelGGL(metrics_pass1_kernel, dim3(p.p1_blocks), dim3(P1_NT), 0, s, z, y, n, w.ka, w.tot,
                      w.part);
   DCNR_LAUNCH_CHECK();
@@ -889,18 +889,16 @@ __global__ void group_empty_kernel(dcnr_group_summary* out) {
 
 }  // namespace
 
-int group_metrics_passes(int64_t n_groups) { return group_passes(n_groups); }
-
-size_t group_metrics_ws_bytes(int64_t n, int64_t n_groups) {
+static size_t group_metrics_ws_bytes(int64_t n, int64_t n_groups) {
   if (n <= 0 || n_groups < 1) return 0;
   return gcarve(make_plan(n), group_passes(n_groups), n, nullptr).total;
 }
 
-dcnr_status eval_group_metrics(const float* z, const float* y, const int64_t* g, int64_t n,
-                               int64_t n_groups, const int32_t* ks_host, int32_t n_k,
-                               const double* discount, const double* ideal, dcnr_group_summary* out,
-                               dcnr_group_record* per_group, void* ws, hipStream_t s) {
-  if (per_group) TRY_ST(fill_zero(per_group, (size_t)n_groups * sizeof(dcnr_group_record), s));
+static dcnr_status eval_group_metrics(const float* z, const float* y, const int64_t* g, int64_t n,
+                                      int64_t n_groups, const int32_t* ks_host, int32_t n_k,
+                                      const double* discount, const double* ideal, dcnr_group_summary* out,
+                                      dcnr_group_record* per_group, void* ws, hipStream_t s) {
+  if (per_group) TRY(fill_zero(per_group, (size_t)n_groups * sizeof(dcnr_group_record), s));
   if (n == 0) {
     hipLaunchKernelGGL(group_empty_kernel, dim3(1), dim3(1), 0, s, out);
     DCNR_LAUNCH_CHECK();
@@ -913,7 +911,7 @@ dcnr_status eval_group_metrics(const float* z, const float* y, const int64_t* g,
   const int npass = group_passes(n_groups);
   const GWs w = gcarve(p, npass, n, ws);
   const int nb = p.auc_blocks;
-  TRY_ST(fill_zero(w.tot, gtot_bytes(npass), s));
+  TRY(fill_zero(w.tot, gtot_bytes(npass), s));
   hipLaunchKernelGGL(group_pass1_kernel, dim3(p.p1_blocks), dim3(P1_NT), 0, s, z, y, g, n, n_groups,
                      npass, w.ka, w.tot);
   DCNR_LAUNCH_CHECK();
@@ -1401,18 +1399,18 @@ __global__ void list_empty_kernel(dcnr_list_summary* out) {
 
 }  // namespace
 
-size_t list_metrics_ws_bytes(int64_t R, int64_t n_items) {
+static size_t list_metrics_ws_bytes(int64_t R, int64_t n_items) {
   if (R <= 0 || n_items < 1) return 0;
   return lcarve(R, n_items, nullptr).total;
 }
 
-dcnr_status eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* offsets,
-                              const int32_t* counts, int64_t R, int32_t at, const float* table,
-                              const float* inv_norms, int32_t d, int64_t n_items, const float* scores,
-                              const double* info, const int64_t* rel_rows, int64_t n_rel_rows,
-                              const int64_t* rel_offsets, const int32_t* ks_host, int32_t n_k,
-                              const double* discount, const double* ideal, dcnr_list_summary* out,
-                              dcnr_list_record* per_list, void* ws, hipStream_t s) {
+static dcnr_status eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* offsets,
+                                     const int32_t* counts, int64_t R, int32_t at, const float* table,
+                                     const float* inv_norms, int32_t d, int64_t n_items, const float* scores,
+                                     const double* info, const int64_t* rel_rows, int64_t n_rel_rows,
+                                     const int64_t* rel_offsets, const int32_t* ks_host, int32_t n_k,
+                                     const double* discount, const double* ideal, dcnr_list_summary* out,
+                                     dcnr_list_record* per_list, void* ws, hipStream_t s) {
   if (R == 0) {
     hipLaunchKernelGGL(list_empty_kernel, dim3(1), dim3(1), 0, s, out);
     DCNR_LAUNCH_CHECK();
@@ -1427,7 +1425,7 @@ dcnr_status eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* off
   for (int j = 0; j < GK; ++j) a.ks.k[j] = j < a.ks.nk ? ks_host[j] : 0;
   a.discount = discount; a.ideal = ideal; a.per_list = per_list;
   const LWs w = lcarve(R, n_items, ws);
-  TRY_ST(fill_zero(ws, w.clear, s));
+  TRY(fill_zero(ws, w.clear, s));
   const bool wave = at <= 32;
   const int lpb = wave ? LM_NT / WAVE : 1;
   const int nb = (int)std::min<int64_t>(LM_MAXB, cdiv(R, lpb));
@@ -1436,7 +1434,7 @@ dcnr_status eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* off
   const size_t lds = (size_t)lpb * at * list_row_stride(d, vec ? 4 : 1) * sizeof(float);
 #define DCNR_LIST_LAUNCH(TEAM, VEC)                                                              \
   do {                                                                                           \
-    TRY_ST(set_max_dyn_lds((const void*)list_metrics_kernel<TEAM, VEC>, lds));                   \
+    TRY(set_max_dyn_lds((const void*)list_metrics_kernel<TEAM, VEC>, lds));                   \
     hipLaunchKernelGGL((list_metrics_kernel<TEAM, VEC>), dim3(nb), dim3(LM_NT), lds, s, a, w.c,  \
                        w.part);                                                                  \
   } while (0)
@@ -1457,3 +1455,112 @@ dcnr_status eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* off
 
 }  // namespace dcnr
 
+using namespace dcnr;
+
+// the workspace check of the three entries: too small, then null
+static dcnr_status metrics_ws_check(const char* who, const void* ws, size_t ws_bytes, size_t need) {
+  if (ws_bytes < need) {
+    set_error("%s: workspace too small: %zu < %zu", who, ws_bytes, need);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  if (need && !ws) {
+    set_error("%s: null workspace", who);
+    return DCNR_BAD_ARG;
+  }
+  return DCNR_OK;
+}
+
+extern "C" {
+
+size_t dcnr_eval_metrics_workspace_size(int64_t n) { return metrics_ws_bytes(n); }
+
+dcnr_status dcnr_eval_metrics(const float* logits, const float* labels, int64_t n, dcnr_metrics* out,
+                              void* ws, size_t ws_bytes, dcnr_stream_t stream) {
+  if (n < 0 || n >= ((int64_t)1 << 31) || !out || (n > 0 && (!logits || !labels))) {
+    set_error("dcnr_eval_metrics: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  TRY(metrics_ws_check("dcnr_eval_metrics", ws, ws_bytes, metrics_ws_bytes(n)));
+  hipStream_t s = (hipStream_t)stream;
+  // algorithmic bytes: the inputs once, the keys written and read once per sort pass
+  TRYB(DCNR_K_HEAD, s, 8.0 * (double)n + 3.0 * 16.0 * (double)n,
+       eval_metrics(logits, labels, n, out, ws, s));
+  return DCNR_OK;
+}
+
+static bool group_metrics_sizes_ok(int64_t n, int64_t n_groups) {
+  return n >= 0 && n < ((int64_t)1 << 31) && n_groups >= 1 && n_groups <= ((int64_t)1 << 31) - 1;
+}
+
+size_t dcnr_eval_group_metrics_workspace_size(int64_t n, int64_t n_groups) {
+  return group_metrics_sizes_ok(n, n_groups) ? group_metrics_ws_bytes(n, n_groups) : 0;
+}
+
+dcnr_status dcnr_eval_group_metrics(const float* logits, const float* labels, const int64_t* groups,
+                                    int64_t n, int64_t n_groups, const int32_t* ks, int32_t n_k,
+                                    const double* discount, const double* ideal,
+                                    dcnr_group_summary* out, dcnr_group_record* per_group, void* ws,
+                                    size_t ws_bytes, dcnr_stream_t stream) {
+  bool ok = group_metrics_sizes_ok(n, n_groups) && out && n_k >= 0 && n_k <= DCNR_GROUP_MAX_K &&
+            (n == 0 || (logits && labels && groups)) && (n_k == 0 || (ks && discount && ideal));
+  for (int j = 0; ok && j < n_k; ++j)
+    ok = ks[j] >= 1 && ks[j] <= (1 << 20) && (j == 0 || ks[j] > ks[j - 1]);
+  if (!ok) {
+    set_error("dcnr_eval_group_metrics: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  TRY(metrics_ws_check("dcnr_eval_group_metrics", ws, ws_bytes, group_metrics_ws_bytes(n, n_groups)));
+  hipStream_t s = (hipStream_t)stream;
+  // algorithmic bytes: the inputs once, the keys written and read once per sort pass
+  // and read by the two walks
+  const double passes = (double)group_passes(n_groups);
+  TRYB(DCNR_K_HEAD, s, 16.0 * (double)n + (passes + 1.0) * 16.0 * (double)n,
+       eval_group_metrics(logits, labels, groups, n, n_groups, ks, n_k, discount, ideal, out,
+                          per_group, ws, s));
+  return DCNR_OK;
+}
+
+static bool list_metrics_shape_ok(int64_t R, int64_t n_items) {
+  return R <= ((int64_t)1 << 22) && n_items < ((int64_t)1 << 31);
+}
+
+size_t dcnr_eval_list_metrics_workspace_size(int64_t R, int64_t n_items) {
+  return list_metrics_shape_ok(R, n_items) ? list_metrics_ws_bytes(R, n_items) : 0;
+}
+
+dcnr_status dcnr_eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* offsets,
+                                   const int32_t* counts, int64_t R, int32_t at,
+                                   const float* table, const float* inv_norms, int32_t d,
+                                   int64_t n_items, const float* scores, const double* info,
+                                   const int64_t* rel_rows, int64_t n_rel_rows,
+                                   const int64_t* rel_offsets, const int32_t* ks, int32_t n_k,
+                                   const double* discount, const double* ideal,
+                                   dcnr_list_summary* out, dcnr_list_record* per_list, void* ws,
+                                   size_t ws_bytes, dcnr_stream_t stream) {
+  bool ok = R >= 0 && n >= 0 && n_rel_rows >= 0 && n_items >= 1 && at >= 1 && at <= 128 && d >= 1 &&
+            d <= 256 && out && n_k >= 0 && n_k <= DCNR_GROUP_MAX_K &&
+            (R == 0 || (offsets && table && inv_norms)) && (R == 0 || n == 0 || rows) &&
+            (!rel_offsets || n_rel_rows == 0 || rel_rows) && (n_k == 0 || ks) &&
+            (n_k == 0 || !rel_offsets || (discount && ideal));
+  for (int j = 0; ok && j < n_k; ++j) ok = ks[j] >= 1 && ks[j] <= at && (j == 0 || ks[j] > ks[j - 1]);
+  if (!ok) {
+    set_error("dcnr_eval_list_metrics: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  if (!list_metrics_shape_ok(R, n_items) || n > ((int64_t)1 << 30)) {
+    set_error("dcnr_eval_list_metrics: R %lld > 2^22, n %lld > 2^30 or n_items %lld >= 2^31",
+              (long long)R, (long long)n, (long long)n_items);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  TRY(metrics_ws_check("dcnr_eval_list_metrics", ws, ws_bytes, list_metrics_ws_bytes(R, n_items)));
+  hipStream_t s = (hipStream_t)stream;
+  // algorithmic bytes: the measured rows of the table at most once each, the
+  // row ids, the counts cleared, written and read
+  TRYB(DCNR_K_HEAD, s, (double)std::min<int64_t>(n, R * at) * (4.0 * d + 12.0) + 12.0 * (double)n_items,
+       eval_list_metrics(rows, n, offsets, counts, R, at, table, inv_norms, d, n_items, scores, info,
+                         rel_rows, n_rel_rows, rel_offsets, ks, n_k, discount, ideal, out, per_list,
+                         ws, s));
+  return DCNR_OK;
+}
+
+}  // extern "C"

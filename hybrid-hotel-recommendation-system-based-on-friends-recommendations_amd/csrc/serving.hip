@@ -1278,63 +1278,63 @@ __global__ __launch_bounds__(CI_NT) void csr_remove_kernel(CsrRemove a) {
 
 }  // namespace
 
-dcnr_status csr_remove(const int64_t* old_off, int64_t U, int64_t M_old, int n_payloads,
-                       const int32_t* const* old_val, const int64_t* removed, int64_t m,
-                       int64_t* new_off, int32_t* const* new_val, hipStream_t s) {
-  CsrRemove a;
-  a.old_off = old_off; a.removed = removed; a.new_off = new_off;
-  a.U = U; a.M_old = M_old; a.m = m;
-  a.n_payloads = n_payloads;
-  a.vec = 1;
-  for (int w = 0; w < 2; ++w) {
-    const bool on = w < n_payloads && m < M_old;
-    a.old_val[w] = on ? old_val[w] : nullptr;
-    a.new_val[w] = on ? new_val[w] : nullptr;
-    if (((uintptr_t)a.old_val[w] | (uintptr_t)a.new_val[w]) & 15) a.vec = 0;
-  }
-  // with every entry removed there are no payloads to write: the offsets only
-  a.n_pay_units = cdiv(M_old - m, CI_CHUNK);
-  a.n_units = a.n_pay_units + cdiv(U + 1, CI_CHUNK);
-  int64_t grid = a.n_units < CI_MAX_BLOCKS ? a.n_units : CI_MAX_BLOCKS;
-  a.units_per_block = cdiv(a.n_units, grid);
-  grid = cdiv(a.n_units, a.units_per_block);
-  hipLaunchKernelGGL(csr_remove_kernel, dim3((unsigned)grid), dim3(CI_NT), 0, s, a);
-  DCNR_LAUNCH_CHECK();
-  return DCNR_OK;
+// the neighbour source of a call: the table where one is given (nbr), else
+// the positives' own top-k lists
+template <class F>
+static dcnr_status with_neighbours(const int64_t* idx, int k, const int32_t* nbr, int kt, int64_t n_items, F f) {
+  return nbr ? f(NbrTable{nbr, kt, n_items}) : f(KnnLists{idx, k});
 }
 
-dcnr_status csr_insert(const int64_t* old_off, int64_t U_old, int64_t U_new, int64_t M_old,
-                       int n_payloads, const int32_t* const* old_val, const int64_t* touched,
-                       const int64_t* prefix, int64_t t, const int64_t* ins_pos,
-                       const int32_t* const* ins_val, int64_t m, int64_t* new_off,
-                       int32_t* const* new_val, hipStream_t s) {
-  CsrInsert a;
-  a.old_off = old_off; a.touched = touched; a.prefix = prefix; a.ins_pos = ins_pos;
-  a.new_off = new_off;
-  a.U_old = U_old; a.U_new = U_new; a.M_old = M_old; a.m = m; a.t = t;
-  a.n_payloads = n_payloads;
-  a.vec = 1;
-  for (int w = 0; w < 2; ++w) {
-    const bool on = w < n_payloads && m > 0;
-    a.old_val[w] = on ? old_val[w] : nullptr;
-    a.ins_val[w] = on ? ins_val[w] : nullptr;
-    a.new_val[w] = on ? new_val[w] : nullptr;
-    if (((uintptr_t)a.old_val[w] | (uintptr_t)a.new_val[w]) & 15) a.vec = 0;
+static dcnr_status candidate_union(const int64_t* pos, int64_t Q, const int64_t* idx, int k,
+                                   const int32_t* nbr, int kt, int64_t n_items, int64_t* out,
+                                   int32_t* out_count, hipStream_t s) {
+  if (Q < 0 || k < 1 || Q * k > SV_MAX) {
+    set_error("candidate_union: Q*k=%lld exceeds %d", (long long)(Q * k), SV_MAX);
+    return DCNR_UNSUPPORTED_SHAPE;
   }
-  // without inserts the payloads are the old generation's: the offsets only
-  a.n_pay_units = m > 0 ? cdiv(M_old + m, CI_CHUNK) : 0;
-  a.n_units = a.n_pay_units + cdiv(U_new + 1, CI_CHUNK);
-  int64_t grid = a.n_units < CI_MAX_BLOCKS ? a.n_units : CI_MAX_BLOCKS;
-  a.units_per_block = cdiv(a.n_units, grid);
-  grid = cdiv(a.n_units, a.units_per_block);
-  hipLaunchKernelGGL(csr_insert_kernel, dim3((unsigned)grid), dim3(CI_NT), 0, s, a);
-  DCNR_LAUNCH_CHECK();
-  return DCNR_OK;
+  return with_neighbours(idx, k, nbr, kt, n_items, [&](auto src) {
+    hipLaunchKernelGGL(union_kernel<decltype(src)>, dim3(1), dim3(SV_NT), 0, s, pos, Q, src, k, out, out_count);
+    DCNR_LAUNCH_CHECK();
+    return DCNR_OK;
+  });
 }
 
-dcnr_status gather_rows(const int64_t* idx, int64_t n, int64_t n_src, int n_arrays,
-                        const void* const* src, void* const* dst, const int64_t* row_bytes,
-                        hipStream_t s) {
+// ---- a batch of R requests: one workgroup per request
+// (the MMR's workspace: the ranked lists [R][cap])
+struct RequestsWs { int64_t* rrows; float* rscores; };
+static RequestsWs requests_ws(Bump& b, int64_t R, int cap) {
+  RequestsWs w;
+  w.rrows = (int64_t*)b.take((size_t)R * cap * sizeof(int64_t));
+  w.rscores = (float*)b.take((size_t)R * cap * sizeof(float));
+  return w;
+}
+static size_t requests_ws_bytes(int64_t R, int cap) {
+  Bump b(nullptr);
+  requests_ws(b, R, cap);
+  return b.off;
+}
+
+// ---- requests by user (the interaction store on the device)
+static ReqStore req_store(const dcnr_interactions& s) {
+  return ReqStore{s.n_reviewers, s.friend_offsets, s.friend_rows, s.n_friend_rows,
+                  s.review_offsets, s.review_items, s.review_rows, s.n_reviews};
+}
+
+}  // namespace dcnr
+
+using namespace dcnr;
+
+extern "C" {
+
+dcnr_status dcnr_gather_rows(const int64_t* idx, int64_t n, int64_t n_src, int32_t n_arrays,
+                             const void* const* src, void* const* dst, const int64_t* row_bytes,
+                             dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!src || !dst || !row_bytes || (n > 0 && !idx)) {
+    set_error("dcnr_gather_rows: null argument");
+    return DCNR_BAD_ARG;
+  }
+  ProfScope ps(DCNR_K_SERVE, s);
   if (n_arrays < 1 || n_arrays > 8 || n < 0 || n_src < 1) {
     set_error("gather_rows: 1..8 arrays, n_src >= 1");
     return DCNR_BAD_ARG;
@@ -1358,39 +1358,64 @@ dcnr_status gather_rows(const int64_t* idx, int64_t n, int64_t n_src, int n_arra
   return DCNR_OK;
 }
 
-// the neighbour source of a call: the table where one is given (nbr), else
-// the positives' own top-k lists
-template <class F>
-dcnr_status with_neighbours(const int64_t* idx, int k, const int32_t* nbr, int kt, int64_t n_items, F f) {
-  return nbr ? f(NbrTable{nbr, kt, n_items}) : f(KnnLists{idx, k});
-}
-
-dcnr_status candidate_union(const int64_t* pos, int64_t Q, const int64_t* idx, int k,
-                            const int32_t* nbr, int kt, int64_t n_items, int64_t* out,
-                            int32_t* out_count, hipStream_t s) {
-  if (Q < 0 || k < 1 || Q * k > SV_MAX) {
-    set_error("candidate_union: Q*k=%lld exceeds %d", (long long)(Q * k), SV_MAX);
-    return DCNR_UNSUPPORTED_SHAPE;
+dcnr_status dcnr_candidate_union(const int64_t* positives, int64_t Q, const int64_t* knn_idx,
+                                 int32_t k, int64_t* out_rows, int32_t* out_count,
+                                 dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (Q < 0 || (Q > 0 && (!positives || !knn_idx || !out_rows || !out_count))) {
+    set_error("dcnr_candidate_union: bad argument");
+    return DCNR_BAD_ARG;
   }
-  return with_neighbours(idx, k, nbr, kt, n_items, [&](auto src) {
-    hipLaunchKernelGGL(union_kernel<decltype(src)>, dim3(1), dim3(SV_NT), 0, s, pos, Q, src, k, out, out_count);
-    DCNR_LAUNCH_CHECK();
-    return DCNR_OK;
-  });
+  if (Q == 0) return DCNR_OK;
+  TRYP(DCNR_K_SERVE, s, candidate_union(positives, Q, knn_idx, k, nullptr, 0, 0, out_rows, out_count, s));
+  return DCNR_OK;
 }
 
-dcnr_status ranking_batch(const int64_t* rows, int64_t n, int64_t user_row, const int64_t* item_cat,
-                          int K, const float* item_num, int F, int64_t n_items, int64_t* user_out,
-                          int64_t* item_out, int64_t* cat_out, float* num_out, hipStream_t s) {
+dcnr_status dcnr_candidate_union_table(const int64_t* positives, int64_t Q, const int32_t* nbr,
+                                       int32_t kt, int64_t n_items, int32_t k, int64_t* out_rows,
+                                       int32_t* out_count, dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (Q < 0 || k < 1 || kt < k || n_items < 1 ||
+      (Q > 0 && (!positives || !nbr || !out_rows || !out_count))) {
+    set_error("dcnr_candidate_union_table: bad argument (Q=%lld, k=%d, kt=%d, n_items=%lld)",
+              (long long)Q, k, kt, (long long)n_items);
+    return DCNR_BAD_ARG;
+  }
+  if (Q == 0) return DCNR_OK;
+  TRYP(DCNR_K_SERVE, s, candidate_union(positives, Q, nullptr, k, nbr, kt, n_items, out_rows, out_count, s));
+  return DCNR_OK;
+}
+
+dcnr_status dcnr_ranking_batch(const int64_t* item_rows, int64_t n, int64_t user_row,
+                               const int64_t* item_cat, int32_t n_cat, const float* item_num,
+                               int32_t n_num, int64_t n_items, int64_t* user_ids,
+                               int64_t* item_ids, int64_t* cat_features, float* num_features,
+                               dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n < 0 || n_items < 1 || n_cat < 0 || n_num < 0 ||
+      (n > 0 && (!item_rows || !user_ids || !item_ids || (n_cat && (!item_cat || !cat_features)) ||
+                 (n_num && (!item_num || !num_features))))) {
+    set_error("dcnr_ranking_batch: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  ProfScope ps(DCNR_K_SERVE, s);
   if (n <= 0) return DCNR_OK;
   dim3 blk(16, 16);
-  hipLaunchKernelGGL(batch_kernel, dim3((unsigned)cdiv(n, 16)), blk, 0, s, rows, n, user_row,
-                     item_cat, K, item_num, F, n_items, user_out, item_out, cat_out, num_out);
+  hipLaunchKernelGGL(batch_kernel, dim3((unsigned)cdiv(n, 16)), blk, 0, s, item_rows, n, user_row,
+                     item_cat, n_cat, item_num, n_num, n_items, user_ids, item_ids, cat_features,
+                     num_features);
   DCNR_LAUNCH_CHECK();
   return DCNR_OK;
 }
 
-dcnr_status rank_desc(const float* scores, int64_t n, int64_t* order, hipStream_t s) {
+dcnr_status dcnr_rank_by_score(const float* scores, int64_t n, int64_t* order,
+                               dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n < 0 || (n > 0 && (!scores || !order))) {
+    set_error("dcnr_rank_by_score: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  ProfScope ps(DCNR_K_SERVE, s);
   if (n > SV_MAX) {
     set_error("rank_by_score: n=%lld exceeds %d", (long long)n, SV_MAX);
     return DCNR_UNSUPPORTED_SHAPE;
@@ -1401,10 +1426,18 @@ dcnr_status rank_desc(const float* scores, int64_t n, int64_t* order, hipStream_
   return DCNR_OK;
 }
 
-dcnr_status mmr_rerank(const float* table, const float* inv, int d, const int64_t* rows,
-                       const float* scores, int64_t n, float lambda, int top_k, int64_t* out_pos,
-                       int32_t* out_count, hipStream_t s) {
-  if (n > SV_MAX || d > 256 || d < 1 || top_k < 1) {
+dcnr_status dcnr_mmr_rerank(const float* table, const float* inv_norms, int32_t d,
+                            const int64_t* rows, const float* scores, int64_t n,
+                            float lambda_param, int32_t top_k, int64_t* out_pos,
+                            int32_t* out_count, dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n < 0 || top_k < 1 || (n > 0 && (!table || !inv_norms || !rows || !scores || !out_pos ||
+                                       !out_count))) {
+    set_error("dcnr_mmr_rerank: bad argument");
+    return DCNR_BAD_ARG;
+  }
+  ProfScope ps(DCNR_K_SERVE, s);
+  if (n > SV_MAX || d > 256 || d < 1) {   // (top_k >= 1: checked above)
     set_error("mmr_rerank: n=%lld (max %d), d=%d (max 256), top_k=%d", (long long)n, SV_MAX, d,
               top_k);
     return DCNR_UNSUPPORTED_SHAPE;
@@ -1414,121 +1447,358 @@ dcnr_status mmr_rerank(const float* table, const float* inv, int d, const int64_
   // same order, as the kernel that re-reads them from the table)
   const size_t lds = mmr_lds_bytes(n, d);
   if (lds <= MMR_LDS_MAX) {
-    TRY_ST(set_max_dyn_lds((const void*)mmr_lds_kernel, MMR_LDS_MAX));
-    hipLaunchKernelGGL(mmr_lds_kernel, dim3(1), dim3(SV_NT), lds, s, table, inv, d, rows, scores, (int)n,
-                       lambda, top_k, out_pos, out_count);
+    TRY(set_max_dyn_lds((const void*)mmr_lds_kernel, MMR_LDS_MAX));
+    hipLaunchKernelGGL(mmr_lds_kernel, dim3(1), dim3(SV_NT), lds, s, table, inv_norms, d, rows, scores,
+                       (int)n, lambda_param, top_k, out_pos, out_count);
   } else {
-    hipLaunchKernelGGL(mmr_kernel, dim3(1), dim3(SV_NT), 0, s, table, inv, d, rows, scores, (int)n,
-                       lambda, top_k, out_pos, out_count);
+    hipLaunchKernelGGL(mmr_kernel, dim3(1), dim3(SV_NT), 0, s, table, inv_norms, d, rows, scores, (int)n,
+                       lambda_param, top_k, out_pos, out_count);
   }
   DCNR_LAUNCH_CHECK();
   return DCNR_OK;
 }
 
-// ---- a batch of R requests: one workgroup per request
-int requests_cap_max() { return SV_MAX; }
+// ---- a batch of requests (the req_* kernels).  Shapes the kernels
+// do not take: more requests than DCNR_REQ_MAX_R (one workgroup each), k above
+// the top-k's 64, a set CSR of 2^31 rows or more.
+namespace {
+constexpr int64_t DCNR_REQ_MAX_R = int64_t(1) << 22;
 
-size_t requests_ws_bytes(int64_t R, int cap) {
-  Bump b(nullptr);
-  requests_ws(b, R, cap);
-  return b.off;
+// the checks the three entry points share; DCNR_OK: launch
+dcnr_status requests_shape(const char* who, int64_t R, int32_t cap) {
+  if (R < 0 || cap < 1 || cap > SV_MAX) {
+    set_error("%s: R=%lld (>= 0), cap=%d (1..%d)", who, (long long)R, cap, SV_MAX);
+    return DCNR_BAD_ARG;
+  }
+  if (R > DCNR_REQ_MAX_R) {
+    set_error("%s: R=%lld exceeds %lld requests per call", who, (long long)R,
+              (long long)DCNR_REQ_MAX_R);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  return DCNR_OK;
+}
+}  // namespace
+
+size_t dcnr_requests_workspace_size(int64_t R, int64_t Q_total, int32_t k, int32_t cap) {
+  if (R <= 0 || R > DCNR_REQ_MAX_R || Q_total < 0 || k < 1 || cap < 1 || cap > SV_MAX)
+    return 0;
+  return requests_ws_bytes(R, cap) + 256;
 }
 
-RequestsWs requests_ws(Bump& b, int64_t R, int cap) {
-  RequestsWs w;
-  w.rrows = (int64_t*)b.take((size_t)R * cap * sizeof(int64_t));
-  w.rscores = (float*)b.take((size_t)R * cap * sizeof(float));
-  return w;
-}
-
-dcnr_status requests_candidates(const RequestsIn& in, int min_candidates, int64_t n_items, int cap,
-                                int64_t* out_rows, int32_t* out_count, int32_t* status,
-                                int64_t* offsets, int64_t* host_offsets, int32_t* host_status,
-                                hipStream_t s) {
-  ReqSets st{in.set_rows, in.n_set_rows, in.set_off, in.S, in.allowed, in.excluded, in.fallback};
-  TRY_ST(with_neighbours(in.idx, in.k, in.nbr, in.kt, n_items, [&](auto src) {
-    hipLaunchKernelGGL(req_candidates_kernel<decltype(src)>, dim3((unsigned)in.R), dim3(SV_NT), 0, s, in.pos,
-                       in.pos_off, in.R, in.Q_total, src, in.k, st, min_candidates, n_items, cap,
-                       out_rows, out_count, status);
+namespace {
+// dcnr_requests_candidates and its table form: neighbours from knn_idx
+// [Q_total][k], or (nbr != null) from the item neighbour table [n_items][kt]
+dcnr_status requests_candidates_api(const char* who, const int64_t* positives,
+                                    const int64_t* pos_offsets, int64_t R, int64_t Q_total,
+                                    const int64_t* knn_idx, const int32_t* nbr, int32_t kt, int32_t k,
+                                    const int64_t* set_rows, int64_t n_set_rows,
+                                    const int64_t* set_offsets, int32_t S, const int32_t* allowed,
+                                    const int32_t* excluded, const int32_t* fallback,
+                                    int32_t min_candidates, int64_t n_items, int32_t cap,
+                                    int64_t* out_rows, int32_t* out_count, int32_t* status,
+                                    int64_t* offsets, int64_t* host_offsets, int32_t* host_status,
+                                    hipStream_t s) {
+  TRY(requests_shape(who, R, cap));
+  if (Q_total < 0 || k < 1 || S < 0 || n_set_rows < 0 || n_items < 1) {
+    set_error("%s: Q_total=%lld, k=%d, S=%d, n_set_rows=%lld, n_items=%lld", who,
+              (long long)Q_total, k, S, (long long)n_set_rows, (long long)n_items);
+    return DCNR_BAD_ARG;
+  }
+  if (R > 0 && (!pos_offsets || !out_rows || !out_count || !status || !offsets ||
+                (Q_total > 0 && (!positives || (!knn_idx && !nbr))) || (S > 0 && !set_offsets) ||
+                (n_set_rows > 0 && !set_rows) ||
+                (S == 0 && (allowed || excluded || fallback)))) {
+    set_error("%s: null argument (or set indices without sets)", who);
+    return DCNR_BAD_ARG;
+  }
+  if (k > 64 || n_set_rows > INT32_MAX) {
+    set_error("%s: k=%d (max 64), n_set_rows=%lld (max 2^31 - 1)", who, k, (long long)n_set_rows);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  if (R == 0) return DCNR_OK;
+  ProfScope ps(DCNR_K_SERVE, s);
+  ReqSets st{set_rows, n_set_rows, set_offsets, S, allowed, excluded, fallback};
+  TRY(with_neighbours(knn_idx, k, nbr, kt, n_items, [&](auto src) {
+    hipLaunchKernelGGL(req_candidates_kernel<decltype(src)>, dim3((unsigned)R), dim3(SV_NT), 0, s, positives,
+                       pos_offsets, R, Q_total, src, k, st, min_candidates, n_items, cap, out_rows,
+                       out_count, status);
     DCNR_LAUNCH_CHECK();
     return DCNR_OK;
   }));
-  hipLaunchKernelGGL(req_offsets_kernel, dim3(1), dim3(SV_NT), 0, s, out_count, status, in.R, cap,
-                     offsets, host_offsets, host_status);
+  hipLaunchKernelGGL(req_offsets_kernel, dim3(1), dim3(SV_NT), 0, s, out_count, status, R, cap, offsets,
+                     host_offsets, host_status);
   DCNR_LAUNCH_CHECK();
   return DCNR_OK;
 }
+}  // namespace
 
-dcnr_status requests_batch(const int64_t* slots, int cap, const int64_t* offsets, int64_t R,
-                           int64_t n, const int64_t* user_rows, const int64_t* item_cat, int K,
-                           const float* item_num, int F, int64_t n_items, int64_t* user_out,
-                           int64_t* item_out, int64_t* cat_out, float* num_out, hipStream_t s) {
+dcnr_status dcnr_requests_candidates(const int64_t* positives, const int64_t* pos_offsets,
+                                     int64_t R, int64_t Q_total, const int64_t* knn_idx, int32_t k,
+                                     const int64_t* set_rows, int64_t n_set_rows,
+                                     const int64_t* set_offsets, int32_t S, const int32_t* allowed,
+                                     const int32_t* excluded, const int32_t* fallback,
+                                     int32_t min_candidates, int64_t n_items, int32_t cap,
+                                     int64_t* out_rows, int32_t* out_count, int32_t* status,
+                                     int64_t* offsets, int64_t* host_offsets,
+                                     int32_t* host_status, dcnr_stream_t stream) {
+  return requests_candidates_api("dcnr_requests_candidates", positives, pos_offsets, R, Q_total,
+                                 knn_idx, nullptr, 0, k, set_rows, n_set_rows, set_offsets, S, allowed,
+                                 excluded, fallback, min_candidates, n_items, cap, out_rows, out_count,
+                                 status, offsets, host_offsets, host_status, (hipStream_t)stream);
+}
+
+dcnr_status dcnr_requests_candidates_table(const int64_t* positives, const int64_t* pos_offsets,
+                                           int64_t R, int64_t Q_total, const int32_t* nbr, int32_t kt,
+                                           int32_t k, const int64_t* set_rows, int64_t n_set_rows,
+                                           const int64_t* set_offsets, int32_t S,
+                                           const int32_t* allowed, const int32_t* excluded,
+                                           const int32_t* fallback, int32_t min_candidates,
+                                           int64_t n_items, int32_t cap, int64_t* out_rows,
+                                           int32_t* out_count, int32_t* status, int64_t* offsets,
+                                           int64_t* host_offsets, int32_t* host_status,
+                                           dcnr_stream_t stream) {
+  if (kt < k || (R > 0 && Q_total > 0 && !nbr)) {
+    set_error("dcnr_requests_candidates_table: kt=%d below k=%d, or a null table", kt, k);
+    return DCNR_BAD_ARG;
+  }
+  return requests_candidates_api("dcnr_requests_candidates_table", positives, pos_offsets, R, Q_total,
+                                 nullptr, nbr, kt, k, set_rows, n_set_rows, set_offsets, S, allowed,
+                                 excluded, fallback, min_candidates, n_items, cap, out_rows, out_count,
+                                 status, offsets, host_offsets, host_status, (hipStream_t)stream);
+}
+
+dcnr_status dcnr_requests_ranking_batch(const int64_t* cand_rows, int32_t cap,
+                                        const int64_t* offsets, int64_t R, int64_t n,
+                                        const int64_t* user_rows, const int64_t* item_cat,
+                                        int32_t n_cat, const float* item_num, int32_t n_num,
+                                        int64_t n_items, int64_t* user_ids, int64_t* item_ids,
+                                        int64_t* cat_features, float* num_features,
+                                        dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TRY(requests_shape("dcnr_requests_ranking_batch", R, cap));
+  if (n < 0 || n > R * cap || n_items < 1 || n_cat < 0 || n_num < 0 ||
+      (n > 0 && (!cand_rows || !offsets || !user_rows || !user_ids || !item_ids ||
+                 (n_cat && (!item_cat || !cat_features)) ||
+                 (n_num && (!item_num || !num_features))))) {
+    set_error("dcnr_requests_ranking_batch: bad argument (n=%lld of at most R*cap=%lld)",
+              (long long)n, (long long)(R * cap));
+    return DCNR_BAD_ARG;
+  }
+  if (R == 0) return DCNR_OK;
+  ProfScope ps(DCNR_K_SERVE, s);
   if (n <= 0) return DCNR_OK;
   dim3 blk(16, 16);
-  hipLaunchKernelGGL(req_batch_kernel, dim3((unsigned)cdiv(n, 16)), blk, 0, s, slots, cap, offsets,
-                     R, n, user_rows, item_cat, K, item_num, F, n_items, user_out, item_out,
-                     cat_out, num_out);
+  hipLaunchKernelGGL(req_batch_kernel, dim3((unsigned)cdiv(n, 16)), blk, 0, s, cand_rows, cap, offsets,
+                     R, n, user_rows, item_cat, n_cat, item_num, n_num, n_items, user_ids, item_ids,
+                     cat_features, num_features);
   DCNR_LAUNCH_CHECK();
   return DCNR_OK;
 }
 
-dcnr_status requests_rank_mmr(const float* logits, int64_t n, const int64_t* slots, int cap,
-                              const int64_t* offsets, int64_t R, const float* table,
-                              const float* inv, int d, int64_t n_items, const float* lambda,
-                              const int32_t* top_k, const RequestsWs& w, int64_t* out_rows,
-                              float* out_logits, int32_t* out_count, int32_t* status,
-                              hipStream_t s) {
-  TRY_ST(set_max_dyn_lds((const void*)req_rank_mmr_kernel, MMR_LDS_MAX));
+dcnr_status dcnr_requests_rank_mmr(const float* logits, int64_t n, const int64_t* cand_rows,
+                                   int32_t cap, const int64_t* offsets, int64_t R,
+                                   const float* table, const float* inv_norms, int32_t d,
+                                   int64_t n_items, const float* lambda_param,
+                                   const int32_t* top_k, int64_t* out_rows, float* out_logits,
+                                   int32_t* out_count, int32_t* status, void* ws, size_t ws_bytes,
+                                   dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TRY(requests_shape("dcnr_requests_rank_mmr", R, cap));
+  if (n < 0 || n > R * cap || d < 1 || d > 256 || n_items < 1 ||
+      (R > 0 && (!cand_rows || !offsets || !table || !inv_norms || !lambda_param || !top_k ||
+                 !out_count || !status || !ws || (n > 0 && (!logits || !out_rows || !out_logits))))) {
+    set_error("dcnr_requests_rank_mmr: bad argument (n=%lld of at most R*cap=%lld, d=%d of 1..256)",
+              (long long)n, (long long)(R * cap), d);
+    return DCNR_BAD_ARG;
+  }
+  if (R == 0) return DCNR_OK;
+  const size_t need = requests_ws_bytes(R, cap) + 256;
+  if (ws_bytes < need) {
+    set_error("dcnr_requests_rank_mmr: workspace too small: %zu < %zu", ws_bytes, need);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  Bump b((void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255));
+  const RequestsWs w = requests_ws(b, R, cap);
+  ProfScope ps(DCNR_K_SERVE, s);
+  TRY(set_max_dyn_lds((const void*)req_rank_mmr_kernel, MMR_LDS_MAX));
   hipLaunchKernelGGL(req_rank_mmr_kernel, dim3((unsigned)R), dim3(SV_NT), MMR_LDS_MAX, s, logits, n,
-                     slots, cap, offsets, R, table, inv, d, n_items, lambda, top_k, w.rrows,
-                     w.rscores, out_rows, out_logits, out_count, status);
+                     cand_rows, cap, offsets, R, table, inv_norms, d, n_items, lambda_param, top_k,
+                     w.rrows, w.rscores, out_rows, out_logits, out_count, status);
   DCNR_LAUNCH_CHECK();
   return DCNR_OK;
 }
 
-// ---- requests by user (the interaction store on the device)
-static ReqStore req_store(const dcnr_interactions& s) {
-  return ReqStore{s.n_reviewers, s.friend_offsets, s.friend_rows, s.n_friend_rows,
-                  s.review_offsets, s.review_items, s.review_rows, s.n_reviews};
-}
+// ---- requests by user.  The store's lengths are checked here; what lies in
+// device memory (offsets, rows) the kernels check against them.
+namespace {
+constexpr int64_t DCNR_STORE_MAX_ITEMS = int64_t(1) << 29;   // hotel row * 4 + class bits in 32
 
-dcnr_status requests_sources(const dcnr_interactions& store, const int32_t* reviewers,
-                             const int32_t* modes, int64_t R, int64_t n_items,
-                             const int64_t* pos_off, int64_t Q_total, int64_t* pos,
-                             const int64_t* neg_off, int64_t neg_lo, int64_t neg_hi, int64_t* neg,
-                             int32_t* counts, int32_t* status, int32_t* host_counts,
-                             int32_t* host_status, hipStream_t s) {
-  hipLaunchKernelGGL(req_sources_kernel, dim3((unsigned)R), dim3(SV_NT), 0, s, req_store(store),
-                     reviewers, modes, R, n_items, pos_off, Q_total, pos, neg_off, neg_lo, neg_hi,
-                     neg, counts, status, host_counts, host_status);
+dcnr_status store_shape(const char* who, const dcnr_interactions* st, int64_t n_items) {
+  if (!st || st->n_reviewers < 0 || st->n_friend_rows < 0 || st->n_reviews < 0 || n_items < 1 ||
+      !st->friend_offsets || !st->review_offsets || (st->n_friend_rows > 0 && !st->friend_rows) ||
+      (st->n_reviews > 0 && (!st->review_items || !st->review_rows))) {
+    set_error("%s: null or negative store field, or n_items < 1", who);
+    return DCNR_BAD_ARG;
+  }
+  if (n_items > DCNR_STORE_MAX_ITEMS || st->n_reviewers >= INT32_MAX ||
+      st->n_reviews > INT32_MAX || st->n_friend_rows > INT32_MAX) {
+    set_error("%s: n_items=%lld (max 2^29), n_reviewers=%lld, n_reviews=%lld, n_friend_rows=%lld "
+              "(max 2^31 - 1)", who, (long long)n_items, (long long)st->n_reviewers,
+              (long long)st->n_reviews, (long long)st->n_friend_rows);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  return DCNR_OK;
+}
+}  // namespace
+
+dcnr_status dcnr_requests_sources(const dcnr_interactions* store, const int32_t* reviewers,
+                                  const int32_t* modes, int64_t R, int64_t n_items,
+                                  const int64_t* pos_offsets, int64_t Q_total, int64_t* positives,
+                                  const int64_t* neg_offsets, int64_t neg_lo, int64_t neg_hi,
+                                  int64_t* neg_rows, int32_t* counts, int32_t* status,
+                                  int32_t* host_counts, int32_t* host_status,
+                                  dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TRY(requests_shape("dcnr_requests_sources", R, 1));
+  TRY(store_shape("dcnr_requests_sources", store, n_items));
+  if (Q_total < 0 || neg_lo < 0 || neg_hi < neg_lo ||
+      (R > 0 && (!reviewers || !modes || !pos_offsets || !neg_offsets || !counts || !status ||
+                 (Q_total > 0 && !positives) || (neg_hi > neg_lo && !neg_rows)))) {
+    set_error("dcnr_requests_sources: bad argument (Q_total=%lld, negatives [%lld, %lld))",
+              (long long)Q_total, (long long)neg_lo, (long long)neg_hi);
+    return DCNR_BAD_ARG;
+  }
+  if (R == 0) return DCNR_OK;
+  ProfScope ps(DCNR_K_SERVE, s);
+  hipLaunchKernelGGL(req_sources_kernel, dim3((unsigned)R), dim3(SV_NT), 0, s, req_store(*store),
+                     reviewers, modes, R, n_items, pos_offsets, Q_total, positives, neg_offsets, neg_lo,
+                     neg_hi, neg_rows, counts, status, host_counts, host_status);
   DCNR_LAUNCH_CHECK();
   return DCNR_OK;
 }
 
-dcnr_status requests_recommended_by(const dcnr_interactions& store, const int32_t* reviewers,
-                                    int64_t R, int64_t n_items, const int64_t* out_rows, int64_t n,
-                                    const int64_t* offsets, const int32_t* out_count,
-                                    const int64_t* list_off, int64_t L_total, int32_t* lists,
-                                    int32_t* by_count, int64_t* by_off, int32_t* by_reviewers,
-                                    int32_t* status, hipStream_t s) {
+dcnr_status dcnr_requests_recommended_by(const dcnr_interactions* store, const int32_t* reviewers,
+                                         int64_t R, int64_t n_items, const int64_t* out_rows,
+                                         int64_t n, const int64_t* offsets,
+                                         const int32_t* out_count, const int64_t* list_offsets,
+                                         int64_t n_list_rows, int32_t* lists, int32_t* by_count,
+                                         int64_t* by_offsets, int32_t* by_reviewers,
+                                         int32_t* status, dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TRY(requests_shape("dcnr_requests_recommended_by", R, 1));
+  TRY(store_shape("dcnr_requests_recommended_by", store, n_items));
+  if (n < 0 || n > R * SV_MAX || n_list_rows < 0 ||
+      (R > 0 && (!reviewers || !offsets || !out_count || !list_offsets || !by_offsets || !status ||
+                 (n > 0 && (!out_rows || !by_count)) ||
+                 (n_list_rows > 0 && (!lists || !by_reviewers))))) {
+    set_error("dcnr_requests_recommended_by: bad argument (n=%lld, n_list_rows=%lld)",
+              (long long)n, (long long)n_list_rows);
+    return DCNR_BAD_ARG;
+  }
+  if (R == 0) return DCNR_OK;
+  ProfScope ps(DCNR_K_SERVE, s);
   // (positions no valid segment covers count 0)
-  if (n > 0) TRY_ST(fill_zero(by_count, (size_t)n * sizeof(int32_t), s));
+  if (n > 0) TRY(fill_zero(by_count, (size_t)n * sizeof(int32_t), s));
   hipLaunchKernelGGL(req_recommended_by_kernel, dim3((unsigned)R), dim3(SV_NT), 0, s,
-                     req_store(store), reviewers, R, n_items, out_rows, n, offsets, out_count,
-                     list_off, L_total, lists, by_count, status);
+                     req_store(*store), reviewers, R, n_items, out_rows, n, offsets, out_count,
+                     list_offsets, n_list_rows, lists, by_count, status);
   DCNR_LAUNCH_CHECK();
   // by_off = the exclusive sum of by_count over the n positions
   hipLaunchKernelGGL(req_offsets_kernel, dim3(1), dim3(SV_NT), 0, s, by_count,
-                     (const int32_t*)nullptr, n, INT_MAX, by_off, (int64_t*)nullptr,
+                     (const int32_t*)nullptr, n, INT_MAX, by_offsets, (int64_t*)nullptr,
                      (int32_t*)nullptr);
   DCNR_LAUNCH_CHECK();
-  const int64_t threads = n > L_total ? n : L_total;
+  const int64_t threads = n > n_list_rows ? n : n_list_rows;
   if (threads > 0) {
     hipLaunchKernelGGL(req_by_gather_kernel, dim3((unsigned)cdiv(threads, 256)), dim3(256), 0, s,
-                       lists, list_off, L_total, offsets, R, n, by_count, by_off, by_reviewers);
+                       lists, list_offsets, n_list_rows, offsets, R, n, by_count, by_offsets, by_reviewers);
     DCNR_LAUNCH_CHECK();
   }
   return DCNR_OK;
 }
 
-}  // namespace dcnr
+dcnr_status dcnr_csr_insert(const int64_t* old_offsets, int64_t n_old_owners, int64_t n_new_owners,
+                            int64_t n_old_entries, int32_t n_payloads,
+                            const int32_t* const* old_payloads, const int64_t* touched,
+                            const int64_t* insert_prefix, int64_t t, const int64_t* insert_pos,
+                            const int32_t* const* insert_payloads, int64_t m, int64_t* new_offsets,
+                            int32_t* const* new_payloads, dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  bool bad = !old_offsets || !new_offsets || n_old_owners < 0 || n_new_owners < n_old_owners ||
+             n_old_entries < 0 || n_payloads < 1 || n_payloads > 2 || t < 0 || m < 0 || t > m ||
+             (m > 0 && (t == 0 || !touched || !insert_prefix || !insert_pos || !old_payloads ||
+                        !insert_payloads || !new_payloads));
+  for (int w = 0; !bad && m > 0 && w < n_payloads; ++w)
+    bad = !insert_payloads[w] || !new_payloads[w] || (n_old_entries > 0 && !old_payloads[w]);
+  if (bad) {
+    set_error("dcnr_csr_insert: bad argument (owners %lld -> %lld, entries=%lld, payloads=%d, "
+              "t=%lld, m=%lld)", (long long)n_old_owners, (long long)n_new_owners,
+              (long long)n_old_entries, n_payloads, (long long)t, (long long)m);
+    return DCNR_BAD_ARG;
+  }
+  if (m == 0 && n_new_owners == n_old_owners) return DCNR_OK;
+  ProfScope ps(DCNR_K_SERVE, s);
+  CsrInsert a;
+  a.old_off = old_offsets; a.touched = touched; a.prefix = insert_prefix; a.ins_pos = insert_pos;
+  a.new_off = new_offsets;
+  a.U_old = n_old_owners; a.U_new = n_new_owners; a.M_old = n_old_entries; a.m = m; a.t = t;
+  a.n_payloads = n_payloads;
+  a.vec = 1;
+  for (int w = 0; w < 2; ++w) {
+    const bool on = w < n_payloads && m > 0;
+    a.old_val[w] = on ? old_payloads[w] : nullptr;
+    a.ins_val[w] = on ? insert_payloads[w] : nullptr;
+    a.new_val[w] = on ? new_payloads[w] : nullptr;
+    if (((uintptr_t)a.old_val[w] | (uintptr_t)a.new_val[w]) & 15) a.vec = 0;
+  }
+  // without inserts the payloads are the old generation's: the offsets only
+  a.n_pay_units = m > 0 ? cdiv(n_old_entries + m, CI_CHUNK) : 0;
+  a.n_units = a.n_pay_units + cdiv(n_new_owners + 1, CI_CHUNK);
+  int64_t grid = a.n_units < CI_MAX_BLOCKS ? a.n_units : CI_MAX_BLOCKS;
+  a.units_per_block = cdiv(a.n_units, grid);
+  grid = cdiv(a.n_units, a.units_per_block);
+  hipLaunchKernelGGL(csr_insert_kernel, dim3((unsigned)grid), dim3(CI_NT), 0, s, a);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
+dcnr_status dcnr_csr_remove(const int64_t* old_offsets, int64_t n_owners, int64_t n_old_entries,
+                            int32_t n_payloads, const int32_t* const* old_payloads,
+                            const int64_t* removed, int64_t m, int64_t* new_offsets,
+                            int32_t* const* new_payloads, dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const bool pay = m > 0 && m < n_old_entries;   // some payload words are copied
+  bool bad = !old_offsets || !new_offsets || n_owners < 0 || n_old_entries < 0 || n_payloads < 1 ||
+             n_payloads > 2 || m < 0 || m > n_old_entries || (m > 0 && !removed) ||
+             (pay && (!old_payloads || !new_payloads));
+  for (int w = 0; !bad && pay && w < n_payloads; ++w) bad = !old_payloads[w] || !new_payloads[w];
+  if (bad) {
+    set_error("dcnr_csr_remove: bad argument (owners=%lld, entries=%lld, payloads=%d, m=%lld)",
+              (long long)n_owners, (long long)n_old_entries, n_payloads, (long long)m);
+    return DCNR_BAD_ARG;
+  }
+  if (m == 0) return DCNR_OK;
+  ProfScope ps(DCNR_K_SERVE, s);
+  CsrRemove a;
+  a.old_off = old_offsets; a.removed = removed; a.new_off = new_offsets;
+  a.U = n_owners; a.M_old = n_old_entries; a.m = m;
+  a.n_payloads = n_payloads;
+  a.vec = 1;
+  for (int w = 0; w < 2; ++w) {
+    const bool on = w < n_payloads && m < n_old_entries;
+    a.old_val[w] = on ? old_payloads[w] : nullptr;
+    a.new_val[w] = on ? new_payloads[w] : nullptr;
+    if (((uintptr_t)a.old_val[w] | (uintptr_t)a.new_val[w]) & 15) a.vec = 0;
+  }
+  // with every entry removed there are no payloads to write: the offsets only
+  a.n_pay_units = cdiv(n_old_entries - m, CI_CHUNK);
+  a.n_units = a.n_pay_units + cdiv(n_owners + 1, CI_CHUNK);
+  int64_t grid = a.n_units < CI_MAX_BLOCKS ? a.n_units : CI_MAX_BLOCKS;
+  a.units_per_block = cdiv(a.n_units, grid);
+  grid = cdiv(a.n_units, a.units_per_block);
+  hipLaunchKernelGGL(csr_remove_kernel, dim3((unsigned)grid), dim3(CI_NT), 0, s, a);
+  DCNR_LAUNCH_CHECK();
+  return DCNR_OK;
+}
+
+}  // extern "C"

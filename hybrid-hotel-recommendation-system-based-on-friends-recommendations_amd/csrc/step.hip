@@ -1,5 +1,6 @@
-// libdcnr C ABI: the native runtime that sequences the DCN-R forward/backward
-// kernels on one HIP stream over caller-owned memory (include/dcnr.h).
+// The train / eval step of libdcnr's C ABI (include/dcnr.h): sequences the
+// DCN-R forward/backward kernels on one HIP stream over caller-owned memory.
+// (Every other entry point stands beside its kernels, in that subsystem's file.)
 //
 // Forward  = DCN_RecSys.forward (train.py:155-170):
 //   gather+x0+cross (1 kernel) -> initial Linear (MFMA GEMM) ->
@@ -13,97 +14,12 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <map>
 #include <mutex>
-#include <utility>
 #include <vector>
 
 namespace dcnr {
-
-static thread_local char g_err[1024] = "";
-
-void set_error(const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-
-dcnr_status set_max_dyn_lds(const void* kernel, size_t bytes) {
-  static std::mutex mu;
-  static std::map<std::pair<const void*, int>, size_t> done;
-  int dev = 0;
-  DCNR_HIP(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  size_t& cur = done[{kernel, dev}];
-  if (bytes > cur) {
-    DCNR_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    cur = bytes;
-  }
-  return DCNR_OK;
-}
-
-// ------------------------------------------------------------ profiling
-// Optional per-launch HIP-event timing by kernel class (dcnr_profile_*).
-// Each record carries the launch's ALGORITHMIC bytes (the operands the
-// function must move: inputs read once, outputs written once; 0 = not
-// accounted) so the bench prices every kernel class against HBM.
-struct ProfRec { int cat; double bytes; hipEvent_t a, b; };
-static std::mutex g_pm;
-static bool g_prof = false;
-static int g_prof_mode = 0;   // 1: every class, each launch alone; 2: gemm_dw only, concurrent
-static std::vector<ProfRec> g_recs;
-static std::vector<hipEvent_t> g_pool;
-
-static hipEvent_t prof_event() {
-  if (!g_pool.empty()) { hipEvent_t e = g_pool.back(); g_pool.pop_back(); return e; }
-  hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
-  return e;
-}
-
-struct ProfScope {
-  int cat; hipStream_t s; double bytes; hipEvent_t a = nullptr;
-  ProfScope(int c, hipStream_t st, double nbytes = 0.0) : cat(c), s(st), bytes(nbytes) {
-    if (!g_prof || (g_prof_mode == 2 && c != DCNR_K_GEMM_DW)) return;
-    std::lock_guard<std::mutex> lk(g_pm);
-    a = prof_event();
-    (void)hipEventRecord(a, s);
-  }
-  ~ProfScope() {
-    if (!a) return;
-    std::lock_guard<std::mutex> lk(g_pm);
-    hipEvent_t b = prof_event();
-    (void)hipEventRecord(b, s);
-    g_recs.push_back(ProfRec{cat, bytes, a, b});
-  }
-};
-
 namespace {
-
-#define TRY(x)                       \
-  do {                               \
-    dcnr_status st_ = (x);           \
-    if (st_ != DCNR_OK) return st_;  \
-  } while (0)
-// TRY with the launch timed on `stream` and attributed to a kernel class
-#define TRYP(cat, stream, x)            \
-  do {                                  \
-    ProfScope ps_(cat, stream);         \
-    dcnr_status st_ = (x);              \
-    if (st_ != DCNR_OK) return st_;     \
-  } while (0)
-// ... and its algorithmic bytes
-#define TRYB(cat, stream, nbytes, x)              \
-  do {                                            \
-    ProfScope ps_(cat, stream, (double)(nbytes)); \
-    dcnr_status st_ = (x);                        \
-    if (st_ != DCNR_OK) return st_;               \
-  } while (0)
 
 // Flags of the fork/join events between the caller's stream and the side
 // stream (both on this device: a device-scope release/acquire orders them;
@@ -1366,9 +1282,6 @@ using namespace dcnr;
 
 extern "C" {
 
-int dcnr_abi_version(void) { return DCNR_ABI_VERSION; }
-const char* dcnr_last_error(void) { return g_err; }
-
 int64_t dcnr_input_dim(const dcnr_model_desc* desc) {
   Dims d;
   if (make_dims(desc, &d) != DCNR_OK) return -1;
@@ -1552,7 +1465,7 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
   // (a run-time choice, not a plan field: not while kernel classes are being
   // timed, where every launch is priced alone, on the main stream -- except
   // in profile mode 2, which times the side stream's gemm_dw launches in place)
-  if (d.prec == DCNR_PREC_BF16 && (!g_prof || g_prof_mode == 2)) {
+  if (d.prec == DCNR_PREC_BF16 && prof_side_stream_ok()) {
     TRY(dwp.init(sj.side, pl.dw_lag));
     pipe = &dwp;
   }
@@ -1592,514 +1505,6 @@ dcnr_status dcnr_backward(const dcnr_model_desc* desc, void* const* params, void
        emb_segment_sum(eb, L.emb, B, L.dx0, dq_of(d), L.xcoef, accumulate, s));
   if (!desc->grad_ready) TRY(dwp.join(s));
   TRY(grads_ready(desc, DCNR_GRADS_EMBEDDING, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_gather_rows(const int64_t* idx, int64_t n, int64_t n_src, int32_t n_arrays,
-                             const void* const* src, void* const* dst, const int64_t* row_bytes,
-                             dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!src || !dst || !row_bytes || (n > 0 && !idx)) {
-    set_error("dcnr_gather_rows: null argument");
-    return DCNR_BAD_ARG;
-  }
-  TRYP(DCNR_K_SERVE, s, gather_rows(idx, n, n_src, n_arrays, src, dst, row_bytes, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_candidate_union(const int64_t* positives, int64_t Q, const int64_t* knn_idx,
-                                 int32_t k, int64_t* out_rows, int32_t* out_count,
-                                 dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (Q < 0 || (Q > 0 && (!positives || !knn_idx || !out_rows || !out_count))) {
-    set_error("dcnr_candidate_union: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  if (Q == 0) return DCNR_OK;
-  TRYP(DCNR_K_SERVE, s, candidate_union(positives, Q, knn_idx, k, nullptr, 0, 0, out_rows, out_count, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_candidate_union_table(const int64_t* positives, int64_t Q, const int32_t* nbr,
-                                       int32_t kt, int64_t n_items, int32_t k, int64_t* out_rows,
-                                       int32_t* out_count, dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (Q < 0 || k < 1 || kt < k || n_items < 1 ||
-      (Q > 0 && (!positives || !nbr || !out_rows || !out_count))) {
-    set_error("dcnr_candidate_union_table: bad argument (Q=%lld, k=%d, kt=%d, n_items=%lld)",
-              (long long)Q, k, kt, (long long)n_items);
-    return DCNR_BAD_ARG;
-  }
-  if (Q == 0) return DCNR_OK;
-  TRYP(DCNR_K_SERVE, s, candidate_union(positives, Q, nullptr, k, nbr, kt, n_items, out_rows, out_count, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_ranking_batch(const int64_t* item_rows, int64_t n, int64_t user_row,
-                               const int64_t* item_cat, int32_t n_cat, const float* item_num,
-                               int32_t n_num, int64_t n_items, int64_t* user_ids,
-                               int64_t* item_ids, int64_t* cat_features, float* num_features,
-                               dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (n < 0 || n_items < 1 || n_cat < 0 || n_num < 0 ||
-      (n > 0 && (!item_rows || !user_ids || !item_ids || (n_cat && (!item_cat || !cat_features)) ||
-                 (n_num && (!item_num || !num_features))))) {
-    set_error("dcnr_ranking_batch: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  TRYP(DCNR_K_SERVE, s, ranking_batch(item_rows, n, user_row, item_cat, n_cat, item_num, n_num,
-                                   n_items, user_ids, item_ids, cat_features, num_features, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_rank_by_score(const float* scores, int64_t n, int64_t* order,
-                               dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (n < 0 || (n > 0 && (!scores || !order))) {
-    set_error("dcnr_rank_by_score: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  TRYP(DCNR_K_SERVE, s, rank_desc(scores, n, order, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_mmr_rerank(const float* table, const float* inv_norms, int32_t d,
-                            const int64_t* rows, const float* scores, int64_t n,
-                            float lambda_param, int32_t top_k, int64_t* out_pos,
-                            int32_t* out_count, dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (n < 0 || top_k < 1 || (n > 0 && (!table || !inv_norms || !rows || !scores || !out_pos ||
-                                       !out_count))) {
-    set_error("dcnr_mmr_rerank: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  TRYP(DCNR_K_SERVE, s, mmr_rerank(table, inv_norms, d, rows, scores, n, lambda_param, top_k,
-                                out_pos, out_count, s));
-  return DCNR_OK;
-}
-
-// ---- a batch of requests (serving.hip's req_* kernels).  Shapes the kernels
-// do not take: more requests than DCNR_REQ_MAX_R (one workgroup each), k above
-// the top-k's 64, a set CSR of 2^31 rows or more.
-namespace {
-constexpr int64_t DCNR_REQ_MAX_R = int64_t(1) << 22;
-
-// the checks the three entry points share; DCNR_OK: launch
-dcnr_status requests_shape(const char* who, int64_t R, int32_t cap) {
-  if (R < 0 || cap < 1 || cap > requests_cap_max()) {
-    set_error("%s: R=%lld (>= 0), cap=%d (1..%d)", who, (long long)R, cap, requests_cap_max());
-    return DCNR_BAD_ARG;
-  }
-  if (R > DCNR_REQ_MAX_R) {
-    set_error("%s: R=%lld exceeds %lld requests per call", who, (long long)R,
-              (long long)DCNR_REQ_MAX_R);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  return DCNR_OK;
-}
-}  // namespace
-
-size_t dcnr_requests_workspace_size(int64_t R, int64_t Q_total, int32_t k, int32_t cap) {
-  if (R <= 0 || R > DCNR_REQ_MAX_R || Q_total < 0 || k < 1 || cap < 1 || cap > requests_cap_max())
-    return 0;
-  return requests_ws_bytes(R, cap) + 256;
-}
-
-namespace {
-// dcnr_requests_candidates and its table form: neighbours from knn_idx
-// [Q_total][k], or (nbr != null) from the item neighbour table [n_items][kt]
-dcnr_status requests_candidates_api(const char* who, const int64_t* positives,
-                                    const int64_t* pos_offsets, int64_t R, int64_t Q_total,
-                                    const int64_t* knn_idx, const int32_t* nbr, int32_t kt, int32_t k,
-                                    const int64_t* set_rows, int64_t n_set_rows,
-                                    const int64_t* set_offsets, int32_t S, const int32_t* allowed,
-                                    const int32_t* excluded, const int32_t* fallback,
-                                    int32_t min_candidates, int64_t n_items, int32_t cap,
-                                    int64_t* out_rows, int32_t* out_count, int32_t* status,
-                                    int64_t* offsets, int64_t* host_offsets, int32_t* host_status,
-                                    hipStream_t s) {
-  TRY(requests_shape(who, R, cap));
-  if (Q_total < 0 || k < 1 || S < 0 || n_set_rows < 0 || n_items < 1) {
-    set_error("%s: Q_total=%lld, k=%d, S=%d, n_set_rows=%lld, n_items=%lld", who,
-              (long long)Q_total, k, S, (long long)n_set_rows, (long long)n_items);
-    return DCNR_BAD_ARG;
-  }
-  if (R > 0 && (!pos_offsets || !out_rows || !out_count || !status || !offsets ||
-                (Q_total > 0 && (!positives || (!knn_idx && !nbr))) || (S > 0 && !set_offsets) ||
-                (n_set_rows > 0 && !set_rows) ||
-                (S == 0 && (allowed || excluded || fallback)))) {
-    set_error("%s: null argument (or set indices without sets)", who);
-    return DCNR_BAD_ARG;
-  }
-  if (k > 64 || n_set_rows > INT32_MAX) {
-    set_error("%s: k=%d (max 64), n_set_rows=%lld (max 2^31 - 1)", who, k, (long long)n_set_rows);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  if (R == 0) return DCNR_OK;
-  RequestsIn in{positives, pos_offsets, R, Q_total, knn_idx, k, nbr, kt, set_rows, n_set_rows,
-                set_offsets, S, allowed, excluded, fallback};
-  TRYP(DCNR_K_SERVE, s, requests_candidates(in, min_candidates, n_items, cap, out_rows, out_count,
-                                            status, offsets, host_offsets, host_status, s));
-  return DCNR_OK;
-}
-}  // namespace
-
-dcnr_status dcnr_requests_candidates(const int64_t* positives, const int64_t* pos_offsets,
-                                     int64_t R, int64_t Q_total, const int64_t* knn_idx, int32_t k,
-                                     const int64_t* set_rows, int64_t n_set_rows,
-                                     const int64_t* set_offsets, int32_t S, const int32_t* allowed,
-                                     const int32_t* excluded, const int32_t* fallback,
-                                     int32_t min_candidates, int64_t n_items, int32_t cap,
-                                     int64_t* out_rows, int32_t* out_count, int32_t* status,
-                                     int64_t* offsets, int64_t* host_offsets,
-                                     int32_t* host_status, dcnr_stream_t stream) {
-  return requests_candidates_api("dcnr_requests_candidates", positives, pos_offsets, R, Q_total,
-                                 knn_idx, nullptr, 0, k, set_rows, n_set_rows, set_offsets, S, allowed,
-                                 excluded, fallback, min_candidates, n_items, cap, out_rows, out_count,
-                                 status, offsets, host_offsets, host_status, (hipStream_t)stream);
-}
-
-dcnr_status dcnr_requests_candidates_table(const int64_t* positives, const int64_t* pos_offsets,
-                                           int64_t R, int64_t Q_total, const int32_t* nbr, int32_t kt,
-                                           int32_t k, const int64_t* set_rows, int64_t n_set_rows,
-                                           const int64_t* set_offsets, int32_t S,
-                                           const int32_t* allowed, const int32_t* excluded,
-                                           const int32_t* fallback, int32_t min_candidates,
-                                           int64_t n_items, int32_t cap, int64_t* out_rows,
-                                           int32_t* out_count, int32_t* status, int64_t* offsets,
-                                           int64_t* host_offsets, int32_t* host_status,
-                                           dcnr_stream_t stream) {
-  if (kt < k || (R > 0 && Q_total > 0 && !nbr)) {
-    set_error("dcnr_requests_candidates_table: kt=%d below k=%d, or a null table", kt, k);
-    return DCNR_BAD_ARG;
-  }
-  return requests_candidates_api("dcnr_requests_candidates_table", positives, pos_offsets, R, Q_total,
-                                 nullptr, nbr, kt, k, set_rows, n_set_rows, set_offsets, S, allowed,
-                                 excluded, fallback, min_candidates, n_items, cap, out_rows, out_count,
-                                 status, offsets, host_offsets, host_status, (hipStream_t)stream);
-}
-
-dcnr_status dcnr_requests_ranking_batch(const int64_t* cand_rows, int32_t cap,
-                                        const int64_t* offsets, int64_t R, int64_t n,
-                                        const int64_t* user_rows, const int64_t* item_cat,
-                                        int32_t n_cat, const float* item_num, int32_t n_num,
-                                        int64_t n_items, int64_t* user_ids, int64_t* item_ids,
-                                        int64_t* cat_features, float* num_features,
-                                        dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  TRY(requests_shape("dcnr_requests_ranking_batch", R, cap));
-  if (n < 0 || n > R * cap || n_items < 1 || n_cat < 0 || n_num < 0 ||
-      (n > 0 && (!cand_rows || !offsets || !user_rows || !user_ids || !item_ids ||
-                 (n_cat && (!item_cat || !cat_features)) ||
-                 (n_num && (!item_num || !num_features))))) {
-    set_error("dcnr_requests_ranking_batch: bad argument (n=%lld of at most R*cap=%lld)",
-              (long long)n, (long long)(R * cap));
-    return DCNR_BAD_ARG;
-  }
-  if (R == 0) return DCNR_OK;
-  TRYP(DCNR_K_SERVE, s, requests_batch(cand_rows, cap, offsets, R, n, user_rows, item_cat, n_cat,
-                                       item_num, n_num, n_items, user_ids, item_ids,
-                                       cat_features, num_features, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_requests_rank_mmr(const float* logits, int64_t n, const int64_t* cand_rows,
-                                   int32_t cap, const int64_t* offsets, int64_t R,
-                                   const float* table, const float* inv_norms, int32_t d,
-                                   int64_t n_items, const float* lambda_param,
-                                   const int32_t* top_k, int64_t* out_rows, float* out_logits,
-                                   int32_t* out_count, int32_t* status, void* ws, size_t ws_bytes,
-                                   dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  TRY(requests_shape("dcnr_requests_rank_mmr", R, cap));
-  if (n < 0 || n > R * cap || d < 1 || d > 256 || n_items < 1 ||
-      (R > 0 && (!cand_rows || !offsets || !table || !inv_norms || !lambda_param || !top_k ||
-                 !out_count || !status || !ws || (n > 0 && (!logits || !out_rows || !out_logits))))) {
-    set_error("dcnr_requests_rank_mmr: bad argument (n=%lld of at most R*cap=%lld, d=%d of 1..256)",
-              (long long)n, (long long)(R * cap), d);
-    return DCNR_BAD_ARG;
-  }
-  if (R == 0) return DCNR_OK;
-  const size_t need = requests_ws_bytes(R, cap) + 256;
-  if (ws_bytes < need) {
-    set_error("dcnr_requests_rank_mmr: workspace too small: %zu < %zu", ws_bytes, need);
-    return DCNR_WORKSPACE_TOO_SMALL;
-  }
-  Bump b((void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255));
-  const RequestsWs w = requests_ws(b, R, cap);
-  TRYP(DCNR_K_SERVE, s, requests_rank_mmr(logits, n, cand_rows, cap, offsets, R, table, inv_norms, d,
-                                          n_items, lambda_param, top_k, w, out_rows, out_logits,
-                                          out_count, status, s));
-  return DCNR_OK;
-}
-
-// ---- requests by user.  The store's lengths are checked here; what lies in
-// device memory (offsets, rows) the kernels check against them.
-namespace {
-constexpr int64_t DCNR_STORE_MAX_ITEMS = int64_t(1) << 29;   // hotel row * 4 + class bits in 32
-
-dcnr_status store_shape(const char* who, const dcnr_interactions* st, int64_t n_items) {
-  if (!st || st->n_reviewers < 0 || st->n_friend_rows < 0 || st->n_reviews < 0 || n_items < 1 ||
-      !st->friend_offsets || !st->review_offsets || (st->n_friend_rows > 0 && !st->friend_rows) ||
-      (st->n_reviews > 0 && (!st->review_items || !st->review_rows))) {
-    set_error("%s: null or negative store field, or n_items < 1", who);
-    return DCNR_BAD_ARG;
-  }
-  if (n_items > DCNR_STORE_MAX_ITEMS || st->n_reviewers >= INT32_MAX ||
-      st->n_reviews > INT32_MAX || st->n_friend_rows > INT32_MAX) {
-    set_error("%s: n_items=%lld (max 2^29), n_reviewers=%lld, n_reviews=%lld, n_friend_rows=%lld "
-              "(max 2^31 - 1)", who, (long long)n_items, (long long)st->n_reviewers,
-              (long long)st->n_reviews, (long long)st->n_friend_rows);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  return DCNR_OK;
-}
-}  // namespace
-
-dcnr_status dcnr_requests_sources(const dcnr_interactions* store, const int32_t* reviewers,
-                                  const int32_t* modes, int64_t R, int64_t n_items,
-                                  const int64_t* pos_offsets, int64_t Q_total, int64_t* positives,
-                                  const int64_t* neg_offsets, int64_t neg_lo, int64_t neg_hi,
-                                  int64_t* neg_rows, int32_t* counts, int32_t* status,
-                                  int32_t* host_counts, int32_t* host_status,
-                                  dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  TRY(requests_shape("dcnr_requests_sources", R, 1));
-  TRY(store_shape("dcnr_requests_sources", store, n_items));
-  if (Q_total < 0 || neg_lo < 0 || neg_hi < neg_lo ||
-      (R > 0 && (!reviewers || !modes || !pos_offsets || !neg_offsets || !counts || !status ||
-                 (Q_total > 0 && !positives) || (neg_hi > neg_lo && !neg_rows)))) {
-    set_error("dcnr_requests_sources: bad argument (Q_total=%lld, negatives [%lld, %lld))",
-              (long long)Q_total, (long long)neg_lo, (long long)neg_hi);
-    return DCNR_BAD_ARG;
-  }
-  if (R == 0) return DCNR_OK;
-  TRYP(DCNR_K_SERVE, s, requests_sources(*store, reviewers, modes, R, n_items, pos_offsets, Q_total,
-                                         positives, neg_offsets, neg_lo, neg_hi, neg_rows, counts,
-                                         status, host_counts, host_status, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_requests_recommended_by(const dcnr_interactions* store, const int32_t* reviewers,
-                                         int64_t R, int64_t n_items, const int64_t* out_rows,
-                                         int64_t n, const int64_t* offsets,
-                                         const int32_t* out_count, const int64_t* list_offsets,
-                                         int64_t n_list_rows, int32_t* lists, int32_t* by_count,
-                                         int64_t* by_offsets, int32_t* by_reviewers,
-                                         int32_t* status, dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  TRY(requests_shape("dcnr_requests_recommended_by", R, 1));
-  TRY(store_shape("dcnr_requests_recommended_by", store, n_items));
-  if (n < 0 || n > R * requests_cap_max() || n_list_rows < 0 ||
-      (R > 0 && (!reviewers || !offsets || !out_count || !list_offsets || !by_offsets || !status ||
-                 (n > 0 && (!out_rows || !by_count)) ||
-                 (n_list_rows > 0 && (!lists || !by_reviewers))))) {
-    set_error("dcnr_requests_recommended_by: bad argument (n=%lld, n_list_rows=%lld)",
-              (long long)n, (long long)n_list_rows);
-    return DCNR_BAD_ARG;
-  }
-  if (R == 0) return DCNR_OK;
-  TRYP(DCNR_K_SERVE, s, requests_recommended_by(*store, reviewers, R, n_items, out_rows, n, offsets,
-                                                out_count, list_offsets, n_list_rows, lists,
-                                                by_count, by_offsets, by_reviewers, status, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_csr_insert(const int64_t* old_offsets, int64_t n_old_owners, int64_t n_new_owners,
-                            int64_t n_old_entries, int32_t n_payloads,
-                            const int32_t* const* old_payloads, const int64_t* touched,
-                            const int64_t* insert_prefix, int64_t t, const int64_t* insert_pos,
-                            const int32_t* const* insert_payloads, int64_t m, int64_t* new_offsets,
-                            int32_t* const* new_payloads, dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  bool bad = !old_offsets || !new_offsets || n_old_owners < 0 || n_new_owners < n_old_owners ||
-             n_old_entries < 0 || n_payloads < 1 || n_payloads > 2 || t < 0 || m < 0 || t > m ||
-             (m > 0 && (t == 0 || !touched || !insert_prefix || !insert_pos || !old_payloads ||
-                        !insert_payloads || !new_payloads));
-  for (int w = 0; !bad && m > 0 && w < n_payloads; ++w)
-    bad = !insert_payloads[w] || !new_payloads[w] || (n_old_entries > 0 && !old_payloads[w]);
-  if (bad) {
-    set_error("dcnr_csr_insert: bad argument (owners %lld -> %lld, entries=%lld, payloads=%d, "
-              "t=%lld, m=%lld)", (long long)n_old_owners, (long long)n_new_owners,
-              (long long)n_old_entries, n_payloads, (long long)t, (long long)m);
-    return DCNR_BAD_ARG;
-  }
-  if (m == 0 && n_new_owners == n_old_owners) return DCNR_OK;
-  TRYP(DCNR_K_SERVE, s, csr_insert(old_offsets, n_old_owners, n_new_owners, n_old_entries,
-                                   n_payloads, old_payloads, touched, insert_prefix, t, insert_pos,
-                                   insert_payloads, m, new_offsets, new_payloads, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_csr_remove(const int64_t* old_offsets, int64_t n_owners, int64_t n_old_entries,
-                            int32_t n_payloads, const int32_t* const* old_payloads,
-                            const int64_t* removed, int64_t m, int64_t* new_offsets,
-                            int32_t* const* new_payloads, dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const bool pay = m > 0 && m < n_old_entries;   // some payload words are copied
-  bool bad = !old_offsets || !new_offsets || n_owners < 0 || n_old_entries < 0 || n_payloads < 1 ||
-             n_payloads > 2 || m < 0 || m > n_old_entries || (m > 0 && !removed) ||
-             (pay && (!old_payloads || !new_payloads));
-  for (int w = 0; !bad && pay && w < n_payloads; ++w) bad = !old_payloads[w] || !new_payloads[w];
-  if (bad) {
-    set_error("dcnr_csr_remove: bad argument (owners=%lld, entries=%lld, payloads=%d, m=%lld)",
-              (long long)n_owners, (long long)n_old_entries, n_payloads, (long long)m);
-    return DCNR_BAD_ARG;
-  }
-  if (m == 0) return DCNR_OK;
-  TRYP(DCNR_K_SERVE, s, csr_remove(old_offsets, n_owners, n_old_entries, n_payloads, old_payloads,
-                                   removed, m, new_offsets, new_payloads, s));
-  return DCNR_OK;
-}
-
-static dcnr_status city_sets_shape(int64_t M, int64_t n_items, int32_t n_cities, int32_t top) {
-  if (M < 0 || n_items < 0 || n_cities < 0 || top < 0) return DCNR_BAD_ARG;
-  if (top < 1 || top > 256 || n_cities < 1 || n_cities > 65536 || n_items > ((int64_t)1 << 29) ||
-      M >= 2147483647ll)
-    return DCNR_UNSUPPORTED_SHAPE;
-  return DCNR_OK;
-}
-
-size_t dcnr_city_sets_workspace_size(int64_t M, int64_t n_items, int32_t n_cities, int32_t top) {
-  if (city_sets_shape(M, n_items, n_cities, top) != DCNR_OK) return 0;
-  return city_sets_ws_bytes(M, n_items, n_cities, top) + 256;
-}
-
-dcnr_status dcnr_city_sets_build(const int32_t* review_item, const int32_t* review_city,
-                                 const double* review_key, const int32_t* review_row, int64_t M,
-                                 int64_t n_items, int32_t n_cities, int32_t top, int64_t* set_offsets,
-                                 int64_t* set_rows, int64_t cap, int32_t* top_rows, int32_t* status,
-                                 int64_t* host_offsets, int32_t* host_status, void* ws, size_t ws_bytes,
-                                 dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const dcnr_status shape = city_sets_shape(M, n_items, n_cities, top);
-  if (shape == DCNR_BAD_ARG || cap < 0 || !set_offsets || !top_rows || !status ||
-      (cap > 0 && !set_rows) || (M > 0 && (!review_item || !review_city || !review_key || !ws))) {
-    set_error("dcnr_city_sets_build: bad argument (M=%lld, n_items=%lld, cities=%d, top=%d, cap=%lld)",
-              (long long)M, (long long)n_items, n_cities, top, (long long)cap);
-    return DCNR_BAD_ARG;
-  }
-  if (shape != DCNR_OK) {
-    set_error("dcnr_city_sets_build: unsupported shape (M=%lld, n_items=%lld, cities=%d, top=%d)",
-              (long long)M, (long long)n_items, n_cities, top);
-    return shape;
-  }
-  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  const size_t need = M > 0 ? city_sets_ws_bytes(M, n_items, n_cities, top) : 0;
-  if (M > 0 && ws_bytes < need + ((char*)base - (char*)ws)) {
-    set_error("dcnr_city_sets_build: workspace too small: %zu < %zu", ws_bytes, need + 256);
-    return DCNR_WORKSPACE_TOO_SMALL;
-  }
-  TRYP(DCNR_K_SERVE, s, city_sets_build(review_item, review_city, review_key, review_row, M, n_items,
-                                        n_cities, top, set_offsets, set_rows, cap, top_rows, status,
-                                        host_offsets, host_status, base, s));
-  return DCNR_OK;
-}
-
-static dcnr_status item_features_shape(int64_t M, int64_t n_items, int32_t n_cat, int32_t n_num) {
-  if (M < 0 || n_items < 0 || n_cat < 0 || n_num < 0) return DCNR_BAD_ARG;
-  if (n_cat > 64 || n_num > 64 || n_items > ((int64_t)1 << 29) || M >= 2147483647ll)
-    return DCNR_UNSUPPORTED_SHAPE;
-  return DCNR_OK;
-}
-
-size_t dcnr_item_features_workspace_size(int64_t M, int64_t n_items, int32_t n_cat, int32_t n_num) {
-  if (item_features_shape(M, n_items, n_cat, n_num) != DCNR_OK) return 0;
-  return item_features_ws_bytes(n_items) + 256;
-}
-
-dcnr_status dcnr_item_features_build(const int32_t* review_item, const int32_t* review_row,
-                                     const int32_t* review_cat, const double* review_num,
-                                     const double* scaler_scale, const double* scaler_min, int64_t M,
-                                     int64_t n_items, int32_t n_cat, int32_t n_num, int32_t* first_row,
-                                     int64_t* item_cat, float* item_num, int32_t* counts,
-                                     int32_t* host_counts, void* ws, size_t ws_bytes,
-                                     dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const dcnr_status shape = item_features_shape(M, n_items, n_cat, n_num);
-  if (shape == DCNR_BAD_ARG || !counts ||
-      (n_items > 0 && (!first_row || (n_cat > 0 && !item_cat) || (n_num > 0 && !item_num))) ||
-      (n_num > 0 && n_items > 0 && (!scaler_scale || !scaler_min)) ||
-      (M > 0 && (!review_item || !ws || (n_cat > 0 && !review_cat) || (n_num > 0 && !review_num)))) {
-    set_error("dcnr_item_features_build: bad argument (M=%lld, n_items=%lld, n_cat=%d, n_num=%d)",
-              (long long)M, (long long)n_items, n_cat, n_num);
-    return DCNR_BAD_ARG;
-  }
-  if (shape != DCNR_OK) {
-    set_error("dcnr_item_features_build: unsupported shape (M=%lld, n_items=%lld, n_cat=%d, n_num=%d)",
-              (long long)M, (long long)n_items, n_cat, n_num);
-    return shape;
-  }
-  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  const size_t need = M > 0 ? item_features_ws_bytes(n_items) : 0;
-  if (M > 0 && ws_bytes < need + ((char*)base - (char*)ws)) {
-    set_error("dcnr_item_features_build: workspace too small: %zu < %zu", ws_bytes, need + 256);
-    return DCNR_WORKSPACE_TOO_SMALL;
-  }
-  TRYP(DCNR_K_SERVE, s, item_features_build(review_item, review_row, review_cat, review_num,
-                                            scaler_scale, scaler_min, M, n_items, n_cat, n_num,
-                                            first_row, item_cat, item_num, counts, host_counts, base,
-                                            s));
-  return DCNR_OK;
-}
-
-static dcnr_status train_table_shape(int64_t M, int32_t n_cat, int32_t n_raw, int32_t n_derived) {
-  if (M < 0 || n_cat < 0 || n_raw < 0 || n_derived < 0) return DCNR_BAD_ARG;
-  if (M >= 2147483647ll || n_cat > 64 || (int64_t)n_raw + n_derived > 64) return DCNR_UNSUPPORTED_SHAPE;
-  return DCNR_OK;
-}
-
-size_t dcnr_train_table_workspace_size(int64_t M, int32_t n_cat, int32_t n_raw, int32_t n_derived) {
-  if (train_table_shape(M, n_cat, n_raw, n_derived) != DCNR_OK) return 0;
-  return train_table_ws_bytes(M, n_raw + n_derived) + 256;
-}
-
-dcnr_status dcnr_train_table_build(const dcnr_train_table_args* a, void* ws, size_t ws_bytes,
-                                   dcnr_stream_t stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!a) {
-    set_error("dcnr_train_table_build: null args");
-    return DCNR_BAD_ARG;
-  }
-  const dcnr_status shape = train_table_shape(a->M, a->n_cat, a->n_raw, a->n_derived);
-  bool bad = shape == DCNR_BAD_ARG || !a->counts || a->filter_col < -1 ||
-             (a->filter_col >= 0 && a->filter_col >= a->n_raw) || (a->n_derived > 0 && !a->derived);
-  if (!bad)
-    for (int d = 0; d < a->n_derived; ++d) {
-      const int32_t op = a->derived[3 * d], i = a->derived[3 * d + 1], j = a->derived[3 * d + 2];
-      bad |= (op != DCNR_DERIVED_RATIO && op != DCNR_DERIVED_DIFF) || i < 0 || i >= a->n_raw || j < 0 ||
-             j >= a->n_raw;
-    }
-  if (!bad && a->M > 0) {
-    const bool num = a->n_raw + a->n_derived > 0;
-    bad = !a->user || !a->item || !a->target || !ws || (a->n_cat > 0 && (!a->cat_key || !a->cat || !a->cat_keys)) ||
-          (a->n_raw > 0 && !a->raw) || (num && (!a->num || !a->stats)) || !a->row || !a->collab || !a->y ||
-          !a->user_ids || !a->item_ids;
-  }
-  if (bad) {
-    set_error("dcnr_train_table_build: bad argument (M=%lld, n_cat=%d, n_raw=%d, n_derived=%d, filter_col=%d)",
-              (long long)a->M, a->n_cat, a->n_raw, a->n_derived, a->filter_col);
-    return DCNR_BAD_ARG;
-  }
-  if (shape != DCNR_OK) {
-    set_error("dcnr_train_table_build: unsupported shape (M=%lld, n_cat=%d, n_raw=%d, n_derived=%d)",
-              (long long)a->M, a->n_cat, a->n_raw, a->n_derived);
-    return shape;
-  }
-  const int n_counts = DCNR_TRAIN_TABLE_COUNTS + a->n_cat;
-  if (a->M == 0) {
-    DCNR_HIP(hipMemsetAsync(a->counts, 0, (size_t)n_counts * 4, s));
-    if (a->host_counts)
-      for (int i = 0; i < n_counts; ++i) a->host_counts[i] = 0;
-    return DCNR_OK;
-  }
-  const size_t need = train_table_ws_bytes(a->M, a->n_raw + a->n_derived) + 256;
-  if (ws_bytes < need) {
-    set_error("dcnr_train_table_build: workspace too small: %zu < %zu", ws_bytes, need);
-    return DCNR_WORKSPACE_TOO_SMALL;
-  }
-  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  TRYP(DCNR_K_SERVE, s, train_table_build(*a, base, s));
   return DCNR_OK;
 }
 
@@ -2148,43 +1553,6 @@ dcnr_status dcnr_emb_touched_rows(const dcnr_model_desc* desc, const void* ws, s
                           (hipStream_t)stream);
 }
 
-dcnr_status dcnr_sparse_pack(const float* grad, const int64_t* offsets, int64_t ld,
-                             const int64_t* table_counts, int32_t n_tables, int32_t width,
-                             int64_t* out_offsets, float* out_rows, dcnr_stream_t stream) {
-  if (!grad || !offsets || !table_counts || !out_offsets || !out_rows || ld < 0 || n_tables < 1 ||
-      width < 1) {
-    set_error("dcnr_sparse_pack: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  TRYP(DCNR_K_SERVE, s, sparse_pack(grad, offsets, ld, table_counts, n_tables, width, out_offsets, out_rows, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_sparse_accumulate(float* shard, int64_t shard_lo, int64_t shard_elems, int32_t width,
-                                   const int64_t* offsets, const float* rows,
-                                   const int64_t* source_counts, int32_t n_sources,
-                                   dcnr_stream_t stream) {
-  if (!shard || shard_lo < 0 || shard_elems < 0 || width < 1 || n_sources < 0 ||
-      (n_sources > 0 && !source_counts)) {
-    set_error("dcnr_sparse_accumulate: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  int64_t n = 0;
-  for (int r = 0; r < n_sources; ++r) {
-    if (source_counts[r] < 0) { set_error("dcnr_sparse_accumulate: negative count"); return DCNR_BAD_ARG; }
-    n += source_counts[r];
-  }
-  if (n > 0 && (!offsets || !rows)) {
-    set_error("dcnr_sparse_accumulate: null rows");
-    return DCNR_BAD_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  TRYP(DCNR_K_SERVE, s, sparse_accumulate(shard, shard_lo, shard_elems, width, offsets, rows, source_counts,
-                                       n_sources, s));
-  return DCNR_OK;
-}
-
 dcnr_status dcnr_bce_with_logits(const float* logits, const float* labels, int64_t B, float* loss,
                                  float* dlogits, float grad_scale, void* ws, size_t ws_bytes,
                                  dcnr_stream_t stream) {
@@ -2198,382 +1566,6 @@ dcnr_status dcnr_bce_with_logits(const float* logits, const float* labels, int64
   }
   hipStream_t s = (hipStream_t)stream;
   TRYP(DCNR_K_HEAD, s, bce(logits, labels, B, loss, dlogits, grad_scale, (double*)ws, s));
-  return DCNR_OK;
-}
-
-size_t dcnr_eval_metrics_workspace_size(int64_t n) { return metrics_ws_bytes(n); }
-
-dcnr_status dcnr_eval_metrics(const float* logits, const float* labels, int64_t n, dcnr_metrics* out,
-                              void* ws, size_t ws_bytes, dcnr_stream_t stream) {
-  if (n < 0 || n >= ((int64_t)1 << 31) || !out || (n > 0 && (!logits || !labels))) {
-    set_error("dcnr_eval_metrics: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  const size_t need = metrics_ws_bytes(n);
-  if (ws_bytes < need) {
-    set_error("dcnr_eval_metrics: workspace too small: %zu < %zu", ws_bytes, need);
-    return DCNR_WORKSPACE_TOO_SMALL;
-  }
-  if (need && !ws) {
-    set_error("dcnr_eval_metrics: null workspace");
-    return DCNR_BAD_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  // algorithmic bytes: the inputs once, the keys written and read once per sort pass
-  TRYB(DCNR_K_HEAD, s, 8.0 * (double)n + 3.0 * 16.0 * (double)n,
-       eval_metrics(logits, labels, n, out, ws, s));
-  return DCNR_OK;
-}
-
-static bool group_metrics_sizes_ok(int64_t n, int64_t n_groups) {
-  return n >= 0 && n < ((int64_t)1 << 31) && n_groups >= 1 && n_groups <= ((int64_t)1 << 31) - 1;
-}
-
-size_t dcnr_eval_group_metrics_workspace_size(int64_t n, int64_t n_groups) {
-  return group_metrics_sizes_ok(n, n_groups) ? group_metrics_ws_bytes(n, n_groups) : 0;
-}
-
-dcnr_status dcnr_eval_group_metrics(const float* logits, const float* labels, const int64_t* groups,
-                                    int64_t n, int64_t n_groups, const int32_t* ks, int32_t n_k,
-                                    const double* discount, const double* ideal,
-                                    dcnr_group_summary* out, dcnr_group_record* per_group, void* ws,
-                                    size_t ws_bytes, dcnr_stream_t stream) {
-  bool ok = group_metrics_sizes_ok(n, n_groups) && out && n_k >= 0 && n_k <= DCNR_GROUP_MAX_K &&
-            (n == 0 || (logits && labels && groups)) && (n_k == 0 || (ks && discount && ideal));
-  for (int j = 0; ok && j < n_k; ++j)
-    ok = ks[j] >= 1 && ks[j] <= (1 << 20) && (j == 0 || ks[j] > ks[j - 1]);
-  if (!ok) {
-    set_error("dcnr_eval_group_metrics: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  const size_t need = group_metrics_ws_bytes(n, n_groups);
-  if (ws_bytes < need) {
-    set_error("dcnr_eval_group_metrics: workspace too small: %zu < %zu", ws_bytes, need);
-    return DCNR_WORKSPACE_TOO_SMALL;
-  }
-  if (need && !ws) {
-    set_error("dcnr_eval_group_metrics: null workspace");
-    return DCNR_BAD_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  // algorithmic bytes: the inputs once, the keys written and read once per sort pass
-  // and read by the two walks
-  const double passes = (double)group_metrics_passes(n_groups);
-  TRYB(DCNR_K_HEAD, s, 16.0 * (double)n + (passes + 1.0) * 16.0 * (double)n,
-       eval_group_metrics(logits, labels, groups, n, n_groups, ks, n_k, discount, ideal, out,
-                          per_group, ws, s));
-  return DCNR_OK;
-}
-
-static bool list_metrics_shape_ok(int64_t R, int64_t n_items) {
-  return R <= ((int64_t)1 << 22) && n_items < ((int64_t)1 << 31);
-}
-
-size_t dcnr_eval_list_metrics_workspace_size(int64_t R, int64_t n_items) {
-  return list_metrics_shape_ok(R, n_items) ? list_metrics_ws_bytes(R, n_items) : 0;
-}
-
-dcnr_status dcnr_eval_list_metrics(const int64_t* rows, int64_t n, const int64_t* offsets,
-                                   const int32_t* counts, int64_t R, int32_t at,
-                                   const float* table, const float* inv_norms, int32_t d,
-                                   int64_t n_items, const float* scores, const double* info,
-                                   const int64_t* rel_rows, int64_t n_rel_rows,
-                                   const int64_t* rel_offsets, const int32_t* ks, int32_t n_k,
-                                   const double* discount, const double* ideal,
-                                   dcnr_list_summary* out, dcnr_list_record* per_list, void* ws,
-                                   size_t ws_bytes, dcnr_stream_t stream) {
-  bool ok = R >= 0 && n >= 0 && n_rel_rows >= 0 && n_items >= 1 && at >= 1 && at <= 128 && d >= 1 &&
-            d <= 256 && out && n_k >= 0 && n_k <= DCNR_GROUP_MAX_K &&
-            (R == 0 || (offsets && table && inv_norms)) && (R == 0 || n == 0 || rows) &&
-            (!rel_offsets || n_rel_rows == 0 || rel_rows) && (n_k == 0 || ks) &&
-            (n_k == 0 || !rel_offsets || (discount && ideal));
-  for (int j = 0; ok && j < n_k; ++j) ok = ks[j] >= 1 && ks[j] <= at && (j == 0 || ks[j] > ks[j - 1]);
-  if (!ok) {
-    set_error("dcnr_eval_list_metrics: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  if (!list_metrics_shape_ok(R, n_items) || n > ((int64_t)1 << 30)) {
-    set_error("dcnr_eval_list_metrics: R %lld > 2^22, n %lld > 2^30 or n_items %lld >= 2^31",
-              (long long)R, (long long)n, (long long)n_items);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  const size_t need = list_metrics_ws_bytes(R, n_items);
-  if (ws_bytes < need) {
-    set_error("dcnr_eval_list_metrics: workspace too small: %zu < %zu", ws_bytes, need);
-    return DCNR_WORKSPACE_TOO_SMALL;
-  }
-  if (need && !ws) {
-    set_error("dcnr_eval_list_metrics: null workspace");
-    return DCNR_BAD_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  // algorithmic bytes: the measured rows of the table at most once each, the
-  // row ids, the counts cleared, written and read
-  TRYB(DCNR_K_HEAD, s, (double)std::min<int64_t>(n, R * at) * (4.0 * d + 12.0) + 12.0 * (double)n_items,
-       eval_list_metrics(rows, n, offsets, counts, R, at, table, inv_norms, d, n_items, scores, info,
-                         rel_rows, n_rel_rows, rel_offsets, ks, n_k, discount, ideal, out, per_list,
-                         ws, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_adam_step(int32_t n_tensors, float* const* params, const float* const* grads,
-                           float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
-                           float lr, float beta1, float beta2, float eps, float weight_decay,
-                           int64_t step, int decoupled, dcnr_stream_t stream) {
-  if (n_tensors < 0 || (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel)) ||
-      step < 1) {
-    set_error("dcnr_adam_step: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  double nparam = 0;
-  for (int i = 0; i < n_tensors; ++i) nparam += (double)numel[i];
-  TRYB(DCNR_K_ADAM, s, 28.0 * nparam, adam(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2,
-                         eps, weight_decay, step, decoupled, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_adam_step_rows(int32_t n_tensors, float* const* params, const float* const* grads,
-                                float* const* exp_avg, float* const* exp_avg_sq, const int64_t* numel,
-                                const uint8_t* const* row_map, const int32_t* row_width,
-                                float lr, float beta1, float beta2, float eps, float weight_decay,
-                                int64_t step, int decoupled, dcnr_stream_t stream) {
-  if (n_tensors < 0 || (n_tensors > 0 && (!params || !grads || !exp_avg || !exp_avg_sq || !numel ||
-                                          !row_map || !row_width)) || step < 1) {
-    set_error("dcnr_adam_step_rows: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  double nbytes = 0;
-  for (int i = 0; i < n_tensors; ++i) {
-    if (row_map[i] && (row_width[i] < 1 || numel[i] % row_width[i])) {
-      set_error("dcnr_adam_step_rows: tensor %d: %lld elements in rows of %d", i, (long long)numel[i],
-                row_width[i]);
-      return DCNR_BAD_ARG;
-    }
-    // p, m, v read and written, the map byte per row; the gradient of a
-    // mapped tensor only where marked (a share the library does not know:
-    // not counted, so the figure is a floor)
-    nbytes += (row_map[i] ? 24.0 : 28.0) * (double)numel[i] +
-              (row_map[i] ? (double)numel[i] / row_width[i] : 0.0);
-  }
-  hipStream_t s = (hipStream_t)stream;
-  TRYB(DCNR_K_ADAM, s, nbytes, adam(n_tensors, params, grads, exp_avg, exp_avg_sq, numel, lr, beta1, beta2,
-                                 eps, weight_decay, step, decoupled, s, row_map, row_width));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_row_inv_norms(const float* table, int64_t N, int32_t d, float* inv_norms,
-                               dcnr_stream_t stream) {
-  if (!table || !inv_norms || d < 1 || N < 0) {
-    set_error("dcnr_row_inv_norms: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  return row_inv_norms(table, N, d, inv_norms, (hipStream_t)stream);
-}
-
-size_t dcnr_cosine_topk_workspace_size(int64_t N, int64_t Q, int32_t k) {
-  if (N < 1 || Q < 1 || k < 1) return 256;   // nothing to plan (cosine_topk returns or rejects)
-  return topk_ws(N, Q, k) + 256;
-}
-
-dcnr_status dcnr_cosine_pack_rows(const float* table, const float* inv_norms, int64_t N, int32_t d,
-                                  uint16_t* packed, dcnr_stream_t stream) {
-  if (!table || !inv_norms || !packed || d < 1 || N < 0) {
-    set_error("dcnr_cosine_pack_rows: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  return cosine_pack_rows(table, inv_norms, N, d, (bf16*)packed, (hipStream_t)stream);
-}
-
-dcnr_status dcnr_cosine_topk_packed(const float* table, const float* inv_norms, const uint16_t* packed,
-                                    int64_t N, int32_t d, const float* queries, int64_t Q, int32_t k,
-                                    int64_t* idx, float* dist, void* ws, size_t ws_bytes,
-                                    dcnr_stream_t stream) {
-  // (no queries: the query and output pointers may be null)
-  if (!table || !inv_norms || (Q > 0 && (!queries || !idx || !dist || !ws))) {
-    set_error("dcnr_cosine_topk: null argument");
-    return DCNR_BAD_ARG;
-  }
-  if (k > N) {
-    set_error("Expected n_neighbors <= n_samples_fit, but n_neighbors = %d, n_samples_fit = %lld",
-              k, (long long)N);
-    return DCNR_BAD_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  TRYB(DCNR_K_KNN, s, (double)N * (4.0 * d + 4.0),
-       cosine_topk(table, inv_norms, (const bf16*)packed, N, d, queries, Q, k, idx, dist, ws, ws_bytes, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_cosine_topk(const float* table, const float* inv_norms, int64_t N, int32_t d,
-                             const float* queries, int64_t Q, int32_t k, int64_t* idx, float* dist,
-                             void* ws, size_t ws_bytes, dcnr_stream_t stream) {
-  return dcnr_cosine_topk_packed(table, inv_norms, nullptr, N, d, queries, Q, k, idx, dist, ws, ws_bytes,
-                                 stream);
-}
-
-size_t dcnr_cosine_topk_within_workspace_size(int64_t Q, int32_t k, int32_t d, int64_t max_set_rows) {
-  return cosine_topk_within_ws(Q, k, d, max_set_rows);   // (0 for what the call rejects)
-}
-
-dcnr_status dcnr_cosine_topk_within(const float* table, const float* inv_norms, int64_t N, int32_t d,
-                                    const float* queries, int64_t Q, const int64_t* exclude,
-                                    const int64_t* seg_offsets, int64_t G, const int32_t* seg_set,
-                                    const int64_t* set_rows, int64_t n_set_rows, const int64_t* set_offsets,
-                                    int32_t S, int64_t max_set_rows, int32_t k, int64_t ld, int64_t* idx,
-                                    float* dist, int32_t* seg_status, void* ws, size_t ws_bytes,
-                                    dcnr_stream_t stream) {
-  if (Q < 0 || G < 0 || S < 0 || N < 1 || n_set_rows < 0 || max_set_rows < 0 || k < 1 || ld < k) {
-    set_error("dcnr_cosine_topk_within: bad argument (N=%lld, Q=%lld, G=%lld, S=%d, k=%d, ld=%lld, "
-              "n_set_rows=%lld, max_set_rows=%lld)", (long long)N, (long long)Q, (long long)G, S, k,
-              (long long)ld, (long long)n_set_rows, (long long)max_set_rows);
-    return DCNR_BAD_ARG;
-  }
-  // (set_rows may be null when the CSR holds no row)
-  if (Q > 0 && (!table || !inv_norms || !queries || !idx || !dist || !ws ||
-                (G > 0 && (!seg_offsets || !seg_set || !set_offsets || (n_set_rows > 0 && !set_rows))))) {
-    set_error("dcnr_cosine_topk_within: null argument");
-    return DCNR_BAD_ARG;
-  }
-  if (k > 64 || d % 4 || d < 4 || d > 256 || N > INT32_MAX || n_set_rows > INT32_MAX ||
-      max_set_rows > INT32_MAX || Q > INT32_MAX || G > INT32_MAX) {
-    set_error("dcnr_cosine_topk_within: unsupported k=%d d=%d N=%lld n_set_rows=%lld Q=%lld G=%lld "
-              "(k<=64, d%%4==0, 4<=d<=256, the rest below 2^31)", k, d, (long long)N, (long long)n_set_rows,
-              (long long)Q, (long long)G);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  if (Q == 0 || G == 0) return DCNR_OK;   // (no query, or none in a segment: nothing is written)
-  if (ws_bytes < cosine_topk_within_ws(Q, k, d, max_set_rows)) {
-    set_error("dcnr_cosine_topk_within: workspace too small");
-    return DCNR_WORKSPACE_TOO_SMALL;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  // (bytes: the longest set once per window of 8 queries)
-  TRYB(DCNR_K_KNN, s, (double)((Q + 7) / 8) * (double)max_set_rows * (4.0 * d + 12.0),
-       cosine_topk_within(table, inv_norms, N, d, queries, Q, exclude, seg_offsets, G, seg_set, set_rows,
-                          n_set_rows, set_offsets, S, max_set_rows, k, ld, idx, dist, seg_status, ws, ws_bytes,
-                          s));
-  return DCNR_OK;
-}
-
-size_t dcnr_cosine_neighbor_table_workspace_size(int64_t N, int32_t k) {
-  if (N < 1 || N > INT32_MAX || k < 1 || k > 64 || k > N) return 256;   // (the build rejects these)
-  return neighbor_table_ws(N, k);   // (exact: one byte less is DCNR_WORKSPACE_TOO_SMALL)
-}
-
-dcnr_status dcnr_cosine_neighbor_table(const float* table, const float* inv_norms, const uint16_t* packed,
-                                       int64_t N, int32_t d, int32_t k, int64_t row_lo, int64_t row_hi,
-                                       int32_t* out_idx, float* out_dist, void* ws, size_t ws_bytes,
-                                       dcnr_stream_t stream) {
-  if (!table || !inv_norms || N < 1 || row_lo < 0 || row_lo > row_hi || row_hi > N || k < 1 || k > N) {
-    set_error("dcnr_cosine_neighbor_table: bad argument (N=%lld, k=%d, rows [%lld, %lld))", (long long)N, k,
-              (long long)row_lo, (long long)row_hi);
-    return DCNR_BAD_ARG;
-  }
-  if (N > INT32_MAX || k > 64) {
-    set_error("dcnr_cosine_neighbor_table: N=%lld (below 2^31), k=%d (max 64)", (long long)N, k);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  if (row_lo == row_hi) return DCNR_OK;
-  if (!out_idx || !ws) {
-    set_error("dcnr_cosine_neighbor_table: null argument");
-    return DCNR_BAD_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  // (bytes: one pass over the table and the result; every chunk of queries streams the table again)
-  TRYB(DCNR_K_KNN, s, (double)N * (4.0 * d + 4.0) + (double)(row_hi - row_lo) * k * 8.0,
-       neighbor_table(table, inv_norms, (const bf16*)packed, N, d, k, row_lo, row_hi, out_idx, out_dist, ws,
-                      ws_bytes, s));
-  return DCNR_OK;
-}
-
-// the shapes both update calls take: dcnr_cosine_neighbor_table's, and a width
-// the search takes (cosine_topk rejects the others only once it runs)
-static dcnr_status nbr_update_shape(const char* what, int64_t N, int32_t d, int32_t k) {
-  if (N < 1 || k < 1 || k > N) {
-    set_error("%s: bad argument (N=%lld, k=%d)", what, (long long)N, k);
-    return DCNR_BAD_ARG;
-  }
-  if (N > INT32_MAX || k > 64 || d < 4 || d % 4 || d > 256) {
-    set_error("%s: N=%lld (below 2^31), k=%d (max 64), d=%d (d %% 4 == 0, 4 <= d <= 256)", what, (long long)N, k,
-              d);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  return DCNR_OK;
-}
-
-size_t dcnr_cosine_neighbor_table_update_workspace_size(int64_t N, int32_t d, int32_t k, int64_t m) {
-  if (nbr_update_shape("dcnr_cosine_neighbor_table_update", N, d, k) != DCNR_OK || m < 0 ||
-      m > neighbor_table_update_max_m())
-    return 256;   // (the calls reject these)
-  return neighbor_table_update_ws(N, d, k, m);   // (exact: one byte less is DCNR_WORKSPACE_TOO_SMALL)
-}
-
-dcnr_status dcnr_cosine_neighbor_table_update(const float* table, const float* inv_norms, const uint16_t* packed,
-                                              int64_t N, int32_t d, int32_t k, const int32_t* changed, int64_t m,
-                                              int32_t* nbr, int32_t* counts, int32_t* host_counts,
-                                              int32_t* research_rows, void* ws, size_t ws_bytes,
-                                              dcnr_stream_t stream) {
-  if (!table || !inv_norms || m < 0) {
-    set_error("dcnr_cosine_neighbor_table_update: bad argument (m=%lld)", (long long)m);
-    return DCNR_BAD_ARG;
-  }
-  TRY_ST(nbr_update_shape("dcnr_cosine_neighbor_table_update", N, d, k));
-  if (m > neighbor_table_update_max_m()) {
-    set_error("dcnr_cosine_neighbor_table_update: m=%lld changed rows (max %d per call)", (long long)m,
-              neighbor_table_update_max_m());
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  if (m == 0) return DCNR_OK;
-  if (!changed || !nbr || !counts || !research_rows || !ws) {
-    set_error("dcnr_cosine_neighbor_table_update: null argument");
-    return DCNR_BAD_ARG;
-  }
-  for (int64_t i = 0; i < m; ++i)
-    if (changed[i] < 0 || changed[i] >= N || (i > 0 && changed[i] <= changed[i - 1])) {
-      set_error("dcnr_cosine_neighbor_table_update: changed[%lld] = %d (ascending, distinct, inside [0, %lld))",
-                (long long)i, changed[i], (long long)N);
-      return DCNR_BAD_ARG;
-    }
-  hipStream_t s = (hipStream_t)stream;
-  // (bytes: the lists, each row's k-th neighbour gathered, one pass over the rows, the changed rows)
-  TRYB(DCNR_K_KNN, s,
-       (double)N * (4.0 * k + 8.0 + 4.0 * d) + (double)N * d * ((d == 32 || d == 64) && packed ? 2.0 : 4.0) +
-           (double)m * (4.0 * d + 8.0),
-       neighbor_table_update(table, inv_norms, (const bf16*)packed, N, d, k, changed, m, nbr, counts, host_counts,
-                             research_rows, ws, ws_bytes, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_cosine_neighbor_table_rows(const float* table, const float* inv_norms, const uint16_t* packed,
-                                            int64_t N, int32_t d, int32_t k, const int32_t* rows, int64_t n,
-                                            int32_t* nbr, void* ws, size_t ws_bytes, dcnr_stream_t stream) {
-  if (!table || !inv_norms || n < 0) {
-    set_error("dcnr_cosine_neighbor_table_rows: bad argument (n=%lld)", (long long)n);
-    return DCNR_BAD_ARG;
-  }
-  TRY_ST(nbr_update_shape("dcnr_cosine_neighbor_table_rows", N, d, k));
-  if (n == 0) return DCNR_OK;
-  if (!rows || !nbr || !ws) {
-    set_error("dcnr_cosine_neighbor_table_rows: null argument");
-    return DCNR_BAD_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  // (bytes: as the build's -- every chunk of queries streams the table again)
-  TRYB(DCNR_K_KNN, s, (double)N * (4.0 * d + 4.0) + (double)n * (4.0 * d + 12.0 * k + 4.0),
-       neighbor_table_rows(table, inv_norms, (const bf16*)packed, N, d, k, rows, n, nbr, ws, ws_bytes, s));
-  return DCNR_OK;
-}
-
-dcnr_status dcnr_topk_merge(const float* dist, const int64_t* idx, int32_t lists, int64_t Q,
-                            int32_t k, int64_t* out_idx, float* out_dist, dcnr_stream_t stream) {
-  if (!dist || !idx || !out_idx || !out_dist || Q < 0) {
-    set_error("dcnr_topk_merge: bad argument");
-    return DCNR_BAD_ARG;
-  }
-  hipStream_t s = (hipStream_t)stream;
-  TRYB(DCNR_K_KNN, s, (double)lists * Q * k * 12.0 + Q * k * 12.0,
-       topk_merge(dist, idx, lists, Q, k, out_idx, out_dist, s));
   return DCNR_OK;
 }
 
@@ -2611,57 +1603,6 @@ dcnr_status dcnr_linear_wgrad_bf16(const void* dY, int64_t ldy, const void* X, i
   }
   return wgrad_bf16(dY, ldy, N, X, ldx, K, B, (float*)ws, (int64_t)(ws_bytes / 4), dW, N, K,
                     accumulate, (hipStream_t)stream);
-}
-
-void dcnr_profile_enable(int on) {
-  std::lock_guard<std::mutex> lk(g_pm);
-  g_prof = on != 0;
-  g_prof_mode = on;
-}
-
-dcnr_status dcnr_profile_collect(double* ms, int64_t* launches, int32_t n) {
-  return dcnr_profile_collect_bytes(ms, launches, nullptr, n);
-}
-
-dcnr_status dcnr_profile_collect_bytes(double* ms, int64_t* launches, double* bytes, int32_t n) {
-  std::vector<ProfRec> recs;
-  {
-    std::lock_guard<std::mutex> lk(g_pm);
-    recs.swap(g_recs);
-  }
-  for (int i = 0; i < n; ++i) {
-    if (ms) ms[i] = 0.0;
-    if (launches) launches[i] = 0;
-    if (bytes) bytes[i] = 0.0;
-  }
-  dcnr_status st = DCNR_OK;
-  for (auto& r : recs) {
-    float t = 0.f;
-    if (hipEventSynchronize(r.b) != hipSuccess || hipEventElapsedTime(&t, r.a, r.b) != hipSuccess) {
-      set_error("profile: event query failed");
-      st = DCNR_HIP_ERROR;
-    }
-    if (r.cat >= 0 && r.cat < n) {
-      if (ms) ms[r.cat] += t;
-      if (launches) launches[r.cat] += 1;
-      if (bytes) bytes[r.cat] += r.bytes;
-    }
-  }
-  std::lock_guard<std::mutex> lk(g_pm);
-  for (auto& r : recs) { g_pool.push_back(r.a); g_pool.push_back(r.b); }
-  return st;
-}
-
-dcnr_status dcnr_check_errors(void* ws, size_t ws_bytes, dcnr_stream_t stream) {
-  if (!ws || ws_bytes < 4) { set_error("bad workspace"); return DCNR_BAD_ARG; }
-  int flag = 0;
-  DCNR_HIP(hipMemcpyAsync(&flag, ws, 4, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  DCNR_HIP(hipStreamSynchronize((hipStream_t)stream));
-  if (flag) {
-    set_error("index out of range in self");
-    return DCNR_INDEX_OOB;
-  }
-  return DCNR_OK;
 }
 
 }  // extern "C"

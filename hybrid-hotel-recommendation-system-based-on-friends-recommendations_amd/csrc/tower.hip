@@ -440,7 +440,7 @@ dcnr_status eval_tower(const TowerArgs& a0, hipStream_t s) {
     case 14: k = (const void*)tower_kernel<14>; break;
     case 16: k = (const void*)tower_kernel<16>; break;
   }
-  TRY_ST(set_max_dyn_lds(k, lds));
+  TRY(set_max_dyn_lds(k, lds));
   // 32-bit buffer offsets into x0: launches of < 2^31 bytes of rows
   const int64_t chunk = std::max<int64_t>(TW_TILE, ((int64_t(1) << 31) - 1) / (a.ldx * 2) / TW_TILE * TW_TILE);
   for (int64_t m0 = 0; m0 < a0.M; m0 += chunk) {

@@ -674,11 +674,11 @@ dcnr_status sort_records(TRec*& src, TRec*& dst, int64_t M, const Plan& p, const
 
 }  // namespace
 
-size_t train_table_ws_bytes(int64_t M, int n_num) {
+static size_t train_table_ws_bytes(int64_t M, int n_num) {
   return carve(make_plan(M), M, n_num, nullptr).total;
 }
 
-dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, hipStream_t s) {
+static dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, hipStream_t s) {
   const int64_t M = a.M;
   const int n_cat = a.n_cat, n_raw = a.n_raw, n_num = a.n_raw + a.n_derived;
   const int n_counts = DCNR_TRAIN_TABLE_COUNTS + n_cat;
@@ -698,7 +698,7 @@ dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, hipStrea
   hipLaunchKernelGGL(tt_rows_kernel, dim3(p.blocks), dim3(TT_NT), 0, s, a.cat_key, a.raw, M, n_cat, n_raw,
                      a.filter_col, a.filter_lo, a.filter_hi, dv, w.colmaj, w.flags, w.sa, a.counts);
   DCNR_LAUNCH_CHECK();
-  TRY_ST(scan_inplace<false>(w.sa, nullptr, M, p, w, s));
+  TRY(scan_inplace<false>(w.sa, nullptr, M, p, w, s));
   hipLaunchKernelGGL(tt_emit_kernel, dim3(p.blocks), dim3(TT_NT), 0, s, (const uint8_t*)w.flags,
                      (const uint32_t*)w.sa, a.target, M, a.row, a.y, a.counts);
   DCNR_LAUNCH_CHECK();
@@ -731,13 +731,13 @@ dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, hipStrea
       hipLaunchKernelGGL(tt_records_kernel, dim3(p.blocks), dim3(TT_NT), 0, s, a.cat_key, n_cat, col - 2, flip,
                          (const int32_t*)a.row, (const int32_t*)a.counts, M, src);
     DCNR_LAUNCH_CHECK();
-    TRY_ST(sort_records(src, dst, M, p, w, s));
+    TRY(sort_records(src, dst, M, p, w, s));
     if (ids) {
       hipLaunchKernelGGL(tt_heads_kernel<true>, dim3(p.blocks), dim3(TT_NT), 0, s, (const TRec*)src,
                          (const int32_t*)a.counts, M, w.sa, w.sb);
       DCNR_LAUNCH_CHECK();
-      TRY_ST(scan_inplace<true>(w.sa, a.counts, M, p, w, s));
-      TRY_ST(scan_inplace<false>(w.sb, a.counts, M, p, w, s));
+      TRY(scan_inplace<true>(w.sa, a.counts, M, p, w, s));
+      TRY(scan_inplace<false>(w.sb, a.counts, M, p, w, s));
       hipLaunchKernelGGL(tt_id_codes_kernel, dim3(p.blocks), dim3(TT_NT), 0, s, (const TRec*)src,
                          (const uint32_t*)w.sa, (const uint32_t*)w.sb, (const int32_t*)a.counts, M, col, flip,
                          a.collab, col ? a.item_ids : a.user_ids, a.counts + 1 + col);
@@ -745,7 +745,7 @@ dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, hipStrea
       hipLaunchKernelGGL(tt_heads_kernel<false>, dim3(p.blocks), dim3(TT_NT), 0, s, (const TRec*)src,
                          (const int32_t*)a.counts, M, w.sa, w.sb);
       DCNR_LAUNCH_CHECK();
-      TRY_ST(scan_inplace<false>(w.sa, a.counts, M, p, w, s));
+      TRY(scan_inplace<false>(w.sa, a.counts, M, p, w, s));
       hipLaunchKernelGGL(tt_cat_codes_kernel, dim3(p.blocks), dim3(TT_NT), 0, s, (const TRec*)src,
                          (const uint32_t*)w.sa, (const int32_t*)a.counts, M, n_cat, col - 2, a.cat,
                          a.cat_keys + (int64_t)(col - 2) * M, a.counts + DCNR_TRAIN_TABLE_COUNTS + (col - 2));
@@ -761,3 +761,69 @@ dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, hipStrea
 }
 
 }  // namespace dcnr
+
+using namespace dcnr;
+
+extern "C" {
+
+static dcnr_status train_table_shape(int64_t M, int32_t n_cat, int32_t n_raw, int32_t n_derived) {
+  if (M < 0 || n_cat < 0 || n_raw < 0 || n_derived < 0) return DCNR_BAD_ARG;
+  if (M >= 2147483647ll || n_cat > 64 || (int64_t)n_raw + n_derived > TT_MAXC) return DCNR_UNSUPPORTED_SHAPE;
+  return DCNR_OK;
+}
+
+size_t dcnr_train_table_workspace_size(int64_t M, int32_t n_cat, int32_t n_raw, int32_t n_derived) {
+  if (train_table_shape(M, n_cat, n_raw, n_derived) != DCNR_OK) return 0;
+  return train_table_ws_bytes(M, n_raw + n_derived) + 256;
+}
+
+dcnr_status dcnr_train_table_build(const dcnr_train_table_args* a, void* ws, size_t ws_bytes,
+                                   dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!a) {
+    set_error("dcnr_train_table_build: null args");
+    return DCNR_BAD_ARG;
+  }
+  const dcnr_status shape = train_table_shape(a->M, a->n_cat, a->n_raw, a->n_derived);
+  bool bad = shape == DCNR_BAD_ARG || !a->counts || a->filter_col < -1 ||
+             (a->filter_col >= 0 && a->filter_col >= a->n_raw) || (a->n_derived > 0 && !a->derived);
+  if (!bad)
+    for (int d = 0; d < a->n_derived; ++d) {
+      const int32_t op = a->derived[3 * d], i = a->derived[3 * d + 1], j = a->derived[3 * d + 2];
+      bad |= (op != DCNR_DERIVED_RATIO && op != DCNR_DERIVED_DIFF) || i < 0 || i >= a->n_raw || j < 0 ||
+             j >= a->n_raw;
+    }
+  if (!bad && a->M > 0) {
+    const bool num = a->n_raw + a->n_derived > 0;
+    bad = !a->user || !a->item || !a->target || !ws || (a->n_cat > 0 && (!a->cat_key || !a->cat || !a->cat_keys)) ||
+          (a->n_raw > 0 && !a->raw) || (num && (!a->num || !a->stats)) || !a->row || !a->collab || !a->y ||
+          !a->user_ids || !a->item_ids;
+  }
+  if (bad) {
+    set_error("dcnr_train_table_build: bad argument (M=%lld, n_cat=%d, n_raw=%d, n_derived=%d, filter_col=%d)",
+              (long long)a->M, a->n_cat, a->n_raw, a->n_derived, a->filter_col);
+    return DCNR_BAD_ARG;
+  }
+  if (shape != DCNR_OK) {
+    set_error("dcnr_train_table_build: unsupported shape (M=%lld, n_cat=%d, n_raw=%d, n_derived=%d)",
+              (long long)a->M, a->n_cat, a->n_raw, a->n_derived);
+    return shape;
+  }
+  const int n_counts = DCNR_TRAIN_TABLE_COUNTS + a->n_cat;
+  if (a->M == 0) {
+    DCNR_HIP(hipMemsetAsync(a->counts, 0, (size_t)n_counts * 4, s));
+    if (a->host_counts)
+      for (int i = 0; i < n_counts; ++i) a->host_counts[i] = 0;
+    return DCNR_OK;
+  }
+  const size_t need = train_table_ws_bytes(a->M, a->n_raw + a->n_derived) + 256;
+  if (ws_bytes < need) {
+    set_error("dcnr_train_table_build: workspace too small: %zu < %zu", ws_bytes, need);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  TRYP(DCNR_K_SERVE, s, train_table_build(*a, base, s));
+  return DCNR_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 """Stage-by-stage check of the eval forward, bf16 or fp32, on every scoring
-path (csrc/dcnr_api.hip make_plan, eval fields):
+path (csrc/step.hip make_plan, eval fields):
 
   T  the fused tower (csrc/tower.hip; DCNR_FLAG_FUSED_TOWER, or B >= 16384):
      x0 and zc are all it stores
@@ -437,7 +437,7 @@ class EvalCase:
 
 
 def check_launches(path, cnt):
-    """The kernel classes each plan launches (dcnr_api.hip Fwd::tower, eval_epi,
+    """The kernel classes each plan launches (step.hip Fwd::tower, eval_epi,
     unfused_head, layers): the tower or not; head_parts is one head-class
     launch, row_dot + head_logits are two; only `layers` runs row passes."""
     assert cnt["tower"] == (1 if path == "T" else 0), (path, cnt)

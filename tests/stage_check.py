@@ -1,5 +1,5 @@
 """Stage-by-stage check of one training step, bf16 or fp32, on whichever
-kernel path the step's plan takes (csrc/dcnr_api.hip make_plan).
+kernel path the step's plan takes (csrc/step.hip make_plan).
 
 End to end a bf16 step cannot be pinned element-wise to any other
 implementation (tests/test_bf16_train_gpu.py explains the sensitivity), and

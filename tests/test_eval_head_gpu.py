@@ -126,7 +126,7 @@ def test_eval_tower_chunked_launch(dev):
 
 def test_eval_tower_batch_threshold(dev):
     """Without DCNR_FLAG_FUSED_TOWER the bf16 eval forward launches the fused
-    tower from 16384 samples on (dcnr_api.hip TOWER_MIN_B: below it the
+    tower from 16384 samples on (step.hip TOWER_MIN_B: below it the
     layer-by-layer path is faster) -- counted by the library's per-class
     launch profiler -- and its logits there equal the forced tower's bit
     for bit."""

@@ -98,7 +98,7 @@ def test_tail_combine_equals_standalone(dev, hidden, wide, B, n_res):
 # ---------------------------------------------------------------- fixed-order emulation
 def _splits(N, K, B):
     """gemm_dw_splits and the rows per split of dw_args (csrc/gemm_dw.hip,
-    csrc/dcnr_api.hip), checked against the library's workspace size."""
+    csrc/step.hip), checked against the library's workspace size."""
     tiles = -(-N // 256) * -(-K // 256)
     s = max(8, (256 // tiles) // 8 * 8)
     while s > 8 and -(-B // s) < 64:

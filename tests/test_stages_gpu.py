@@ -218,7 +218,7 @@ def test_step_stage_by_stage_batch_regimes(dev, case):
     """Narrow models at batch sizes past B = 8192, where the code that depends
     on B alone changes path, under the same stage checks and the same bit-equal
     second run.  The counts below follow csrc/elementwise.hip (run_rowcol,
-    reduce_fused) and csrc/dcnr_api.hip (linear_dw, make_layout) by hand.
+    reduce_fused) and csrc/step.hip (linear_dw, make_layout) by hand.
 
     Reduction row passes: rows = max(32, cdiv(B, 2048)) per chunk, nc = cdiv(B, rows)
     chunks; nc > 256 takes the two-stage reduce_fused_kernel, 32 chunk groups of
