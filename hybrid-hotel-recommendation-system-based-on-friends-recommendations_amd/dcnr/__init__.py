@@ -48,6 +48,13 @@ System-Based-on-Friends-Recommendations):
                                      device: raw review columns to the training
                                      tensors, id maps, encoders and scaler;
                                      prepare_data_host: the numpy yardstick
+  Preprocessor, Transformed, IdMap   a fitted preprocessing applied to rows it was
+                                     not fitted on (preprocess_for_ranking,
+                                     main.py:215-230), on the device: raw ids
+                                     through a device hash table, category keys,
+                                     NaN fill, scaler; PreparedData.preprocessor(),
+                                     Preprocessor.from_artifacts; transform_host:
+                                     the numpy yardstick
   artifacts.save_artifacts /         final_dcn_model.pth + item_embeddings.npy
   artifacts.load_artifacts           (train.py:391-394, main.py:256-270)
   artifacts.save_neighbor_table /    item_neighbors.npy (+ fingerprint): the
@@ -69,6 +76,7 @@ from .interactions import InteractionStore  # noqa: F401
 from .cities import CitySets  # noqa: F401
 from .item_features import ItemFeatures  # noqa: F401
 from .prepare import PreparedData, category_keys, prepare_data, prepare_data_host  # noqa: F401
+from .transform import IdMap, Preprocessor, Transformed  # noqa: F401
 from . import artifacts  # noqa: F401
 
 __version__ = "0.1.0"

@@ -274,6 +274,11 @@ _SIGS = {
     "dcnr_train_table_workspace_size": (ctypes.c_size_t, [_I64, ctypes.c_int32, ctypes.c_int32,
                                                           ctypes.c_int32]),
     "dcnr_train_table_build": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P]),
+    "dcnr_id_map_build": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "dcnr_id_map_lookup": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _P, _P]),
+    "dcnr_rows_transform_workspace_size": (ctypes.c_size_t, [_I64, ctypes.c_int32, ctypes.c_int32,
+                                                             ctypes.c_int32]),
+    "dcnr_rows_transform": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P]),
     "dcnr_check_errors": (ctypes.c_int, [_P, ctypes.c_size_t, _P]),
     "dcnr_linear_bf16": (ctypes.c_int, [_P, _I64, _I64, ctypes.c_int32, _P, _I64, ctypes.c_int32,
                                         _P, _P, _I64, ctypes.c_int, _P]),

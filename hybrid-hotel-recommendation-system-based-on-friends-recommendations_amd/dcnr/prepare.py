@@ -9,6 +9,8 @@ dcnr_gather_rows per split.  What comes out plugs into ``DeviceLoader``,
 ``FusedTrainer.fit``, ``DCN_RecSys(*model_dims, params)`` and
 ``ItemFeatures.set_scaler``.  ``prepare_data_host`` is the numpy yardstick of the
 same contract; it needs neither pandas nor scikit-learn.
+Both results keep the fit's ``derived`` and ``noise_filter``, and their
+``preprocessor()`` applies the fit to other rows (dcnr/transform.py).
 
 Arguments of both: ``user``, ``item`` [M] raw ids (any int64); ``target`` [M]
 0 / 1; ``cat`` a list of n_cat columns, each either int64 keys (negative:
@@ -153,6 +155,14 @@ class _Prepared:
                               for k, name in enumerate(self.cat_names)}
         return self._encoders
 
+    def preprocessor(self):
+        """The fitted state as a ``Preprocessor``: ``transform`` encodes rows the
+        fit has not seen (dcnr/transform.py)."""
+        from .transform import Preprocessor
+        return Preprocessor(self.user_ids, self.item_ids, self.cat_keys, self._cat_categories, self.median_,
+                            self.scale_, self.min_, self.cat_names, derived=self.derived,
+                            noise_filter=self.noise_filter)
+
     def artifacts(self) -> dict:
         """The reference's ``artifacts`` dict (train.py:80-84); the scaler entry
         holds MinMaxScaler's fitted arrays (joblib stays with the caller)."""
@@ -188,8 +198,10 @@ class PreparedData(_Prepared):
                             device=self.train[0].device)
 
 
-def _finish(out: _Prepared, cat_names, n_num):
+def _finish(out: _Prepared, cat_names, n_num, derived=(), noise_filter=None):
     out.cat_names = list(cat_names)
+    out.derived = [(str(op), int(i), int(j)) for op, i, j in derived]
+    out.noise_filter = None if noise_filter is None else tuple(noise_filter)
     out._user_map = out._item_map = out._encoders = None
     out.model_dims = (int(len(out.user_ids)), int(len(out.item_ids)),
                       {name: int(len(out.cat_keys[k])) for k, name in enumerate(cat_names)}, int(n_num))
@@ -318,7 +330,7 @@ def prepare_data_host(user, item, target, cat, num, *, cat_names=None, noise_fil
     out._cat_categories = [c for _, c in cols]
     out.median_, out.data_min_, out.data_max_, out.scale_, out.min_ = median, data_min, data_max, scale, mn
     out.n_after_filter = int(keep.sum())
-    _finish(out, names, n_num)
+    _finish(out, names, n_num, derived, noise_filter)
     tr, va = split_indices(n, test_size, random_state)
     out.train = tuple(t[tr] for t in out.full)
     out.val = tuple(t[va] for t in out.full)
@@ -416,7 +428,7 @@ def prepare_data(user, item, target, cat, num, *, cat_names=None, noise_filter=N
     out._cat_categories = [c for _, c in cols]
     out.median_, out.data_min_, out.data_max_, out.scale_, out.min_ = (t["stats"][q] for q in range(5))
     out.n_after_filter = t["n_after_filter"]
-    _finish(out, names, t["n_num"])
+    _finish(out, names, t["n_num"], derived, noise_filter)
 
     lib = _lib.load()
     src = list(out.full) + [out.rows]

@@ -1169,6 +1169,89 @@ size_t dcnr_train_table_workspace_size(int64_t M, int32_t n_cat, int32_t n_raw, 
 dcnr_status dcnr_train_table_build(const dcnr_train_table_args* args, void* ws, size_t ws_bytes,
                                    dcnr_stream_t stream);
 
+/* A raw-id dictionary on the device (dcnr.IdMap): an open-addressing hash
+ * table of `capacity` 16-byte slots {int64 key, int64 index}, capacity a power
+ * of two above n, `table` 16-byte aligned device memory of capacity * 16 bytes.
+ * The build clears the table, then one lane per id claims a slot (linear
+ * probing from a 64-bit mixing hash, a compare-and-swap on the key word, then
+ * the index is stored): the index of ids[i] is i.  INT64_MIN marks an empty
+ * slot and is no legal id.  status (device int32, also stored to host_status:
+ * pinned, or NULL): 0, DCNR_REQ_BAD_DATA for a duplicate or the reserved id,
+ * DCNR_REQ_OVERFLOW when a lane found no free slot; the table is then
+ * unusable.  The lookup writes out[q] = the index of raw[q], or default_index
+ * for an id the table does not hold (the reserved one included); it only
+ * reads the table.  Every probe loop ends after `capacity` slots and no lane
+ * waits for another.  DCNR_BAD_ARG before any launch: a needed null pointer
+ * (ids with n = 0 and raw / out with M = 0 may be NULL), a negative size, a
+ * capacity that is no power of two or not above n, a misaligned table;
+ * DCNR_UNSUPPORTED_SHAPE: capacity > 2^40.  Stream-ordered; no allocation, no
+ * host synchronisation. */
+dcnr_status dcnr_id_map_build(const int64_t* ids, int64_t n, void* table, int64_t capacity, int32_t* status,
+                              int32_t* host_status, dcnr_stream_t stream);
+dcnr_status dcnr_id_map_lookup(const void* table, int64_t capacity, const int64_t* raw, int64_t M,
+                               int64_t default_index, int64_t* out, dcnr_stream_t stream);
+
+/* A fitted preprocessing applied to rows it was not fitted on (dcnr.Preprocessor
+ * .transform; preprocess_for_ranking, main.py:215-230, in train.py's order of
+ * steps; DESIGN.md section 9 has the contract in full).  The inputs are those
+ * of dcnr_train_table_args, but target may be NULL, and y with it; the fit,
+ * device memory unless stated:
+ *   user_table, item_table   id maps built over the fit's user_ids / item_ids
+ *                            (their capacities; n_users, n_items ids)
+ *   cat_keys, cat_offsets    the columns' ascending present keys, one list
+ *                            behind the other; cat_offsets [n_cat + 1] HOST
+ *   fit [3][n_num]           float64: median_, scale_, min_
+ *   fill_nan                 not 0: a NaN numeric (after the derived columns)
+ *                            becomes its column's median_; 0: it stays NaN
+ *   drop_unknown             0: an unknown user becomes n_users / 2, an
+ *                            unknown hotel 0, an unknown or missing (negative)
+ *                            category key 0, and the row's bit in unknown_bits
+ *                            says so (bit 0 the user, bit 1 the hotel, bit
+ *                            2 + c category c); not 0: such rows are left out
+ * Rows that fail the filter are left out first; the kept rows keep their input
+ * order.  num = float32(x * scale_ + min_), the product and the sum each
+ * rounded to float64 (never an fma); y = target != 0.
+ * Outputs, device memory, each with room for M rows: row [n] int32 (the input
+ * positions kept), collab [n][2], cat [n][n_cat], unknown_bits [n] (int64),
+ * num [n][n_num], y [n] (float32).
+ *   counts [DCNR_ROWS_TRANSFORM_COUNTS + n_cat]  int32: {n, rows the filter
+ *                            removed, rows with an unknown user, with an
+ *                            unknown hotel, status}, then per category column
+ *                            the rows with an unknown or missing key (all
+ *                            counted over the rows that passed the filter);
+ *                            also stored to host_counts (pinned, or NULL) with
+ *                            system-scope stores.  The status is 0, or
+ *                            DCNR_REQ_BAD_DATA when a kept value is +-inf.
+ * Every atomic is an integer one and no atomic decides a position: the same
+ * bytes on every run.  Workspace: dcnr_rows_transform_workspace_size bytes,
+ * about 4 M (0 for arguments the call rejects).  DCNR_BAD_ARG before any
+ * launch: a null args, a needed null pointer (a column of width 0 may be NULL,
+ * and with M = 0 everything but counts), target without y or y without target,
+ * a negative size, a capacity that is no power of two or not above its id
+ * count, a misaligned table, offsets that do not start at 0 or descend, a
+ * derived op that is neither, a derived or filter column outside [0, n_raw);
+ * DCNR_UNSUPPORTED_SHAPE: M >= 2^31 - 1, n_cat > 62, n_raw + n_derived > 64;
+ * DCNR_WORKSPACE_TOO_SMALL.  With M = 0 no kernel is launched.  Stream-ordered;
+ * no allocation, no host synchronisation. */
+#define DCNR_ROWS_TRANSFORM_COUNTS 5
+typedef struct {
+  const int64_t* user; const int64_t* item; const uint8_t* target;
+  const int64_t* cat_key; const double* raw;
+  int64_t M; int32_t n_cat, n_raw;
+  int32_t filter_col; double filter_lo, filter_hi;
+  int32_t n_derived; const int32_t* derived;
+  int32_t fill_nan, drop_unknown;
+  const void* user_table; int64_t user_capacity, n_users;
+  const void* item_table; int64_t item_capacity, n_items;
+  const int64_t* cat_keys; const int64_t* cat_offsets;
+  const double* fit;
+  int32_t* row; int64_t* collab; int64_t* cat; float* num; float* y; int64_t* unknown_bits;
+  int32_t* counts; int32_t* host_counts;
+} dcnr_rows_transform_args;
+size_t dcnr_rows_transform_workspace_size(int64_t M, int32_t n_cat, int32_t n_raw, int32_t n_derived);
+dcnr_status dcnr_rows_transform(const dcnr_rows_transform_args* args, void* ws, size_t ws_bytes,
+                                dcnr_stream_t stream);
+
 /* The deep tower's Linear layer as a standalone bf16 call (nn.Linear forward,
  * train.py:143,105,109): C[M,N] = X[M,K] . W[N,K]^T + bias, X/W bf16
  * row-major (K, ldx, ldw multiples of 8), C bf16 (out_f32 = 0) or fp32.
