@@ -10,6 +10,18 @@
 //            its key word and then stores the index; lookups run in later
 //            kernels and only read.  Every probe loop ends after `capacity`
 //            slots: a full table sets DCNR_REQ_OVERFLOW and the lane returns.
+//   insert   dcnr_id_map_insert admits ids the table does not hold.  find: a
+//            read-only lookup settles the known rows and sees the reserved id
+//            before anything is written.  claim: a row with an unknown id
+//            claims its slot's key word by compare-and-swap (or finds it
+//            claimed by a row with the same id) and takes an integer atomicMin
+//            of its row number on the slot's index word.  mark, scan: a row
+//            that finds its own number there is its id's first appearance; the
+//            sum scan of those marks numbers the new ids in first-appearance
+//            order.  head: the first rows write the index word and new_ids.
+//            rest: the other rows read it.  Which slot an id lands in depends
+//            on which lane wins a probe chain, as in the build; out, new_ids
+//            and the count do not -- no atomic decides a number.
 //   flags    one lane per input row: the filter, the two id probes and the
 //            category binary searches; keep[i] and the count words (a ballot
 //            per counter, LDS adds, one global integer add per workgroup)
@@ -20,7 +32,8 @@
 //            only and cache-resident; no per-row scratch is written and read
 //            back), the derived columns, the NaN fill, the scaler, y
 //
-// Every atomic is an integer add or or: the same bytes on every run.
+// Every atomic is an integer add, or, min or compare-and-swap: the same results
+// on every run (the id map's slot positions aside).
 #include "dcnr_internal.h"
 
 namespace dcnr {
@@ -199,6 +212,92 @@ __global__ __launch_bounds__(RT_NT) void rt_tile_apply_kernel(uint32_t* a, int64
     run += x[q];
     if (i0 + q < M) a[i0 + q] = run;
   }
+}
+
+// ------------------------------------------------------------ id map insert
+// The index word of a slot claimed by this call holds, between the claim and
+// the head pass, SIGN | (the least batch row that carries the slot's id): below
+// the -1 of an empty slot as an unsigned number, negative as a signed one.
+__device__ __forceinline__ bool ins_bad(const int32_t* counts) { return (counts[1] & DCNR_REQ_BAD_DATA) != 0; }
+
+// out[q] = the index of a known id, -1 otherwise; the reserved id sets the status
+__global__ __launch_bounds__(RT_NT) void im_ins_find_kernel(const Slot* t, int64_t cap, const int64_t* raw, int64_t M,
+                                                            int64_t* out, int32_t* counts) {
+  const int64_t i0 = (int64_t)blockIdx.x * RT_NT + threadIdx.x, step = (int64_t)gridDim.x * RT_NT;
+  bool reserved = false;
+  for (int64_t i = i0; i < M; i += step) {
+    const int64_t id = raw[i];
+    reserved |= id == ID_EMPTY;
+    out[i] = map_find(t, cap, id);
+  }
+  if (reserved) atomicOr(counts + 1, DCNR_REQ_BAD_DATA);
+}
+
+// every unknown row claims (or finds claimed) its id's slot and offers its row number
+__global__ __launch_bounds__(RT_NT) void im_ins_claim_kernel(Slot* t, int64_t cap, const int64_t* raw, int64_t M,
+                                                             const int64_t* out, int64_t* slot, int32_t* counts) {
+  if (ins_bad(counts)) return;   // decided by the kernel before: the table stays as it was
+  const uint64_t mask = (uint64_t)cap - 1ull;
+  const int64_t i0 = (int64_t)blockIdx.x * RT_NT + threadIdx.x, step = (int64_t)gridDim.x * RT_NT;
+  for (int64_t i = i0; i < M; i += step) {
+    if (out[i] >= 0) continue;
+    const int64_t id = raw[i];
+    uint64_t s = mix64((uint64_t)id) & mask;
+    int64_t at = -1;
+    for (int64_t p = 0; p < cap; ++p) {   // bounded: no lane waits for another
+      const unsigned long long old = atomicCAS((unsigned long long*)&t[s].key, (unsigned long long)ID_EMPTY,
+                                               (unsigned long long)id);
+      if ((int64_t)old == ID_EMPTY || (int64_t)old == id) {
+        at = (int64_t)s;
+        break;
+      }
+      s = (s + 1ull) & mask;
+    }
+    slot[i] = at;
+    if (at >= 0)
+      atomicMin((unsigned long long*)&t[at].index, (unsigned long long)(SIGN | (uint64_t)i));
+    else
+      atomicOr(counts + 1, DCNR_REQ_OVERFLOW);
+  }
+}
+
+// mark[q] = 1 for the first row of every new id
+__global__ __launch_bounds__(RT_NT) void im_ins_mark_kernel(const Slot* t, const int64_t* out, const int64_t* slot,
+                                                            int64_t M, uint32_t* mark, const int32_t* counts) {
+  const bool bad = ins_bad(counts);
+  const int64_t i0 = (int64_t)blockIdx.x * RT_NT + threadIdx.x, step = (int64_t)gridDim.x * RT_NT;
+  for (int64_t i = i0; i < M; i += step) {
+    uint32_t m = 0u;
+    if (!bad && out[i] < 0 && slot[i] >= 0) m = t[slot[i]].index == (int64_t)(SIGN | (uint64_t)i) ? 1u : 0u;
+    mark[i] = m;
+  }
+}
+
+// scan: the inclusive scan of mark.  The heads number their ids n, n + 1, ...
+__global__ __launch_bounds__(RT_NT) void im_ins_head_kernel(Slot* t, const int64_t* raw, int64_t M, int64_t n,
+                                                            const int64_t* slot, const uint32_t* scan, int64_t* out,
+                                                            int64_t* new_ids, int32_t* counts) {
+  if (ins_bad(counts)) return;
+  const int64_t i0 = (int64_t)blockIdx.x * RT_NT + threadIdx.x, step = (int64_t)gridDim.x * RT_NT;
+  for (int64_t i = i0; i < M; i += step) {
+    const uint32_t inc = scan[i], before = i ? scan[i - 1] : 0u;
+    if (inc != before) {
+      const int64_t j = (int64_t)before;
+      t[slot[i]].index = n + j;
+      new_ids[j] = raw[i];
+      out[i] = n + j;
+    }
+    if (i == M - 1) counts[0] = (int32_t)inc;
+  }
+}
+
+// the other rows of a new id read what its head wrote
+__global__ __launch_bounds__(RT_NT) void im_ins_rest_kernel(const Slot* t, const int64_t* slot, int64_t M,
+                                                            int64_t* out, const int32_t* counts) {
+  if (ins_bad(counts)) return;
+  const int64_t i0 = (int64_t)blockIdx.x * RT_NT + threadIdx.x, step = (int64_t)gridDim.x * RT_NT;
+  for (int64_t i = i0; i < M; i += step)
+    if (out[i] < 0 && slot[i] >= 0) out[i] = t[slot[i]].index;
 }
 
 // --------------------------------------------------------------- the rows
@@ -413,6 +512,55 @@ dcnr_status rows_shape(int64_t M, int32_t n_cat, int32_t n_raw, int32_t n_derive
   return DCNR_OK;
 }
 
+struct InsWs {
+  int64_t* slot;       // [M]: the slot of every row with an unknown id
+  uint32_t* mark;      // [M]: the first-appearance marks, then their inclusive scan
+  uint32_t* tile_tot;  // [tiles]
+  size_t total;
+};
+
+InsWs ins_carve(int64_t M, void* base) {
+  Bump b(base);
+  InsWs w;
+  w.slot = (int64_t*)b.take((size_t)M * 8);
+  w.mark = (uint32_t*)b.take((size_t)M * 4);
+  w.tile_tot = (uint32_t*)b.take((size_t)std::max<int64_t>(1, cdiv(M, RT_TILE)) * 4);
+  w.total = b.off;
+  return w;
+}
+
+dcnr_status id_map_insert(Slot* t, int64_t cap, int64_t n, const int64_t* raw, int64_t M, int64_t* out,
+                          int64_t* new_ids, int32_t* counts, int32_t* host_counts, void* ws, hipStream_t s) {
+  const InsWs w = ins_carve(M, ws);
+  const int64_t tiles = std::max<int64_t>(1, cdiv(M, RT_TILE));
+  const dim3 g(grid_for(M)), b(RT_NT);
+  DCNR_HIP(hipMemsetAsync(counts, 0, 8, s));
+  hipLaunchKernelGGL(im_ins_find_kernel, g, b, 0, s, (const Slot*)t, cap, raw, M, out, counts);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(im_ins_claim_kernel, g, b, 0, s, t, cap, raw, M, (const int64_t*)out, w.slot, counts);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(im_ins_mark_kernel, g, b, 0, s, (const Slot*)t, (const int64_t*)out, (const int64_t*)w.slot, M,
+                     w.mark, (const int32_t*)counts);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rt_tile_sum_kernel, dim3((unsigned)tiles), b, 0, s, (const uint32_t*)w.mark, M, w.tile_tot);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rt_tile_scan_kernel, dim3(1), dim3(RT_SCAN_NT), 0, s, w.tile_tot, tiles);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(rt_tile_apply_kernel, dim3((unsigned)tiles), b, 0, s, w.mark, M, (const uint32_t*)w.tile_tot);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(im_ins_head_kernel, g, b, 0, s, t, raw, M, n, (const int64_t*)w.slot, (const uint32_t*)w.mark,
+                     out, new_ids, counts);
+  DCNR_LAUNCH_CHECK();
+  hipLaunchKernelGGL(im_ins_rest_kernel, g, b, 0, s, (const Slot*)t, (const int64_t*)w.slot, M, out,
+                     (const int32_t*)counts);
+  DCNR_LAUNCH_CHECK();
+  if (host_counts) {
+    hipLaunchKernelGGL(rt_mirror_kernel, dim3(1), b, 0, s, (const int32_t*)counts, 2, host_counts);
+    DCNR_LAUNCH_CHECK();
+  }
+  return DCNR_OK;
+}
+
 }  // namespace
 
 }  // namespace dcnr
@@ -463,7 +611,41 @@ dcnr_status dcnr_id_map_lookup(const void* table, int64_t capacity, const int64_
   return DCNR_OK;
 }
 
-size_t dcnr_rows_transform_workspace_size(int64_t M, int32_t n_cat, int32_t n_raw, int32_t n_derived) {
+size_t dcnr_id_map_insert_workspace_size(int64_t M) {
+  if (M < 0 || M >= 2147483647ll) return 0;
+  return ins_carve(M, nullptr).total + 256;
+}
+
+dcnr_status dcnr_id_map_insert(void* table, int64_t capacity, int64_t n, const int64_t* raw, int64_t M, int64_t* out,
+                               int64_t* new_ids, int32_t* counts, int32_t* host_counts, void* ws, size_t ws_bytes,
+                               dcnr_stream_t stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (M < 0 || n < 0 || !table || ((uintptr_t)table & 15) || !counts || !pow2(capacity) || capacity <= n ||
+      (M > 0 && (!raw || !out || !new_ids || !ws))) {
+    set_error("dcnr_id_map_insert: bad argument (M=%lld, n=%lld, capacity=%lld: a power of two above n)",
+              (long long)M, (long long)n, (long long)capacity);
+    return DCNR_BAD_ARG;
+  }
+  if (M >= 2147483647ll || capacity > (1ll << 40)) {
+    set_error("dcnr_id_map_insert: unsupported shape (M=%lld, capacity=%lld)", (long long)M, (long long)capacity);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  if (M == 0) {
+    DCNR_HIP(hipMemsetAsync(counts, 0, 8, s));
+    if (host_counts) host_counts[0] = host_counts[1] = 0;
+    return DCNR_OK;
+  }
+  const size_t need = ins_carve(M, nullptr).total + 256;
+  if (ws_bytes < need) {
+    set_error("dcnr_id_map_insert: workspace too small: %zu < %zu", ws_bytes, need);
+    return DCNR_WORKSPACE_TOO_SMALL;
+  }
+  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  TRYP(DCNR_K_SERVE, s, id_map_insert((Slot*)table, capacity, n, raw, M, out, new_ids, counts, host_counts, base, s));
+  return DCNR_OK;
+}
+
+size_t dcnr_rows_transform_workspace_size(int64_t M,int32_t n_cat, int32_t n_raw, int32_t n_derived) {
   if (rows_shape(M, n_cat, n_raw, n_derived) != DCNR_OK) return 0;
   return carve(M, nullptr).total + 256;
 }

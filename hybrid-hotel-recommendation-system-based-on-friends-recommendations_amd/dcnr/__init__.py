@@ -55,6 +55,15 @@ System-Based-on-Friends-Recommendations):
                                      NaN fill, scaler; PreparedData.preprocessor(),
                                      Preprocessor.from_artifacts; transform_host:
                                      the numpy yardstick
+  admission                          a user or hotel the fit has not seen, admitted
+                                     in place: IdMap.insert / Preprocessor.admit /
+                                     transform(unknown="admit") number the new ids
+                                     by first appearance (train.py:42-43);
+                                     DCN_RecSys.grow_ and FusedTrainer.grow add
+                                     their table rows (moments kept);
+                                     NearestNeighbors.append_rows and
+                                     RankingPipeline.append_items their index rows
+                                     and neighbour lists, as a fresh fit + build
   artifacts.save_artifacts /         final_dcn_model.pth + item_embeddings.npy
   artifacts.load_artifacts           (train.py:391-394, main.py:256-270)
   artifacts.save_neighbor_table /    item_neighbors.npy (+ fingerprint): the

@@ -230,6 +230,9 @@ _SIGS = {
     "dcnr_cosine_neighbor_table_update": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.c_int32,
                                                          ctypes.c_int32, _P, _I64, _P, _P, _P, _P, _P,
                                                          ctypes.c_size_t, _P]),
+    "dcnr_cosine_neighbor_table_affected": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.c_int32,
+                                                           ctypes.c_int32, _P, _I64, _P, _P, _P, _P, _P,
+                                                           ctypes.c_size_t, _P]),
     "dcnr_cosine_neighbor_table_rows": (ctypes.c_int, [_P, _P, _P, _I64, ctypes.c_int32, ctypes.c_int32,
                                                        _P, _I64, _P, _P, ctypes.c_size_t, _P]),
     "dcnr_topk_merge": (ctypes.c_int, [_P, _P, ctypes.c_int32, _I64, ctypes.c_int32, _P, _P, _P]),
@@ -276,6 +279,8 @@ _SIGS = {
     "dcnr_train_table_build": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P]),
     "dcnr_id_map_build": (ctypes.c_int, [_P, _I64, _P, _I64, _P, _P, _P]),
     "dcnr_id_map_lookup": (ctypes.c_int, [_P, _I64, _P, _I64, _I64, _P, _P]),
+    "dcnr_id_map_insert_workspace_size": (ctypes.c_size_t, [_I64]),
+    "dcnr_id_map_insert": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _P, _P, _P, _P, _P, ctypes.c_size_t, _P]),
     "dcnr_rows_transform_workspace_size": (ctypes.c_size_t, [_I64, ctypes.c_int32, ctypes.c_int32,
                                                              ctypes.c_int32]),
     "dcnr_rows_transform": (ctypes.c_int, [_P, _P, ctypes.c_size_t, _P]),

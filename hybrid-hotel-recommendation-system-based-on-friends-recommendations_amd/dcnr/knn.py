@@ -290,6 +290,118 @@ class NearestNeighbors:
                     stats["researched"] += c[3]
         return stats if return_stats else None
 
+    def append_rows(self, vectors=None, table=None, storage=None, return_stats=False, rebuild=None):
+        """Append m rows to the fitted table, with everything derived from it
+        ending exactly as ``fit`` + ``build_neighbor_table(kt)`` give it on the
+        grown table: ``_inv``, ``_packed`` and the neighbour table.
+
+        vectors  [m, d]: copied behind the fitted table
+        storage  instead: an fp32 device tensor [N + m, d], contiguous, whose
+                 first N rows equal the fitted table and whose last m rows are
+                 the new vectors; adopted without a copy (a pipeline's index
+                 shares the model's grown item table as it shared the old one)
+        table    int32 [N, kt] on the device, exact for the fitted table;
+                 default ``neighbor_table_``; with neither only the norms and
+                 the packed copy grow
+
+        Returns the grown [N + m, kt] neighbour table (None without one), also
+        kept as ``neighbor_table_`` when that was the table grown (otherwise a
+        kept ``neighbor_table_`` is dropped: it is not the index's any more); with
+        ``return_stats`` ``(table, stats)``, the stats as ``update_rows``'.
+
+        The appended rows are the changed rows of the grown table: no list of
+        an old row can hold a new row, so an old row is either untouched or
+        gains new rows.  ``update_rows``' filter finds the rows that may gain
+        (a superset, by a margin far above float32's rounding), and they are
+        searched as the build searches them, the new rows with them whatever
+        their lists hold (they are filled with row 0 first).  The filter's rows
+        do not go through ``update_rows``' merge: it scores a kept entry again,
+        and at a million rows some two neighbours lie within one float32 step,
+        where the merge and the search need not order them alike (measured:
+        DESIGN.md section 8, "Admitting new rows").  More than
+        UPDATE_MAX_ROWS rows are appended as consecutive appends, each onto the
+        exact table of the rows before it; ``rebuild`` as in ``update_rows``.
+        Ordered on the current stream; not safe against requests in flight on
+        other streams."""
+        if self._table is None:
+            raise RuntimeError("This NearestNeighbors instance is not fitted yet")
+        N, d = self._table.shape
+        if (vectors is None) == (storage is None):
+            raise ValueError("append_rows: give vectors or storage, not both")
+        if storage is not None:
+            if (not torch.is_tensor(storage) or storage.dtype != torch.float32 or storage.dim() != 2
+                    or storage.shape[1] != d or storage.shape[0] < N or storage.device != self._table.device
+                    or not storage.is_contiguous()):
+                raise ValueError(f"append_rows: storage must be a contiguous fp32 [>= {N}, {d}] tensor on "
+                                 f"{self._table.device}")
+            grown = storage.detach()
+        else:
+            v = torch.as_tensor(np.asarray(vectors, dtype=np.float32)) if not torch.is_tensor(vectors) \
+                else vectors
+            v = v.detach().to(self.device, torch.float32).reshape(-1, d)
+            grown = torch.cat([self._table, v], dim=0)
+        m = int(grown.shape[0]) - N
+        own = table is None or table is self.neighbor_table_
+        table = self.neighbor_table_ if table is None else table
+        if table is not None:
+            if (not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 2
+                    or table.shape[0] != N or not 1 <= table.shape[1] <= N
+                    or table.device != self._table.device or not table.is_contiguous()):
+                raise ValueError(f"append_rows: table must be a contiguous int32 [{N}, kt] tensor on "
+                                 f"{self._table.device}")
+        stats = dict(changed=m, affected=0, merged=0, researched=0, rebuilt=False)
+        if m == 0:
+            if storage is not None:
+                self._table = grown
+            return (table, stats) if return_stats else table
+        # the norms and packed rows of the new rows, by the fit's kernels (each
+        # row's bits depend on that row alone)
+        lib = _lib.load()
+        stream = _lib.stream_ptr(self.device)
+        new = grown[N:]
+        inv = torch.empty(N + m, dtype=torch.float32, device=self.device)
+        inv[:N] = self._inv
+        _lib.check(lib.dcnr_row_inv_norms(new.data_ptr(), m, d, inv[N:].data_ptr(), stream), "dcnr_row_inv_norms")
+        packed = None
+        if d in PACKED_D and N + m > PACKED_MIN_ROWS:
+            packed = torch.empty((N + m, d), dtype=torch.int16, device=self.device)
+            if self._packed is not None:
+                packed[:N] = self._packed
+                lo = N
+            else:   # the table has just grown past the point where the fit packs
+                lo = 0
+            _lib.check(lib.dcnr_cosine_pack_rows(grown[lo:].data_ptr(), inv[lo:].data_ptr(), N + m - lo, d,
+                                                 packed[lo:].data_ptr(), stream), "dcnr_cosine_pack_rows")
+        if table is not None:
+            kt = table.shape[1]
+            nbr = torch.zeros((N + m, kt), dtype=torch.int32, device=self.device)   # new lists: row 0
+            nbr[:N] = table
+        self._table, self._inv, self._packed = grown, inv, packed
+        self.n_samples_fit_ = N + m
+        if table is None:
+            return (None, stats) if return_stats else None
+        full = bool(rebuild) if rebuild is not None else rebuild_is_cheaper(m, kt, N + m)
+        if full:
+            self._build_into(nbr)
+            stats.update(rebuilt=True, researched=N + m)
+        else:
+            try:
+                for lo in range(N, N + m, UPDATE_MAX_ROWS):
+                    hi = min(N + m, lo + UPDATE_MAX_ROWS)
+                    # an append of rows [lo, hi) onto the exact table of rows [0, lo)
+                    self._table, self._inv = grown[:hi], inv[:hi]
+                    self._packed = None if packed is None else packed[:hi]
+                    c = self._update_table(np.arange(lo, hi, dtype=np.int64), nbr[:hi], return_stats, merge=False)
+                    if return_stats:
+                        stats["affected"] += c[1]
+                        stats["merged"] += c[2]
+                        stats["researched"] += c[3]
+            finally:
+                self._table, self._inv, self._packed = grown, inv, packed
+        # a kept table that was not the one grown no longer matches the index
+        self.neighbor_table_ = nbr if own else None
+        return (nbr, stats) if return_stats else nbr
+
     def _refresh_rows(self, r, v):
         """Writes v (or nothing) into rows r of the table and recomputes their
         inverse norms and packed rows with the fit's kernels on the gathered
@@ -324,12 +436,13 @@ class NearestNeighbors:
                                                   ws.numel(), _lib.stream_ptr(self.device)),
                    "dcnr_cosine_neighbor_table")
 
-    def _update_table(self, r, table, want_counts, events=None):
+    def _update_table(self, r, table, want_counts, events=None, merge=True):
         """One native update of the sorted rows r (norms and packed rows
         already new): filter and merge, the one wait, the re-search.  Returns
         the four counts (the pinned mirror's) when asked.  ``events``: two
         torch events, recorded behind the first call and behind the second
-        (tools/bench_neighbor_update.py)."""
+        (tools/bench_neighbor_update.py).  ``merge=False``: no merge -- every
+        row the filter finds is searched again (dcnr_cosine_neighbor_table_affected)."""
         lib = _lib.load()
         N, d = self._table.shape
         kt, m = table.shape[1], int(r.size)
@@ -342,10 +455,12 @@ class NearestNeighbors:
             self._pin = torch.zeros(4, dtype=torch.int32).pin_memory()
         packed = self._packed.data_ptr() if self._packed is not None else None
         stream = _lib.stream_ptr(self.device)
-        _lib.check(lib.dcnr_cosine_neighbor_table_update(
+        first = lib.dcnr_cosine_neighbor_table_update if merge else lib.dcnr_cosine_neighbor_table_affected
+        _lib.check(first(
             self._table.data_ptr(), self._inv.data_ptr(), packed, N, d, kt, changed.ctypes.data, m,
             table.data_ptr(), counts.data_ptr(), self._pin.data_ptr(), research.data_ptr(), ws.data_ptr(),
-            ws.numel(), stream), "dcnr_cosine_neighbor_table_update")
+            ws.numel(), stream), "dcnr_cosine_neighbor_table_update" if merge else
+            "dcnr_cosine_neighbor_table_affected")
         if events:
             events[0].record()
         torch.cuda.current_stream(self.device).synchronize()   # the update's one wait

@@ -547,6 +547,71 @@ class DCN_RecSys(nn.Module):
         self.flat_offsets = offs
         return flat, gflat
 
+    # ------------------------------------------------------------ admission
+    def grow_(self, n_users=None, n_items=None, init="fallback"):
+        """Grow the user and / or hotel table in place to ``n_users`` /
+        ``n_items`` rows (None: as it is; a smaller count is a ``ValueError``).
+        The ``nn.Parameter`` objects stay; their ``.data`` is a new tensor whose
+        leading rows are the old table.  ``init``: ``"fallback"`` -- new user
+        rows copy row ``n_users_old // 2`` and new hotel rows row 0, what an
+        unknown id was scored with until now (main.py:217, 220); ``"normal"`` --
+        ``nn.Embedding``'s N(0, 1) from torch's default generator; a tensor
+        ``[n_added, emb_dim]`` (a pair ``(users, items)`` when both tables grow).
+        A flattened model is no longer flat afterwards (``FusedTrainer.grow``
+        flattens again).  Returns ``(n_users_added, n_items_added)``."""
+        d = self._dims
+        old = (int(d['n_users']), int(d['n_items']))
+        new = (old[0] if n_users is None else int(n_users), old[1] if n_items is None else int(n_items))
+        for what, o, n in zip(("n_users", "n_items"), old, new):
+            if n < o:
+                raise ValueError(f"grow_: {what}={n} is below the table's {o} rows")
+        added = (new[0] - old[0], new[1] - old[1])
+        rows = [None, None]
+        if isinstance(init, str):
+            if init not in ("fallback", "normal"):
+                raise ValueError(f"init={init!r}: 'fallback', 'normal', a tensor or a pair of tensors")
+        elif isinstance(init, (tuple, list)):
+            if len(init) != 2:
+                raise ValueError("init: a pair (user rows, hotel rows)")
+            rows = list(init)
+        elif added[0] and added[1]:
+            raise ValueError("init: both tables grow, so a pair (user rows, hotel rows)")
+        else:
+            rows[0 if added[0] else 1] = init
+        tables = (self.user_embedding, self.item_embedding)
+        fallback_row = (old[0] // 2, 0)
+        grown = []
+        for k, emb in enumerate(tables):   # every check before the first assignment
+            if not added[k]:
+                grown.append(None)
+                continue
+            w = emb.weight
+            if isinstance(init, str):
+                if init == "normal":
+                    r = torch.empty((added[k], w.shape[1]), dtype=w.dtype, device=w.device).normal_()
+                else:
+                    if old[k] == 0:
+                        raise ValueError("init='fallback' needs a table with a row to copy")
+                    r = w.detach()[fallback_row[k]].expand(added[k], -1)
+            else:
+                r = rows[k]
+                if not isinstance(r, torch.Tensor) or tuple(r.shape) != (added[k], int(w.shape[1])):
+                    raise ValueError(f"init: the new {'hotel' if k else 'user'} rows must be a tensor "
+                                     f"[{added[k]}, {int(w.shape[1])}]")
+                r = r.detach().to(device=w.device, dtype=w.dtype)
+            grown.append(torch.cat([w.detach(), r], dim=0).contiguous())
+        for k, emb in enumerate(tables):
+            if grown[k] is None:
+                continue
+            emb.weight.data = grown[k]
+            emb.weight.grad = None
+            emb.num_embeddings = new[k]
+        d['n_users'], d['n_items'] = new
+        if added[0] or added[1]:
+            self._flat = None
+            self.__dict__['_ptr_cache'] = None
+        return added
+
 
 def _hook_error(model):
     hook = getattr(model, "_sync_bn_hook", None)

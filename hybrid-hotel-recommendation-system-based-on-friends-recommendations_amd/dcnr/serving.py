@@ -331,6 +331,70 @@ class RankingPipeline:
                 w[r] = v.to(w.device, w.dtype).reshape(-1, w.shape[1])
         return out
 
+    def append_items(self, item_cat=None, item_num=None, item_features=None, return_stats=False):
+        """Admit the hotels the model's item table has grown by
+        (``model.grow_(n_items=...)`` first): rows [N, N + m) of the model's
+        table go through ``index.append_rows`` -- as ``storage`` when the grown
+        weight is fp32 on the device, so the index shares the model's table as
+        it shared the old one -- and the neighbour table this pipeline serves
+        from grows with them, all as a pipeline built fresh on the grown model
+        would hold them.  Old rows of the model's table that no longer equal
+        the index's (training steps since) are first brought in through
+        ``index.update_rows``.  The new hotels' features: ``item_cat`` [m, n_cat]
+        and ``item_num`` [m, n_num] for a pipeline built from arrays, or an
+        ``ItemFeatures`` built with the new ``n_items``, which replaces the old
+        one.  ``n_items`` / ``n_rows`` follow.  Ordered on the current stream;
+        not safe against requests in flight on other streams."""
+        w = self.model.item_embedding.weight.detach()
+        N = int(self.index._table.shape[0])
+        m = int(w.shape[0]) - N
+        if m < 0 or w.shape[1] != self.index._table.shape[1]:
+            raise ValueError(f"append_items: the model's item table {list(w.shape)} does not extend the "
+                             f"index's {list(self.index._table.shape)}")
+        if self._tables is None:
+            if item_features is None or item_cat is not None or item_num is not None:
+                raise ValueError("append_items: this pipeline serves from item_features; give the new one")
+            if (item_features.n_cat, item_features.n_num) != (self._features.n_cat, self._features.n_num):
+                raise ValueError("append_items: item_features has other columns than the one it replaces")
+            if item_features.n_items != self.n_items + m:
+                raise ValueError(f"append_items: item_features holds {item_features.n_items} hotels, "
+                                 f"the grown table {self.n_items + m}")
+            tables = None
+        else:
+            if item_features is not None or item_cat is None or item_num is None:
+                raise ValueError("append_items: this pipeline serves from arrays; give the new rows' "
+                                 "item_cat and item_num")
+            old_cat, old_num = self._tables
+            cat = torch.as_tensor(item_cat).to(self.device, torch.int64).reshape(-1, old_cat.shape[1])
+            num = torch.as_tensor(item_num).to(self.device, torch.float32).reshape(-1, old_num.shape[1])
+            if cat.shape[0] != m or num.shape[0] != m:
+                raise ValueError(f"append_items: {m} new hotels, {cat.shape[0]} item_cat and "
+                                 f"{num.shape[0]} item_num rows")
+            tables = (torch.cat([old_cat, cat]).contiguous(), torch.cat([old_num, num]).contiguous())
+        stats = {}
+        old = self.index._table
+        if w.data_ptr() != old.data_ptr():
+            moved = torch.nonzero((w[:N] != old.to(w.dtype)).any(dim=1)).reshape(-1)
+            if moved.numel():
+                s = self.index.update_rows(moved, w[moved], table=self._nbr, return_stats=return_stats)
+                stats["updated"] = s
+        shared = w.dtype == torch.float32 and w.device == old.device and w.is_contiguous()
+        out = self.index.append_rows(vectors=None if shared else w[N:], storage=w if shared else None,
+                                     table=self._nbr, return_stats=return_stats)
+        if return_stats:
+            out, s = out
+            stats.update(s)
+        if self._nbr is not None:
+            self._nbr = out
+        if tables is None:
+            self._features = item_features
+        else:
+            self._tables = tables
+        self.n_items += m
+        self.n_rows = min(self.n_items, self.index._table.shape[0])
+        self._city_joined = None
+        return stats if return_stats else None
+
     # ---------------------------------------------------------- /similar_items
     def similar_items(self, item_row: int, n: int = 10, within=None) -> torch.Tensor:
         """main.py:294-303: the n nearest hotels, the hotel itself dropped

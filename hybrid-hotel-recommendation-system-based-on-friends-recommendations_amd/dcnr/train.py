@@ -146,8 +146,8 @@ class FusedTrainer:
         # both tables and the shards are padded to multiples of lcm(64, emb_dim)
         d = model._dims['emb_dim']
         unit = 64 * d // math.gcd(64, d) if exchange == "sparse" else 64
-        self.flat, self.gflat = model.flatten_(pad_to=unit * self.world * self.chunks,
-                                               table_align=unit)
+        self._flat_args = dict(pad_to=unit * self.world * self.chunks, table_align=unit)   # grow() reuses them
+        self.flat, self.gflat = model.flatten_(**self._flat_args)
         self.E = model.flat_emb_end                      # embedding segment [0, E)
         N = self.flat.numel()
         self.Es = self.E // self.world if self.shard else self.E   # this rank's embedding moments
@@ -324,6 +324,42 @@ class FusedTrainer:
                 history["stopped_early"] = True
                 break
         return history
+
+    def grow(self, n_users=None, n_items=None, init="fallback"):
+        """Admit new users and hotels into a live trainer: ``model.grow_`` (its
+        arguments), the flat buffers laid out again with the construction's
+        ``pad_to`` and ``table_align``, and the moments carried over tensor by
+        tensor -- a new row's are zero, ``step_count`` stays.  The step
+        workspace is dropped (the next ``step`` sizes a new one).  World 1
+        only.  Returns ``grow_``'s ``(n_users_added, n_items_added)``."""
+        if self.world > 1:
+            raise NotImplementedError(
+                "FusedTrainer.grow runs at world 1 only: the sharded moments would need a re-split "
+                "over the ranks, which is not implemented; build a new trainer on the grown model "
+                "instead")
+        model = self.model
+        old_offs = list(model.flat_offsets)
+        old_numel = [p.numel() for p in model.param_tensors()]
+        added = model.grow_(n_users=n_users, n_items=n_items, init=init)
+        if not (added[0] or added[1]):
+            return added
+        self.flat, self.gflat = model.flatten_(**self._flat_args)
+        self.E = self.Es = model.flat_emb_end
+        offs = model.flat_offsets
+        d = model._dims['emb_dim']
+        self._sparse_layout = dict(width=d, tables=(0, 1), elem_off=(offs[0], offs[1]),
+                                   dense_lo=offs[2], dense_hi=self.E)
+        m, v = torch.zeros_like(self.flat), torch.zeros_like(self.flat)
+        for o_old, o_new, n in zip(old_offs, offs, old_numel):   # a table's old rows lead its new ones
+            m[o_new:o_new + n].copy_(self.m[o_old:o_old + n])
+            v[o_new:o_new + n].copy_(self.v[o_old:o_old + n])
+        self.m, self.v = m, v
+        if self.gshard is not None:
+            self.gshard = torch.empty(self.Es, dtype=torch.float32, device=self.flat.device)
+        self._grads =[p.grad for p in model.param_tensors()]
+        self._ws = None
+        self._rows_cache = None
+        return added
 
     def materialize_table_grads(self):
         """Zero the table-gradient rows the last row-map step did not write.

@@ -140,6 +140,96 @@ class IdMap:
                                                           _lib.stream_ptr(self.device)), "dcnr_id_map_lookup")
         return out
 
+    def _build_table(self, cap: int):
+        """A fresh table of ``cap`` slots from ``ids`` (dcnr_id_map_build)."""
+        n = self._n
+        with torch.cuda.device(self.device):
+            table = torch.empty((cap, 2), dtype=torch.int64, device=self.device)
+            status = torch.zeros(1, dtype=torch.int32, device=self.device)
+            pin = torch.zeros(1, dtype=torch.int32).pin_memory()
+            _lib.check(_lib.load().dcnr_id_map_build(self.ids.data_ptr() if n else None, n, table.data_ptr(), cap,
+                                                     status.data_ptr(), pin.data_ptr(),
+                                                     _lib.stream_ptr(self.device)), "dcnr_id_map_build")
+            torch.cuda.current_stream(self.device).synchronize()
+        if int(pin[0]):
+            raise RuntimeError(f"IdMap: rebuilding the table failed (status {int(pin[0])})")
+        self._table, self.capacity = table, cap
+
+    def insert_host(self, raw):
+        """``insert`` in numpy (the yardstick, and the path of ``device="cpu"``):
+        ``(indices int64 [M], new_ids int64 [n_new])``.  The distinct unknown ids
+        are numbered ``len(self), len(self) + 1, ...`` in the order of their
+        first appearance, as ``enumerate(df[col].unique())`` would have numbered
+        them at fit time (train.py:42-43).  A device map's table is rebuilt from
+        the grown ``ids``."""
+        q = _host(raw).astype(np.int64, copy=False).reshape(-1)
+        if (q == RESERVED_ID).any():
+            raise ValueError("IdMap.insert: the reserved id -2**63")
+        out = self.lookup_host(q, -1)
+        unknown = np.flatnonzero(out < 0)
+        uniq, first, inv = np.unique(q[unknown], return_index=True, return_inverse=True)
+        order = np.argsort(first, kind="stable")           # the distinct new ids by first appearance
+        rank = np.empty(order.size, dtype=np.int64)
+        rank[order] = np.arange(order.size, dtype=np.int64)
+        out[unknown] = self._n + rank[inv.reshape(-1)]
+        new_ids = uniq[order].astype(np.int64)
+        if new_ids.size:
+            self.ids = torch.cat([self.ids, torch.from_numpy(new_ids).to(self.ids.device)])
+            self._n += int(new_ids.size)
+            self._sorted = None
+            if self._table is not None:
+                self._build_table(max(self.capacity, _pow2_at_least(2 * self._n)))
+        return out, new_ids
+
+    def insert(self, raw, capacity: Optional[int] = None):
+        """Admit the ids of ``raw`` the map does not hold (dcnr_id_map_insert):
+        ``(indices, new_ids)``, device int64 ``[M]`` and ``[n_new]``.  ``raw`` is
+        any batch -- known ids, new ones, duplicates; the distinct new ids get
+        ``len(self), len(self) + 1, ...`` in the order of their first appearance
+        and are appended to ``ids`` in that order.  The table keeps capacity
+        >= 2 (n + M): a larger one is built from ``ids`` first (``capacity=``, a
+        power of two above n, overrides that for tests of a nearly full table).
+        One read of the pinned count words.  ``ValueError`` for the reserved id
+        -2**63, with the map unchanged.  ``device="cpu"``: ``insert_host``."""
+        if self._table is None:
+            out, new = self.insert_host(raw)
+            return torch.from_numpy(out), torch.from_numpy(new)
+        q = raw if isinstance(raw, torch.Tensor) else torch.from_numpy(
+            np.ascontiguousarray(np.asarray(raw).astype(np.int64, copy=False).reshape(-1)))
+        q = q.to(device=self.device, dtype=torch.int64).reshape(-1).contiguous()
+        M, n = int(q.numel()), self._n
+        cap = max(self.capacity, _pow2_at_least(2 * (n + M))) if capacity is None else int(capacity)
+        if cap < n + 1 or cap & (cap - 1):
+            raise ValueError(f"IdMap.insert: capacity {cap} is not a power of two >= n + 1 = {n + 1}")
+        if cap != self.capacity:
+            self._build_table(cap)
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            nb = int(lib.dcnr_id_map_insert_workspace_size(M))
+            if nb == 0:
+                raise RuntimeError(f"IdMap.insert: the device call does not take M={M}: DCNR_UNSUPPORTED_SHAPE")
+            new = lambda k, dt: torch.empty(k, dtype=dt, device=self.device)
+            out, new_ids, ws = new(M, torch.int64), new(M, torch.int64), new(nb, torch.uint8)
+            counts = new(2, torch.int32)
+            pin = torch.zeros(2, dtype=torch.int32).pin_memory()
+            p = lambda t: t.data_ptr() if t.numel() else None
+            _lib.check(lib.dcnr_id_map_insert(self._table.data_ptr(), self.capacity, n, p(q), M, p(out), p(new_ids),
+                                              counts.data_ptr(), pin.data_ptr(), p(ws), nb,
+                                              _lib.stream_ptr(self.device)), "dcnr_id_map_insert")
+            torch.cuda.current_stream(self.device).synchronize()   # the one host wait
+        n_new, status = int(pin[0]), int(pin[1])
+        if status & REQ_BAD_DATA:
+            raise ValueError("IdMap.insert: the reserved id -2**63")
+        if status & REQ_OVERFLOW:
+            self._build_table(self.capacity)     # the table is unusable: back to the ids it had
+            raise RuntimeError("IdMap.insert: the table is full")
+        new_ids = new_ids[:n_new].clone()
+        if n_new:
+            self.ids = torch.cat([self.ids, new_ids])
+            self._n += n_new
+            self._sorted = None
+        return out, new_ids
+
 
 # ----------------------------------------------------------------- Transformed
 class Transformed:
@@ -150,11 +240,17 @@ class Transformed:
     category c: the fallback was used; all zero under ``"drop"``).  Host counts:
     ``n``, ``n_filtered`` (rows the filter removed) and, over the rows that passed
     it, ``n_unknown_users``, ``n_unknown_items`` and ``n_unknown_cat[c]`` (an
-    unseen or missing key)."""
+    unseen or missing key).  Under ``"admit"`` bits 0 and 1 mean "admitted by
+    this call", the two counts are the rows that carry such an id, and
+    ``new_user_ids`` / ``new_item_ids`` (numpy int64, empty otherwise) are the
+    admitted ids in the order of their new indices."""
 
     def __init__(self, collab, cat, num, y, rows, unknown_bits, n, n_filtered, n_unknown_users, n_unknown_items,
-                 n_unknown_cat):
+                 n_unknown_cat, new_user_ids=None, new_item_ids=None):
         self.collab, self.cat, self.num, self.y = collab, cat, num, y
+        empty = np.zeros(0, dtype=np.int64)
+        self.new_user_ids = empty if new_user_ids is None else new_user_ids
+        self.new_item_ids = empty if new_item_ids is None else new_item_ids
         self.rows, self.unknown_bits = rows, unknown_bits
         self.n, self.n_filtered = int(n), int(n_filtered)
         self.n_unknown_users, self.n_unknown_items = int(n_unknown_users), int(n_unknown_items)
@@ -273,8 +369,8 @@ class Preprocessor:
     # ---------------------------------------------------------------- options
     @staticmethod
     def _policy(unknown) -> bool:
-        if unknown not in ("reference", "drop"):
-            raise ValueError(f"unknown={unknown!r} is neither 'reference' nor 'drop'")
+        if unknown not in ("reference", "drop", "admit"):
+            raise ValueError(f"unknown={unknown!r} is neither 'reference' nor 'drop' nor 'admit'")
         return unknown == "drop"
 
     def _filter(self, noise_filter):
@@ -287,6 +383,62 @@ class Preprocessor:
     def _check_fill(self, fill_nan):
         if fill_nan and self.median_ is None and self.n_num:
             raise ValueError("fill_nan=True needs the fit's medians (from_artifacts(..., median=))")
+
+    # -------------------------------------------------------------- admission
+    @staticmethod
+    def _check_reserved(*raws):
+        for r in raws:
+            if r is not None and bool((r == RESERVED_ID).any()):
+                raise ValueError("admit: the reserved id -2**63")
+
+    def _admit(self, which, raw, key):
+        """Insert ``raw`` into the ``which`` ("users" / "items") map of every
+        state this preprocessing holds -- first into the device state ``key``
+        (None: the host state), whose numbering the others then repeat from the
+        new ids in order -- and grow ``user_ids`` / ``item_ids``.  Returns
+        (the indices of ``raw`` where the first insert ran, the new ids in numpy)."""
+        k = 0 if which == "users" else 1
+        if key is None:
+            primary = self._host_fit()[k]
+            idx, new = primary.insert_host(raw)
+        else:
+            primary = self._state[key][which]
+            idx, new = primary.insert(raw)
+            new = new.cpu().numpy()
+        if new.size:
+            for st in self._state.values():
+                if st[which] is not primary:
+                    st[which].insert(new)
+            if self._host_state is not None and self._host_state[k] is not primary:
+                self._host_state[k].insert_host(new)
+            attr = "user_ids" if k == 0 else "item_ids"
+            old = getattr(self, attr)
+            if isinstance(old, torch.Tensor):
+                grown = torch.cat([old.reshape(-1), torch.from_numpy(new).to(device=old.device, dtype=old.dtype)])
+            else:
+                grown = np.concatenate([np.asarray(old).reshape(-1), new.astype(np.asarray(old).dtype, copy=False)])
+            setattr(self, attr, grown)
+        return idx, new
+
+    def admit(self, users=None, items=None):
+        """Admit raw user and hotel ids the fit has not seen: each id map of
+        every device state held, and of the host state, gets the distinct new
+        ids numbered on from its length in the order of their first appearance
+        (``IdMap.insert``), and ``user_ids`` / ``item_ids`` grow by them, so
+        mappings built from those afterwards include the new ids.  Known ids
+        and duplicates are fine.  Returns ``(new_user_ids, new_item_ids)``,
+        numpy int64.  ``ValueError`` for the reserved id -2**63, with nothing
+        changed."""
+        as_ids = lambda r: None if r is None else (
+            r.reshape(-1).to(torch.int64) if isinstance(r, torch.Tensor) else
+            np.asarray(r).astype(np.int64, copy=False).reshape(-1))
+        users, items = as_ids(users), as_ids(items)
+        self._check_reserved(users, items)
+        key = next(iter(self._state), None)
+        out = []
+        for which, raw in (("users", users), ("items", items)):
+            out.append(np.zeros(0, dtype=np.int64) if raw is None else self._admit(which, raw, key)[1])
+        return tuple(out)
 
     # ------------------------------------------------------------------ numpy
     def _host_fit(self):
@@ -354,16 +506,26 @@ class Preprocessor:
             xs = x * self.scale_
             xs = xs + self.min_
         count = lambda b: int(np.count_nonzero(bits & np.uint64(1) << np.uint64(b)))
+        new_u = new_h = None
+        if unknown == "admit":
+            self._check_reserved(user[kept], item[kept])
+            fu, fh = kept & (bits & np.uint64(1) != 0), kept & (bits & np.uint64(2) != 0)
+            u[fu], new_u = self._admit("users", user[fu], None)
+            h[fh], new_h = self._admit("items", item[fh], None)
         return Transformed(np.stack([u, h], axis=1)[kept].reshape(n, 2),
                            np.stack(codes, axis=1)[kept] if codes else np.zeros((n, 0), np.int64),
                            xs.astype(np.float32).reshape(n, self.n_num),
                            None if tgt is None else (tgt[kept] != 0).astype(np.float32),
                            rows, bits[kept].view(np.int64), n, M - int(passed.sum()), count(0), count(1),
-                           [count(2 + c) for c in range(self.n_cat)])
+                           [count(2 + c) for c in range(self.n_cat)], new_u, new_h)
 
     # ----------------------------------------------------------------- device
+    @staticmethod
+    def _device_key(dev):
+        return (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+
     def _device_fit(self, dev):
-        key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
+        key = self._device_key(dev)
         st = self._state.get(key)
         if st is None:
             keys = [_host(k).astype(np.int64).reshape(-1) for k in self.cat_keys]
@@ -446,5 +608,18 @@ class Preprocessor:
         n, n_filtered, n_uu, n_ui, status = (int(v) for v in c[:N_COUNTS])
         if status & REQ_BAD_DATA:
             raise ValueError(INF_MESSAGE)
+        new_u = new_h = None
+        if unknown == "admit" and (n_uu or n_ui):
+            key = self._device_key(dev)
+            kept = row[:n].to(torch.int64)
+            ku, kh = user[kept], item[kept]
+            fu, fh = (bits[:n] & 1) != 0, (bits[:n] & 2) != 0
+            self._check_reserved(ku[fu], kh[fh])
+            if n_uu:
+                idx, new_u = self._admit("users", ku[fu], key)
+                collab[:n, 0][fu] = idx
+            if n_ui:
+                idx, new_h = self._admit("items", kh[fh], key)
+                collab[:n, 1][fh] = idx
         return Transformed(collab[:n], cats[:n], num_out[:n], None if y is None else y[:n], row[:n], bits[:n],
-                           n, n_filtered, n_uu, n_ui, c[N_COUNTS:])
+                           n, n_filtered, n_uu, n_ui, c[N_COUNTS:], new_u, new_h)

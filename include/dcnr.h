@@ -705,6 +705,23 @@ dcnr_status dcnr_cosine_neighbor_table_rows(const float* table, const float* inv
                                             int64_t N, int32_t d, int32_t k, const int32_t* rows, int64_t n,
                                             int32_t* nbr, void* ws, size_t ws_bytes, dcnr_stream_t stream);
 
+/* _update without its merge (dcnr.NearestNeighbors.append_rows): phase A alone
+ * -- the same kernels -- finds the rows a change can reach, and every one of
+ * them joins the re-search list behind the changed rows; nbr is only read.
+ * counts: {changed, affected, 0, changed + affected}.  _rows on that list then
+ * gives every list that can differ the build's own answer, so the result does
+ * not depend on the merge scoring a kept entry to the same last bit as the
+ * search did: among 2^20 rows some pair of neighbours lies within one float32
+ * step, and there the two need not order alike.  The filter's bound carries a
+ * margin (1e-5) far above such a step, so no row a changed row could enter is
+ * missed.  Everything else -- arguments, shapes, workspace, errors -- as
+ * _update. */
+dcnr_status dcnr_cosine_neighbor_table_affected(const float* table, const float* inv_norms, const uint16_t* packed,
+                                                int64_t N, int32_t d, int32_t k, const int32_t* changed, int64_t m,
+                                                const int32_t* nbr, int32_t* counts, int32_t* host_counts,
+                                                int32_t* research_rows, void* ws, size_t ws_bytes,
+                                                dcnr_stream_t stream);
+
 /* Merge of row-sharded top-k lists (the cfg5 index split over ranks, SURVEY
  * 8(e)): dist fp32 / idx int64 [lists][Q][k] (global rows; padding entries
  * (FLT_MAX, -1) sort last) -> the k best per query, ascending by (dist, row),
@@ -1190,6 +1207,40 @@ dcnr_status dcnr_id_map_build(const int64_t* ids, int64_t n, void* table, int64_
                               int32_t* host_status, dcnr_stream_t stream);
 dcnr_status dcnr_id_map_lookup(const void* table, int64_t capacity, const int64_t* raw, int64_t M,
                                int64_t default_index, int64_t* out, dcnr_stream_t stream);
+
+/* Admit new ids into a built table that holds n (dcnr.IdMap.insert).  raw [M]
+ * is any batch: known ids, new ids, duplicates.  out[q] = the index of raw[q]:
+ * a known id's own; the distinct new ids are numbered n, n + 1, ... in the order
+ * of their first appearance in raw (what enumerate(df[col].unique()) would have
+ * given them, train.py:42-43), and new_ids[j] ([M] room) is the id numbered
+ * n + j.  Every out[q] is final when the call's work is done, and the table
+ * then answers dcnr_id_map_lookup for old and new ids alike.  counts (device
+ * int32 [2], also stored to host_counts: pinned, or NULL) = {n_new, status}:
+ *   0                  success
+ *   DCNR_REQ_BAD_DATA  raw holds the reserved id INT64_MIN: decided by a
+ *                      read-only pass before the first compare-and-swap, so
+ *                      the table is unchanged, n_new is 0 and out holds the
+ *                      plain lookup (-1 for an id the table does not hold)
+ *   DCNR_REQ_OVERFLOW  a lane found no free slot: the table is unusable, as
+ *                      after a failed build
+ * out, new_ids and n_new are the same on every run: the numbering comes from a
+ * sum scan over first-appearance marks, never from an atomic.  Which slot a new
+ * id lands in depends on which lane wins its probe chain, as in the build; only
+ * the table's bytes can differ between runs, never an answer.  Every atomic is
+ * an integer one (compare-and-swap, min, or), every probe loop ends after
+ * `capacity` slots and no lane waits for another.  The caller keeps
+ * n + n_new < capacity (dcnr.IdMap rebuilds a larger table first).  Workspace:
+ * dcnr_id_map_insert_workspace_size(M) bytes, about 12 M (0 for an M the call
+ * rejects).  DCNR_BAD_ARG before any launch: a needed null pointer (with M = 0,
+ * a no-op that zeroes counts, only table and counts are needed), a negative
+ * size, a capacity that is no power of two or not above n, a misaligned table;
+ * DCNR_UNSUPPORTED_SHAPE: M >= 2^31 - 1 or capacity > 2^40;
+ * DCNR_WORKSPACE_TOO_SMALL.  Stream-ordered; no allocation, no host
+ * synchronisation. */
+size_t dcnr_id_map_insert_workspace_size(int64_t M);
+dcnr_status dcnr_id_map_insert(void* table, int64_t capacity, int64_t n, const int64_t* raw, int64_t M,
+                               int64_t* out, int64_t* new_ids, int32_t* counts, int32_t* host_counts,
+                               void* ws, size_t ws_bytes, dcnr_stream_t stream);
 
 /* A fitted preprocessing applied to rows it was not fitted on (dcnr.Preprocessor
  * .transform; preprocess_for_ranking, main.py:215-230, in train.py's order of
