@@ -9,7 +9,7 @@
 //
 //   records   one 16-byte record per row: (~orderable(key), city, position);
 //             items, cities and the row order are validated here
-//   sort A    the shared stable LSD radix sort (dcnr_internal.h) over the 64 +
+//   sort A    the shared stable LSD radix sort (device_prims.h) over the 64 +
 //             bits(C - 1) bits of (city, key): every city becomes one segment in
 //             served order; ties keep the input's order, which is the rows'
 //   bounds    the segments' ends, one lane per sorted record
@@ -30,7 +30,7 @@
 // count is an integer and every output word is written by one lane: the same
 // bits on every run.  Workspace: two 16-byte records per row, the sort's unit
 // counts, 4 * C * (top + 5) bytes of per-city words and one word per tile.
-#include "dcnr_internal.h"
+#include "device_prims.h"
 
 namespace dcnr {
 
@@ -42,7 +42,7 @@ constexpr int CS_NT = 256;
 constexpr int CS_MAXB = 2048;            // workgroups of the grid-stride kernels
 constexpr int CS_TILE_Q = 8;             // a tile of the head kernels: CS_TILE_Q rounds of CS_NT keys
 constexpr int CS_TILE = CS_NT * CS_TILE_Q;
-constexpr int CS_SCAN_NT = 1024;
+constexpr int CS_SCAN_NT = 1024;         // (one lane per run in cs_offsets_kernel)
 constexpr int CS_TOP_MAX = 256;          // (one lane per top row in cs_popular_kernel)
 
 struct alignas(16) Rec {
@@ -216,8 +216,8 @@ __global__ __launch_bounds__(CS_NT) void cs_head_count_kernel(const uint64_t* k,
   }
 }
 
-// v [n] -> its exclusive sum in place, one workgroup: a lane sums its run, the
-// runs' sums are scanned through LDS, the lane writes its run.  Returns the total.
+// the exclusive sum of one value per lane over the workgroup, through LDS
+// (cs_offsets_kernel: a lane sums its run of sets and writes it from there)
 __device__ __forceinline__ int64_t block_exclusive_scan(int64_t mine, int64_t* sh) {
   const int t = threadIdx.x;
   sh[t] = mine;
@@ -229,20 +229,6 @@ __device__ __forceinline__ int64_t block_exclusive_scan(int64_t mine, int64_t* s
     __syncthreads();
   }
   return sh[t] - mine;
-}
-
-__global__ __launch_bounds__(CS_SCAN_NT) void cs_tile_scan_kernel(uint32_t* v, int64_t n) {
-  __shared__ int64_t sh[CS_SCAN_NT];
-  const int64_t per = (n + CS_SCAN_NT - 1) / CS_SCAN_NT;
-  const int64_t lo = min(n, threadIdx.x * per), hi = min(n, lo + per);
-  int64_t s = 0;
-  for (int64_t i = lo; i < hi; ++i) s += v[i];
-  int64_t base = block_exclusive_scan(s, sh);
-  for (int64_t i = lo; i < hi; ++i) {
-    const uint32_t c = v[i];
-    v[i] = (uint32_t)base;
-    base += c;
-  }
 }
 
 // Every head to set_rows at its global rank (below cap), and per city the rank
@@ -356,29 +342,6 @@ __global__ __launch_bounds__(CS_NT) void cs_empty_kernel(int C, int top, int64_t
   }
 }
 
-// npass passes over bits [0, npass * RBITS) of the records; src ends as the sorted array
-template <typename T>
-dcnr_status sort_passes(T*& src, T*& dst, int64_t M, const Plan& p, int npass, const Ws& w, hipStream_t s) {
-  const int sort_blocks = (int)cdiv(p.units, SORT_WAVES);
-  for (int ps = 0; ps < npass; ++ps) {
-    const int shift = ps * RBITS;
-    hipLaunchKernelGGL(sort_hist_kernel<T>, dim3(sort_blocks), dim3(SORT_NT), 0, s, (const T*)src, M,
-                       p.units, p.chunk, shift, w.counts);
-    DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_tot_kernel, dim3(NB / SORT_NT), dim3(SORT_NT), 0, s,
-                       (const uint32_t*)w.counts, p.units, w.tot);
-    DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(NB / WAVE), dim3(SCAN_NT), 0, s, (const uint32_t*)w.tot,
-                       w.counts, p.units);
-    DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_scatter_kernel<T>, dim3(sort_blocks), dim3(SORT_NT), 0, s, (const T*)src, dst,
-                       M, p.units, p.chunk, shift, (const uint32_t*)w.counts);
-    DCNR_LAUNCH_CHECK();
-    std::swap(src, dst);
-  }
-  return DCNR_OK;
-}
-
 }  // namespace
 
 static size_t city_sets_ws_bytes(int64_t M, int64_t n_items, int n_cities, int top) {
@@ -409,7 +372,7 @@ static dcnr_status city_sets_build(const int32_t* item, const int32_t* city, con
                      C, w.ra, status);
   DCNR_LAUNCH_CHECK();
   Rec *src = w.ra, *dst = w.rb;
-  TRY(sort_passes(src, dst, M, p, p.pass_a, w, s));
+  TRY(sort_passes(src, dst, M, p.units, p.chunk, 0, p.pass_a, w.counts, w.tot, nullptr, s));
   hipLaunchKernelGGL(cs_bounds_kernel, dim3(p.blocks), dim3(CS_NT), 0, s, (const Rec*)src, M, cstart, cend);
   DCNR_LAUNCH_CHECK();
   hipLaunchKernelGGL(cs_popular_kernel, dim3(C), dim3(CS_TOP_MAX), 0, s, (const Rec*)src,
@@ -421,11 +384,11 @@ static dcnr_status city_sets_build(const int32_t* item, const int32_t* city, con
   hipLaunchKernelGGL(cs_keys_kernel, dim3(p.blocks), dim3(CS_NT), 0, s, item, city, M, n_items, C, p.ibits,
                      ka);
   DCNR_LAUNCH_CHECK();
-  TRY(sort_passes(ka, kb, M, p, p.pass_b, w, s));
+  TRY(sort_passes(ka, kb, M, p.units, p.chunk, 0, p.pass_b, w.counts, w.tot, nullptr, s));
   hipLaunchKernelGGL(cs_head_count_kernel, dim3((unsigned)p.tiles), dim3(CS_NT), 0, s, (const uint64_t*)ka,
                      M, w.tilebase);
   DCNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cs_tile_scan_kernel, dim3(1), dim3(CS_SCAN_NT), 0, s, w.tilebase, p.tiles);
+  hipLaunchKernelGGL(tscan::tile_scan_kernel<false>, dim3(1), dim3(tscan::TS_SCAN_NT), 0, s, w.tilebase, p.tiles);
   DCNR_LAUNCH_CHECK();
   hipLaunchKernelGGL(cs_write_sets_kernel, dim3((unsigned)p.tiles), dim3(CS_NT), 0, s, (const uint64_t*)ka,
                      M, C, p.ibits, (const uint32_t*)w.tilebase, set_rows, cap, cfirst, clast);
@@ -478,7 +441,7 @@ dcnr_status dcnr_city_sets_build(const int32_t* review_item, const int32_t* revi
               (long long)M, (long long)n_items, n_cities, top);
     return shape;
   }
-  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  void* base = ws_align(ws);
   const size_t need = M > 0 ? city_sets_ws_bytes(M, n_items, n_cities, top) : 0;
   if (M > 0 && ws_bytes < need + ((char*)base - (char*)ws)) {
     set_error("dcnr_city_sets_build: workspace too small: %zu < %zu", ws_bytes, need + 256);

@@ -788,160 +788,10 @@ dcnr_status bce(const float* z, const float* y, int64_t B, float* loss, float* d
                 double* part, hipStream_t s);
 
 dcnr_status fill_zero(void* p, size_t bytes, hipStream_t s);
-// *dst = *src with a system-scope store (dst may be pinned host memory)
-dcnr_status mirror_word(const int* src, int* dst, hipStream_t s);
+// dst [n] = src [n] with system-scope stores (dst may be pinned host memory:
+// a call's count words to the caller's mirror), one wave; and the one-word call
+dcnr_status mirror_words(const int* src, int n, int* dst, hipStream_t s);
+inline dcnr_status mirror_word(const int* src, int* dst, hipStream_t s) { return mirror_words(src, 1, dst, s); }
 dcnr_status fill_zero_multi(int n, void* const* ptrs, const int64_t* bytes, hipStream_t s);
-
-// ---------------------------------------------------------------------------
-// The stable LSD radix sort of metrics.hip and city_sets.hip: passes of RBITS
-// bits over records T, a 64-bit key or a struct with its own radix_digit (found
-// by argument-dependent lookup).  A "unit" is the contiguous run of records one
-// wave walks 64 at a time; per pass: per-unit digit counts, a scan over (digit,
-// unit), a stable scatter that ranks equal digits within a wave by match-any
-// over ballots (no atomics: the order within a digit is the input's).  The
-// scan needs tot [NB], the digit totals of the whole input: a digit histogram
-// does not depend on the order of the records, so a caller may count all its
-// passes in one sweep beforehand (metrics.hip) or sum the unit counts
-// (sort_tot_kernel).
-namespace rsort {
-
-constexpr int RBITS = 11;                                  // digit width
-constexpr int NB = 1 << RBITS;                             // buckets per pass
-constexpr int UNIT_KEYS = 4096;                            // keys per unit before MAX_UNITS binds
-constexpr int MAX_UNITS = 1024;
-constexpr int SORT_NT = 256, SORT_WAVES = SORT_NT / WAVE;  // 4 units per block
-constexpr int SORT_UNROLL = 4;                             // 64-key steps loaded ahead
-constexpr int SCAN_NT = 1024, SCAN_SEG = SCAN_NT / WAVE;   // 64 buckets x 16 unit segments
-
-__device__ __forceinline__ uint32_t radix_digit(uint64_t k, int shift) {
-  return (uint32_t)((k >> shift) & (NB - 1));
-}
-
-// counts[u][d] = keys of unit u whose digit is d
-template <typename T>
-__global__ __launch_bounds__(SORT_NT) void sort_hist_kernel(const T* keys, int64_t n, int units,
-                                                            int64_t chunk, int shift, uint32_t* counts) {
-  __shared__ uint32_t h[SORT_WAVES][NB];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int u = blockIdx.x * SORT_WAVES + w;
-  for (int d = lane; d < NB; d += WAVE) h[w][d] = 0u;
-  __syncthreads();
-  if (u < units) {
-    const int64_t lo = (int64_t)u * chunk, hi = min(n, lo + chunk);
-    for (int64_t i0 = lo + lane; i0 < hi; i0 += SORT_UNROLL * WAVE) {
-      T k[SORT_UNROLL];
-#pragma unroll
-      for (int q = 0; q < SORT_UNROLL; ++q) k[q] = i0 + q * WAVE < hi ? keys[i0 + q * WAVE] : T{};
-#pragma unroll
-      for (int q = 0; q < SORT_UNROLL; ++q)
-        if (i0 + q * WAVE < hi) atomicAdd(&h[w][(int)radix_digit(k[q], shift)], 1u);
-    }
-  }
-  __syncthreads();
-  if (u < units)
-    for (int d = lane; d < NB; d += WAVE) counts[(int64_t)u * NB + d] = h[w][d];
-}
-
-// tot[d] = the sum over the units of counts[u][d] (before sort_scan_kernel
-// overwrites the counts): NB / SORT_NT blocks, coalesced over d
-static __global__ __launch_bounds__(SORT_NT) void sort_tot_kernel(const uint32_t* counts, int units,
-                                                                  uint32_t* tot) {
-  const int d = blockIdx.x * SORT_NT + threadIdx.x;
-  uint32_t t = 0u;
-  for (int u = 0; u < units; ++u) t += counts[(int64_t)u * NB + d];
-  tot[d] = t;
-}
-
-// counts[u][d] -> first output position of unit u's keys of digit d: the keys
-// of lower digits (tot), then the lower units' keys of digit d.  One block
-// per 64 digits; thread (j, s) walks digit b0 + j over unit segment s.
-static __global__ __launch_bounds__(SCAN_NT) void sort_scan_kernel(const uint32_t* tot, uint32_t* counts,
-                                                                   int units) {
-  __shared__ uint32_t red[SCAN_SEG];
-  __shared__ uint32_t tl[WAVE];
-  __shared__ uint32_t seg[SCAN_SEG][WAVE];
-  const int tid = threadIdx.x, j = tid & 63, s = tid >> 6;
-  const int b0 = blockIdx.x * WAVE;
-  uint32_t a = 0u;
-  for (int d = tid; d < b0; d += SCAN_NT) a += tot[d];
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) a += (uint32_t)__shfl_xor((int)a, o, 64);
-  if (j == 0) red[s] = a;
-  if (tid < WAVE) tl[tid] = tot[b0 + tid];
-  const int useg = (units + SCAN_SEG - 1) / SCAN_SEG;
-  const int u0 = min(units, s * useg), u1 = min(units, u0 + useg);
-  uint32_t t = 0u;
-  for (int u = u0; u < u1; ++u) t += counts[(int64_t)u * NB + b0 + j];
-  seg[s][j] = t;
-  __syncthreads();
-  uint32_t base = 0u;
-  for (int k = 0; k < SCAN_SEG; ++k) base += red[k];
-  for (int k = 0; k < j; ++k) base += tl[k];
-  for (int k = 0; k < s; ++k) base += seg[k][j];
-  for (int u = u0; u < u1; ++u) {
-    const int64_t idx = (int64_t)u * NB + b0 + j;
-    const uint32_t c = counts[idx];
-    counts[idx] = base;
-    base += c;
-  }
-}
-
-// Stable scatter of one pass.  A wave walks its unit 64 keys at a time; the
-// lanes holding the same digit find each other with RBITS ballots, the lowest
-// of them advances the unit's offset of that digit by their number, and each
-// writes at offset + (equal-digit lanes below it).
-template <typename T>
-__global__ __launch_bounds__(SORT_NT) void sort_scatter_kernel(const T* in, T* out, int64_t n, int units,
-                                                               int64_t chunk, int shift,
-                                                               const uint32_t* counts) {
-  __shared__ uint32_t c[SORT_WAVES][NB];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int u = blockIdx.x * SORT_WAVES + w;
-  if (u < units)
-    for (int d = lane; d < NB; d += WAVE) c[w][d] = counts[(int64_t)u * NB + d];
-  __syncthreads();
-  if (u >= units) return;
-  const uint64_t lt = (1ull << lane) - 1ull;
-  const int64_t lo = (int64_t)u * chunk, hi = min(n, lo + chunk);
-  for (int64_t i0 = lo; i0 < hi; i0 += SORT_UNROLL * WAVE) {   // wave-uniform trip count
-    // the loads of SORT_UNROLL steps up front (the walk is latency-bound: one
-    // dependent chain through the unit's LDS offsets), then the steps in order
-    T keys[SORT_UNROLL];
-    bool valids[SORT_UNROLL];
-#pragma unroll
-    for (int q = 0; q < SORT_UNROLL; ++q) {
-      const int64_t i = i0 + q * WAVE + lane;
-      valids[q] = i < hi;
-      keys[q] = valids[q] ? in[i] : T{};
-    }
-#pragma unroll
-    for (int q = 0; q < SORT_UNROLL; ++q) {
-      const bool valid = valids[q];
-      const T key = keys[q];
-      const uint32_t d = radix_digit(key, shift);
-      uint64_t mask = __ballot(valid);
-#pragma unroll
-      for (int b = 0; b < RBITS; ++b) {
-        const bool bit = (d >> b) & 1u;
-        const uint64_t bal = __ballot(bit);
-        mask &= bit ? bal : ~bal;
-      }
-      const int leader = valid ? __ffsll((unsigned long long)mask) - 1 : lane;
-      uint32_t pre = 0u;
-      if (valid && lane == leader) {
-        pre = c[w][d];
-        c[w][d] = pre + (uint32_t)__popcll(mask);
-      }
-      pre = (uint32_t)__shfl((int)pre, leader, 64);
-      if (valid) {
-        const uint32_t pos = pre + (uint32_t)__popcll(mask & lt);
-        if ((int64_t)pos < n) out[pos] = key;
-      }
-      __builtin_amdgcn_wave_barrier();
-    }
-  }
-}
-
-}  // namespace rsort
 
 }  // namespace dcnr

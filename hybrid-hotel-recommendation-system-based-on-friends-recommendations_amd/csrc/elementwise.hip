@@ -1085,10 +1085,11 @@ namespace {
 __global__ __launch_bounds__(64) void zero_words_kernel(int* p, int n) {
   for (int i = threadIdx.x; i < n; i += 64) p[i] = 0;
 }
-__global__ __launch_bounds__(64) void mirror_word_kernel(const int* src, int* dst) {
-  // dst may be pinned host memory: a system-scope store, visible to the host
+__global__ __launch_bounds__(64) void mirror_words_kernel(const int* src, int n, int* dst) {
+  // dst may be pinned host memory: system-scope stores, visible to the host
   // once the stream's work up to here has completed
-  if (threadIdx.x == 0) __hip_atomic_store(dst, *src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  for (int i = threadIdx.x; i < n; i += 64)
+    __hip_atomic_store(dst + i, src[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 }  // namespace
 
@@ -1103,8 +1104,8 @@ dcnr_status fill_zero(void* p, size_t bytes, hipStream_t s) {
   return DCNR_OK;
 }
 
-dcnr_status mirror_word(const int* src, int* dst, hipStream_t s) {
-  hipLaunchKernelGGL(mirror_word_kernel, dim3(1), dim3(64), 0, s, src, dst);
+dcnr_status mirror_words(const int* src, int n, int* dst, hipStream_t s) {
+  hipLaunchKernelGGL(mirror_words_kernel, dim3(1), dim3(64), 0, s, src, n, dst);
   DCNR_LAUNCH_CHECK();
   return DCNR_OK;
 }

@@ -28,17 +28,12 @@
 //   finish   one workgroup sums those words; the two count words to their
 //            host mirrors
 //
-// The scale is MinMaxScaler.transform's: X *= scale_; X += min_ in float64,
-// two separately rounded operations, then torch's float32 conversion (to
-// nearest even).  hipcc contracts x * s + m into an fma by default, so
-// contraction is turned off for that function with `#pragma clang fp
-// contract(off)` (this ROCm has no __dmul_rn / __dadd_rn).  NaN payloads,
-// +-inf and -0.0 go through v_mul_f64 / v_add_f64 / v_cvt_f32_f64 as numpy's
-// float64 operations and its float32 cast pass them.
+// The scale is MinMaxScaler.transform's as prepare_data applies it: scaled()
+// of device_prims.h.
 //
 // Every word is an integer or written by one lane: the same bits on every run.
 // Workspace: 4 * n_items bytes and one word per workgroup of the gather.
-#include "dcnr_internal.h"
+#include "device_prims.h"
 
 namespace dcnr {
 
@@ -104,15 +99,6 @@ __global__ __launch_bounds__(IF_NT) void if_scan_kernel(const int32_t* item, con
     }
   }
   if (bad) atomicOr(counts + 1, DCNR_REQ_BAD_DATA);
-}
-
-// MinMaxScaler.transform and the float32 conversion: two float64 roundings,
-// then one to float32 -- never an fma (see the head of the file)
-__device__ __forceinline__ float scaled(double x, double scale, double mn) {
-#pragma clang fp contract(off)
-  double y = x * scale;
-  y = y + mn;
-  return (float)y;
 }
 
 __global__ __launch_bounds__(IF_NT) void if_gather_kernel(const int32_t* firstpos, const int32_t* row,
@@ -260,7 +246,7 @@ dcnr_status dcnr_item_features_build(const int32_t* review_item, const int32_t* 
               (long long)M, (long long)n_items, n_cat, n_num);
     return shape;
   }
-  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  void* base = ws_align(ws);
   const size_t need = M > 0 ? item_features_ws_bytes(n_items) : 0;
   if (M > 0 && ws_bytes < need + ((char*)base - (char*)ws)) {
     set_error("dcnr_item_features_build: workspace too small: %zu < %zu", ws_bytes, need + 256);

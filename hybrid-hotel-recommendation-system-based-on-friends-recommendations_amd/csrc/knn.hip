@@ -2668,12 +2668,6 @@ __global__ void upd_list_counts_kernel(int* counts) {
   if (threadIdx.x == 0) counts[3] = counts[0] + counts[1];
 }
 
-// the four count words to the caller's pinned host words
-__global__ void upd_mirror_kernel(const int* counts, int* host_counts) {
-  if (threadIdx.x < 4)
-    __hip_atomic_store(host_counts + threadIdx.x, counts[threadIdx.x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // Phase C: the listed rows as a chunk of queries, and the chunk's answers
 // into the listed table rows (a row id outside the table is read as row 0
 // and written nowhere)
@@ -2931,33 +2925,36 @@ size_t dcnr_cosine_neighbor_table_update_workspace_size(int64_t N, int32_t d, in
   return neighbor_table_update_ws(N, d, k, m);   // (exact: one byte less is DCNR_WORKSPACE_TOO_SMALL)
 }
 
-dcnr_status dcnr_cosine_neighbor_table_update(const float* table, const float* inv_norms, const uint16_t* packed,
-                                              int64_t N, int32_t d, int32_t k, const int32_t* changed, int64_t m,
-                                              int32_t* nbr, int32_t* counts, int32_t* host_counts,
-                                              int32_t* research_rows, void* ws, size_t ws_bytes,
-                                              dcnr_stream_t stream) {
+// dcnr_cosine_neighbor_table_update and _affected: the checks (the messages
+// name the entry, `what`), phase A -- C's bitmap, the rows' exact k-th
+// distances, the filter's superset of the rows a changed row may enter --, then
+// the merge into `merge_nbr` or, without one, the affected rows to the
+// re-search list; the count words to the caller's mirror.
+static dcnr_status nbr_update_call(const char* what, const float* table, const float* inv_norms,
+                                   const uint16_t* packed, int64_t N, int32_t d, int32_t k, const int32_t* changed,
+                                   int64_t m, const int32_t* nbr, int32_t* merge_nbr, int32_t* counts,
+                                   int32_t* host_counts, int32_t* research_rows, void* ws, size_t ws_bytes,
+                                   hipStream_t s) {
   if (!table || !inv_norms || m < 0) {
-    set_error("dcnr_cosine_neighbor_table_update: bad argument (m=%lld)", (long long)m);
+    set_error("%s: bad argument (m=%lld)", what, (long long)m);
     return DCNR_BAD_ARG;
   }
-  TRY(nbr_update_shape("dcnr_cosine_neighbor_table_update", N, d, k));
+  TRY(nbr_update_shape(what, N, d, k));
   if (m > UPD_MAX_M) {
-    set_error("dcnr_cosine_neighbor_table_update: m=%lld changed rows (max %d per call)", (long long)m,
-              UPD_MAX_M);
+    set_error("%s: m=%lld changed rows (max %d per call)", what, (long long)m, UPD_MAX_M);
     return DCNR_UNSUPPORTED_SHAPE;
   }
   if (m == 0) return DCNR_OK;
   if (!changed || !nbr || !counts || !research_rows || !ws) {
-    set_error("dcnr_cosine_neighbor_table_update: null argument");
+    set_error("%s: null argument", what);
     return DCNR_BAD_ARG;
   }
   for (int64_t i = 0; i < m; ++i)
     if (changed[i] < 0 || changed[i] >= N || (i > 0 && changed[i] <= changed[i - 1])) {
-      set_error("dcnr_cosine_neighbor_table_update: changed[%lld] = %d (ascending, distinct, inside [0, %lld))",
-                (long long)i, changed[i], (long long)N);
+      set_error("%s: changed[%lld] = %d (ascending, distinct, inside [0, %lld))", what, (long long)i, changed[i],
+                (long long)N);
       return DCNR_BAD_ARG;
     }
-  hipStream_t s = (hipStream_t)stream;
   // (bytes: the lists, each row's k-th neighbour gathered, one pass over the rows, the changed rows)
   ProfScope ps(DCNR_K_KNN, s,
                (double)N * (4.0 * k + 8.0 + 4.0 * d) +
@@ -2965,7 +2962,7 @@ dcnr_status dcnr_cosine_neighbor_table_update(const float* table, const float* i
   const bf16* tb = (const bf16*)packed;
   const UpdWs w = carve_upd(ws, N, d, k, m);
   if (ws_bytes < std::max(w.ab_total, w.c_total)) {
-    set_error("neighbor_table_update: workspace too small");
+    set_error("%s: workspace too small", what + sizeof("dcnr_cosine_") - 1);
     return DCNR_WORKSPACE_TOO_SMALL;
   }
   DCNR_HIP(hipMemcpyAsync(w.chg, changed, (size_t)m * 4, hipMemcpyHostToDevice, s));
@@ -2988,15 +2985,29 @@ dcnr_status dcnr_cosine_neighbor_table_update(const float* table, const float* i
                        (int)m, w.kth, w.aff, counts);
   }
   DCNR_LAUNCH_CHECK();
-  const unsigned mb = (unsigned)std::min<int64_t>(cdiv(N, UPD_G), 4096);
-  hipLaunchKernelGGL(upd_merge_kernel, dim3(mb), dim3(NT), 0, s, table, inv_norms, (int)N, d, k, w.chg, (int)m,
-                     w.bits, w.aff, nbr, research_rows, counts);
-  DCNR_LAUNCH_CHECK();
-  if (host_counts) {
-    hipLaunchKernelGGL(upd_mirror_kernel, dim3(1), dim3(64), 0, s, counts, host_counts);
+  if (merge_nbr) {
+    const unsigned mb = (unsigned)std::min<int64_t>(cdiv(N, UPD_G), 4096);
+    hipLaunchKernelGGL(upd_merge_kernel, dim3(mb), dim3(NT), 0, s, table, inv_norms, (int)N, d, k, w.chg, (int)m,
+                       w.bits, w.aff, merge_nbr, research_rows, counts);
+    DCNR_LAUNCH_CHECK();
+  } else {   // (at most N - m affected rows behind the m changed rows)
+    hipLaunchKernelGGL(upd_list_kernel, dim3((unsigned)std::min<int64_t>(cdiv(N, 256), 4096)), dim3(256), 0, s,
+                       (const int*)w.aff, (int)m, research_rows, counts);
+    DCNR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(upd_list_counts_kernel, dim3(1), dim3(64), 0, s, counts);
     DCNR_LAUNCH_CHECK();
   }
+  if (host_counts) TRY(mirror_words(counts, 4, host_counts, s));
   return DCNR_OK;
+}
+
+dcnr_status dcnr_cosine_neighbor_table_update(const float* table, const float* inv_norms, const uint16_t* packed,
+                                              int64_t N, int32_t d, int32_t k, const int32_t* changed, int64_t m,
+                                              int32_t* nbr, int32_t* counts, int32_t* host_counts,
+                                              int32_t* research_rows, void* ws, size_t ws_bytes,
+                                              dcnr_stream_t stream) {
+  return nbr_update_call("dcnr_cosine_neighbor_table_update", table, inv_norms, packed, N, d, k, changed, m, nbr,
+                         nbr, counts, host_counts, research_rows, ws, ws_bytes, (hipStream_t)stream);
 }
 
 dcnr_status dcnr_cosine_neighbor_table_affected(const float* table, const float* inv_norms, const uint16_t* packed,
@@ -3004,70 +3015,9 @@ dcnr_status dcnr_cosine_neighbor_table_affected(const float* table, const float*
                                                 const int32_t* nbr, int32_t* counts, int32_t* host_counts,
                                                 int32_t* research_rows, void* ws, size_t ws_bytes,
                                                 dcnr_stream_t stream) {
-  if (!table || !inv_norms || m < 0) {
-    set_error("dcnr_cosine_neighbor_table_affected: bad argument (m=%lld)", (long long)m);
-    return DCNR_BAD_ARG;
-  }
-  TRY(nbr_update_shape("dcnr_cosine_neighbor_table_affected", N, d, k));
-  if (m > UPD_MAX_M) {
-    set_error("dcnr_cosine_neighbor_table_affected: m=%lld changed rows (max %d per call)", (long long)m,
-              UPD_MAX_M);
-    return DCNR_UNSUPPORTED_SHAPE;
-  }
-  if (m == 0) return DCNR_OK;
-  if (!changed || !nbr || !counts || !research_rows || !ws) {
-    set_error("dcnr_cosine_neighbor_table_affected: null argument");
-    return DCNR_BAD_ARG;
-  }
-  for (int64_t i = 0; i < m; ++i)
-    if (changed[i] < 0 || changed[i] >= N || (i > 0 && changed[i] <= changed[i - 1])) {
-      set_error("dcnr_cosine_neighbor_table_affected: changed[%lld] = %d (ascending, distinct, inside [0, %lld))",
-                (long long)i, changed[i], (long long)N);
-      return DCNR_BAD_ARG;
-    }
-  hipStream_t s = (hipStream_t)stream;
-  ProfScope ps(DCNR_K_KNN, s,
-               (double)N * (4.0 * k + 8.0 + 4.0 * d) +
-                   (double)N * d * ((d == 32 || d == 64) && packed ? 2.0 : 4.0) + (double)m * (4.0 * d + 8.0));
-  const bf16* tb = (const bf16*)packed;
-  const UpdWs w = carve_upd(ws, N, d, k, m);
-  if (ws_bytes < std::max(w.ab_total, w.c_total)) {
-    set_error("neighbor_table_affected: workspace too small");
-    return DCNR_WORKSPACE_TOO_SMALL;
-  }
-  // phase A of the update (its kernels, unchanged): C's bitmap, the rows' exact
-  // k-th distances, the filter's superset of the rows a changed row may enter
-  DCNR_HIP(hipMemcpyAsync(w.chg, changed, (size_t)m * 4, hipMemcpyHostToDevice, s));
-  DCNR_HIP(hipMemsetAsync(w.bits, 0, (size_t)cdiv(N, 32) * 4, s));
-  hipLaunchKernelGGL(upd_mark_kernel, dim3((unsigned)cdiv(m, 256)), dim3(256), 0, s, w.chg, (int)m, w.bits,
-                     research_rows, counts);
-  DCNR_LAUNCH_CHECK();
-  const unsigned rb = (unsigned)cdiv(N, 256);
-  hipLaunchKernelGGL(upd_kth_kernel, dim3(rb), dim3(256), 0, s, table, inv_norms, (int)N, d / 4, k, nbr, w.bits,
-                     w.kth, w.aff, counts);
-  DCNR_LAUNCH_CHECK();
-  if (d == 32 || d == 64) {
-    with_v4_rows(d, tb != nullptr, [&](auto ks, auto pk) {
-      hipLaunchKernelGGL((upd_filter4_kernel<decltype(ks)::value, decltype(pk)::value>),
-                         dim3((unsigned)cdiv(N, UPD_RPB)), dim3(256), 0, s, table, inv_norms, tb, (int)N, w.chg,
-                         (int)m, w.kth, w.aff, counts);
-    });
-  } else {
-    hipLaunchKernelGGL(upd_filter_exact_kernel, dim3(rb), dim3(256), 0, s, table, inv_norms, (int)N, d / 4, w.chg,
-                       (int)m, w.kth, w.aff, counts);
-  }
-  DCNR_LAUNCH_CHECK();
-  // no merge: every affected row joins the re-search list (at most N - m of them behind the m changed rows)
-  hipLaunchKernelGGL(upd_list_kernel, dim3((unsigned)std::min<int64_t>(cdiv(N, 256), 4096)), dim3(256), 0, s,
-                     (const int*)w.aff, (int)m, research_rows, counts);
-  DCNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(upd_list_counts_kernel, dim3(1), dim3(64), 0, s, counts);
-  DCNR_LAUNCH_CHECK();
-  if (host_counts) {
-    hipLaunchKernelGGL(upd_mirror_kernel, dim3(1), dim3(64), 0, s, counts, host_counts);
-    DCNR_LAUNCH_CHECK();
-  }
-  return DCNR_OK;
+  // no merge: every affected row is searched again
+  return nbr_update_call("dcnr_cosine_neighbor_table_affected", table, inv_norms, packed, N, d, k, changed, m, nbr,
+                         nullptr, counts, host_counts, research_rows, ws, ws_bytes, (hipStream_t)stream);
 }
 
 dcnr_status dcnr_cosine_neighbor_table_rows(const float* table, const float* inv_norms, const uint16_t* packed,

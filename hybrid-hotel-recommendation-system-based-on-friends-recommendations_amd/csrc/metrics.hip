@@ -21,14 +21,14 @@
 //
 // Every count is an integer, every fp64 sum has a fixed order that depends on
 // n alone: two calls on the same input give the same bits.
-#include "dcnr_internal.h"
+#include "device_prims.h"
 
 namespace dcnr {
 
 namespace {
 
 // (tests/metrics_cases.py places n around UNIT_KEYS and AUC_TILE_MIN)
-// the sort's kernels and constants (RBITS, NB, UNIT_KEYS ...): dcnr_internal.h
+// the sort's kernels and constants (RBITS, NB, UNIT_KEYS ...): device_prims.h
 using namespace rsort;
 constexpr int KEY_BITS = 33;
 constexpr int NPASS = (KEY_BITS + RBITS - 1) / RBITS;      // 3
@@ -315,20 +315,7 @@ static dcnr_status eval_metrics(const float* z, const float* y, int64_t n, dcnr_
                      w.part);
   DCNR_LAUNCH_CHECK();
   uint64_t *src = w.ka, *dst = w.kb;
-  const int sort_blocks = (int)cdiv(p.units, SORT_WAVES);
-  for (int ps = 0; ps < NPASS; ++ps) {
-    const int shift = ps * RBITS;
-    hipLaunchKernelGGL(sort_hist_kernel<uint64_t>, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, n, p.units,
-                       p.chunk, shift, w.counts);
-    DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(NB / WAVE), dim3(SCAN_NT), 0, s, w.tot + ps * NB,
-                       w.counts, p.units);
-    DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_scatter_kernel<uint64_t>, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, dst, n,
-                       p.units, p.chunk, shift, w.counts);
-    DCNR_LAUNCH_CHECK();
-    std::swap(src, dst);
-  }
+  TRY(sort_passes(src, dst, n, p.units, p.chunk, 0, NPASS, w.counts, nullptr, w.tot, s));
   hipLaunchKernelGGL(auc_walk_kernel<false>, dim3(p.auc_blocks), dim3(AUC_NT), 0, s, src, n, p.auc_tile,
                      (const long long*)nullptr, w.summary);
   DCNR_LAUNCH_CHECK();
@@ -916,20 +903,7 @@ static dcnr_status eval_group_metrics(const float* z, const float* y, const int6
                      npass, w.ka, w.tot);
   DCNR_LAUNCH_CHECK();
   uint64_t *src = w.ka, *dst = w.kb;
-  const int sort_blocks = (int)cdiv(p.units, SORT_WAVES);
-  for (int ps = 0; ps < npass; ++ps) {
-    const int shift = 1 + ps * RBITS;
-    hipLaunchKernelGGL(sort_hist_kernel<uint64_t>, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, n, p.units,
-                       p.chunk, shift, w.counts);
-    DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(NB / WAVE), dim3(SCAN_NT), 0, s, w.tot + ps * NB,
-                       w.counts, p.units);
-    DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_scatter_kernel<uint64_t>, dim3(sort_blocks), dim3(SORT_NT), 0, s, src, dst, n,
-                       p.units, p.chunk, shift, w.counts);
-    DCNR_LAUNCH_CHECK();
-    std::swap(src, dst);
-  }
+  TRY(sort_passes(src, dst, n, p.units, p.chunk, 1, npass, w.counts, nullptr, w.tot, s));
   hipLaunchKernelGGL(group_heads_kernel, dim3(nb), dim3(GW_NT), 0, s, src, n, p.auc_tile, w.tsum);
   DCNR_LAUNCH_CHECK();
   hipLaunchKernelGGL(group_carry_kernel, dim3(1), dim3(AUC_MAXB), 0, s, w.tsum, nb, w.tcarry);

@@ -35,25 +35,20 @@
 //             number of heads before it.
 //
 // Every atomic is an integer min, max, add or or: the same bytes on every run.
-#include "dcnr_internal.h"
+#include "device_prims.h"
 
 namespace dcnr {
 
 namespace {
 
 using namespace rsort;
+using namespace tscan;
 
 constexpr int TT_NT = 256;
 constexpr int TT_MAXB = 2048;                 // workgroups of the grid-stride kernels
 constexpr int TT_COLB = 256;                  // workgroups per column of the column passes
-constexpr int TT_TILE = TT_NT * 4;            // elements per scan tile
-constexpr int TT_SCAN_NT = 1024;
-constexpr int TT_MAXC = 64;
 constexpr int SEL_PASSES = 6;                 // 9 + 5 * 11 bits
 constexpr uint64_t KEY_NONE = ~0ull;
-constexpr uint64_t SIGN = 0x8000000000000000ull;
-
-struct Derived { int n; int op[TT_MAXC], a[TT_MAXC], b[TT_MAXC]; };
 
 struct alignas(16) TRec {
   uint64_t key;
@@ -68,12 +63,6 @@ __device__ __forceinline__ uint32_t radix_digit(const TRec& r, int shift) {
 }
 constexpr int REC_PASSES = (65 + RBITS - 1) / RBITS;
 
-__device__ __forceinline__ bool is_nan(double x) {
-  return ((uint64_t)__double_as_longlong(x) & ~SIGN) > 0x7FF0000000000000ull;
-}
-__device__ __forceinline__ bool is_inf(double x) {
-  return ((uint64_t)__double_as_longlong(x) & ~SIGN) == 0x7FF0000000000000ull;
-}
 // IEEE order as an unsigned order (not for NaN); -0.0 takes +0.0's key
 __device__ __forceinline__ uint64_t okey(double x) {
   uint64_t u = (uint64_t)__double_as_longlong(x);
@@ -82,98 +71,6 @@ __device__ __forceinline__ uint64_t okey(double x) {
 }
 __device__ __forceinline__ double okey_value(uint64_t k) {
   return __longlong_as_double((long long)((k & SIGN) ? (k & ~SIGN) : ~k));
-}
-
-// inclusive scan over the workgroup (sum, or max); sm holds NT / 64 words
-template <bool MAX>
-__device__ __forceinline__ uint32_t comb(uint32_t a, uint32_t b) { return MAX ? (a > b ? a : b) : a + b; }
-
-template <bool MAX, int NT>
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* sm, uint32_t& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = (uint32_t)__shfl_up((int)v, o, 64);
-    if (lane >= o) v = comb<MAX>(v, t);
-  }
-  if (lane == 63) sm[w] = v;
-  __syncthreads();
-  uint32_t pre = 0u;
-  total = 0u;
-  for (int k = 0; k < NT / 64; ++k) {
-    if (k < w) pre = comb<MAX>(pre, sm[k]);
-    total = comb<MAX>(total, sm[k]);
-  }
-  __syncthreads();
-  return comb<MAX>(pre, v);
-}
-
-// ------------------------------------------------------------------ scan
-// a [M] -> its inclusive scan in place over the first n = *np (or M) elements
-template <bool MAX>
-__global__ __launch_bounds__(TT_NT) void tt_tile_sum_kernel(const uint32_t* a, const int32_t* np, int64_t M,
-                                                            uint32_t* tile_tot) {
-  __shared__ uint32_t sm[TT_NT / 64];
-  const int64_t n = np ? min((int64_t)*np, M) : M;
-  const int64_t i0 = (int64_t)blockIdx.x * TT_TILE + threadIdx.x * 4;
-  uint32_t v = 0u;
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    if (i0 + q < n) v = comb<MAX>(v, a[i0 + q]);
-  uint32_t total;
-  block_scan<MAX, TT_NT>(v, sm, total);
-  if (threadIdx.x == 0) tile_tot[blockIdx.x] = total;
-}
-
-// tile_tot [tiles] -> its exclusive scan in place (one workgroup)
-template <bool MAX>
-__global__ __launch_bounds__(TT_SCAN_NT) void tt_tile_scan_kernel(uint32_t* tile_tot, int64_t tiles) {
-  __shared__ uint32_t sm[TT_SCAN_NT / 64];
-  uint32_t carry = 0u;
-  for (int64_t t0 = 0; t0 < tiles; t0 += TT_SCAN_NT) {   // uniform trip count
-    const int64_t t = t0 + threadIdx.x;
-    const uint32_t v = t < tiles ? tile_tot[t] : 0u;
-    uint32_t total;
-    const uint32_t inc = block_scan<MAX, TT_SCAN_NT>(v, sm, total);
-    // exclusive: what lies before this tile
-    uint32_t before = (uint32_t)__shfl_up((int)inc, 1, 64);
-    __shared__ uint32_t last[TT_SCAN_NT / 64];
-    if ((threadIdx.x & 63) == 63) last[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) before = threadIdx.x ? last[(threadIdx.x >> 6) - 1] : 0u;
-    if (t < tiles) tile_tot[t] = comb<MAX>(carry, before);
-    carry = comb<MAX>(carry, total);
-    __syncthreads();
-  }
-}
-
-template <bool MAX>
-__global__ __launch_bounds__(TT_NT) void tt_tile_apply_kernel(uint32_t* a, const int32_t* np, int64_t M,
-                                                              const uint32_t* tile_tot) {
-  __shared__ uint32_t sm[TT_NT / 64];
-  const int64_t n = np ? min((int64_t)*np, M) : M;
-  const int64_t i0 = (int64_t)blockIdx.x * TT_TILE + threadIdx.x * 4;
-  uint32_t x[4];
-  uint32_t v = 0u;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    x[q] = i0 + q < n ? a[i0 + q] : 0u;
-    v = comb<MAX>(v, x[q]);
-  }
-  uint32_t total;
-  const uint32_t inc = block_scan<MAX, TT_NT>(v, sm, total);
-  // what lies before this lane's four: the tile's base and the lanes below
-  uint32_t before = (uint32_t)__shfl_up((int)inc, 1, 64);
-  __shared__ uint32_t last[TT_NT / 64];
-  if ((threadIdx.x & 63) == 63) last[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) before = threadIdx.x ? last[(threadIdx.x >> 6) - 1] : 0u;
-  uint32_t run = comb<MAX>(tile_tot[blockIdx.x], before);
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    run = comb<MAX>(run, x[q]);
-    if (i0 + q < n) a[i0 + q] = run;
-  }
 }
 
 // --------------------------------------------------------------- init, rows
@@ -211,17 +108,7 @@ __global__ __launch_bounds__(TT_NT) void tt_rows_kernel(const int64_t* cat_key, 
     alive[i] = live ? 1u : 0u;
     passed += pass ? 1 : 0;
     for (int c = 0; c < n_raw; ++c) colmaj[(int64_t)c * M + i] = r[c];
-    for (int d = 0; d < dv.n; ++d) {
-      const double a = r[dv.a[d]], b = r[dv.b[d]];
-      double v;
-      if (dv.op[d] == DCNR_DERIVED_RATIO) {
-        v = a / b;
-        if (is_inf(v) || is_nan(v)) v = 0.0;
-      } else {
-        v = a - b;
-      }
-      colmaj[(int64_t)(n_raw + d) * M + i] = v;
-    }
+    for (int d = 0; d < dv.n; ++d) colmaj[(int64_t)(n_raw + d) * M + i] = derived_value(dv, d, r);
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) passed += __shfl_xor(passed, o, 64);
@@ -430,7 +317,7 @@ __device__ __forceinline__ void fit_scale(double dmin, double dmax, double& scal
 }
 
 // stats [5][n_num]: median, data_min_, data_max_, scale_, min_
-__global__ __launch_bounds__(TT_MAXC) void tt_stats_kernel(const uint64_t* mm, const double* median, int n_num,
+__global__ __launch_bounds__(MAXC) void tt_stats_kernel(const uint64_t* mm, const double* median, int n_num,
                                                            double* stats, double* host_stats) {
   const int c = threadIdx.x;
   if (c >= n_num) return;
@@ -450,19 +337,10 @@ __global__ __launch_bounds__(TT_MAXC) void tt_stats_kernel(const uint64_t* mm, c
   }
 }
 
-// MinMaxScaler.transform and the float32 conversion: two float64 roundings,
-// then one to float32 -- never an fma (item_features.hip has the same rule)
-__device__ __forceinline__ float scaled(double x, double scale, double mn) {
-#pragma clang fp contract(off)
-  double y = x * scale;
-  y = y + mn;
-  return (float)y;
-}
-
 __global__ __launch_bounds__(TT_NT) void tt_transform_kernel(const double* colmaj, const int32_t* row,
                                                              const int32_t* counts, int64_t M, int n_num,
                                                              const double* stats, float* num) {
-  __shared__ double st[3][TT_MAXC];   // median, scale_, min_
+  __shared__ double st[3][MAXC];   // median, scale_, min_
   if (threadIdx.x < n_num) {
     st[0][threadIdx.x] = stats[threadIdx.x];
     st[1][threadIdx.x] = stats[3 * n_num + threadIdx.x];
@@ -559,16 +437,9 @@ __global__ __launch_bounds__(TT_NT) void tt_cat_codes_kernel(const TRec* rec, co
   }
 }
 
-__global__ __launch_bounds__(TT_NT) void tt_mirror_kernel(const int32_t* counts, int n, int32_t* host_counts) {
-  if ((int)threadIdx.x < n)
-    __hip_atomic_store(host_counts + threadIdx.x, counts[threadIdx.x], __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // ------------------------------------------------------------------- host
 struct Plan {
   int units; int64_t chunk;   // sort units and records per unit
-  int64_t tiles;              // of the scans
   int blocks, colb;           // of the grid-stride kernels; per column of the column passes
 };
 
@@ -576,7 +447,6 @@ Plan make_plan(int64_t M) {
   Plan p;
   p.units = (int)std::min<int64_t>(MAX_UNITS, std::max<int64_t>(1, cdiv(M, UNIT_KEYS)));
   p.chunk = rup(cdiv(M, p.units), WAVE);
-  p.tiles = std::max<int64_t>(1, cdiv(M, TT_TILE));
   p.blocks = (int)std::min<int64_t>(TT_MAXB, std::max<int64_t>(1, cdiv(M, TT_NT)));
   p.colb = (int)std::min<int64_t>(TT_COLB, std::max<int64_t>(1, cdiv(M, TT_NT)));
   return p;
@@ -587,7 +457,7 @@ struct Ws {
   TRec *ra, *rb;       // [M] each
   uint32_t *sa, *sb;   // [M] each: scan arrays
   uint8_t* flags;      // [M]
-  uint32_t* tile_tot;  // [tiles]
+  uint32_t* tile_tot;  // [scan_tiles(M)]
   uint32_t* scounts;   // [units][NB]
   uint32_t* stot;      // [NB]
   uint32_t* ghist;     // [n_num][2][NB]
@@ -606,7 +476,7 @@ Ws carve(const Plan& p, int64_t M, int n_num, void* base) {
   w.sa = (uint32_t*)b.take((size_t)M * 4);
   w.sb = (uint32_t*)b.take((size_t)M * 4);
   w.flags = (uint8_t*)b.take((size_t)M);
-  w.tile_tot = (uint32_t*)b.take((size_t)p.tiles * 4);
+  w.tile_tot = (uint32_t*)b.take((size_t)scan_tiles(M) * 4);
   w.scounts = (uint32_t*)b.take((size_t)p.units * NB * 4);
   w.stot = (uint32_t*)b.take((size_t)NB * 4);
   w.ghist = (uint32_t*)b.take((size_t)std::max(1, n_num) * 2 * NB * 4);
@@ -615,61 +485,6 @@ Ws carve(const Plan& p, int64_t M, int n_num, void* base) {
   w.median = (double*)b.take((size_t)std::max(1, n_num) * 8);
   w.total = b.off;
   return w;
-}
-
-template <bool MAX>
-dcnr_status scan_inplace(uint32_t* a, const int32_t* np, int64_t M, const Plan& p, const Ws& w, hipStream_t s) {
-  hipLaunchKernelGGL(tt_tile_sum_kernel<MAX>, dim3((unsigned)p.tiles), dim3(TT_NT), 0, s, (const uint32_t*)a, np,
-                     M, w.tile_tot);
-  DCNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tt_tile_scan_kernel<MAX>, dim3(1), dim3(TT_SCAN_NT), 0, s, w.tile_tot, p.tiles);
-  DCNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(tt_tile_apply_kernel<MAX>, dim3((unsigned)p.tiles), dim3(TT_NT), 0, s, a, np, M,
-                     (const uint32_t*)w.tile_tot);
-  DCNR_LAUNCH_CHECK();
-  return DCNR_OK;
-}
-
-// tot[d] = the sum over the units of counts[u][d], for the sort's scan: one
-// workgroup per 64 digits, thread (j, s) sums digit b0 + j over unit segment s.
-// (rsort's own sort_tot_kernel walks all the units with 8 workgroups: 156 us a
-// pass at 1024 units, half of this call's time before this kernel replaced it)
-__global__ __launch_bounds__(SCAN_NT) void tt_sort_tot_kernel(const uint32_t* counts, int units, uint32_t* tot) {
-  __shared__ uint32_t seg[SCAN_SEG][WAVE];
-  const int j = threadIdx.x & 63, s = threadIdx.x >> 6, b0 = blockIdx.x * WAVE;
-  const int useg = (units + SCAN_SEG - 1) / SCAN_SEG;
-  const int u0 = min(units, s * useg), u1 = min(units, u0 + useg);
-  uint32_t t = 0u;
-  for (int u = u0; u < u1; ++u) t += counts[(int64_t)u * NB + b0 + j];
-  seg[s][j] = t;
-  __syncthreads();
-  if (s == 0) {
-    uint32_t sum = 0u;
-    for (int k = 0; k < SCAN_SEG; ++k) sum += seg[k][j];
-    tot[b0 + j] = sum;
-  }
-}
-
-// the records sorted by (dead, key), stable; src ends as the sorted array
-dcnr_status sort_records(TRec*& src, TRec*& dst, int64_t M, const Plan& p, const Ws& w, hipStream_t s) {
-  const int sort_blocks = (int)cdiv(p.units, SORT_WAVES);
-  for (int ps = 0; ps < REC_PASSES; ++ps) {
-    const int shift = ps * RBITS;
-    hipLaunchKernelGGL(sort_hist_kernel<TRec>, dim3(sort_blocks), dim3(SORT_NT), 0, s, (const TRec*)src, M,
-                       p.units, p.chunk, shift, w.scounts);
-    DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tt_sort_tot_kernel, dim3(NB / WAVE), dim3(SCAN_NT), 0, s, (const uint32_t*)w.scounts,
-                       p.units, w.stot);
-    DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_scan_kernel, dim3(NB / WAVE), dim3(SCAN_NT), 0, s, (const uint32_t*)w.stot,
-                       w.scounts, p.units);
-    DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sort_scatter_kernel<TRec>, dim3(sort_blocks), dim3(SORT_NT), 0, s, (const TRec*)src, dst,
-                       M, p.units, p.chunk, shift, (const uint32_t*)w.scounts);
-    DCNR_LAUNCH_CHECK();
-    std::swap(src, dst);
-  }
-  return DCNR_OK;
 }
 
 }  // namespace
@@ -684,13 +499,7 @@ static dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, h
   const int n_counts = DCNR_TRAIN_TABLE_COUNTS + n_cat;
   const Plan p = make_plan(M);
   const Ws w = carve(p, M, n_num, ws);
-  Derived dv;
-  dv.n = a.n_derived;
-  for (int d = 0; d < a.n_derived; ++d) {
-    dv.op[d] = a.derived[3 * d];
-    dv.a[d] = a.derived[3 * d + 1];
-    dv.b[d] = a.derived[3 * d + 2];
-  }
+  const Derived dv = derived_pack(a.derived, a.n_derived);
   const int64_t n_hist = (int64_t)n_num * 2 * NB;
   hipLaunchKernelGGL(tt_init_kernel, dim3((unsigned)std::max<int64_t>(1, cdiv(std::max<int64_t>(n_hist, 512), TT_NT))),
                      dim3(TT_NT), 0, s, a.counts, n_counts, w.ghist, n_hist, w.sel, n_num, w.mm);
@@ -698,7 +507,7 @@ static dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, h
   hipLaunchKernelGGL(tt_rows_kernel, dim3(p.blocks), dim3(TT_NT), 0, s, a.cat_key, a.raw, M, n_cat, n_raw,
                      a.filter_col, a.filter_lo, a.filter_hi, dv, w.colmaj, w.flags, w.sa, a.counts);
   DCNR_LAUNCH_CHECK();
-  TRY(scan_inplace<false>(w.sa, nullptr, M, p, w, s));
+  TRY(scan_inplace<false>(w.sa, nullptr, M, w.tile_tot, s));
   hipLaunchKernelGGL(tt_emit_kernel, dim3(p.blocks), dim3(TT_NT), 0, s, (const uint8_t*)w.flags,
                      (const uint32_t*)w.sa, a.target, M, a.row, a.y, a.counts);
   DCNR_LAUNCH_CHECK();
@@ -713,7 +522,7 @@ static dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, h
     hipLaunchKernelGGL(tt_minmax_kernel, dim3(p.colb, n_num), dim3(TT_NT), 0, s, (const double*)w.colmaj,
                        (const uint8_t*)w.flags, M, (const double*)w.median, w.mm, a.counts);
     DCNR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tt_stats_kernel, dim3(1), dim3(TT_MAXC), 0, s, (const uint64_t*)w.mm,
+    hipLaunchKernelGGL(tt_stats_kernel, dim3(1), dim3(MAXC), 0, s, (const uint64_t*)w.mm,
                        (const double*)w.median, n_num, a.stats, a.host_stats);
     DCNR_LAUNCH_CHECK();
     hipLaunchKernelGGL(tt_transform_kernel, dim3(p.blocks), dim3(TT_NT), 0, s, (const double*)w.colmaj,
@@ -731,13 +540,14 @@ static dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, h
       hipLaunchKernelGGL(tt_records_kernel, dim3(p.blocks), dim3(TT_NT), 0, s, a.cat_key, n_cat, col - 2, flip,
                          (const int32_t*)a.row, (const int32_t*)a.counts, M, src);
     DCNR_LAUNCH_CHECK();
-    TRY(sort_records(src, dst, M, p, w, s));
+    // the records by (dead, key), stable: a head is its key's first row
+    TRY(sort_passes(src, dst, M, p.units, p.chunk, 0, REC_PASSES, w.scounts, w.stot, nullptr, s));
     if (ids) {
       hipLaunchKernelGGL(tt_heads_kernel<true>, dim3(p.blocks), dim3(TT_NT), 0, s, (const TRec*)src,
                          (const int32_t*)a.counts, M, w.sa, w.sb);
       DCNR_LAUNCH_CHECK();
-      TRY(scan_inplace<true>(w.sa, a.counts, M, p, w, s));
-      TRY(scan_inplace<false>(w.sb, a.counts, M, p, w, s));
+      TRY(scan_inplace<true>(w.sa, a.counts, M, w.tile_tot, s));
+      TRY(scan_inplace<false>(w.sb, a.counts, M, w.tile_tot, s));
       hipLaunchKernelGGL(tt_id_codes_kernel, dim3(p.blocks), dim3(TT_NT), 0, s, (const TRec*)src,
                          (const uint32_t*)w.sa, (const uint32_t*)w.sb, (const int32_t*)a.counts, M, col, flip,
                          a.collab, col ? a.item_ids : a.user_ids, a.counts + 1 + col);
@@ -745,18 +555,14 @@ static dcnr_status train_table_build(const dcnr_train_table_args& a, void* ws, h
       hipLaunchKernelGGL(tt_heads_kernel<false>, dim3(p.blocks), dim3(TT_NT), 0, s, (const TRec*)src,
                          (const int32_t*)a.counts, M, w.sa, w.sb);
       DCNR_LAUNCH_CHECK();
-      TRY(scan_inplace<false>(w.sa, a.counts, M, p, w, s));
+      TRY(scan_inplace<false>(w.sa, a.counts, M, w.tile_tot, s));
       hipLaunchKernelGGL(tt_cat_codes_kernel, dim3(p.blocks), dim3(TT_NT), 0, s, (const TRec*)src,
                          (const uint32_t*)w.sa, (const int32_t*)a.counts, M, n_cat, col - 2, a.cat,
                          a.cat_keys + (int64_t)(col - 2) * M, a.counts + DCNR_TRAIN_TABLE_COUNTS + (col - 2));
     }
     DCNR_LAUNCH_CHECK();
   }
-  if (a.host_counts) {
-    hipLaunchKernelGGL(tt_mirror_kernel, dim3(1), dim3(TT_NT), 0, s, (const int32_t*)a.counts, n_counts,
-                       a.host_counts);
-    DCNR_LAUNCH_CHECK();
-  }
+  if (a.host_counts) TRY(mirror_words(a.counts, n_counts, a.host_counts, s));
   return DCNR_OK;
 }
 
@@ -768,7 +574,7 @@ extern "C" {
 
 static dcnr_status train_table_shape(int64_t M, int32_t n_cat, int32_t n_raw, int32_t n_derived) {
   if (M < 0 || n_cat < 0 || n_raw < 0 || n_derived < 0) return DCNR_BAD_ARG;
-  if (M >= 2147483647ll || n_cat > 64 || (int64_t)n_raw + n_derived > TT_MAXC) return DCNR_UNSUPPORTED_SHAPE;
+  if (M >= 2147483647ll || n_cat > 64 || (int64_t)n_raw + n_derived > MAXC) return DCNR_UNSUPPORTED_SHAPE;
   return DCNR_OK;
 }
 
@@ -786,13 +592,7 @@ dcnr_status dcnr_train_table_build(const dcnr_train_table_args* a, void* ws, siz
   }
   const dcnr_status shape = train_table_shape(a->M, a->n_cat, a->n_raw, a->n_derived);
   bool bad = shape == DCNR_BAD_ARG || !a->counts || a->filter_col < -1 ||
-             (a->filter_col >= 0 && a->filter_col >= a->n_raw) || (a->n_derived > 0 && !a->derived);
-  if (!bad)
-    for (int d = 0; d < a->n_derived; ++d) {
-      const int32_t op = a->derived[3 * d], i = a->derived[3 * d + 1], j = a->derived[3 * d + 2];
-      bad |= (op != DCNR_DERIVED_RATIO && op != DCNR_DERIVED_DIFF) || i < 0 || i >= a->n_raw || j < 0 ||
-             j >= a->n_raw;
-    }
+             (a->filter_col >= 0 && a->filter_col >= a->n_raw) || !derived_ok(a->derived, a->n_derived, a->n_raw);
   if (!bad && a->M > 0) {
     const bool num = a->n_raw + a->n_derived > 0;
     bad = !a->user || !a->item || !a->target || !ws || (a->n_cat > 0 && (!a->cat_key || !a->cat || !a->cat_keys)) ||
@@ -809,20 +609,13 @@ dcnr_status dcnr_train_table_build(const dcnr_train_table_args* a, void* ws, siz
               (long long)a->M, a->n_cat, a->n_raw, a->n_derived);
     return shape;
   }
-  const int n_counts = DCNR_TRAIN_TABLE_COUNTS + a->n_cat;
-  if (a->M == 0) {
-    DCNR_HIP(hipMemsetAsync(a->counts, 0, (size_t)n_counts * 4, s));
-    if (a->host_counts)
-      for (int i = 0; i < n_counts; ++i) a->host_counts[i] = 0;
-    return DCNR_OK;
-  }
+  if (a->M == 0) return zero_counts(a->counts, a->host_counts, DCNR_TRAIN_TABLE_COUNTS + a->n_cat, s);
   const size_t need = train_table_ws_bytes(a->M, a->n_raw + a->n_derived) + 256;
   if (ws_bytes < need) {
     set_error("dcnr_train_table_build: workspace too small: %zu < %zu", ws_bytes, need);
     return DCNR_WORKSPACE_TOO_SMALL;
   }
-  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  TRYP(DCNR_K_SERVE, s, train_table_build(*a, base, s));
+  TRYP(DCNR_K_SERVE, s, train_table_build(*a, ws_align(ws), s));
   return DCNR_OK;
 }
 

@@ -34,35 +34,25 @@
 //
 // Every atomic is an integer add, or, min or compare-and-swap: the same results
 // on every run (the id map's slot positions aside).
-#include "dcnr_internal.h"
+#include "device_prims.h"
 
 namespace dcnr {
 
 namespace {
 
+using namespace tscan;
+
 constexpr int RT_NT = 256;
 constexpr int RT_MAXB = 4096;                 // workgroups of the grid-stride kernels
-constexpr int RT_TILE = RT_NT * 4;            // elements per scan tile
-constexpr int RT_SCAN_NT = 1024;
-constexpr int RT_MAXC = 64;                   // numeric columns
 constexpr int RT_MAXCAT = 62;                 // category columns: bits 2 .. 63 of unknown_bits
 constexpr int64_t ID_EMPTY = INT64_MIN;       // the reserved id: an empty slot
-constexpr uint64_t SIGN = 0x8000000000000000ull;
 
 struct alignas(16) Slot {
   int64_t key;
   int64_t index;
 };
 
-struct Derived { int n; int op[RT_MAXC], a[RT_MAXC], b[RT_MAXC]; };
 struct CatOff { int64_t off[RT_MAXCAT + 1]; };
-
-__device__ __forceinline__ bool is_nan(double x) {
-  return ((uint64_t)__double_as_longlong(x) & ~SIGN) > 0x7FF0000000000000ull;
-}
-__device__ __forceinline__ bool is_inf(double x) {
-  return ((uint64_t)__double_as_longlong(x) & ~SIGN) == 0x7FF0000000000000ull;
-}
 
 // splitmix64's finalizer: every input bit reaches every output bit, so ids that
 // agree in their low 32 bits, or are all multiples of 2^32, spread over the table
@@ -138,79 +128,6 @@ __global__ __launch_bounds__(RT_NT) void im_lookup_kernel(const Slot* t, int64_t
   for (int64_t i = i0; i < M; i += step) {
     const int64_t r = map_find(t, cap, raw[i]);
     out[i] = r < 0 ? dflt : r;
-  }
-}
-
-__global__ __launch_bounds__(RT_NT) void rt_mirror_kernel(const int32_t* counts, int n, int32_t* host_counts) {
-  if ((int)threadIdx.x < n)
-    __hip_atomic_store(host_counts + threadIdx.x, counts[threadIdx.x], __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
-// ------------------------------------------------------------------ scan
-template <int NT>
-__device__ __forceinline__ uint32_t block_scan(uint32_t v, uint32_t* sm, uint32_t& total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = (uint32_t)__shfl_up((int)v, o, 64);
-    if (lane >= o) v += t;
-  }
-  if (lane == 63) sm[w] = v;
-  __syncthreads();
-  uint32_t pre = 0u;
-  total = 0u;
-  for (int k = 0; k < NT / 64; ++k) {
-    if (k < w) pre += sm[k];
-    total += sm[k];
-  }
-  __syncthreads();
-  return pre + v;
-}
-
-__global__ __launch_bounds__(RT_NT) void rt_tile_sum_kernel(const uint32_t* a, int64_t M, uint32_t* tile_tot) {
-  __shared__ uint32_t sm[RT_NT / 64];
-  const int64_t i0 = (int64_t)blockIdx.x * RT_TILE + threadIdx.x * 4;
-  uint32_t v = 0u;
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-    if (i0 + q < M) v += a[i0 + q];
-  uint32_t total;
-  block_scan<RT_NT>(v, sm, total);
-  if (threadIdx.x == 0) tile_tot[blockIdx.x] = total;
-}
-
-// tile_tot [tiles] -> its exclusive scan in place (one workgroup)
-__global__ __launch_bounds__(RT_SCAN_NT) void rt_tile_scan_kernel(uint32_t* tile_tot, int64_t tiles) {
-  __shared__ uint32_t sm[RT_SCAN_NT / 64];
-  uint32_t carry = 0u;
-  for (int64_t t0 = 0; t0 < tiles; t0 += RT_SCAN_NT) {   // uniform trip count
-    const int64_t t = t0 + threadIdx.x;
-    const uint32_t v = t < tiles ? tile_tot[t] : 0u;
-    uint32_t total;
-    const uint32_t inc = block_scan<RT_SCAN_NT>(v, sm, total);
-    if (t < tiles) tile_tot[t] = carry + inc - v;
-    carry += total;
-  }
-}
-
-__global__ __launch_bounds__(RT_NT) void rt_tile_apply_kernel(uint32_t* a, int64_t M, const uint32_t* tile_tot) {
-  __shared__ uint32_t sm[RT_NT / 64];
-  const int64_t i0 = (int64_t)blockIdx.x * RT_TILE + threadIdx.x * 4;
-  uint32_t x[4];
-  uint32_t v = 0u;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    x[q] = i0 + q < M ? a[i0 + q] : 0u;
-    v += x[q];
-  }
-  uint32_t total;
-  const uint32_t inc = block_scan<RT_NT>(v, sm, total);
-  uint32_t run = tile_tot[blockIdx.x] + inc - v;   // what lies before this lane's four
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    run += x[q];
-    if (i0 + q < M) a[i0 + q] = run;
   }
 }
 
@@ -384,20 +301,11 @@ __global__ __launch_bounds__(RT_NT) void rt_flags_kernel(RowsIn in, CatOff co, u
     if (cnt[k]) atomicAdd(counts + (k < 3 ? 1 + k : DCNR_ROWS_TRANSFORM_COUNTS + (k - 3)), cnt[k]);
 }
 
-// MinMaxScaler.transform and the float32 conversion: two float64 roundings,
-// then one to float32 -- never an fma (train_table.hip has the same rule)
-__device__ __forceinline__ float scaled(double x, double scale, double mn) {
-#pragma clang fp contract(off)
-  double y = x * scale;
-  y = y + mn;
-  return (float)y;
-}
-
 __global__ __launch_bounds__(RT_NT) void rt_emit_kernel(RowsIn in, CatOff co, Derived dv, const uint32_t* pos,
                                                         const uint8_t* target, const double* fit, int fill_nan,
                                                         int32_t* row, int64_t* collab, int64_t* cat, float* num,
                                                         float* y, int64_t* unknown_bits, int32_t* counts) {
-  __shared__ double st[3][RT_MAXC];   // median, scale_, min_
+  __shared__ double st[3][MAXC];   // median, scale_, min_
   const int n_num = in.n_raw + dv.n;
   if ((int)threadIdx.x < n_num) {
     st[0][threadIdx.x] = fit[threadIdx.x];
@@ -420,19 +328,7 @@ __global__ __launch_bounds__(RT_NT) void rt_emit_kernel(RowsIn in, CatOff co, De
     if (y) y[j] = target[i] ? 1.0f : 0.0f;
     const double* r = in.raw + i * in.n_raw;
     for (int c = 0; c < n_num; ++c) {
-      double x;
-      if (c < in.n_raw) {
-        x = r[c];
-      } else {
-        const int d = c - in.n_raw;
-        const double a = r[dv.a[d]], b = r[dv.b[d]];
-        if (dv.op[d] == DCNR_DERIVED_RATIO) {
-          x = a / b;
-          if (is_inf(x) || is_nan(x)) x = 0.0;
-        } else {
-          x = a - b;
-        }
-      }
+      double x = c < in.n_raw ? r[c] : derived_value(dv, c - in.n_raw, r);
       if (fill_nan && is_nan(x)) x = st[0][c];
       inf |= is_inf(x);
       num[j * n_num + c] = scaled(x, st[1][c], st[2][c]);
@@ -445,7 +341,7 @@ int grid_for(int64_t n) { return (int)std::min<int64_t>(RT_MAXB, std::max<int64_
 
 struct Ws {
   uint32_t* keep;      // [M]: the flags, then their inclusive scan
-  uint32_t* tile_tot;  // [tiles]
+  uint32_t* tile_tot;  // [scan_tiles(M)]
   size_t total;
 };
 
@@ -453,7 +349,7 @@ Ws carve(int64_t M, void* base) {
   Bump b(base);
   Ws w;
   w.keep = (uint32_t*)b.take((size_t)M * 4);
-  w.tile_tot = (uint32_t*)b.take((size_t)std::max<int64_t>(1, cdiv(M, RT_TILE)) * 4);
+  w.tile_tot = (uint32_t*)b.take((size_t)scan_tiles(M) * 4);
   w.total = b.off;
   return w;
 }
@@ -462,7 +358,6 @@ dcnr_status rows_transform(const dcnr_rows_transform_args& a, void* ws, hipStrea
   const int64_t M = a.M;
   const int n_counts = DCNR_ROWS_TRANSFORM_COUNTS + a.n_cat;
   const Ws w = carve(M, ws);
-  const int64_t tiles = std::max<int64_t>(1, cdiv(M, RT_TILE));
   RowsIn in;
   in.user = a.user; in.item = a.item; in.cat_key = a.cat_key; in.raw = a.raw;
   in.M = M; in.n_cat = a.n_cat; in.n_raw = a.n_raw;
@@ -473,33 +368,16 @@ dcnr_status rows_transform(const dcnr_rows_transform_args& a, void* ws, hipStrea
   in.cat_keys = a.cat_keys;
   CatOff co = {};
   for (int c = 0; c <= a.n_cat; ++c) co.off[c] = a.n_cat ? a.cat_offsets[c] : 0;
-  Derived dv = {};
-  dv.n = a.n_derived;
-  for (int d = 0; d < a.n_derived; ++d) {
-    dv.op[d] = a.derived[3 * d];
-    dv.a[d] = a.derived[3 * d + 1];
-    dv.b[d] = a.derived[3 * d + 2];
-  }
+  const Derived dv = derived_pack(a.derived, a.n_derived);
   DCNR_HIP(hipMemsetAsync(a.counts, 0, (size_t)n_counts * 4, s));
   hipLaunchKernelGGL(rt_flags_kernel, dim3(grid_for(M)), dim3(RT_NT), 0, s, in, co, w.keep, a.counts);
   DCNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rt_tile_sum_kernel, dim3((unsigned)tiles), dim3(RT_NT), 0, s, (const uint32_t*)w.keep, M,
-                     w.tile_tot);
-  DCNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rt_tile_scan_kernel, dim3(1), dim3(RT_SCAN_NT), 0, s, w.tile_tot, tiles);
-  DCNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rt_tile_apply_kernel, dim3((unsigned)tiles), dim3(RT_NT), 0, s, w.keep, M,
-                     (const uint32_t*)w.tile_tot);
-  DCNR_LAUNCH_CHECK();
+  TRY(scan_inplace<false>(w.keep, nullptr, M, w.tile_tot, s));
   hipLaunchKernelGGL(rt_emit_kernel, dim3(grid_for(M)), dim3(RT_NT), 0, s, in, co, dv, (const uint32_t*)w.keep,
                      a.target, a.fit, a.fill_nan ? 1 : 0, a.row, a.collab, a.cat, a.num, a.y, a.unknown_bits,
                      a.counts);
   DCNR_LAUNCH_CHECK();
-  if (a.host_counts) {
-    hipLaunchKernelGGL(rt_mirror_kernel, dim3(1), dim3(RT_NT), 0, s, (const int32_t*)a.counts, n_counts,
-                       a.host_counts);
-    DCNR_LAUNCH_CHECK();
-  }
+  if (a.host_counts) TRY(mirror_words(a.counts, n_counts, a.host_counts, s));
   return DCNR_OK;
 }
 
@@ -507,7 +385,7 @@ bool pow2(int64_t c) { return c > 0 && (c & (c - 1)) == 0; }
 
 dcnr_status rows_shape(int64_t M, int32_t n_cat, int32_t n_raw, int32_t n_derived) {
   if (M < 0 || n_cat < 0 || n_raw < 0 || n_derived < 0) return DCNR_BAD_ARG;
-  if (M >= 2147483647ll || n_cat > RT_MAXCAT || (int64_t)n_raw + n_derived > RT_MAXC)
+  if (M >= 2147483647ll || n_cat > RT_MAXCAT || (int64_t)n_raw + n_derived > MAXC)
     return DCNR_UNSUPPORTED_SHAPE;
   return DCNR_OK;
 }
@@ -515,7 +393,7 @@ dcnr_status rows_shape(int64_t M, int32_t n_cat, int32_t n_raw, int32_t n_derive
 struct InsWs {
   int64_t* slot;       // [M]: the slot of every row with an unknown id
   uint32_t* mark;      // [M]: the first-appearance marks, then their inclusive scan
-  uint32_t* tile_tot;  // [tiles]
+  uint32_t* tile_tot;  // [scan_tiles(M)]
   size_t total;
 };
 
@@ -524,7 +402,7 @@ InsWs ins_carve(int64_t M, void* base) {
   InsWs w;
   w.slot = (int64_t*)b.take((size_t)M * 8);
   w.mark = (uint32_t*)b.take((size_t)M * 4);
-  w.tile_tot = (uint32_t*)b.take((size_t)std::max<int64_t>(1, cdiv(M, RT_TILE)) * 4);
+  w.tile_tot = (uint32_t*)b.take((size_t)scan_tiles(M) * 4);
   w.total = b.off;
   return w;
 }
@@ -532,7 +410,6 @@ InsWs ins_carve(int64_t M, void* base) {
 dcnr_status id_map_insert(Slot* t, int64_t cap, int64_t n, const int64_t* raw, int64_t M, int64_t* out,
                           int64_t* new_ids, int32_t* counts, int32_t* host_counts, void* ws, hipStream_t s) {
   const InsWs w = ins_carve(M, ws);
-  const int64_t tiles = std::max<int64_t>(1, cdiv(M, RT_TILE));
   const dim3 g(grid_for(M)), b(RT_NT);
   DCNR_HIP(hipMemsetAsync(counts, 0, 8, s));
   hipLaunchKernelGGL(im_ins_find_kernel, g, b, 0, s, (const Slot*)t, cap, raw, M, out, counts);
@@ -542,22 +419,14 @@ dcnr_status id_map_insert(Slot* t, int64_t cap, int64_t n, const int64_t* raw, i
   hipLaunchKernelGGL(im_ins_mark_kernel, g, b, 0, s, (const Slot*)t, (const int64_t*)out, (const int64_t*)w.slot, M,
                      w.mark, (const int32_t*)counts);
   DCNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rt_tile_sum_kernel, dim3((unsigned)tiles), b, 0, s, (const uint32_t*)w.mark, M, w.tile_tot);
-  DCNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rt_tile_scan_kernel, dim3(1), dim3(RT_SCAN_NT), 0, s, w.tile_tot, tiles);
-  DCNR_LAUNCH_CHECK();
-  hipLaunchKernelGGL(rt_tile_apply_kernel, dim3((unsigned)tiles), b, 0, s, w.mark, M, (const uint32_t*)w.tile_tot);
-  DCNR_LAUNCH_CHECK();
+  TRY(scan_inplace<false>(w.mark, nullptr, M, w.tile_tot, s));
   hipLaunchKernelGGL(im_ins_head_kernel, g, b, 0, s, t, raw, M, n, (const int64_t*)w.slot, (const uint32_t*)w.mark,
                      out, new_ids, counts);
   DCNR_LAUNCH_CHECK();
   hipLaunchKernelGGL(im_ins_rest_kernel, g, b, 0, s, (const Slot*)t, (const int64_t*)w.slot, M, out,
                      (const int32_t*)counts);
   DCNR_LAUNCH_CHECK();
-  if (host_counts) {
-    hipLaunchKernelGGL(rt_mirror_kernel, dim3(1), b, 0, s, (const int32_t*)counts, 2, host_counts);
-    DCNR_LAUNCH_CHECK();
-  }
+  if (host_counts) TRY(mirror_words(counts, 2, host_counts, s));
   return DCNR_OK;
 }
 
@@ -589,10 +458,7 @@ dcnr_status dcnr_id_map_build(const int64_t* ids, int64_t n, void* table, int64_
                        status);
     DCNR_LAUNCH_CHECK();
   }
-  if (host_status) {
-    hipLaunchKernelGGL(rt_mirror_kernel, dim3(1), dim3(RT_NT), 0, s, (const int32_t*)status, 1, host_status);
-    DCNR_LAUNCH_CHECK();
-  }
+  if (host_status) TRY(mirror_word(status, host_status, s));
   return DCNR_OK;
 }
 
@@ -630,18 +496,14 @@ dcnr_status dcnr_id_map_insert(void* table, int64_t capacity, int64_t n, const i
     set_error("dcnr_id_map_insert: unsupported shape (M=%lld, capacity=%lld)", (long long)M, (long long)capacity);
     return DCNR_UNSUPPORTED_SHAPE;
   }
-  if (M == 0) {
-    DCNR_HIP(hipMemsetAsync(counts, 0, 8, s));
-    if (host_counts) host_counts[0] = host_counts[1] = 0;
-    return DCNR_OK;
-  }
+  if (M == 0) return zero_counts(counts, host_counts, 2, s);
   const size_t need = ins_carve(M, nullptr).total + 256;
   if (ws_bytes < need) {
     set_error("dcnr_id_map_insert: workspace too small: %zu < %zu", ws_bytes, need);
     return DCNR_WORKSPACE_TOO_SMALL;
   }
-  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  TRYP(DCNR_K_SERVE, s, id_map_insert((Slot*)table, capacity, n, raw, M, out, new_ids, counts, host_counts, base, s));
+  TRYP(DCNR_K_SERVE, s,
+       id_map_insert((Slot*)table, capacity, n, raw, M, out, new_ids, counts, host_counts, ws_align(ws), s));
   return DCNR_OK;
 }
 
@@ -659,15 +521,9 @@ dcnr_status dcnr_rows_transform(const dcnr_rows_transform_args* a, void* ws, siz
   }
   const dcnr_status shape = rows_shape(a->M, a->n_cat, a->n_raw, a->n_derived);
   bool bad = shape == DCNR_BAD_ARG || !a->counts || a->filter_col < -1 ||
-             (a->filter_col >= 0 && a->filter_col >= a->n_raw) || (a->n_derived > 0 && !a->derived) ||
+             (a->filter_col >= 0 && a->filter_col >= a->n_raw) || !derived_ok(a->derived, a->n_derived, a->n_raw) ||
              a->n_users < 0 || a->n_items < 0 || !pow2(a->user_capacity) || !pow2(a->item_capacity) ||
              a->user_capacity <= a->n_users || a->item_capacity <= a->n_items;
-  if (!bad)
-    for (int d = 0; d < a->n_derived; ++d) {
-      const int32_t op = a->derived[3 * d], i = a->derived[3 * d + 1], j = a->derived[3 * d + 2];
-      bad |= (op != DCNR_DERIVED_RATIO && op != DCNR_DERIVED_DIFF) || i < 0 || i >= a->n_raw || j < 0 ||
-             j >= a->n_raw;
-    }
   if (!bad && shape == DCNR_OK && a->n_cat > 0) {
     bad = !a->cat_offsets;
     if (!bad) {
@@ -693,20 +549,13 @@ dcnr_status dcnr_rows_transform(const dcnr_rows_transform_args* a, void* ws, siz
               a->n_cat, a->n_raw, a->n_derived);
     return shape;
   }
-  const int n_counts = DCNR_ROWS_TRANSFORM_COUNTS + a->n_cat;
-  if (a->M == 0) {
-    DCNR_HIP(hipMemsetAsync(a->counts, 0, (size_t)n_counts * 4, s));
-    if (a->host_counts)
-      for (int i = 0; i < n_counts; ++i) a->host_counts[i] = 0;
-    return DCNR_OK;
-  }
+  if (a->M == 0) return zero_counts(a->counts, a->host_counts, DCNR_ROWS_TRANSFORM_COUNTS + a->n_cat, s);
   const size_t need = carve(a->M, nullptr).total + 256;
   if (ws_bytes < need) {
     set_error("dcnr_rows_transform: workspace too small: %zu < %zu", ws_bytes, need);
     return DCNR_WORKSPACE_TOO_SMALL;
   }
-  void* base = (void*)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-  TRYP(DCNR_K_SERVE, s, rows_transform(*a, base, s));
+  TRYP(DCNR_K_SERVE, s, rows_transform(*a, ws_align(ws), s));
   return DCNR_OK;
 }
 

@@ -258,13 +258,7 @@ class NearestNeighbors:
             if v.shape[0] != r.size:
                 raise ValueError(f"update_rows: {r.size} rows, {v.shape[0]} vectors")
             v = v[torch.from_numpy(order).to(self.device)]
-        table = self.neighbor_table_ if table is None else table
-        if table is not None:
-            if (not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 2
-                    or table.shape[0] != N or not 1 <= table.shape[1] <= N
-                    or table.device != self._table.device or not table.is_contiguous()):
-                raise ValueError(f"update_rows: table must be a contiguous int32 [{N}, kt] tensor on "
-                                 f"{self._table.device}")
+        table = self._table_arg("update_rows", table)
         stats = dict(changed=int(r.size), affected=0, merged=0, researched=0, rebuilt=False)
         m = int(r.size)
         if m == 0:
@@ -285,9 +279,7 @@ class NearestNeighbors:
                 self._refresh_rows(r[lo:hi], None if vectors is None else v[lo:hi])
                 c = self._update_table(r[lo:hi], table, return_stats)
                 if return_stats:
-                    stats["affected"] += c[1]
-                    stats["merged"] += c[2]
-                    stats["researched"] += c[3]
+                    _add_counts(stats, c)
         return stats if return_stats else None
 
     def append_rows(self, vectors=None, table=None, storage=None, return_stats=False, rebuild=None):
@@ -342,13 +334,7 @@ class NearestNeighbors:
             grown = torch.cat([self._table, v], dim=0)
         m = int(grown.shape[0]) - N
         own = table is None or table is self.neighbor_table_
-        table = self.neighbor_table_ if table is None else table
-        if table is not None:
-            if (not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 2
-                    or table.shape[0] != N or not 1 <= table.shape[1] <= N
-                    or table.device != self._table.device or not table.is_contiguous()):
-                raise ValueError(f"append_rows: table must be a contiguous int32 [{N}, kt] tensor on "
-                                 f"{self._table.device}")
+        table = self._table_arg("append_rows", table)
         stats = dict(changed=m, affected=0, merged=0, researched=0, rebuilt=False)
         if m == 0:
             if storage is not None:
@@ -393,14 +379,25 @@ class NearestNeighbors:
                     self._packed = None if packed is None else packed[:hi]
                     c = self._update_table(np.arange(lo, hi, dtype=np.int64), nbr[:hi], return_stats, merge=False)
                     if return_stats:
-                        stats["affected"] += c[1]
-                        stats["merged"] += c[2]
-                        stats["researched"] += c[3]
+                        _add_counts(stats, c)
             finally:
                 self._table, self._inv, self._packed = grown, inv, packed
         # a kept table that was not the one grown no longer matches the index
         self.neighbor_table_ = nbr if own else None
         return (nbr, stats) if return_stats else nbr
+
+    def _table_arg(self, what, table):
+        """The neighbour table ``what`` works on: ``table``, by default
+        ``neighbor_table_``, checked against the fitted table; None with neither."""
+        table = self.neighbor_table_ if table is None else table
+        N = self._table.shape[0]
+        if table is not None:
+            if (not torch.is_tensor(table) or table.dtype != torch.int32 or table.dim() != 2
+                    or table.shape[0] != N or not 1 <= table.shape[1] <= N
+                    or table.device != self._table.device or not table.is_contiguous()):
+                raise ValueError(f"{what}: table must be a contiguous int32 [{N}, kt] tensor on "
+                                 f"{self._table.device}")
+        return table
 
     def _refresh_rows(self, r, v):
         """Writes v (or nothing) into rows r of the table and recomputes their
@@ -504,6 +501,13 @@ class NearestNeighbors:
         if return_distance:
             return dist.cpu().numpy(), idx_np
         return idx_np
+
+
+def _add_counts(stats, c):
+    """The four count words of one native update, added to the stats."""
+    stats["affected"] += c[1]
+    stats["merged"] += c[2]
+    stats["researched"] += c[3]
 
 
 def rebuild_is_cheaper(m: int, kt: int, N: int) -> bool:

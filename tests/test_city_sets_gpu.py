@@ -119,6 +119,15 @@ def test_three_cities_around_the_chunks(dev, M):
     check_case(dev, item, city, key, None, 200, 3, 100)
 
 
+# 1, 17 and 34 sort units: the sort's totals kernel sums the units in 16
+# segments, of one, two and three units here; 2, 33 and 67 tiles of heads for
+# the one-workgroup scan of the tile counts
+@pytest.mark.parametrize("M,C", [(4096, 300), (65537, 3), (135173, 300)])
+def test_more_units_than_total_segments(dev, M, C):
+    item, city, key = cc.table(M, C, 200, seed=M)
+    check_case(dev, item, city, key, None, 200, C, 100)
+
+
 def test_one_city_holds_everything(dev):
     check_case(dev, *one_city(20000, 5), None, 50, 1, 100)
     item, _, key = one_city(20000, 6, ties=False)

@@ -134,7 +134,11 @@ SHAPES = [dict(seed=1, M=2), dict(seed=3, M=63), dict(seed=4, M=64), dict(seed=5
           dict(seed=12, M=20000, n_users=50, n_items=7),                       # heavy duplication
           dict(seed=8, M=300, n_cat=0), dict(seed=15, M=257, n_raw=64, n_derived=0),
           dict(seed=16, M=1500, n_raw=40, n_derived=24, n_cat=3),              # 64 columns, derived among them
-          dict(seed=10, M=500, nan=0.5, missing=0.3), dict(seed=17, M=9000, wide_ids=False, use_filter=False)]
+          dict(seed=10, M=500, nan=0.5, missing=0.3), dict(seed=17, M=9000, wide_ids=False, use_filter=False),
+          # 17 and 34 sort units: the sort's totals kernel sums the units in 16 segments, of
+          # two and of three units here (20000 rows are 5 units, one segment each); 65 and 133
+          # scan tiles; few ids, so that every id repeats across the units
+          dict(seed=18, M=65537, n_users=50, n_items=7), dict(seed=19, M=135173, n_users=300, n_items=40)]
 
 
 @pytest.mark.parametrize("kw", SHAPES, ids=lambda kw: f"M{kw['M']}s{kw['seed']}")
