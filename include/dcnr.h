@@ -1306,6 +1306,9 @@ dcnr_status dcnr_rows_transform(const dcnr_rows_transform_args* args, void* ws, 
 /* The deep tower's Linear layer as a standalone bf16 call (nn.Linear forward,
  * train.py:143,105,109): C[M,N] = X[M,K] . W[N,K]^T + bias, X/W bf16
  * row-major (K, ldx, ldw multiples of 8), C bf16 (out_f32 = 0) or fp32.
+ * ldc must be a multiple of 8 where the weight-stationary kernels take the
+ * call (K <= 512 and N a multiple of 8: DCNR_UNSUPPORTED_SHAPE otherwise,
+ * nothing written); the generic kernel (any other K, N) takes any ldc >= N.
  * Used by the deep tower internally; exported for unit tests and kernel
  * benchmarks. */
 dcnr_status dcnr_linear_bf16(const void* X, int64_t ldx, int64_t M, int32_t K, const void* W,

@@ -10,8 +10,10 @@ Shapes (the head pass reduces over chunks of max(32, B / 2048) rows, four
 thread rows per chunk; the dX GEMMs take 32-row tiles): B = 33 (a second
 chunk and a second tile of one row), 1000 (32 chunks, the last of 8 rows: a
 partial tile) and 4099 (129 chunks, the last of 3 rows: a thread row with
-nothing to do)."""
+nothing to do); and, once, B = 262144 + 33, past the dX GEMMs' 32-bit-offset
+launch cut (test_fused_pair_equals_three_calls_past_launch_cut)."""
 import copy
+import time
 
 import pytest
 import torch
@@ -84,10 +86,7 @@ def _assert_same(a, b, names):
         assert torch.equal(a[4][k], b[4][k]), ("state", k)
 
 
-@pytest.mark.parametrize("dropout", [0.0, 0.6])
-@pytest.mark.parametrize("n_res", [1, 2])
-@pytest.mark.parametrize("B", [33, 1000, 4099])
-def test_fused_pair_equals_three_calls(dev, B, n_res, dropout):
+def _fused_pair_equals_three_calls(dev, B, n_res, dropout, grad_scales, accumulates):
     from dcnr import _lib
     cfg = _cfg(n_res, dropout)
     m = _model(cfg, dev)
@@ -97,8 +96,8 @@ def test_fused_pair_equals_three_calls(dev, B, n_res, dropout):
     g = torch.Generator(device=dev).manual_seed(9)
     g0 = [torch.randn(p.shape, device=dev, generator=g) * 1e-3 for p in m.param_tensors()]
     seed_d = 0x5EED0000 + B
-    for grad_scale in (1.0, 0.5):
-        for accumulate in (False, True):
+    for grad_scale in grad_scales:
+        for accumulate in accumulates:
             old = _step(m, sd0, batch, seed_d, False, grad_scale, accumulate, g0)
             new = _step(m, sd0, batch, seed_d, True, grad_scale, accumulate, g0)
             _assert_same(old, new, names)
@@ -110,6 +109,33 @@ def test_fused_pair_equals_three_calls(dev, B, n_res, dropout):
                 assert off >= 0
                 nb = B * HIDDEN * 2
                 assert torch.equal(old[5][off:off + nb], new[5][off:off + nb]), "stored du"
+
+
+@pytest.mark.parametrize("dropout", [0.0, 0.6])
+@pytest.mark.parametrize("n_res", [1, 2])
+@pytest.mark.parametrize("B", [33, 1000, 4099])
+def test_fused_pair_equals_three_calls(dev, B, n_res, dropout):
+    _fused_pair_equals_three_calls(dev, B, n_res, dropout, (1.0, 0.5), (False, True))
+
+
+def test_fused_pair_equals_three_calls_past_launch_cut(dev):
+    """B = 262144 + 33: the dX GEMMs (hidden 512: 2 * ldc = 1024 binds, 2^29 /
+    2048 = 262144 rows, csrc/gemm_ws.hip launch_ws) run as two launches, the
+    second of one 32-row tile and one row.  With DCNR_FLAG_HEAD_STATS the last
+    block's dX GEMM rebuilds its rank-1 residual from r1_dz + m0 and
+    r1_bits + m0 * ldhb, offsets no kept-intermediates step takes
+    (DCNR_FLAG_KEEP_INTERMEDIATES switches head_stats, r1_resid and own_dt
+    off, so tests/test_stages_gpu.py's h512_r2_B262241 pins the stored-du path
+    and this case the rebuilt one).  One grad_scale, both accumulate values;
+    the same bit equality as at the small shapes.  Measured on an MI355X: 0.3 s
+    (tests/test_stages_gpu.py's cfg2_B131072 case: 2.2 s in the same session)."""
+    B = 262144 + 33
+    assert B > (1 << 29) // (2 * 2 * HIDDEN) // 32 * 32
+    torch.cuda.empty_cache()
+    t0 = time.perf_counter()
+    _fused_pair_equals_three_calls(dev, B, 2, 0.6, (0.5,), (False, True))
+    torch.cuda.empty_cache()
+    print(f"  B = {B}: wall {time.perf_counter() - t0:.1f} s")
 
 
 @pytest.mark.parametrize("label", [0, 1])

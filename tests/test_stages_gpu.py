@@ -10,9 +10,12 @@ kernel path, test_fp32_step_stage_by_stage_paths at the fp32 step's shapes
 (fp64 references, one fp32 ulp + 2^-18 x the summed |terms|), and
 test_step_stage_by_stage_batch_regimes, in both precisions, at narrow models
 whose batch size alone takes the reductions and the fp32 split-K past what
-B <= 8192 reaches.  Every small case then runs the same step again in the
-layout a real step uses.
+B <= 8192 reaches, and past 262144 / 524288 rows, where the deep tower's GEMMs
+run as several launches of 32-bit buffer offsets.  Every small case then runs
+the same step again in the layout a real step uses.
 """
+import time
+
 import pytest
 import torch
 
@@ -37,7 +40,9 @@ def _cfg(full):
 @pytest.mark.parametrize("full", [False, True, "h384"], ids=["cfg3r_B1024", "cfg2_B131072", "h384_B8192"])
 def test_bf16_step_stage_by_stage(dev, full):
     cfg, B = _cfg(full)
+    t0 = time.perf_counter()
     stage_check(dev, cfg, B, 7)
+    print(f"  B = {B}: wall {time.perf_counter() - t0:.1f} s")
 
 
 # golden_common.CFG3R's tables and cross network (D = 456), as tests/test_paths_gpu.py's CFG
@@ -75,6 +80,7 @@ def _run_case(dev, case, precision, hidden, n_res, p, B, tb, seed, flags, input_
                params=dict(emb_dim=tb["emb_dim"], hidden_dim=hidden, n_cross_layers=3,
                            n_res_blocks=n_res, dropout=p))
     assert {k for k, v in expected_plan(hidden, precision).items() if v} == set(flags.split()), "the case's path"
+    t0 = time.perf_counter()
     res = stage_check(dev, cfg, B, seed, precision)
     assert res["grads"]["initial_deep_layer.weight"].shape[1] == input_dim
     logits, loss, grads = res["plain_step"]()
@@ -87,7 +93,8 @@ def _run_case(dev, case, precision, hidden, n_res, p, B, tb, seed, flags, input_
     print(f"  CASE {case}: {'flip' if precision == 'bf16' else 'diff/bound'} "
           f"{max(s[1] for s in res['stats']):.2e} diff "
           f"{max(s[2] for s in res['stats']):.2e} rel {worst[1]:.2e} ({worst[0]}) "
-          f"second run {'bit-equal' if not diff else 'DIFFERS ' + str(diff)}")
+          f"second run {'bit-equal' if not diff else 'DIFFERS ' + str(diff)} "
+          f"wall {time.perf_counter() - t0:.1f} s")
     assert not diff, diff
 
 
@@ -209,8 +216,15 @@ BATCH_CASES = {
     "h100_r2_B70001": ("bf16", 100, 2, 0.6, 70001, _tables(), 11, ""),
     "f32_h96_r2_D68_B8225": ("fp32", 96, 2, 0.6, 8225, _tables(2, 16, 4), 11, ""),
     "f32_h96_r2_D68_B70001": ("fp32", 96, 2, 0.6, 70001, _tables(2, 16, 4), 11, ""),
+    # past the GEMMs' 32-bit-offset launch cut (csrc/gemm_ws.hip launch_ws, csrc/gemm_wsp.hip launch_wsp)
+    "h512_r2_B262241": ("bf16", 512, 2, 0.6, 262144 + 97, _tables(2, 16, 4), 11,
+                        "masks stats_epi xbn head_fused rank1"),
+    "h256_r2_B524385": ("bf16", 256, 2, 0.6, 524288 + 97, _tables(2, 16, 4), 11, "masks stats_epi"),
+    "h512_r1_B524385": ("bf16", 512, 1, 0.6, 524288 + 97, _tables(2, 16, 4), 11,
+                        "masks stats_epi xbn head_fused rank1"),
 }
-BATCH_INPUT_DIM = {"f32_h96_r2_D68_B8225": 68, "f32_h96_r2_D68_B70001": 68}
+BATCH_INPUT_DIM = {"f32_h96_r2_D68_B8225": 68, "f32_h96_r2_D68_B70001": 68, "h512_r2_B262241": 68,
+                   "h256_r2_B524385": 68, "h512_r1_B524385": 68}
 
 
 @pytest.mark.parametrize("case", list(BATCH_CASES))
@@ -255,8 +269,48 @@ def test_step_stage_by_stage_batch_regimes(dev, case):
       f32_h96_r2_D68_B70001  rows_per_chunk = 35; linear_dw's slab clamp (dW1, dW2: S = 219,
                              kps = 320) and 274 splits on the generic kernel (dW0)
 
+      h512_r2_B262241        every gemm_ws launch of the step in two chunks (below); the gemm_wsp
+                             forward GEMMs in one
+      h256_r2_B524385        gemm_ws BIAS_STATS at 4 and 8 K-tiles, RESID_BN / DROP_BN / RESID
+                             without the operand transform, each in two chunks
+      h512_r1_B524385        gemm_wsp BIAS_STATS in two chunks, the gemm_ws launches in three
+
     D = 68: user and item embeddings of 16, two categorical tables of width 16
     (250 rows), 4 numeric features.
+
+    Past the GEMMs' launch cut.  launch_ws (csrc/gemm_ws.hip) and launch_wsp
+    (csrc/gemm_wsp.hip) address with 32-bit buffer offsets and cut a call into
+    M-chunks, re-basing X, C, R, Hb, r1_dz, r1_bits, headp, T, Tx and dt per chunk
+    and appending each chunk's BatchNorm column partials behind the previous one's:
+      gemm_ws   floor(2^29 / (2 max(ldx, 2 ldc, ldr, 2 ldhb, ldt))) rows, rounded down to
+                the tile rows (64: BIAS, F32, BIAS_STATS; 32: the dX epilogues)
+      gemm_wsp  floor(2^29 / (2 max(ldx, ldc))) rows, rounded down to 32
+    A launch of mtiles tiles and nslices = cdiv(N, 256) column slices reports
+    groups = 256 / nslices rows of `part`, or 8 cdiv(mtiles nslices, 8 nslices) if that
+    is fewer (8 in every last chunk here); B = cut + 97 leaves a last chunk of
+    one full 64-row tile + 33 rows, or three full 32-row tiles + 1 row.
+      Hp = 512 (D = 68, Dp = 72)
+        first layer, gemm_ws BIAS_STATS, K = 72 (4 K-tiles): 2 ldc = 1024 binds, cut 262144
+        t1 / t2, gemm_wsp BIAS_STATS, K = 512: max(ldx, ldc) = 512, cut 524288
+        dX GEMMs (RESID_BN, DROP_BN, RESID_SUM with the operand transform; the last block's
+          DROP_BN without it): 2 ldc = 1024 binds, cut 262144; Tx and dt re-based with X
+        dx0 (F32, K = 512, N = 72): ldx = 512 binds, cut 524288
+        B = 262241: gemm_ws 262144 + 97 rows, 128 + 8 = 136 part rows; gemm_wsp and dx0 unchunked
+        B = 524385: gemm_ws 262144 + 262144 + 97, 128 + 128 + 8 = 264 part rows; gemm_wsp and
+                    dx0 524288 + 97, gemm_wsp 128 + 8 = 136 part rows
+      Hp = 256
+        first layer (K = 72, 4 K-tiles) and t1 / t2 (K = 256, 8 K-tiles), gemm_ws BIAS_STATS:
+          2 ldc = 512 binds, cut 524288; one slice: 256 + 8 = 264 part rows at B = 524385
+        RESID_BN, DROP_BN (264 part rows) and block 0's RESID, K = 256: the same cut
+        dx0 (F32): ldx = 256 binds, cut 1048576, unchunked
+    136 and 264 rows of `part` against PART_CHUNKS = 2100 (csrc/step.hip); 264 > 256
+    chunks also sends GEMM-epilogue partials through the two-stage reduce_fused_kernel
+    for the first time (per = cdiv(264, 32) = 9: groups 0 - 28 full, group 29 has 3,
+    groups 30 and 31 are empty); at B <= 131072 they are at most 128 rows.
+    Row passes (the head pass; at Hp = 256 the last block's bwd_bn2_stats3 and every
+    bwd_bn1_apply2): rows = max(32, cdiv(B, 2048))
+      B = 262241  rows = 129, nc = 2033 (2032 x 129 + 113), per = 64: group 31 has 49
+      B = 524385  rows = 257, nc = 2041 (2040 x 257 + 105), per = 64: group 31 has 57
 
     Measured on an MI355X (worst stage flip fraction -- fp32: max |diff| / bound --,
     worst max |diff| of a stored stage, worst relative error of a gradient, second
@@ -268,8 +322,20 @@ def test_step_stage_by_stage_batch_regimes(dev, case):
       h100_r2_B70001         1.32e-04      6.23e-02    3.69e-07 (dW1[1])     bit-equal
       f32_h96_r2_D68_B8225   1.94e-01      1.36e-06    2.93e-07 (dW1[0])     bit-equal
       f32_h96_r2_D68_B70001  4.93e-01      1.32e-06    3.30e-07 (dW1[0])     bit-equal
+      h512_r2_B262241        2.88e-04      6.22e-02    3.78e-07 (dW1[1])     bit-equal
+      h256_r2_B524385        2.04e-04      6.23e-02    3.54e-07 (dW1[1])     bit-equal
+      h512_r1_B524385        2.89e-04      6.24e-02    2.41e-07 (dW1[0])     bit-equal
 
     (bf16 max |diff|: one bf16 ulp of a value in [8, 16).)
+
+    Wall time of the cases past the cut (stage check + second run, printed per case),
+    in one run with test_bf16_step_stage_by_stage[cfg2_B131072] at 2.2 s:
+    h512_r2_B262241 0.3 s, h256_r2_B524385 0.4 s, h512_r1_B524385 0.4 s.
+
+    With launch_ws's and launch_wsp's second-chunk C pointer moved one row down (a
+    scratch build, not committed) the three cases fail at h0, and
+    tests/test_linear_exact_gpu.py's chunk cases from row cut - 1 on.
     """
     precision, *rest = BATCH_CASES[case]
+    torch.cuda.empty_cache()   # the cases past the cut hold several GB each: one at a time
     _run_case(dev, case, precision, *rest, BATCH_INPUT_DIM.get(case, 456))
