@@ -32,7 +32,11 @@ System-Based-on-Friends-Recommendations):
                                      serves both from the item neighbour table;
                                      neighbors_within= / within= seek the
                                      neighbours inside the target city instead
-                                     of intersecting afterwards (main.py:209-210)
+                                     of intersecting afterwards (main.py:209-210);
+                                     recommend_many answers requests above the
+                                     4096-row capacity in the same device pass
+                                     (the large lane), recommend()'s MMR takes
+                                     any number of candidates
   InteractionStore                   main_df's reviews + friendships_df as the
                                      request path reads them (main.py:172-194,
                                      336-351); RankingPipeline.recommend_users

@@ -259,6 +259,21 @@ _SIGS = {
     "dcnr_requests_rank_mmr": (ctypes.c_int, [_P, _I64, _P, ctypes.c_int32, _P, _I64, _P, _P,
                                               ctypes.c_int32, _I64, _P, _P, _P, _P, _P, _P, _P,
                                               ctypes.c_size_t, _P]),
+    "dcnr_requests_large_workspace_size": (ctypes.c_size_t, [_I64, _I64]),
+    "dcnr_requests_large_candidates": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _P, ctypes.c_int32,
+                                                      ctypes.c_int32, _P, _I64, _P, ctypes.c_int32,
+                                                      _P, _P, _P, ctypes.c_int32, _I64, _P, _P, _I64,
+                                                      _I64, _P, _P, _P, _P, _P, _P, _P,
+                                                      ctypes.c_size_t, _P]),
+    "dcnr_requests_large_ranking_batch": (ctypes.c_int, [_P, _P, _I64, _I64, _P, _I64, _P, _P,
+                                                         ctypes.c_int32, _P, ctypes.c_int32, _I64,
+                                                         _P, _P, _P, _P, _P]),
+    "dcnr_requests_large_rank_mmr": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _P, _P, ctypes.c_int32,
+                                                    _I64, _P, _P, _P, _P, _P, _P, _P,
+                                                    ctypes.c_size_t, _P]),
+    "dcnr_mmr_rerank_large_workspace_size": (ctypes.c_size_t, [_I64]),
+    "dcnr_mmr_rerank_large": (ctypes.c_int, [_P, _P, ctypes.c_int32, _P, _P, _I64, ctypes.c_float,
+                                             ctypes.c_int32, _P, _P, _P, ctypes.c_size_t, _P]),
     "dcnr_requests_sources": (ctypes.c_int, [ctypes.POINTER(Interactions), _P, _P, _I64, _I64, _P,
                                              _I64, _P, _P, _I64, _I64, _P, _P, _P, _P, _P, _P]),
     "dcnr_requests_recommended_by": (ctypes.c_int, [ctypes.POINTER(Interactions), _P, _I64, _I64,

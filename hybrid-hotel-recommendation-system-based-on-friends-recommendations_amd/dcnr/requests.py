@@ -3,7 +3,16 @@ entry points (``recommend_many``, ``lambda_sweep``, ``recommend_users``) share.
 ``pack_requests`` is the host half on plain values (no pipeline, no device):
 it validates the rows and lays out the arrays to upload.  ``_RequestBatch`` is
 the device half as one sequence: one pinned upload, candidates, the call's one
-wait, forward, rank + MMR, and the answers with the host's spliced in."""
+wait, forward, rank + MMR, and the answers with the host's spliced in.
+
+A request whose bound ``need`` = positives * k + fallback rows exceeds SV_MAX
+cannot be promised to fit the one-workgroup kernels.  ``pack_requests`` marks
+those (``large``); a caller that opts in (``large_lane_split``, then
+``_RequestBatch(large=...)``) has them answered by the large lane
+(csrc/serving_large.hip) in the same pass: its candidates are launched behind
+the small lane's, from the same neighbour source, its mirrors are read at the
+same wait, and it is scored by a forward of its own, so the small lane's
+answers keep the bits they have without it."""
 from __future__ import annotations
 
 import numpy as np
@@ -60,7 +69,10 @@ class PackedRequests:
     ``rounds_to_one``; ``cap``: the longest candidate list's bound.  ``S`` sets
     stand in the CSR the set indices name (0: nothing about sets is uploaded),
     its last ``n_adhoc`` rows this call's own.  ``within_*``: None unless some
-    request names a set for its neighbours."""
+    request names a set for its neighbours.  ``need`` [R]: every request's
+    bound, its staged list plus its fallback set's rows (``fallback_len`` [R],
+    0 where it names none); ``large``: the requests (ascending int32) whose
+    bound exceeds SV_MAX -- the others can never overflow."""
     S = n_adhoc = 0
     within_idx = within_longest = within_any_global = None
 
@@ -147,7 +159,30 @@ def pack_requests(users, positive_rows, lambda_param, top_k, allowed, excluded, 
             p.within_longest = int(set_len[w_idx[w_idx >= 0]].max())
             p.within_any_global = bool(((w_idx < 0) & (np.array(lens) > 0)).any())
     p.cap = int(min(SV_MAX, max(1, int(need.max()))))
+    p.need = need
+    p.fallback_len = need - np.array(lens, np.int64) * k
+    p.large = np.flatnonzero(need > SV_MAX).astype(np.int32)
     return p
+
+
+def large_lane_split(p, budget):
+    """Which of the packed requests ``p`` the large lane answers under a budget
+    of ``budget`` staged entries: (lanes, on_host), request indices ascending.
+    The large requests are taken in request order while the sum of their
+    bounds stays within the budget; one that does not fit, and one whose lambda
+    ``rounds_to_one``, is answered on the host (``recommend()``: never
+    truncated).  With ``lanes``: ``stage_off`` [L + 1], the bounds' offsets."""
+    lanes, host, total = [], [], 0
+    for r in p.large.tolist():
+        if p.odd[r] or total + int(p.need[r]) > budget:
+            host.append(r)
+        else:
+            lanes.append(r)
+            total += int(p.need[r])
+    lanes = np.array(lanes, np.int32)
+    stage_off = np.zeros(lanes.size + 1, np.int64)
+    np.cumsum(p.need[lanes], out=stage_off[1:])
+    return lanes, np.array(host, np.int32), stage_off
 
 
 class _RequestBatch:
@@ -161,10 +196,19 @@ class _RequestBatch:
     candidates) and ``st`` [R] (the status words, or-ed) are known --,
     ``score``, ``rank_mmr`` and ``answers``.  ``what`` names the entry point to
     a caller whose batch the device rejects.  Device words, [R] each: count,
-    status, out_count; with ``sources`` src_count [2 R], src_status, by_status."""
+    status, out_count; with ``sources`` src_count [2 R], src_status, by_status.
 
-    def __init__(self, pipe, what, R, arrays, sources=False, tail=0):
+    ``large``: None, or (lanes, stage_off) of ``large_lane_split`` with at
+    least one lane: ``arrays`` then carries ``large_req`` (the lanes),
+    ``large_stage_off``, ``large_lam`` and ``large_topk`` (the lanes' lambdas
+    and top_k), and the large lane runs beside every step: its candidates in
+    ``candidates``, its mirrors (``lseg`` [L + 1], ``ln``) read in ``wait``,
+    then ``large_score`` and ``large_rank_mmr``."""
+
+    def __init__(self, pipe, what, R, arrays, sources=False, tail=0, large=None):
         self.pipe, self.what, self.R, self.sources = pipe, what, R, sources
+        self.large = large
+        self.L = L = 0 if large is None else int(large[0].size)
         self.dev = dev = pipe.device
         at, total = {}, 0
         for name, a in arrays.items():
@@ -175,6 +219,10 @@ class _RequestBatch:
         self._o_cnt = self._o_st + pad           # (the two mirrors of ``sources``)
         self._o_sst = self._o_cnt + 8 * R
         self.tail = self._o_sst + pad if sources else self._o_cnt
+        if L:   # the large lane's mirrors: offsets [L + 1], status [L]
+            self._o_loff = self.tail
+            self._o_lst = self._o_loff + 8 * (L + 1)
+            self.tail = self._o_lst + ((4 * L + 7) & ~7)
         self.pin, self.host = pin, host = pipe._pinned(self.tail + tail)
         for name, a in arrays.items():
             host[at[name]:at[name] + a.nbytes] = a.view(np.uint8)
@@ -218,13 +266,39 @@ class _RequestBatch:
             within = (set_rows, self.view("set_off", S + 1, torch.int64),
                       self.view("pos_off", R + 1, torch.int64),
                       self.view("within", R, torch.int32)) + tuple(within)
-        pipe._requests_candidates(
-            d_pos.data_ptr() if Q else None, d_pos, self.ptr("pos_off"), R, Q,
-            set_rows.data_ptr() if set_rows.numel() else None, set_rows.numel(),
-            self.ptr("set_off"), S, self.ptr("allowed"), self.ptr("excluded"), self.ptr("fallback"),
-            int(min_candidates), pipe.n_rows, cap, self.slots.data_ptr(), self.count, self.status,
+        sets = (set_rows.data_ptr() if set_rows.numel() else None, set_rows.numel(),
+                self.ptr("set_off"), S, self.ptr("allowed"), self.ptr("excluded"), self.ptr("fallback"),
+                int(min_candidates), pipe.n_rows)
+        idx = pipe._requests_candidates(
+            d_pos.data_ptr() if Q else None, d_pos, self.ptr("pos_off"), R, Q, *sets, cap,
+            self.slots.data_ptr(), self.count, self.status,
             self.offsets.data_ptr(), self._pin + self._o_off, self._pin + self._o_st, self.stream,
             within=within)
+        if self.L:
+            self._large_candidates(d_pos, idx, sets)
+
+    def _large_candidates(self, d_pos, idx, sets):
+        """The large lane's candidates, launched behind the small lane's from the neighbour
+        source that call read: ``idx`` (the top-k lists or the set-scoped overlay), or the
+        pipeline's neighbour table where ``idx`` is None."""
+        pipe, L, dev = self.pipe, self.L, self.dev
+        n = self.ln_staged = int(self.large[1][-1])
+        lib = _lib.load()
+        self._lnb = int(lib.dcnr_requests_large_workspace_size(L, n))
+        self._lws = torch.empty(self._lnb, dtype=torch.uint8, device=dev)
+        self.lrows = torch.empty(n, dtype=torch.int64, device=dev)
+        self.loffsets = torch.empty(L + 1, dtype=torch.int64, device=dev)
+        self._lwords = torch.empty(3 * L, dtype=torch.int32, device=dev)
+        self.lcount, self.lstatus, self.lout_count = (self._lwords.data_ptr() + 4 * L * j
+                                                      for j in range(3))
+        nbr = pipe._nbr if idx is None else None
+        _lib.check(lib.dcnr_requests_large_candidates(
+            d_pos.data_ptr() if self.Q else None, self.ptr("pos_off"), self.R, self.Q,
+            None if idx is None else idx.data_ptr(), None if nbr is None else nbr.data_ptr(),
+            0 if nbr is None else nbr.shape[1], pipe.n_neighbors, *sets, self.ptr("large_req"),
+            self.ptr("large_stage_off"), L, n, self.lrows.data_ptr(), self.lcount, self.lstatus,
+            self.loffsets.data_ptr(), self._pin + self._o_loff, self._pin + self._o_lst,
+            self._lws.data_ptr(), self._lnb, self.stream), "dcnr_requests_large_candidates")
 
     def wait(self):
         """The rank workspace (allocated while the device works), the wait, the mirrors read."""
@@ -239,6 +313,12 @@ class _RequestBatch:
         if self.sources:
             self.src_counts = host[self._o_cnt:self._o_sst].view(np.int32).reshape(R, 2)
             self.st = self.st | host[self._o_sst:self._o_sst + 4 * R].view(np.int32)
+        if self.L:
+            self.lseg = host[self._o_loff:self._o_lst].view(np.int64)
+            self.ln = int(self.lseg[self.L])
+            lst = host[self._o_lst:self._o_lst + 4 * self.L].view(np.int32)
+            if lst.any():
+                raise RuntimeError(f"{self.what}: the device rejected validated input")
         if (self.st & REQ_BAD_DATA).any():
             raise RuntimeError(f"{self.what}: the device rejected validated input")
 
@@ -267,6 +347,35 @@ class _RequestBatch:
                 count_ptr, self.status, self._ws.data_ptr(), self._nb, self.stream),
                 "dcnr_requests_rank_mmr")
         return out_rows, out_logits
+
+    def large_score(self):
+        """The ranking batch of the large lane's ln candidates and a forward of its own."""
+        pipe, n = self.pipe, self.ln
+        if not n:   # nothing is launched
+            return torch.empty(0, dtype=torch.float32, device=self.dev)
+        batch, args = pipe._ranking_outputs(n)
+        _lib.check(_lib.load().dcnr_requests_large_ranking_batch(
+            self.lrows.data_ptr(), self.loffsets.data_ptr(), self.L, n, self.ptr("large_req"),
+            self.R, self.ptr("users"), *args, self.stream), "dcnr_requests_large_ranking_batch")
+        return pipe.model(*batch).reshape(-1).to(torch.float32).contiguous()
+
+    def large_rank_mmr(self, logits):
+        """Rank + MMR of the large lane's segments -> {request: (rows, logits)}, views into
+        its two result tensors of the lengths ``answer_lengths`` gives the small lane's."""
+        n, L = self.ln, self.L
+        table, inv = self.pipe.index._table, self.pipe.index._inv
+        out_rows = torch.empty(n, dtype=torch.int64, device=self.dev)
+        out_logits = torch.empty(n, dtype=torch.float32, device=self.dev)
+        if n:
+            _lib.check(_lib.load().dcnr_requests_large_rank_mmr(
+                logits.data_ptr(), n, self.lrows.data_ptr(), self.loffsets.data_ptr(), L,
+                table.data_ptr(), inv.data_ptr(), table.shape[1], table.shape[0],
+                self.ptr("large_lam"), self.ptr("large_topk"), out_rows.data_ptr(),
+                out_logits.data_ptr(), self.lout_count, self.lstatus, self._lws.data_ptr(),
+                self._lnb, self.stream), "dcnr_requests_large_rank_mmr")
+        lanes, n_seg = self.large[0], np.diff(self.lseg)
+        return {int(r): (out_rows[int(o):int(o) + int(c)], out_logits[int(o):int(o) + int(c)])
+                for r, o, c in zip(lanes, self.lseg[:-1], n_seg)}, n_seg
 
     def answer_lengths(self, lam32, topk):
         """How many items each request's answer holds (one lambda and top_k, or R of each)."""

@@ -27,7 +27,12 @@ fill-up, main.py:204-212) are host set operations and take ``allowed`` /
 pass (dcnr_requests_*: one workgroup per request, the filters as binary
 searches in row sets kept on the device by ``register_sets``, one forward over
 all candidates, one host wait); ``similar_items_many`` is its /similar_items
-companion.  ``RankingPipeline.recommend_users`` is the same pass from user
+companion.  The requests of a batch whose bound of candidates exceeds the
+one-workgroup kernels' 4096 (SV_MAX) take the large lane of the same pass
+(dcnr_requests_large_*, serving_large.hip: grids over the entries, a forward of
+their own, the same one wait) up to ``RankingPipeline.large_lane_budget``
+staged entries; ``recommend()``'s MMR above SV_MAX ranked candidates is
+dcnr_mmr_rerank_large (``mmr_positions_large``).  ``RankingPipeline.recommend_users`` is the same pass from user
 ids: the positives, the negatives and the ``recommended_by`` lists (main.py:
 172-194, 336-351) come from a ``dcnr.InteractionStore`` on the device
 (dcnr_requests_sources, dcnr_requests_recommended_by).  The pass itself (pack,
@@ -60,8 +65,8 @@ import torch
 
 from . import _lib
 from .knn import NearestNeighbors
-from .requests import (REQ_OVERFLOW, SV_MAX, _RequestBatch, _row_set, pack_requests, rounds_to_one,
-                       set_entries)
+from .requests import (REQ_OVERFLOW, SV_MAX, _RequestBatch, _row_set, large_lane_split, pack_requests,
+                       rounds_to_one, set_entries)
 
 ml_artifacts: Dict[str, Any] = {}
 
@@ -111,6 +116,29 @@ def mmr_positions(table: torch.Tensor, inv: torch.Tensor, rows: torch.Tensor,
     return out[:int(cnt.item())]
 
 
+def mmr_positions_large(table: torch.Tensor, inv: torch.Tensor, rows: torch.Tensor,
+                        scores: torch.Tensor, lambda_param: float, top_k: int = 20) -> torch.Tensor:
+    """``mmr_positions`` for any number of candidates (dcnr_mmr_rerank_large:
+    every candidate's running max-similarity lives in a workspace, the
+    arithmetic and its order are ``mmr_positions``', so are the picks)."""
+    lib = _lib.load()
+    dev = table.device
+    n = rows.numel()
+    out = torch.empty(max(1, top_k), dtype=torch.int64, device=dev)
+    cnt = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n == 0:
+        return out[:0]
+    rows = rows.to(dev, torch.int64).contiguous()
+    scores = scores.to(dev, torch.float32).contiguous()
+    nb = int(lib.dcnr_mmr_rerank_large_workspace_size(n))
+    ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    _lib.check(lib.dcnr_mmr_rerank_large(table.data_ptr(), inv.data_ptr(), table.shape[1],
+                                         rows.data_ptr(), scores.data_ptr(), n, float(lambda_param),
+                                         int(top_k), out.data_ptr(), cnt.data_ptr(), ws.data_ptr(), nb,
+                                         _lib.stream_ptr(dev)), "dcnr_mmr_rerank_large")
+    return out[:int(cnt.item())]
+
+
 def rerank_with_mmr(ranked_items_with_scores: List[Tuple[float, int]], lambda_param: float,
                     top_k: int = 20) -> List[int]:
     """main.py:133-169: greedy Maximal Marginal Relevance over (score, item_id)
@@ -157,9 +185,14 @@ def _one_generation(fn):
 
 
 class Answers(list):
-    """What ``recommend_many`` returns from a pipeline with ``item_features``:
-    the list of R (ranked rows, logits) pairs, keeping the feature generation
-    the call scored from."""
+    """What ``recommend_many`` returns when a request left the small lane, or
+    from a pipeline with ``item_features``: the list of R (ranked rows,
+    logits) pairs.  ``large``: the requests (indices, ascending) the large
+    lane answered; ``on_host``: those ``recommend()`` answered (both empty
+    where every request took the small lane).  From a pipeline with
+    ``item_features`` it keeps the feature generation the call scored from."""
+    large = ()
+    on_host = ()
 
 
 class UserAnswers(list):
@@ -228,6 +261,12 @@ class RankingPipeline:
                included -- and the batched calls' answers keep it alive.
                ``item_cat`` / ``item_num`` read the newest generation.
                Serialise the object's changes against requests
+    large_lane_budget  (attribute, default 2^20) the staged entries --
+               positives * n_neighbors + fallback rows, summed over a batch's
+               large requests -- ``recommend_many``'s large lane takes in one
+               call; large requests past it are answered by ``recommend()``.
+               The lane's workspace is 49 bytes and its candidate buffer 8
+               bytes per staged entry: 57 MiB at the default
     neighbor_table  False: every request scans the index.  True: the item
                neighbour table is built here with k = n_neighbors; an int:
                with that k (>= n_neighbors; /similar_items reads it up to
@@ -278,6 +317,7 @@ class RankingPipeline:
         self._sets_lock = threading.Lock()
         self._city_joined = None   # (registered rows, CitySets generation, the two joined)
         self._nbr = self._neighbor_table(neighbor_table)
+        self.large_lane_budget = 1 << 20
 
     def _feature_tables(self):
         """(item_cat, item_num) this call scores from: the arrays the pipeline
@@ -542,8 +582,8 @@ class RankingPipeline:
         order = self.rank(scores)
         ranked, rscores = cand[order], scores[order]
         if lambda_param < 1.0 and ranked.numel():
-            pos = mmr_positions(self.index._table, self.index._inv, ranked, rscores,
-                                lambda_param, top_k)
+            mmr = mmr_positions if ranked.numel() <= SV_MAX else mmr_positions_large
+            pos = mmr(self.index._table, self.index._inv, ranked, rscores, lambda_param, top_k)
             return ranked[pos], rscores[pos]
         return ranked, rscores
 
@@ -647,14 +687,15 @@ class RankingPipeline:
         index per request -- device tensors --, the longest named set, whether a
         request with positives names none).  Those requests' neighbours come
         from one set-scoped call laid over the global answers (the table's rows,
-        gathered, or the scan's), which only the others keep."""
+        gathered, or the scan's), which only the others keep.  Returns the
+        knn_idx [Q][k] the kernel read, None where it read the neighbour table."""
         lib = _lib.load()
         k, nbr = self.n_neighbors, self._nbr
         if nbr is not None and (within is None or not Q):
             _lib.check(lib.dcnr_requests_candidates_table(
                 pos_ptr, pos_off_ptr, R, Q, nbr.data_ptr(), nbr.shape[1], k, *rest),
                 "dcnr_requests_candidates_table")
-            return
+            return None
         idx = None
         if Q and (within is None or within[5]):   # someone keeps global neighbours
             idx = nbr[d_pos][:, :k].to(torch.int64) if nbr is not None else \
@@ -664,6 +705,7 @@ class RankingPipeline:
         _lib.check(lib.dcnr_requests_candidates(
             pos_ptr, pos_off_ptr, R, Q, idx.data_ptr() if Q else None, k, *rest),
             "dcnr_requests_candidates")
+        return idx
 
     def register_sets(self, sets) -> List[int]:
         """Upload row sets (a city's hotels, its most reviewed hotels ...) once,
@@ -691,7 +733,11 @@ class RankingPipeline:
                        neighbors_in_city: bool = False):
         """``recommend()`` for R requests in one device pass: returns a list of
         R pairs (ranked rows, their logits), each equal to what ``recommend``
-        returns for that request alone, as views into two result tensors.
+        returns for that request alone, as views into the result tensors of
+        its lane.  The list is an ``Answers`` (its ``large`` / ``on_host`` name
+        the requests that did not take the small lane) when some request took
+        the large lane or ``recommend()``, or the pipeline has
+        ``item_features``; else the plain list it has always been.
 
         user_rows      R user rows
         positive_rows  R sequences of hotel rows (may be empty)
@@ -727,9 +773,18 @@ class RankingPipeline:
         the device ONCE: after the candidate kernels, to read the forward's
         batch size (the last of the request offsets the device mirrors into
         pinned memory).  Rows are validated on the host before anything is
-        launched (ValueError).  A request whose candidates exceed the batched
-        kernels' capacity (SV_MAX) is answered by ``recommend()`` and spliced
-        in, never truncated.
+        launched (ValueError).  A request whose bound of candidates (its
+        positives * n_neighbors + its fallback set's rows) exceeds the
+        one-workgroup kernels' capacity (SV_MAX) takes the large lane: its
+        candidates are found by grids over all such requests' entries behind
+        the same upload, from the same neighbour source and before the same
+        wait; a forward of its own scores them (so the other answers are the
+        bits they are without it), a radix sort ranks them and one workgroup
+        per request runs its MMR (``Answers.large``).  ``recommend()`` answers
+        only a request whose lambda rounds to 1.0f from below, a large request
+        past ``large_lane_budget`` staged entries, and one the small lane
+        reports as overflowing although its bound fits -- spliced in, never
+        truncated (``Answers.on_host``).
 
         The index and the feature tables must hold the same hotels (equal row
         counts; ValueError otherwise -- ``recommend()`` clamps there).  Nothing
@@ -746,15 +801,28 @@ class RankingPipeline:
         city = self._city_arg("recommend_many", city_sets, cities, neighbors_in_city, R, allowed,
                               fallback, neighbors_within)
         p, b = self._many_front(users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
-                                min_candidates, neighbors_within=neighbors_within, city=city)
+                                min_candidates, neighbors_within=neighbors_within, city=city,
+                                large_lane=True)
         out_rows, out_logits = b.rank_mmr(b.score(), b.ptr("lam"), b.out_count)
+        on_host = ((b.st & REQ_OVERFLOW) | p.odd).astype(bool)
+        large = {}
+        if b.L:
+            lanes = b.large[0]
+            large, n_seg = b.large_rank_mmr(b.large_score())
+            cut = np.where(p.lam[lanes] < 1.0, np.minimum(p.topk[lanes], n_seg), n_seg)
+            large = {r: (rows[:c], z[:c]) for (r, (rows, z)), c in zip(large.items(), cut.tolist())}
+            on_host[lanes] = False
 
         def host(r):   # above the batched kernels' capacity, or a lambda that rounds to 1.0f
             return self._on_host(r, users, p, p.pos[p.pos_off[r]:p.pos_off[r + 1]],
                                  self._set_arg(None if excluded is None else excluded[r]),
                                  min_candidates, (city, allowed, fallback, neighbors_within))
-        return b.answers(out_rows, out_logits, b.answer_lengths(p.lam, p.topk),
-                         (b.st & REQ_OVERFLOW) | p.odd, host)
+        small = b.answers(out_rows, out_logits, b.answer_lengths(p.lam, p.topk), on_host, host)
+        if not large and not on_host.any():   # every request in the small lane: the plain list, as ever
+            return small
+        res = Answers(large.get(r, a) for r, a in enumerate(small))
+        res.large, res.on_host = sorted(large), np.flatnonzero(on_host).tolist()
+        return res
 
     def _users_arg(self, what, user_rows):
         """``user_rows`` of the batched call ``what`` as an array, the tables' row counts checked."""
@@ -778,14 +846,25 @@ class RankingPipeline:
         return p, reg_rows if city is None else self._city_join(reg_rows, city[0])
 
     def _many_front(self, users, positive_rows, lambda_param, top_k, allowed, excluded, fallback,
-                    min_candidates, extra=None, tail=0, neighbors_within=None, city=None):
+                    min_candidates, extra=None, tail=0, neighbors_within=None, city=None,
+                    large_lane=False):
         """``recommend_many`` up to its one wait: the packed requests and their
         ``_RequestBatch``, staged (``extra``: further named arrays to carry along;
-        ``tail``: as ``_RequestBatch``'s), the candidates found and waited for."""
+        ``tail``: as ``_RequestBatch``'s), the candidates found and waited for.
+        ``large_lane``: the caller opts in to the large lane for the requests
+        ``large_lane_split`` gives it under ``large_lane_budget`` (the batch's
+        ``large``); without it every request goes the small lane's way."""
         p, reg_rows = self._pack(users, positive_rows, lambda_param, top_k, allowed, excluded,
                                  fallback, neighbors_within, city)
+        large = None
+        if large_lane and p.large.size:
+            lanes, _, stage_off = large_lane_split(p, self.large_lane_budget)
+            if lanes.size:
+                large = (lanes, stage_off)
+                extra = dict(extra or {}, large_req=lanes, large_stage_off=stage_off,
+                             large_lam=p.lam[lanes], large_topk=p.topk[lanes])
         b = _RequestBatch(self, "recommend_many", users.size, dict(p.arrays, **(extra or {})),
-                          tail=tail)
+                          tail=tail, large=large)
         b.candidates(b.view("pos", p.pos.size, torch.int64), b.set_rows(reg_rows, p.n_adhoc), p.S,
                      min_candidates, p.cap,
                      None if p.within_idx is None else (p.within_longest, p.within_any_global))

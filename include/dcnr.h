@@ -895,6 +895,109 @@ dcnr_status dcnr_requests_rank_mmr(const float* logits, int64_t n, const int64_t
                                    int32_t* out_count, int32_t* status, void* ws, size_t ws_bytes,
                                    dcnr_stream_t stream);
 
+/* ---- serving, the large lane: the requests of a batch above the 4096-row capacity ----
+ * A request whose bound need = (its positives) * k + (its fallback set's rows)
+ * is at most 4096 can never be DCNR_REQ_OVERFLOW in the calls above; the L
+ * requests above that go through these calls in the same pass, before the
+ * same ONE wait.  All L are processed together, every step a grid over their
+ * entries (a stable radix sort of (lane, row) keys, flags, a tiled scan: no
+ * atomic decides a position), so there is no capacity but the workspace and
+ * DCNR_REQ_OVERFLOW is never set.  Lane l serves request large_req[l] (int32
+ * [L], each in [0, R)) of the batch: its positives, set indices and user are
+ * read at that index of the batch's own arrays.  The calls take lanes of any
+ * size, the small ones included, and give the bits the calls above give.
+ *
+ *   dcnr_requests_large_candidates     -> cand_rows [offsets[L]] compact, offsets,
+ *                                         count, status
+ *   (host: the batch's one wait; n = offsets[L] from the pinned mirror)
+ *   dcnr_requests_large_ranking_batch  -> the forward's inputs for the n rows
+ *   dcnr_forward (eval)                -> logits [n]
+ *   dcnr_requests_large_rank_mmr       -> ranked rows / logits per segment
+ *
+ * Argument errors come before any launch: DCNR_BAD_ARG (a negative length,
+ * k < 1, kt < k, d outside 1..256, a null pointer with L > 0),
+ * DCNR_UNSUPPORTED_SHAPE (L > 2^22, more than 2^30 entries, k > 64,
+ * n_set_rows >= 2^31, n_items > 2^38), DCNR_WORKSPACE_TOO_SMALL.  L = 0 returns
+ * DCNR_OK without a launch. */
+
+/* Workspace bytes of dcnr_requests_large_candidates and
+ * dcnr_requests_large_rank_mmr for L lanes of n_staged entries in all (the
+ * larger of the two: 24 bytes per entry and the sort's counts for the
+ * candidates, 49 per entry for rank + MMR, + alignment); 0 for L <= 0 or
+ * arguments the calls reject. */
+size_t dcnr_requests_large_workspace_size(int64_t L, int64_t n_staged);
+
+/* Candidates of the L large requests.  stage_offsets [L + 1] (device) splits
+ * [0, n_staged) into the lanes' bounds: lane l stages stage_offsets[l + 1] -
+ * stage_offsets[l] = need entries -- each positive of its request, the
+ * positive's neighbours knn_idx[q][1 .. k) (nbr == NULL; knn_idx [Q_total][k]
+ * as dcnr_requests_candidates takes it) or nbr[p][1 .. k) (the item neighbour
+ * table int32 [n_items][kt], kt >= k), and every row of its fallback set.
+ * Negative positives and neighbours are skipped.  Then, per request, what
+ * dcnr_requests_candidates does: the distinct rows; those the fallback alone
+ * brought kept iff the union has fewer than min_candidates rows; the allowed /
+ * excluded filters.  out_rows [n_staged]: the surviving rows, ascending per
+ * request, the requests' segments one behind the other; offsets [L + 1],
+ * out_count [L], status [L] (written: 0 or DCNR_REQ_BAD_DATA -- a request index
+ * outside [0, R), offsets outside [0, Q_total], a set index or set offsets
+ * outside the CSR, a bound that is not the request's need, a positive,
+ * neighbour or set row >= n_items, for that lane alone; stage_offsets that do
+ * not rise from 0 to n_staged, for every lane).  offsets and status are also
+ * stored to host_offsets [L + 1] / host_status [L] (pinned, or NULL) with
+ * system-scope stores. */
+dcnr_status dcnr_requests_large_candidates(
+    const int64_t* positives, const int64_t* pos_offsets, int64_t R, int64_t Q_total,
+    const int64_t* knn_idx, const int32_t* nbr, int32_t kt, int32_t k, const int64_t* set_rows,
+    int64_t n_set_rows, const int64_t* set_offsets, int32_t S, const int32_t* allowed,
+    const int32_t* excluded, const int32_t* fallback, int32_t min_candidates, int64_t n_items,
+    const int32_t* large_req, const int64_t* stage_offsets, int64_t L, int64_t n_staged,
+    int64_t* out_rows, int32_t* out_count, int32_t* status, int64_t* offsets, int64_t* host_offsets,
+    int32_t* host_status, void* ws, size_t ws_bytes, dcnr_stream_t stream);
+
+/* dcnr_requests_ranking_batch over the large lane's compact rows: row i of
+ * cand_rows [n] belongs to the lane l whose segment [offsets[l], offsets[l + 1])
+ * holds it; its user is user_rows[large_req[l]] (user_rows [R]; an index
+ * outside [0, R) is clamped into it, as the item row is into the tables). */
+dcnr_status dcnr_requests_large_ranking_batch(const int64_t* cand_rows, const int64_t* offsets,
+                                              int64_t L, int64_t n, const int32_t* large_req,
+                                              int64_t R, const int64_t* user_rows,
+                                              const int64_t* item_cat, int32_t n_cat,
+                                              const float* item_num, int32_t n_num, int64_t n_items,
+                                              int64_t* user_ids, int64_t* item_ids,
+                                              int64_t* cat_features, float* num_features,
+                                              dcnr_stream_t stream);
+
+/* dcnr_requests_rank_mmr over the large lane's segments of logits [n] and
+ * cand_rows [n]: lambda_param and top_k are [L], one per lane.  The rank is a
+ * stable radix sort of (lane, -logit), so equal logits keep their order; the
+ * MMR runs one workgroup per lane, its per-candidate state in LDS up to 4096
+ * candidates and in the workspace above -- the arithmetic and its order are
+ * those of dcnr_mmr_rerank, hence the same picks.  Results, counts, status and
+ * the marking of a request whose logits hold -inf or NaN as
+ * dcnr_requests_rank_mmr; offsets that do not rise from 0 within [0, n] are
+ * DCNR_REQ_BAD_DATA for every lane.  ws: dcnr_requests_large_workspace_size(L, n)
+ * bytes. */
+dcnr_status dcnr_requests_large_rank_mmr(const float* logits, int64_t n, const int64_t* cand_rows,
+                                         const int64_t* offsets, int64_t L, const float* table,
+                                         const float* inv_norms, int32_t d, int64_t n_items,
+                                         const float* lambda_param, const int32_t* top_k,
+                                         int64_t* out_rows, float* out_logits, int32_t* out_count,
+                                         int32_t* status, void* ws, size_t ws_bytes,
+                                         dcnr_stream_t stream);
+
+/* dcnr_mmr_rerank for any n up to 2^30: the per-candidate state lives in ws
+ * (dcnr_mmr_rerank_large_workspace_size(n) bytes, 5 per candidate + alignment;
+ * 0 for n <= 0 or above the limit), everything else as dcnr_mmr_rerank: the
+ * same arithmetic in the same order, one workgroup.  DCNR_BAD_ARG,
+ * DCNR_UNSUPPORTED_SHAPE (n, d outside 1..256) and DCNR_WORKSPACE_TOO_SMALL
+ * come before any launch. */
+size_t dcnr_mmr_rerank_large_workspace_size(int64_t n);
+dcnr_status dcnr_mmr_rerank_large(const float* table, const float* inv_norms, int32_t d,
+                                  const int64_t* rows, const float* scores, int64_t n,
+                                  float lambda_param, int32_t top_k, int64_t* out_pos,
+                                  int32_t* out_count, void* ws, size_t ws_bytes,
+                                  dcnr_stream_t stream);
+
 /* ---- serving, requests by user: the reviews and the friend graph on the device ----
  * What /recommendations reads of main_df and friendships_df (get_friends_for_user,
  * main.py:172-178; the positives and negatives of _generate_candidates, main.py:

@@ -6,6 +6,7 @@ it: the loop of ``recommend()`` over the same requests, in the same process.
     python tools/bench_requests.py [--batches 1 8 64 256] [--iters 20] [--rounds 5]
     python tools/bench_requests.py --one-batch 64      # for a kernel trace of its own
     python tools/bench_requests.py --neighbor-table    # the pipeline reads the item neighbour table
+    python tools/bench_requests.py --large 1 4 --no-loop   # large requests in every batch
 
 Workload: bench.py's configs[4] leg (bench_cfg5) -- a 1M x 64 item table, the
 bench model in bf16, 32 random positive hotels per request, lambda 0.7, top 20.
@@ -22,6 +23,17 @@ compared; batch sizes at which they differ are listed under "answers_differ"
 (none is expected while both take the same forward).  With --neighbor-table the
 pipeline is built with ``neighbor_table=True`` (both routes then look their
 neighbours up; the build's seconds are reported).  Prints one JSON line.
+
+``--large N`` puts N requests of 400 to 2000 random positives (seeded) into
+every batch, in place of its first N: requests above the one-workgroup
+kernels' 4096-row capacity, which ``recommend_many`` answers in its large lane
+(before it: through ``recommend()``).  Several values of N run one after the
+other in one process, 0 being the plain workload; a batch with large requests
+is reported under "R+Nlarge".  The large requests take ``--large-lambda``
+(default 1.0: a tree without the large lane cannot answer lambda < 1 above 4096
+candidates, and the same command must run on both).  ``--no-loop`` leaves the
+loop of ``recommend()`` out (it is the same code in both trees).  Results are
+kept under profiles/large_requests/.
 """
 from __future__ import annotations
 
@@ -67,9 +79,14 @@ def forward_seen(fn):
     return "fused tower" if seen["tower"][1] else "layer by layer"
 
 
-def requests(R, g, dev):
+def requests(R, g, dev, n_large=0):
     users = torch.randint(0, 1_000_000, (R,), generator=g, device=dev).tolist()
     pos = [torch.randint(0, N_ITEMS, (32,), generator=g, device=dev).tolist() for _ in range(R)]
+    if n_large:
+        import numpy as np
+        rng = np.random.default_rng(1000 * R + n_large)
+        for r in range(min(n_large, R)):
+            pos[r] = rng.integers(0, N_ITEMS, int(rng.integers(400, 2001))).tolist()
     return users, pos
 
 
@@ -99,6 +116,10 @@ def main():
                     help="warm up, then run one batched call of this size and exit")
     ap.add_argument("--neighbor-table", action="store_true",
                     help="serve the neighbours from the item neighbour table, built at start")
+    ap.add_argument("--large", type=int, nargs="+", default=[0],
+                    help="requests of 400 to 2000 positives in every batch (several: one after the other)")
+    ap.add_argument("--large-lambda", type=float, default=1.0, help="lambda_param of the large requests")
+    ap.add_argument("--no-loop", action="store_true", help="time the batched call only")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_requests.py needs the HIP device")
@@ -109,43 +130,53 @@ def main():
     build_s = time.perf_counter() - t0
 
     if args.one_batch:
-        users, pos = requests(args.one_batch, g, dev)
+        n_large = min(args.large[0], args.one_batch)
+        users, pos = requests(args.one_batch, g, dev, n_large)
+        lam = [args.large_lambda] * n_large + [0.7] * (args.one_batch - n_large)
         for _ in range(args.warmup):
-            pipe.recommend_many(users, pos, lambda_param=0.7)
+            pipe.recommend_many(users, pos, lambda_param=lam)
         torch.cuda.synchronize()
-        pipe.recommend_many(users, pos, lambda_param=0.7)
+        pipe.recommend_many(users, pos, lambda_param=lam)
         torch.cuda.synchronize()
-        print(json.dumps({"one_batch": args.one_batch}))
+        print(json.dumps({"one_batch": args.one_batch, "large": n_large}))
         return
 
     out = {"workload": "bench_cfg5: 1M x 64 item table, bench model bf16, 32 positives per "
                        "request, lambda 0.7, top 20", "iters": args.iters, "rounds": args.rounds,
            "neighbor_table": args.neighbor_table, "pipeline_build_s": round(build_s, 3),
            "batches": {}}
-    for R in args.batches:
-        users, pos = requests(R, g, dev)
+    out["large_lambda"] = args.large_lambda
+    for R, n_large in [(R, n) for R in args.batches for n in args.large]:
+        users, pos = requests(R, g, dev, n_large)
+        n_large = min(n_large, R)
+        lam = [args.large_lambda] * n_large + [0.7] * (R - n_large)
 
         def many():
-            return pipe.recommend_many(users, pos, lambda_param=0.7)
+            return pipe.recommend_many(users, pos, lambda_param=lam)
 
         def loop():
-            return [pipe.recommend(users[r], pos[r], lambda_param=0.7) for r in range(R)]
+            return [pipe.recommend(users[r], pos[r], lambda_param=lam[r]) for r in range(R)]
 
+        routes = {"many": many} if args.no_loop else {"many": many, "loop": loop}
         for _ in range(args.warmup):
-            got, want = many(), loop()
-        for (gr, gl), (wr, wl) in zip(got, want):
+            got = {name: fn() for name, fn in routes.items()}
+        for (gr, gl), (wr, wl) in zip(got["many"], got.get("loop", got["many"])):
             if not (torch.equal(gr, wr) and torch.equal(gl, wl)):
-                out.setdefault("answers_differ", []).append(R)
+                out.setdefault("answers_differ", []).append([R, n_large])
                 break
         n_cand = sum(pipe.candidates(p).numel() for p in pos)
-        rows = {"many": [], "loop": []}
+        rows = {name: [] for name in routes}
         loop_iters = max(5, args.iters // max(1, R // 8))   # a repetition is R requests
         for _ in range(args.rounds):
-            rows["many"].append(timed(many, args.iters))
-            rows["loop"].append(timed(loop, loop_iters))
-        res = {"candidates": n_cand,
-               "forward_many": forward_seen(many), "forward_loop": forward_seen(loop),
+            for name, fn in routes.items():
+                rows[name].append(timed(fn, args.iters if name == "many" else loop_iters))
+        res = {"candidates": n_cand, "large": n_large,
+               "positives_of_large": [len(p) for p in pos[:n_large]],
+               "answered": {"large_lane": len(getattr(got["many"], "large", ())),
+                            "host": len(getattr(got["many"], "on_host", ()))},
                "iters_many": args.iters, "iters_loop": loop_iters}
+        for name, fn in routes.items():
+            res["forward_" + name] = forward_seen(fn)
         for name, v in rows.items():
             host = [h for h, _ in v]
             res[name] = {"ms_per_batch": round(statistics.median(host), 4),
@@ -153,10 +184,11 @@ def main():
                          "ms_worst_median": round(max(host), 4),
                          "event_ms_per_batch": round(statistics.median(e for _, e in v), 4),
                          "requests_per_s": round(R / statistics.median(host) * 1e3, 1)}
-        res["speedup"] = round(res["loop"]["ms_per_batch"] / res["many"]["ms_per_batch"], 2)
-        res["many_worst_at_or_below_loop_worst"] = (res["many"]["ms_worst_median"]
-                                                    <= res["loop"]["ms_worst_median"])
-        out["batches"][str(R)] = res
+        if "loop" in routes:
+            res["speedup"] = round(res["loop"]["ms_per_batch"] / res["many"]["ms_per_batch"], 2)
+            res["many_worst_at_or_below_loop_worst"] = (res["many"]["ms_worst_median"]
+                                                        <= res["loop"]["ms_worst_median"])
+        out["batches"][str(R) if not n_large else f"{R}+{n_large}large"] = res
     print(json.dumps(out))
 
 
