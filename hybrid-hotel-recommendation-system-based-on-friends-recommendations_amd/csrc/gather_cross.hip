@@ -708,6 +708,10 @@ dcnr_status launch_fwd(const GatherDesc& g, const CrossParams& cp, const int64_t
   constexpr int S = FWD_SPW * WPB;
   size_t lds = (size_t)(((2 * cp.L + 1) * g.D + S * g.n_tab + 3) & ~3) * sizeof(float) +
                (size_t)WPB * RM * WAVE * sizeof(bf16);
+  // L = 7 at D > 900 asks for more than the 64 KiB default (71488 B at D = 1024,
+  // 29 tables; with 66 tables 73856 B, and the static table map: well inside 160 KiB)
+  if (lds + sizeof(TabLds) > 65536)
+    TRY(set_max_dyn_lds((const void*)gather_cross_fwd_kernel<T, RM, FWD_SPW>, lds));
   int64_t blocks = std::min<int64_t>(cdiv(B, S), 256 * 8);
   hipLaunchKernelGGL((gather_cross_fwd_kernel<T, RM, FWD_SPW>), dim3((unsigned)blocks), dim3(NT),
                      lds, s, g, cp, user, item, cat, num, B, (T*)o.x0, o.ld_x0, o.zc, err, check, o.cross,

@@ -168,8 +168,16 @@ dcnr_status make_dims(const dcnr_model_desc* d, Dims* o) {
   o->prec = d->precision;
   o->es = d->precision == DCNR_PREC_BF16 ? 2 : 4;
   o->dropout = d->dropout;
-  if (o->Hp > 2048 || o->D > 1024) {
-    set_error("hidden_dim=%d / input_dim=%d unsupported", o->H, o->D);
+  if (o->D > 1024) {
+    set_error("input_dim=%d unsupported (max 1024)", o->D);
+    return DCNR_UNSUPPORTED_SHAPE;
+  }
+  // the row passes (elementwise.hip run_rowcol) give a thread 8 bf16 / 4 fp32
+  // columns of a row and a row at most one 256-thread block
+  const int hp_max = d->precision == DCNR_PREC_BF16 ? 2048 : 1024;
+  if (o->Hp > hp_max) {
+    set_error("hidden_dim=%d unsupported in %s precision (padded to %d, max %d)", o->H,
+              d->precision == DCNR_PREC_BF16 ? "bf16" : "fp32", o->Hp, hp_max);
     return DCNR_UNSUPPORTED_SHAPE;
   }
   return DCNR_OK;

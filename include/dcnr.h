@@ -170,6 +170,16 @@ typedef int (*dcnr_allreduce_fn)(void* ctx, double* device_buf, int64_t count, d
 #define DCNR_GRADS_EMBEDDING 1
 typedef int (*dcnr_grad_ready_fn)(void* ctx, int32_t group, dcnr_stream_t stream);
 
+/* Accepted model shapes.  Every entry point that takes a dcnr_model_desc checks
+ * them first, before anything is launched, and dcnr_last_error names the
+ * offending value:
+ *   n_cat      0..64, every cat_rows[k] >= 1; n_users, n_items >= 1  (DCNR_BAD_ARG)
+ *   emb_dim, hidden >= 1, n_num >= 0; precision FP32 or BF16          (DCNR_BAD_ARG)
+ *   n_res      1..8                                        (DCNR_UNSUPPORTED_SHAPE)
+ *   n_cross    0..7                                        (DCNR_UNSUPPORTED_SHAPE)
+ *   input dim  D <= 1024 (dcnr_input_dim)                  (DCNR_UNSUPPORTED_SHAPE)
+ *   hidden     rounded up to 8: <= 2048 with DCNR_PREC_BF16 (hidden <= 2048),
+ *              <= 1024 with DCNR_PREC_FP32 (hidden <= 1024) (DCNR_UNSUPPORTED_SHAPE) */
 typedef struct {
   int64_t n_users;          /* user_embedding rows      (train.py:136) */
   int64_t n_items;          /* item_embedding rows      (train.py:137) */

@@ -27,6 +27,14 @@ one test id (a probed path costs R H calls).
   f32_h100_r2     L        fp32
   f32_h256_r2     L        fp32 fused head pass
   f32_h512_r2_B33 L        fp32
+  r8              T P K    MAX_RES = MAX_RES_TW = 8 blocks: the tower's 17 packed layers, both h
+                           buffers reused four times (h64)
+  L7              T P K    MAX_CROSS: gather_cross_v4_kernel's elementwise cross stack in eval (h64)
+  tab66           T P K    MAX_CAT: 66 gathered tables on the general front, D = 296 (h64)
+  D1024_L7        P K      D = Dp = 1024 > 512: no tower; the general front at 71488 bytes of
+                           dynamic LDS, the generic initial GEMM at K = 1024 (h512, one block)
+  h2048_r2        L        Hp = 2048, the bf16 limit: row passes at one row a block, row_dot
+  h1100_r1        L        Hp = 1104: tcols = 138, 118 idle threads a block
 
 Measured on an MI355X (worst stage flip fraction, worst |diff| / bound of a
 stored or probed activation, worst |diff| / bound of a logit, the worst
@@ -70,6 +78,19 @@ bit-equal):
   f32_h100_r2     L     -         6.96e-02    1.70e-02   -                    bit-equal
   f32_h256_r2     L     -         9.11e-02    1.83e-02   -                    bit-equal
   f32_h512_r2_B33 L     -         4.98e-02    5.18e-03   -                    bit-equal
+  r8              T     1.04e-04  5.00e-01    1.55e-02   7.81e-03 (1.2e-03)   bit-equal
+  r8              P     1.04e-04  5.00e-01    1.56e-02   0                    bit-equal
+  r8              K     1.04e-04  5.00e-01    1.56e-02   -                    bit-equal
+  L7              T     5.21e-05  4.99e-01    1.69e-02   0                    bit-equal
+  L7              P     5.21e-05  4.99e-01    1.82e-02   0                    bit-equal
+  L7              K     5.21e-05  4.99e-01    1.90e-02   -                    bit-equal
+  tab66           T     1.56e-04  4.99e-01    2.37e-02   0                    bit-equal
+  tab66           P     1.56e-04  4.99e-01    2.30e-02   0                    bit-equal
+  tab66           K     1.56e-04  4.99e-01    1.57e-02   -                    bit-equal
+  D1024_L7        P     9.77e-05  4.98e-01    2.30e-02   0                    bit-equal
+  D1024_L7        K     9.77e-05  4.98e-01    2.30e-02   -                    bit-equal
+  h2048_r2        L     4.39e-03  5.00e-01    4.20e-03   -                    bit-equal
+  h1100_r1        L     1.59e-03  5.00e-01    8.41e-03   -                    bit-equal
 
 (bf16 diff / bound 0.5: the stored value is the reference rounded, half a bf16
 ulp away at the most, against a bound of one ulp and more; 0.71 at h500_r1 is
@@ -80,17 +101,18 @@ by one bf16 ulp of a value in [1, 2) at the most.  fp32: the worst element
 uses a tenth of its bound.  The one-hot probe and the h0 device reproduced the
 kept path's stored h_k and h0 bit for bit in every K case.  A probed case costs
 R H (the tower and the kept path: (R + 2) H) forward calls and stays below
-0.3 s; the whole module runs in 7 s.)
+0.3 s; the whole module ran in 7 s before the six limit cases, which stay below 0.4 s a
+path.)
 """
 import pytest
 
 from eval_check import eval_check
 from stage_check import ACC_EPS, BF16_ULPS, FLIP_FRAC, REL  # noqa: F401  (the bounds in force)
-from test_stages_gpu import _tables
+from test_stages_gpu import _D1024, _T66, _tables
 
 pytestmark = pytest.mark.gpu
 
-# id: (precision, hidden, blocks, B, tables, seed, paths, input width)
+# id: (precision, hidden, blocks, B, tables, seed, paths, input width[, cross layers (default 3)])
 # One seed serves every case: no case's flip fraction came near FLIP_FRAC with it.
 CASES = {
     "h40_r2": ("bf16", 40, 2, 300, _tables(), 11, "TPK", 456),
@@ -108,15 +130,22 @@ CASES = {
     "f32_h100_r2": ("fp32", 100, 2, 300, _tables(), 11, "L", 456),
     "f32_h256_r2": ("fp32", 256, 2, 300, _tables(), 11, "L", 456),
     "f32_h512_r2_B33": ("fp32", 512, 2, 33, _tables(), 11, "L", 456),
+    # the limits of the accepted shapes (test_stages_gpu.LIMIT_CASES has the train step's)
+    "r8": ("bf16", 64, 8, 300, _tables(), 11, "TPK", 456),
+    "L7": ("bf16", 64, 1, 300, _tables(), 11, "TPK", 456, 7),
+    "tab66": ("bf16", 64, 1, 300, _T66, 11, "TPK", 296),
+    "D1024_L7": ("bf16", 512, 1, 300, _D1024, 11, "PK", 1024, 7),
+    "h2048_r2": ("bf16", 2048, 2, 300, _tables(), 11, "L", 456),
+    "h1100_r1": ("bf16", 1100, 1, 300, _tables(), 11, "L", 456),
 }
 IDS = [(case, path) for case, v in CASES.items() for path in v[6]]
 
 
 @pytest.mark.parametrize("case,path", IDS, ids=[f"{c}-{p}" for c, p in IDS])
 def test_eval_stage_by_stage(dev, case, path):
-    precision, hidden, n_res, B, tb, seed, _, input_dim = CASES[case]
+    precision, hidden, n_res, B, tb, seed, _, input_dim, *n_cross = CASES[case]
     cfg = dict(n_users=tb["n_users"], n_items=tb["n_items"], cat_dims=tb["cat_dims"], n_num=tb["n_num"],
-               params=dict(emb_dim=tb["emb_dim"], hidden_dim=hidden, n_cross_layers=3,
+               params=dict(emb_dim=tb["emb_dim"], hidden_dim=hidden, n_cross_layers=(n_cross or [3])[0],
                            n_res_blocks=n_res, dropout=0.6))
     res = eval_check(dev, cfg, B, seed, precision, path)
     assert res["input_dim"] == input_dim

@@ -314,3 +314,72 @@ def test_row_map_workspace_is_last():
         for idx in (0, 1):
             assert m.workspace_offset(B, _lib.TRAIN, kind, idx) == \
                 m.workspace_offset(B, _lib.TRAIN, kind, idx, extra_flags=F), kind
+
+
+def _ws_query(n_cross=3, n_res=2, cat_rows=(1000,) * 4, emb=32, n_num=8, hidden=64, precision=1, mode=1):
+    """dcnr_workspace_size of a descriptor built by hand (no model, no device):
+    (status, bytes, dcnr_last_error, dcnr_input_dim)."""
+    import ctypes
+    from dcnr import _lib
+    lib = _lib.load()
+    rows = (ctypes.c_int64 * max(1, len(cat_rows)))(*cat_rows)
+    d = _lib.ModelDesc()
+    d.n_users, d.n_items, d.n_cat = 4096, 1024, len(cat_rows)
+    d.cat_rows = ctypes.cast(rows, ctypes.POINTER(ctypes.c_int64))
+    d.emb_dim, d.n_num, d.hidden, d.n_cross, d.n_res = emb, n_num, hidden, n_cross, n_res
+    d.dropout, d.precision, d.flags = 0.5, precision, 0
+    n = ctypes.c_size_t(0)
+    st = lib.dcnr_workspace_size(ctypes.byref(d), 300, mode, ctypes.byref(n))
+    msg = (lib.dcnr_last_error() or b"").decode() if st != _lib.DCNR_OK else ""
+    return st, int(n.value), msg, int(lib.dcnr_input_dim(ctypes.byref(d)))
+
+
+# 27 tables of width 32 (1000 rows), emb 64: D = 128 + 864 + n_num
+_WIDE = dict(cat_rows=(1000,) * 27, emb=64)
+# what: (arguments, status, what dcnr_last_error must name)
+SHAPE_REFUSED = {
+    "L=8": (dict(n_cross=8), "UNSUPPORTED_SHAPE", "n_cross_layers=8"),
+    "L=-1": (dict(n_cross=-1), "UNSUPPORTED_SHAPE", "n_cross_layers=-1"),
+    "R=0": (dict(n_res=0), "UNSUPPORTED_SHAPE", "n_res_blocks=0"),
+    "R=9": (dict(n_res=9), "UNSUPPORTED_SHAPE", "n_res_blocks=9"),
+    "65 tables": (dict(cat_rows=(12,) * 65, emb=16), "BAD_ARG", "n_cat=65"),
+    "D=1025": (dict(n_num=33, **_WIDE), "UNSUPPORTED_SHAPE", "input_dim=1025"),
+    "Hp=2056": (dict(hidden=2049), "UNSUPPORTED_SHAPE", "hidden_dim=2049"),
+    "fp32 Hp=1032": (dict(hidden=1025, precision=0), "UNSUPPORTED_SHAPE", "hidden_dim=1025 unsupported in fp32"),
+    "fp32 Hp=2048": (dict(hidden=2048, precision=0), "UNSUPPORTED_SHAPE", "hidden_dim=2048 unsupported in fp32"),
+    "a table of 0 rows": (dict(cat_rows=(1000, 0, 1000)), "BAD_ARG", "cat table 1 has 0 rows"),
+    "precision 2": (dict(precision=2), "BAD_ARG", "bad precision 2"),
+    "precision -1": (dict(precision=-1), "BAD_ARG", "bad precision -1"),
+}
+SHAPE_ACCEPTED = {
+    "L=7": dict(n_cross=7),
+    "L=0": dict(n_cross=0),
+    "R=8": dict(n_res=8),
+    "R=1": dict(n_res=1),
+    "64 tables": dict(cat_rows=(12,) * 64, emb=16),
+    "no tables": dict(cat_rows=(), n_num=0),
+    "D=1024": dict(n_num=32, **_WIDE),
+    "D=1024, L=7": dict(n_num=32, n_cross=7, **_WIDE),
+    "Hp=2048": dict(hidden=2048),
+    "Hp=2048 from 2041": dict(hidden=2041),
+    "fp32 Hp=1024": dict(hidden=1024, precision=0),
+    "fp32 Hp=1024 from 1017": dict(hidden=1017, precision=0),
+}
+
+
+@pytest.mark.parametrize("mode", [0, 1], ids=["eval", "train"])
+def test_model_shape_limits(mode):
+    """make_dims (csrc/step.hip) through dcnr_workspace_size: a shape one past
+    each limit include/dcnr.h states is refused with the status stated there
+    and an error that names the offending value; each limit itself is accepted
+    with a workspace size (tests/test_stages_gpu.py LIMIT_CASES run them)."""
+    from dcnr import _lib
+    for what, kw in SHAPE_ACCEPTED.items():
+        st, n, _, D = _ws_query(mode=mode, **kw)
+        assert st == _lib.DCNR_OK and n > 0, (what, st, n)
+        if what.startswith("D=1024"):
+            assert D == 1024
+    for what, (kw, status, names) in SHAPE_REFUSED.items():
+        st, n, msg, D = _ws_query(mode=mode, **kw)
+        assert st == getattr(_lib, "DCNR_" + status), (what, st, msg)
+        assert names in msg, (what, msg)

@@ -11,8 +11,10 @@ kernel path, test_fp32_step_stage_by_stage_paths at the fp32 step's shapes
 test_step_stage_by_stage_batch_regimes, in both precisions, at narrow models
 whose batch size alone takes the reductions and the fp32 split-K past what
 B <= 8192 reaches, and past 262144 / 524288 rows, where the deep tower's GEMMs
-run as several launches of 32-bit buffer offsets.  Every small case then runs
-the same step again in the layout a real step uses.
+run as several launches of 32-bit buffer offsets, and
+test_step_stage_by_stage_limits at the limits of the shapes the library
+accepts (cross layers, blocks, tables, input and hidden width).  Every small
+case then runs the same step again in the layout a real step uses.
 """
 import time
 
@@ -46,8 +48,9 @@ def test_bf16_step_stage_by_stage(dev, full):
 
 
 # golden_common.CFG3R's tables and cross network (D = 456), as tests/test_paths_gpu.py's CFG
-def _tables(n_cat=12, emb=32, n_num=8):
-    card = 1000 if emb == 32 else 250   # embedding width int(sqrt(card)) + 1 = emb
+def _tables(n_cat=12, emb=32, n_num=8, card=None):
+    if card is None:
+        card = 1000 if emb == 32 else 250   # embedding width int(sqrt(card)) + 1 = emb
     return dict(n_users=4096, n_items=1024, cat_dims={f"c{k}": card for k in range(n_cat)}, n_num=n_num,
                 emb_dim=emb)
 
@@ -73,15 +76,15 @@ PATH_CASES = {
 INPUT_DIM = {"h64_r1_D164": 164, "h512_r1_D579": 579}
 
 
-def _run_case(dev, case, precision, hidden, n_res, p, B, tb, seed, flags, input_dim):
+def _run_case(dev, case, precision, hidden, n_res, p, B, tb, seed, flags, input_dim, n_cross=3, bound_x=None):
     """The stage check of one case, then the same step in the production
     layout: logits, loss and every gradient bit-equal to the kept run's."""
     cfg = dict(n_users=tb["n_users"], n_items=tb["n_items"], cat_dims=tb["cat_dims"], n_num=tb["n_num"],
-               params=dict(emb_dim=tb["emb_dim"], hidden_dim=hidden, n_cross_layers=3,
+               params=dict(emb_dim=tb["emb_dim"], hidden_dim=hidden, n_cross_layers=n_cross,
                            n_res_blocks=n_res, dropout=p))
     assert {k for k, v in expected_plan(hidden, precision).items() if v} == set(flags.split()), "the case's path"
     t0 = time.perf_counter()
-    res = stage_check(dev, cfg, B, seed, precision)
+    res = stage_check(dev, cfg, B, seed, precision, bound_x)
     assert res["grads"]["initial_deep_layer.weight"].shape[1] == input_dim
     logits, loss, grads = res["plain_step"]()
     diff = [k for k, g in res["grads"].items() if not torch.equal(g, grads[k])]
@@ -339,3 +342,156 @@ def test_step_stage_by_stage_batch_regimes(dev, case):
     precision, *rest = BATCH_CASES[case]
     torch.cuda.empty_cache()   # the cases past the cut hold several GB each: one at a time
     _run_case(dev, case, precision, *rest, BATCH_INPUT_DIM.get(case, 456))
+
+
+_H64 = "masks stats_epi"
+_H512 = "masks stats_epi xbn head_fused rank1"
+_T66 = _tables(64, 16, 8, card=12)         # 64 tables of width 4: D = 32 + 256 + 8 = 296
+_T66_ODD = _tables(64, 16, 3, card=5)      # 64 tables of width 3: D = 32 + 192 + 3 = 227, Dp = 232
+_D1024 = _tables(27, 64, 32, card=1000)    # 27 tables of width 32: D = 128 + 864 + 32 = 1024
+_D904 = _tables(24, 64, 8, card=1000)      # 24 tables of width 32: D = 128 + 768 + 8 = 904
+# id: (precision, hidden, blocks, dropout, B, tables, seed, plan fields expected true, cross layers)
+LIMIT_CASES = {
+    "L0": ("bf16", 64, 1, 0.6, 300, _tables(), 11, _H64, 0),
+    "L4": ("bf16", 64, 1, 0.6, 300, _tables(), 11, _H64, 4),
+    "L5": ("bf16", 64, 1, 0.6, 300, _tables(), 11, _H64, 5),
+    "L7": ("bf16", 64, 1, 0.6, 300, _tables(), 11, _H64, 7),
+    "L7_f32": ("fp32", 64, 1, 0.6, 300, _tables(), 11, "", 7),
+    "L7_B257": ("bf16", 64, 1, 0.6, 257, _tables(), 11, _H64, 7),
+    "r8": ("bf16", 64, 8, 0.6, 300, _tables(), 11, _H64, 3),
+    "r8_f32": ("fp32", 64, 8, 0.6, 300, _tables(), 11, "", 3),
+    "tab32_v4": ("bf16", 64, 1, 0.6, 300, _tables(30, 16, 8, card=12), 11, _H64, 3),
+    "tab66": ("bf16", 64, 1, 0.6, 300, _T66, 11, _H64, 3),
+    "tab66_odd": ("bf16", 64, 1, 0.6, 300, _T66_ODD, 11, _H64, 3),
+    "tab0": ("bf16", 64, 1, 0.6, 300, _tables(0, 32, 0), 11, _H64, 3),
+    "D1024_L3": ("bf16", 512, 1, 0.6, 300, _D1024, 11, _H512, 3),
+    "D1024_L7": ("bf16", 512, 1, 0.6, 300, _D1024, 11, _H512, 7),
+    "D904_L7": ("bf16", 512, 1, 0.6, 300, _D904, 11, _H512, 7),
+    "h2041_r1": ("bf16", 2041, 1, 0.6, 300, _tables(), 11, "masks", 3),
+    "h2048_r2": ("bf16", 2048, 2, 0.6, 300, _tables(), 11, "masks", 3),
+    "h1100_r1": ("bf16", 1100, 1, 0.6, 300, _tables(), 11, "", 3),
+    "f32_h1020_r1": ("fp32", 1020, 1, 0.6, 300, _tables(), 11, "", 3),
+}
+# A case's own bound for a BN-backward stage, as a multiple of the standard one: twice the
+# stage's reference (coefficient sums in torch fp32) against the reference (fp64 sums), both
+# from the stored inputs (stage_check's bound_x; the figures are in the test's docstring)
+LIMIT_BOUNDS = {"h2041_r1": {"dt1[0]": 2 * 2.763}, "h2048_r2": {"dt1[1]": 2 * 1.297}}
+LIMIT_INPUT_DIM = {"tab32_v4": 160, "tab66": 296, "tab66_odd": 227, "tab0": 64, "D1024_L3": 1024,
+                   "D1024_L7": 1024, "D904_L7": 904}
+
+
+@pytest.mark.parametrize("case", list(LIMIT_CASES))
+def test_step_stage_by_stage_limits(dev, case):
+    """The same stage checks and bit-equal second run at the limits of the
+    shapes make_dims (csrc/step.hip) accepts: n_cross_layers 0..7, n_res_blocks
+    1..8, 0..64 categorical tables, input width <= 1024, padded hidden width
+    <= 2048 (bf16) / <= 1024 (fp32).  One past each limit is refused:
+    tests/test_host_cpu.py test_model_shape_limits.
+
+    The front (csrc/gather_cross.hip gather_cross_out): the 16-byte-lane kernels
+    when every width, offset and n_num is a multiple of 4, D <= 512 and
+    4 x tables <= 128 (one id register up to 16 tables, two above), among them
+    gather_lowrank_kernel<L> for L = 1..4 and gather_cross_v4_kernel otherwise;
+    else the general kernel gather_cross_fwd_kernel<T, RM> (RM = 8 up to 512
+    columns, 16 above), whose dynamic LDS is
+    ((2L + 1) D + 16 tables rounded up to 4) x 4 + 4 x RM x 64 x 2 bytes next
+    to a static table map of 1320 bytes.  The cross backward
+    (csrc/cross_bwd.hip) instantiates cross_coef_kernel<L> and
+    x0_alpha_kernel<T, L + 1> per L.
+
+      case          reaches
+      L0            gather_cross_v4_kernel writing x0 with no cross layer (sc is u_f alone);
+                    cross_coef_kernel<0>, x0_alpha_kernel<bf16, 1>
+      L4            gather_lowrank_kernel<.., 4>, the last low-rank instantiation;
+                    cross_coef_kernel<4>, x0_alpha_kernel<bf16, 5>
+      L5            gather_cross_v4_kernel with the elementwise cross stack; cross_coef_kernel<5>
+                    (61 batch-sum slots), x0_alpha_kernel<bf16, 6>
+      L7            MAX_CROSS: cross_coef_kernel<7> (ns_of(7) = 113 slots a thread, red[4][113]),
+                    x0_alpha_kernel<bf16, 8> (red[8][512]), 56 Gram terms of the 64-float gram
+                    buffer, 8 basis vectors in the embedding backward (EmbTabs::V[8])
+      L7_f32        the same with fp32 x0 (x0_alpha_kernel<float, 8>) under the one-ulp bound
+      L7_B257       nblk = nx = 2: cross_coef_kernel's second block holds one sample,
+                    x0_alpha_kernel's second block one row (CT = XA_ROWS = 256)
+      r8            MAX_RES: Layout::h[9], mask_a1[8], mask_h[9] with mask_h[1..7], bn[16];
+                    pack_all's 35 descriptors (W0, b0, the counters, 2 weights + 2 biases a
+                    block) in two launches (MAX_PACK = 20)
+      r8_f32        the same on block_plain with fp32 storage, no masks
+      tab32_v4      emb 16, 30 tables of 12 rows (width 4), n_num 8: D = 160, 32 gathered tables,
+                    4 x 32 = 128: gather_lowrank_kernel<1, 4, 2, 1, 3>, the two-register id map
+      tab66         emb 16, 64 tables of 12 rows, n_num 8: D = 296, MAX_CAT: 4 x 66 > 128, the
+                    general kernel (RM = 8) with 66 tables; emb_ids_kernel at 64 x 256 x 4 = 65536
+                    bytes of dynamic LDS; 66-entry table arrays in the embedding backward
+      tab66_odd     64 tables of 5 rows (width 3), n_num 3: D = 227, Dp = 232, 3-wide rows at odd
+                    offsets (the scalar embedding-backward kernels), padded x0 columns
+      tab0          no categorical tables, n_num 0, emb 32: D = 64, two gathered tables, null cat
+                    and num pointers, emb_ids_kernel's K = 0 return
+      D1024_L3      emb 64, 27 tables of 1000 rows (width 32), n_num 32: D = Dp = 1024, the
+                    D limit: gather_cross_fwd_kernel<bf16, 16> at 16 columns a lane and
+                    (7168 + 464) x 4 + 8192 = 38720 bytes; the initial layer and dW0 at K = 1024
+                    (generic GEMM), dx0 at N = 1024, x0_alpha_kernel's two 512-column passes
+      D1024_L7      the same at L = 7: (15360 + 464) x 4 + 8192 = 71488 bytes of dynamic LDS, past
+                    the 64 KiB default (launch_fwd raises the kernel's limit; the HIP runtime of
+                    the table below launched it without that too)
+      D904_L7       24 tables, n_num 8: D = 904, 26 gathered tables: (13560 + 416) x 4 + 8192 =
+                    64096 bytes, 65416 with the static map: the widest L = 7 request below 65536
+      h2041_r1      Hp = 2048, the hidden limit: bf16 row passes at tcols = Hp / 8 = 256 = NT, one
+                    row per pass; masks with 7 padded bit columns; generic GEMM at K = N = 2048;
+                    the unfused head on row_dot_kernel (N > 512)
+      h2048_r2      the same without padding, two blocks: mask_h[1], du through the generic dX GEMM
+      h1100_r1      Hp = 1104: tcols = 138, rpp = 1, 118 idle threads per block; no masks
+      f32_h1020_r1  fp32 Hp = 1024 with 4 padded columns at the fp32 row-pass limit (tcols = 256)
+
+    Measured on an MI355X (worst stage flip fraction -- fp32: max |diff| / bound --,
+    worst max |diff| of a stored stage, worst relative error of a gradient, second
+    run bit-equal):
+
+      case          flip / bound  max |diff|  gradient rel. error                 second run
+      L0            1.04e-04      2.56e-02    1.13e-07 (dW_f[H:])                 bit-equal
+      L4            1.04e-04      3.08e-02    2.63e-07 (cross_w[1])               bit-equal
+      L5            1.04e-04      3.03e-02    2.56e-06 (dW_f[H:])                 bit-equal
+      L7            1.04e-04      3.09e-02    2.60e-06 (cross_b[4])               bit-equal
+      L7_f32        9.42e-02      2.20e-06    2.64e-06 (cross_b[5])               bit-equal
+      L7_B257       1.22e-04      3.11e-02    2.61e-06 (cross_b[4])               bit-equal
+      r8            1.56e-04      5.75e-02    2.89e-07 (cross_w[1])               bit-equal
+      r8_f32        1.03e-01      2.65e-06    3.30e-07 (cross_w[1])               bit-equal
+      tab32_v4      1.04e-04      2.88e-02    3.33e-07 (cat_embeddings.20.weight) bit-equal
+      tab66         3.12e-04      3.11e-02    3.78e-07 (cat_embeddings.46.weight) bit-equal
+      tab66_odd     5.21e-05      3.03e-02    2.78e-07 (cat_embeddings.35.weight) bit-equal
+      tab0          5.21e-05      2.96e-02    2.49e-07 (dW_f[H:])                 bit-equal
+      D1024_L3      2.47e-04      3.12e-02    2.84e-07 (dW_f[H:])                 bit-equal
+      D1024_L7      1.95e-04      3.12e-02    3.81e-06 (cross_w[6])               bit-equal
+      D904_L7       1.82e-04      3.12e-02    5.72e-06 (cross_b[2])               bit-equal
+      h2041_r1      4.69e-04    3.12e-02    2.92e-07 (cross_w[1])               bit-equal
+      h2048_r2      5.09e-04    3.12e-02    3.01e-07 (cross_w[2])               bit-equal
+      h1100_r1      3.52e-04      3.12e-02    3.08e-07 (cross_b[2])               bit-equal
+      f32_h1020_r1  1.94e-01      3.30e-06    5.75e-07 (dx0)                      bit-equal
+
+    (L >= 5, in either precision: the cross gradients sit at 2.6e-06 - 5.7e-06, ten times
+    the L <= 4 cases' and 1/35 of REL at the most; those cases take the elementwise cross
+    stack, whose s_l carry the fp32 rounding of every element of x_l through the layers,
+    where the low-rank front forms them from L + 1 dot products of x_0 -- supposed from
+    the code, not traced.  Each case takes 0.6 - 0.9 s, the first one of a process 1.8 s.)
+
+    The BN-backward bound at Hp = 2048.  dt = a dr - k1 xh - k2 has k1 and k2 from two sums
+    over the batch, which the kernels make in fp32 per 32-row chunk (fp64 above that) and the
+    reference in fp64.  Where a column's sum cancels to a small part of its summed |terms|
+    the fp32 error of the sum exceeds ACC_EPS x (|k1 xh| + |k2|), and with 2048 columns and
+    614400 elements a stage one such element turns up where dr = 0 and the result is
+    ~4e-12, far below anything a bf16 ulp of the stage's typical values covers (the fp32
+    step's bound carries the sums' own terms for this reason: stage_check.bn_back).  With the
+    standard bound h2041_r1 fails at dt1[0] (1 element, 1.585 x the bound) and h2048_r2 at
+    dt1[1] (1 element, 2.351 x).  The reference against itself, from the same stored inputs --
+    the stage with both sums made by torch in fp32 against the stage with fp64 sums -- is off
+    by MORE than the step in the first case: 2.763 x the standard bound at dt1[0] of
+    h2041_r1, 1.297 x at dt1[1] of h2048_r2 (every other dt stage of both cases: reference
+    vs reference 0.03 - 0.18, the step 0.50).  Those two stages alone get twice their
+    figure (LIMIT_BOUNDS: 5.526 and 2.594 x the standard bound; the step's and torch's
+    summation orders are two independent draws of the same error); the test prints both
+    figures on every run.
+
+    With cross_backward's switch sending n_cross = 5 to cross_coef_kernel<4> (a scratch
+    build, not committed) L5 fails at dW_f[H:] (relative error 3.8e+04).
+    """
+    precision, *rest, n_cross = LIMIT_CASES[case]
+    _run_case(dev, case, precision, *rest, LIMIT_INPUT_DIM.get(case, 456), n_cross=n_cross,
+              bound_x=LIMIT_BOUNDS.get(case))
