@@ -675,9 +675,19 @@ __global__ __launch_bounds__(NTB) void kth_bound_kernel(const float* __restrict_
 // every (row, query) pair + exact fp32 re-scoring of the rows it admits.
 //
 // The coarse cosine is sum_i bf16(x_i * inv_r) * bf16(q_i / |q|), fp32
-// accumulation (v_mfma_f32_16x16x32_bf16: 16x the fp32-MFMA rate).  Each
-// factor carries a relative rounding error <= 2^-9, so for unit vectors
-// |coarse - exact| <= 2^-8 + 2^-16 + fp32 slack < V4_EPS on the distance.
+// accumulation (v_mfma_f32_16x16x32_bf16: 16x the fp32-MFMA rate).  bf16
+// keeps 8 significant bits, so each factor carries a relative rounding error
+// <= 2^-8 (1 + 2^-8 rounds to 1 or to 1 + 2^-7), each product <= 2^-7 + 2^-16
+// and, with xh = x inv_r and qh = q / |q|,
+//   |coarse - exact| <= (2^-7 + 2^-16) sum_i |xh_i qh_i| + fp32 slack
+//                    <= 2^-7 + 2^-16 + fp32 slack < V4_EPS
+// on the distance: the sum is <= |xh| |qh| = 1 (Cauchy-Schwarz), and the
+// bound is approached when every element sits just off a bf16 midpoint with
+// the errors' signs aligned (tests/knn_rounding_cases.py builds such rows:
+// 0.0064 at d = 32; random tables stay near 4e-4, the errors cancelling).
+// The fp32 slack -- the MFMA's accumulation of d <= 64 exact bf16 products,
+// the exact distance's own d fmas, the rounding of x inv_r and q / |q|, each a
+// few 2^-24 -- stays under 2e-5; V4_EPS leaves 7e-5 for it.
 // Every row of the exact top-k has exact distance <= E_k (the k-th best)
 // <= T0 (the k-th best of a V4_S-row exact sample: any subset's k-th best
 // bounds the table's), hence coarse distance <= T0 + V4_EPS: admitting the
@@ -693,7 +703,8 @@ __global__ __launch_bounds__(NTB) void kth_bound_kernel(const float* __restrict_
 // v2's per-wave lists and arithmetic; split over up to V4_FMAX blocks per
 // query for Q <= V4_FQ): no batch-wide flag, no gated launches behind the
 // chain.  Three launches per call: bound5, scan4, rescore.
-constexpr float V4_EPS = 0.004f;
+constexpr float V4_EPS = 0.0079f;   // > 2^-7 + 2^-16 = 0.0078278 (+ the fp32 slack)
+static_assert(V4_EPS > 0.0078125f + 0.0000152587890625f + 2e-5f, "V4_EPS covers 2^-8 per bf16 factor");
 constexpr int V4_S = 65536;     // sample rows for the admission bound
 constexpr int V4_WPS = 3;       // min waves per SIMD of scan4 for NQB > 4
 constexpr int V4_CAP = 4096;     // admitted rows per query
@@ -788,7 +799,7 @@ __device__ __forceinline__ Mins2 v4_load_mins(const float* mq, int ng, int lane)
 // wave-wide: the admission bounds of MQ queries from their block minima:
 // the k-th smallest by a bitwise search over their non-negative float bits,
 // down to 10 mantissa bits, and the upper edge of that bin (>= the k-th,
-// within 2^-10 relative: 5e-4 at the usual bounds against V4_EPS = 0.004).
+// within 2^-10 relative: 5e-4 at the usual bounds against V4_EPS = 0.0079).
 // The MQ searches are interleaved (each step's ballot -> count -> select is
 // otherwise one dependent chain).  Every lane returns the bounds.
 constexpr int V4_LOWBIT = 13;
@@ -1093,10 +1104,10 @@ __global__ __launch_bounds__(256, NQB > 4 ? V4_WPS : 1) void scan4_kernel(const 
       // block's admission checks serialised LDS read -> MFMA -> result ->
       // ballot per block: 146 us for 256 queries), then one ballot per block
       // on the best of its 4 rows -- usually empty -- before the per-row
-      // ones.  The accumulators start at bound - 1, so a check is a sign
-      // test: with |coarse - exact| <= 2^-8 + 2^-16 + fp32 accumulation error
-      // (< 1e-5 here) against V4_EPS = 0.004 the admitted set still contains
-      // every row whose exact distance is <= the bound.
+      // ones.  A check compares the coarse cosine with 1 - (bound + V4_EPS):
+      // with |coarse - exact| <= 2^-7 + 2^-16 (2^-8 per bf16 factor) + fp32
+      // accumulation error (< 2e-5 here) < V4_EPS = 0.0079 the admitted set
+      // contains every row whose exact distance is <= the bound.
       // (LDS fragments: block b + 1's read is issued before block b's MFMAs)
       f32x4 acc[NQB];
       bf16x8 nb[KS];
@@ -2327,8 +2338,9 @@ static size_t neighbor_table_ws(int64_t N, int k) { return carve_nbr(nullptr, N,
 //
 // Phase A marks a superset: the exact k-th distance dk of r (its last entry
 // is outside C, or the row is affected anyway), and then, d = 32 / 64, scan
-// v4's coarse bf16 cosine of r against every c -- |coarse - exact| < V4_EPS
-// (DESIGN section 4), so coarse <= dk + V4_EPS + TH_MARGIN holds for every c
+// v4's coarse bf16 cosine of r against every c -- |coarse - exact| <= 2^-7 +
+// 2^-16 + fp32 slack < V4_EPS, 2^-8 per bf16 factor (scan v4's comment; DESIGN
+// section 4), so coarse <= dk + V4_EPS + TH_MARGIN holds for every c
 // with exact distance <= dk: one margin, because dk itself is exact (a coarse
 // dk would double it and gather as many rows) -- or, other widths, the exact
 // distance against dk + TH_MARGIN.  A row is appended once, by the block that
